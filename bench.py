@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s + learner updates/s of the SAC1 actor-learner hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or plainly as
      `python bench.py --gpus N`: without WORLD_SIZE in the environment this process only spawns the N ranks — before any
      GPU call — relays rank 0's JSON line and exits with the worst return code)
@@ -40,6 +40,12 @@ average launch time measured with HIP events on the launch stream around a learn
 launch gaps count).  `stages` adds the other rows of SURVEY §8(d): rollout-only, store, sample, the config-5 gather.
 `cpu_baseline` times the oracle (CPU restatement of the reference path) on this box's host cores for a bounded sample,
 BEFORE the GPU legs; the GPU legs run last and are repeated for ~10 s (`repeat_blocks`) so that a sampler sees them.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline (`value`, `updates_per_s`, `ms_per_step`, `config`,
+`functional_only`).  Everything else above — `cpu_baseline`, `repeat_blocks`, the other gate, `series`, `roofline`, `free_running`,
+`stages`, the partitioned run's diagnostics — is measured only with `--full`.  `--dump-outputs DIR` writes, after the timed block, what its
+last step computed on rank 0 as float32 .npy files (the transitions the rollout stored, the observations it acts on next, the learner's
+main and target parameters); the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import ctypes
@@ -110,6 +116,11 @@ def parse_args():
     ap.add_argument("--stage-samples", type=int, default=200)
     ap.add_argument("--cfg5-capacity", type=int, default=-1,
                     help="transitions of the config-5 ring (225 804 B each); -1: as many as 90 %% of the free HBM holds (at most 1.15 M = 260 GB); 0: skip config 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baseline, repeated blocks, the other gate, series, roofline, "
+                         "free-running loop, stages, partition diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32, rank 0)")
     return ap.parse_args()
 
 
@@ -615,6 +626,34 @@ def free_running_measure(roll, trainer, opt, args, torch):
     return res
 
 
+DUMP_MAX_ROWS = 1 << 16   # transitions --dump-outputs writes at most (a fixed sample of a larger vector step): <= 7.3 MB in all
+
+
+def dump_outputs(out_dir, roll, learner, torch):
+    """--dump-outputs: what the timed path's last step computed on this rank — the transitions its last vector step appended to the
+    ring, the observations the envs act on next, and the learner's main and target parameters after the step's updates."""
+    import numpy as np
+    from distributed_drl_amd import _lib
+    arrays = {}
+    if roll is not None:
+        rb, n = roll.rb, int(roll.env.n)
+        pick = np.arange(n)
+        if n > DUMP_MAX_ROWS:
+            pick = np.sort(np.random.RandomState(0).choice(n, DUMP_MAX_ROWS, replace=False))
+        pick_d = torch.from_numpy(pick).to(roll.env.obs.device)
+        rows = (pick_d + (rb.ptr - n)) % rb.max_size
+        for name, ring in rb.rings().items():
+            arrays["last_step_" + name[:-len("_buf")]] = ring[rows]
+        arrays["next_obs"] = roll.env.obs[pick_d]
+    if learner is not None:
+        arrays["learner_main_params"] = learner.export(_lib.SAC1_MAIN)
+        arrays["learner_target_params"] = learner.export(_lib.SAC1_TARGET)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+    assert sum(t.numel() * 4 for t in arrays.values()) <= 64 << 20
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -634,7 +673,7 @@ def main():
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     cpu_one = cpu_all = None
-    if world_env == 1 and not args.no_cpu_baseline:
+    if args.full and world_env == 1 and not args.no_cpu_baseline:
         cpu_one, cpu_all = cpu_baseline(args.a_l_ratio, args.cpu_budget)   # before the GPU is touched: the GPU legs run last
 
     rank, world, local = comm.init_from_env()
@@ -708,8 +747,10 @@ def main():
         one_step()
     t_gpu0 = time.perf_counter()
     dt = block()                                   # THE timed region: exactly --steps steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.roll if run is not None else roll, run.learner if run is not None else trainer.agent, torch)
     blocks = [dt]
-    while True:   # every rank takes part in the decision (one collective per round)
+    while args.full:   # every rank takes part in the decision (one collective per round)
         more = time.perf_counter() - t_gpu0 < args.gpu_seconds and len(blocks) < 50
         if comm.allreduce_max(1.0 if more else 0.0, device=dev) < 0.5:
             break
@@ -722,7 +763,9 @@ def main():
     # where the ungated figures come from workers.FreeRunningLoop instead).  N > 1: a second PartitionedRun in the other mode —
     # lock-step under the gate, free-running (partition.py: free_steps) without it
     run_other = None
-    if world > 1:
+    if not args.full:
+        dt_other = None
+    elif world > 1:
         if run.learner is not None:
             run.check()
         run_other = make_run(args.free_steps if other_gate == "free" else 0)
@@ -750,96 +793,98 @@ def main():
     rank_busy = role_times = learner_crc = None
     if run is not None and run.learner is not None:
         run.check()
-    # series 2 of the N-GPU readout: what the rollout ranks produce when nothing holds them back — every rollout rank runs K vector steps
-    # back to back (store into its local shard included, the policy versions of the run's pushes live), all ranks at once
-    k_roll = 50
-    my_roll = run.roll if run is not None else roll
-    if my_roll is not None:
-        for _ in range(5):
-            my_roll.step()
-    torch.cuda.synchronize()
-    comm.barrier()
-    t0 = time.perf_counter()
-    if my_roll is not None:
-        for _ in range(k_roll):
-            my_roll.step()
-    torch.cuda.synchronize()
-    mine_roll = time.perf_counter() - t0
-    comm.barrier()
-    per_rank = [(k_roll * num_envs / mine_roll) if my_roll is not None else None]
-    if world > 1:
-        per_rank = [None] * world
-        torch.distributed.all_gather_object(per_rank, (k_roll * num_envs / mine_roll) if my_roll is not None else None)
-    roll_capacity = {"per_rank_env_steps_per_s": [None if v is None else round(v) for v in per_rank],
-                     "sum_env_steps_per_s": float(sum(v for v in per_rank if v is not None)), "vector_steps": k_roll,
-                     "what": "every rollout rank steps its %d envs %d times back to back, all ranks concurrently, no learner work: policy forward "
-                             "(versions of the run's pushes live) + env.step + store into the local shard" % (num_envs, k_roll)}
-    if run is not None:
-        import zlib
-        import torch.distributed as dist
-        # data-parallel learners must hold the same parameters bit for bit after any number of steps (same start, same averaged gradient)
-        learner_crc = [None] * world
-        dist.all_gather_object(learner_crc, zlib.crc32(run.learner.get_weights_flat().cpu().numpy().tobytes()) if run.learner is not None else None)
-        learner_crc = [c for c in learner_crc if c is not None]
-        rank_busy = [None] * world
-        dist.all_gather_object(rank_busy, busy[0])    # of the last repeated block (the same work as block 0, whose max over ranks is `dt`)
-        # one extra block with the device drained at every phase boundary: where each role's time goes (diagnosis, not the metric)
-        run.timing = True
-        for k in [k for k in run.stats if k.startswith("s_")]:
-            del run.stats[k]
-        n_diag = max(1, min(args.steps, 3))
-        for _ in range(n_diag):
-            one_step()
+    if args.full:
+        # series 2 of the N-GPU readout: what the rollout ranks produce when nothing holds them back — every rollout rank runs K vector steps
+        # back to back (store into its local shard included, the policy versions of the run's pushes live), all ranks at once
+        k_roll = 50
+        my_roll = run.roll if run is not None else roll
+        if my_roll is not None:
+            for _ in range(5):
+                my_roll.step()
         torch.cuda.synchronize()
-        run.timing = False
-        mine = {k: round(v / n_diag * 1e3, 4) for k, v in run.stats.items() if k.startswith("s_")}
-        role_times = [None] * world
-        dist.all_gather_object(role_times, mine)
+        comm.barrier()
+        t0 = time.perf_counter()
+        if my_roll is not None:
+            for _ in range(k_roll):
+                my_roll.step()
+        torch.cuda.synchronize()
+        mine_roll = time.perf_counter() - t0
+        comm.barrier()
+        per_rank = [(k_roll * num_envs / mine_roll) if my_roll is not None else None]
+        if world > 1:
+            per_rank = [None] * world
+            torch.distributed.all_gather_object(per_rank, (k_roll * num_envs / mine_roll) if my_roll is not None else None)
+        roll_capacity = {"per_rank_env_steps_per_s": [None if v is None else round(v) for v in per_rank],
+                         "sum_env_steps_per_s": float(sum(v for v in per_rank if v is not None)), "vector_steps": k_roll,
+                         "what": "every rollout rank steps its %d envs %d times back to back, all ranks concurrently, no learner work: policy forward "
+                                 "(versions of the run's pushes live) + env.step + store into the local shard" % (num_envs, k_roll)}
+        if run is not None:
+            import zlib
+            import torch.distributed as dist
+            # data-parallel learners must hold the same parameters bit for bit after any number of steps (same start, same averaged gradient)
+            learner_crc = [None] * world
+            dist.all_gather_object(learner_crc, zlib.crc32(run.learner.get_weights_flat().cpu().numpy().tobytes()) if run.learner is not None else None)
+            learner_crc = [c for c in learner_crc if c is not None]
+            rank_busy = [None] * world
+            dist.all_gather_object(rank_busy, busy[0])    # of the last repeated block (the same work as block 0, whose max over ranks is `dt`)
+            # one extra block with the device drained at every phase boundary: where each role's time goes (diagnosis, not the metric)
+            run.timing = True
+            for k in [k for k in run.stats if k.startswith("s_")]:
+                del run.stats[k]
+            n_diag = max(1, min(args.steps, 3))
+            for _ in range(n_diag):
+                one_step()
+            torch.cuda.synchronize()
+            run.timing = False
+            mine = {k: round(v / n_diag * 1e3, 4) for k, v in run.stats.items() if k.startswith("s_")}
+            role_times = [None] * world
+            dist.all_gather_object(role_times, mine)
     if rank != 0:
         return
 
-    # ---- roofline of the update's launches: HIP events on the launch stream around learner-only graph replays -------
-    lib = _lib.load()
-    launches_per_update = 5
-    gf = update_flops(**cfgd)
-    roofline = {"kernel": "the %d launches of one SAC1 update (k_dfwd<0>, k_dfwd<1>, k_dg x3: layer 1 + fc GEMMs + heads / losses / "
-                          "Adam / polyak in the epilogues), fp32 MFMA" % launches_per_update,
-                "bound": "mfma", "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "update_flops": gf,
-                "flops_per_launch": gf / launches_per_update}
-    if trainer is not None:
-        n_upd = 40 * args.updates_per_graph
-        t_upd = timed(lambda: trainer.run(n_upd), 3, warm=1) / n_upd
-        stage = np.zeros(_lib.SAC1_STAGES, np.float64)
-        ms = ctypes.c_float()
-        for st in (2, 5, 7, 8, 9):   # eager back-to-back launches of ONE stage (caches warm): a lower bound per launch
-            _lib.check(lib.ddrl_sac1_stage_time(trainer.agent._h, st, args.stage_samples, ctypes.byref(ms), _lib.stream_ptr()))
-            stage[st] = ms.value
-        launch_s = t_upd / launches_per_update
-        roofline.update({"achieved": gf / launches_per_update / launch_s / 1e12,   # per-launch FLOPs / per-launch time
-                         "frac": gf / launches_per_update / launch_s / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                         "avg_launch_us": launch_s * 1e6, "update_us_learner_only": t_upd * 1e6,
-                         "update_roofline_frac": (gf / (PEAK_F32_MFMA_TFLOPS * 1e12)) / t_upd,
-                         "stage_us_warm": {k: round(float(stage[i]) * 1e3, 3) for k, i in
-                                           (("k_dfwd<0>", 2), ("k_dfwd<1>", 5), ("k_dg bq", 7), ("k_dg mid", 8), ("k_dg pi", 9))}})
-    else:
-        upd_s = dt / (args.steps * updates_per_step)
-        roofline.update({"achieved": gf / upd_s / 1e12, "frac": gf / upd_s / 1e12 / PEAK_F32_MFMA_TFLOPS,
-                         "avg_launch_us": upd_s / launches_per_update * 1e6,
-                         "note": "from the timed region of learner rank 0: env step + block transfers + the learner loop (%s)" %
-                                 ("graph-captured, the sampler following the step's feed plan" if len(roles.learners) == 1 else
-                                  "eager: gradients, RCCL all-reduce, Adam per update")})
-    traffic, tsrc, stale = None, None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            traffic, tsrc = tj.get("bytes_per_launch_mean"), tj.get("source")
-            stale = tj.get("kernel_source_sha256") != kernel_source_hash()
-        except Exception:  # noqa
-            pass
-    roofline["traffic"] = traffic
-    roofline["traffic_stale"] = stale   # true: csrc/ changed since the PMC passes behind profiles/traffic.json (tools/prof_round.sh + tools/make_traffic.py)
-    roofline["traffic_source"] = ("static file profiles/traffic.json (%s); PMC counters cannot be collected inside this process" % tsrc) if traffic else None
+    if args.full:
+        # ---- roofline of the update's launches: HIP events on the launch stream around learner-only graph replays -------
+        lib = _lib.load()
+        launches_per_update = 5
+        gf = update_flops(**cfgd)
+        roofline = {"kernel": "the %d launches of one SAC1 update (k_dfwd<0>, k_dfwd<1>, k_dg x3: layer 1 + fc GEMMs + heads / losses / "
+                              "Adam / polyak in the epilogues), fp32 MFMA" % launches_per_update,
+                    "bound": "mfma", "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "update_flops": gf,
+                    "flops_per_launch": gf / launches_per_update}
+        if trainer is not None:
+            n_upd = 40 * args.updates_per_graph
+            t_upd = timed(lambda: trainer.run(n_upd), 3, warm=1) / n_upd
+            stage = np.zeros(_lib.SAC1_STAGES, np.float64)
+            ms = ctypes.c_float()
+            for st in (2, 5, 7, 8, 9):   # eager back-to-back launches of ONE stage (caches warm): a lower bound per launch
+                _lib.check(lib.ddrl_sac1_stage_time(trainer.agent._h, st, args.stage_samples, ctypes.byref(ms), _lib.stream_ptr()))
+                stage[st] = ms.value
+            launch_s = t_upd / launches_per_update
+            roofline.update({"achieved": gf / launches_per_update / launch_s / 1e12,   # per-launch FLOPs / per-launch time
+                             "frac": gf / launches_per_update / launch_s / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                             "avg_launch_us": launch_s * 1e6, "update_us_learner_only": t_upd * 1e6,
+                             "update_roofline_frac": (gf / (PEAK_F32_MFMA_TFLOPS * 1e12)) / t_upd,
+                             "stage_us_warm": {k: round(float(stage[i]) * 1e3, 3) for k, i in
+                                               (("k_dfwd<0>", 2), ("k_dfwd<1>", 5), ("k_dg bq", 7), ("k_dg mid", 8), ("k_dg pi", 9))}})
+        else:
+            upd_s = dt / (args.steps * updates_per_step)
+            roofline.update({"achieved": gf / upd_s / 1e12, "frac": gf / upd_s / 1e12 / PEAK_F32_MFMA_TFLOPS,
+                             "avg_launch_us": upd_s / launches_per_update * 1e6,
+                             "note": "from the timed region of learner rank 0: env step + block transfers + the learner loop (%s)" %
+                                     ("graph-captured, the sampler following the step's feed plan" if len(roles.learners) == 1 else
+                                      "eager: gradients, RCCL all-reduce, Adam per update")})
+        traffic, tsrc, stale = None, None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                traffic, tsrc = tj.get("bytes_per_launch_mean"), tj.get("source")
+                stale = tj.get("kernel_source_sha256") != kernel_source_hash()
+            except Exception:  # noqa
+                pass
+        roofline["traffic"] = traffic
+        roofline["traffic_stale"] = stale   # true: csrc/ changed since the PMC passes behind profiles/traffic.json (tools/prof_round.sh + tools/make_traffic.py)
+        roofline["traffic_source"] = ("static file profiles/traffic.json (%s); PMC counters cannot be collected inside this process" % tsrc) if traffic else None
 
     out = {
         "metric": "env-steps/s + learner updates/s, SAC1 LunarLanderContinuous-v2 @1/2/4/8 GPU",
@@ -878,20 +923,21 @@ def main():
                    "world_size": world, "rank_devices": rank_devices,
                    "distinct_devices": len({(r or {}).get("uuid") or (r or {}).get("pci_bus_id") or (r or {}).get("device") for r in rank_devices}),
                    "parallelism": roles.describe()},
-        "repeat_blocks": {"n": len(blocks), "ms_per_step_median": float(np.median(blocks)) / args.steps * 1e3,
-                          "ms_per_step_min": float(np.min(blocks)) / args.steps * 1e3, "ms_per_step_max": float(np.max(blocks)) / args.steps * 1e3,
-                          "note": "`value` is block 0 (exactly --steps steps); the same block repeated to keep the GPU leg visible"},
-        "roofline": roofline,
     }
-    g_env = args.steps * num_envs * len(roles.rollouts) * vsteps_by_gate[other_gate]
-    g_upd = args.steps * upd_by_gate[other_gate] * len(roles.learners)
-    other = {"value": g_env / dt_other, "updates_per_s": g_upd / dt_other, "ms_per_step": dt_other / args.steps * 1e3,
-             "updates_per_step": upd_by_gate[other_gate], "gate": other_gate, "vector_steps_per_rollout_rank_and_step": vsteps_by_gate[other_gate],
-             "what": "the same timed block of --steps steps under --gate %s%s" % (other_gate, " (identical step at N = 1: not re-run)" if dt_other is dt else "")}
-    out["value_ungated" if other_gate == "free" else "value_gated"] = other["value"]
-    out["other_gate"] = other
-    if args.gate == "free":
-        out["value_ungated"] = out["value"]
+    if args.full:
+        out["repeat_blocks"] = {"n": len(blocks), "ms_per_step_median": float(np.median(blocks)) / args.steps * 1e3,
+                                "ms_per_step_min": float(np.min(blocks)) / args.steps * 1e3, "ms_per_step_max": float(np.max(blocks)) / args.steps * 1e3,
+                                "note": "`value` is block 0 (exactly --steps steps); the same block repeated to keep the GPU leg visible"}
+        out["roofline"] = roofline
+        g_env = args.steps * num_envs * len(roles.rollouts) * vsteps_by_gate[other_gate]
+        g_upd = args.steps * upd_by_gate[other_gate] * len(roles.learners)
+        other = {"value": g_env / dt_other, "updates_per_s": g_upd / dt_other, "ms_per_step": dt_other / args.steps * 1e3,
+                 "updates_per_step": upd_by_gate[other_gate], "gate": other_gate, "vector_steps_per_rollout_rank_and_step": vsteps_by_gate[other_gate],
+                 "what": "the same timed block of --steps steps under --gate %s%s" % (other_gate, " (identical step at N = 1: not re-run)" if dt_other is dt else "")}
+        out["value_ungated" if other_gate == "free" else "value_gated"] = other["value"]
+        out["other_gate"] = other
+        if args.gate == "free":
+            out["value_ungated"] = out["value"]
     functional = os.environ.get("DDRL_BENCH_FUNCTIONAL_ONLY") == "1" or (world > 1 and out["config"]["distinct_devices"] < world) \
         or (world > 1 and out["config"]["backend"] != "nccl")
     out["functional_only"] = bool(functional)
@@ -900,60 +946,61 @@ def main():
                                    "note": "ranks shared a GPU over gloo: host-staged transfers on one device — NOT an N-GPU measurement"}
         out["value"], out["updates_per_s"] = 0.0, 0.0
         out.pop("value_ungated", None)
-    if run is not None:
-        out["partition_stats"] = {k: v for k, v in run.stats.items() if not k.startswith("s_")}
-        s_upd = [t.get("s_updates") for t in role_times if t and t.get("s_updates")]
-        out["scaling_readout"] = {
-            "env_steps_per_sample": env_steps / max(1, updates),
-            "rank_busy_s_in_timed_block": [round(b, 4) for b in rank_busy],
-            "roles": ["learner+rollout" if (r in roles.learners and r in roles.rollouts) else ("learner" if r in roles.learners else "rollout") for r in range(world)],
-            "phase_ms_per_step_drained": role_times,
-            "learner_only_updates_per_s": (updates_per_step * len(roles.learners) / (max(s_upd) * 1e-3)) if s_upd else None,
-            "rollout_only_env_steps_per_s_per_rank": [round(num_envs / (t["s_env"] * 1e-3)) if t and t.get("s_env") else None for t in role_times],
-            "note": "value = env steps of the timed block / its wall time (max over ranks); under --gate hold the learner rank(s) bound it. "
-                    "phase times come from one extra block with the device drained at every phase boundary (s_env: vector env step, "
-                    "s_serve: shard owner draws + sends its blocks, s_receive: learner posts receives + lays the plan, s_updates: the "
-                    "updates, s_push: parameter broadcast, s_drain: sends complete)"}
-    if learner_crc is not None:
-        out["partition_stats"]["learner_weight_crc32"] = learner_crc
-        out["partition_stats"]["learners_identical"] = len(set(learner_crc)) == 1
-    lg_steps = None
-    if world == 1 and "update_us_learner_only" in roofline:
-        lg_steps = 1e6 / roofline["update_us_learner_only"]
-    elif run is not None and out["scaling_readout"]["learner_only_updates_per_s"]:
-        lg_steps = out["scaling_readout"]["learner_only_updates_per_s"] / len(roles.learners)
-    out["series"] = {
-        "gated_env_steps_per_s": out["value"] if not functional else out["functional_value"]["value"],
-        "learner_group_optimizer_steps_per_s": lg_steps,
-        "learner_group_batches_per_s": None if lg_steps is None else lg_steps * len(roles.learners),
-        "rollout_capacity_env_steps_per_s": roll_capacity["sum_env_steps_per_s"],
-        "rollout_capacity": roll_capacity,
-        "learner_ranks": len(roles.learners), "rollout_ranks": len(roles.rollouts),
-        "functional_only": bool(functional),
-        "note": "learner-group rate: the learner rank(s) alone%s; rollout capacity: rollout-only block, all rollout ranks at once; gated: the "
-                "timed region (`value`).  See config.weak_scaling_why for which series the 0.7 target is read against." %
-                (" (graph loop, HIP events)" if world == 1 else " (updates phase of one drained block: feed attached, all-reduce included)")}
-    if world == 1 and trainer is not None and not args.no_free:
-        fr = free_running_measure(roll, trainer, opt, args, torch)
-        out["free_running"] = fr
-        # at N = 1 the gated step and the "free" step of rounds 2-5 were the same step; the ungated figures are now what the two halves
-        # reach when NOTHING holds either back and they share the GPU
-        out["value_ungated"] = fr["env_steps_per_s"]
-        out["updates_per_s_ungated"] = fr["updates_per_s"]
-        out["series"]["rollout_capacity_with_learner_env_steps_per_s"] = fr["env_steps_per_s"]
-        out["series"]["learner_updates_per_s_beside_free_rollout"] = fr["updates_per_s"]
-    if world == 1 and not args.no_stages:
-        out["stages"] = stage_measurements(args, opt, rb, roll, d)
-    if world == 1:
-        out["scaling_readout"] = {
-            "env_steps_per_sample": env_steps / max(1, updates), "roles": ["learner+rollout"],
-            "learner_only_updates_per_s": (1e6 / roofline["update_us_learner_only"]) if "update_us_learner_only" in roofline else None,
-            "rollout_only_env_steps_per_s_per_rank": [out.get("stages", {}).get("rollout_only", {}).get("env_steps_per_s")],
-            "note": "one rank runs the envs and the learner back to back; under the gate the learner is 99.9 % of the step"}
-    out["cpu_baseline"] = cpu_one
-    out["cpu_baseline_all_cores"] = cpu_all
-    if cpu_one is not None:
-        out["gpu_over_cpu"] = {"env_steps": out["value"] / cpu_one["value"], "updates": out["updates_per_s"] / cpu_one["updates_per_s"]}
+    if args.full:
+        if run is not None:
+            out["partition_stats"] = {k: v for k, v in run.stats.items() if not k.startswith("s_")}
+            s_upd = [t.get("s_updates") for t in role_times if t and t.get("s_updates")]
+            out["scaling_readout"] = {
+                "env_steps_per_sample": env_steps / max(1, updates),
+                "rank_busy_s_in_timed_block": [round(b, 4) for b in rank_busy],
+                "roles": ["learner+rollout" if (r in roles.learners and r in roles.rollouts) else ("learner" if r in roles.learners else "rollout") for r in range(world)],
+                "phase_ms_per_step_drained": role_times,
+                "learner_only_updates_per_s": (updates_per_step * len(roles.learners) / (max(s_upd) * 1e-3)) if s_upd else None,
+                "rollout_only_env_steps_per_s_per_rank": [round(num_envs / (t["s_env"] * 1e-3)) if t and t.get("s_env") else None for t in role_times],
+                "note": "value = env steps of the timed block / its wall time (max over ranks); under --gate hold the learner rank(s) bound it. "
+                        "phase times come from one extra block with the device drained at every phase boundary (s_env: vector env step, "
+                        "s_serve: shard owner draws + sends its blocks, s_receive: learner posts receives + lays the plan, s_updates: the "
+                        "updates, s_push: parameter broadcast, s_drain: sends complete)"}
+        if learner_crc is not None:
+            out["partition_stats"]["learner_weight_crc32"] = learner_crc
+            out["partition_stats"]["learners_identical"] = len(set(learner_crc)) == 1
+        lg_steps = None
+        if world == 1 and "update_us_learner_only" in roofline:
+            lg_steps = 1e6 / roofline["update_us_learner_only"]
+        elif run is not None and out["scaling_readout"]["learner_only_updates_per_s"]:
+            lg_steps = out["scaling_readout"]["learner_only_updates_per_s"] / len(roles.learners)
+        out["series"] = {
+            "gated_env_steps_per_s": out["value"] if not functional else out["functional_value"]["value"],
+            "learner_group_optimizer_steps_per_s": lg_steps,
+            "learner_group_batches_per_s": None if lg_steps is None else lg_steps * len(roles.learners),
+            "rollout_capacity_env_steps_per_s": roll_capacity["sum_env_steps_per_s"],
+            "rollout_capacity": roll_capacity,
+            "learner_ranks": len(roles.learners), "rollout_ranks": len(roles.rollouts),
+            "functional_only": bool(functional),
+            "note": "learner-group rate: the learner rank(s) alone%s; rollout capacity: rollout-only block, all rollout ranks at once; gated: the "
+                    "timed region (`value`).  See config.weak_scaling_why for which series the 0.7 target is read against." %
+                    (" (graph loop, HIP events)" if world == 1 else " (updates phase of one drained block: feed attached, all-reduce included)")}
+        if world == 1 and trainer is not None and not args.no_free:
+            fr = free_running_measure(roll, trainer, opt, args, torch)
+            out["free_running"] = fr
+            # at N = 1 the gated step and the "free" step of rounds 2-5 were the same step; the ungated figures are now what the two halves
+            # reach when NOTHING holds either back and they share the GPU
+            out["value_ungated"] = fr["env_steps_per_s"]
+            out["updates_per_s_ungated"] = fr["updates_per_s"]
+            out["series"]["rollout_capacity_with_learner_env_steps_per_s"] = fr["env_steps_per_s"]
+            out["series"]["learner_updates_per_s_beside_free_rollout"] = fr["updates_per_s"]
+        if world == 1 and not args.no_stages:
+            out["stages"] = stage_measurements(args, opt, rb, roll, d)
+        if world == 1:
+            out["scaling_readout"] = {
+                "env_steps_per_sample": env_steps / max(1, updates), "roles": ["learner+rollout"],
+                "learner_only_updates_per_s": (1e6 / roofline["update_us_learner_only"]) if "update_us_learner_only" in roofline else None,
+                "rollout_only_env_steps_per_s_per_rank": [out.get("stages", {}).get("rollout_only", {}).get("env_steps_per_s")],
+                "note": "one rank runs the envs and the learner back to back; under the gate the learner is 99.9 % of the step"}
+        out["cpu_baseline"] = cpu_one
+        out["cpu_baseline_all_cores"] = cpu_all
+        if cpu_one is not None:
+            out["gpu_over_cpu"] = {"env_steps": out["value"] / cpu_one["value"], "updates": out["updates_per_s"] / cpu_one["updates_per_s"]}
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
 

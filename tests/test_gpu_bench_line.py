@@ -1,7 +1,8 @@
 """bench.py's contract, checked on the GPU box: the one JSON line of a short single-GPU run (metric string, roofline and config
 blocks, both gate figures, the three series of the N-GPU readout, a fresh traffic file), of a functional 2-rank run on the one GPU at
 config 3's real sizes (4096 envs per rank, batch 256, 500 k-transition shards) and of a functional 8-rank run at config 4's real sizes
-(2 learner ranks + 6 rollout ranks x 8192 envs, 10^6 transitions over 6 shards) — which must say that they are not scaling points."""
+(2 learner ranks + 6 rollout ranks x 8192 envs, 10^6 transitions over 6 shards) — which must say that they are not scaling points —
+all with --full; and of a plain run, with the arrays --dump-outputs writes."""
 import json
 import os
 import subprocess
@@ -29,7 +30,7 @@ def run_bench(*args, timeout=900):
 
 
 def test_single_gpu_line():
-    j = run_bench("--steps", "2", "--warmup", "1", "--gpu-seconds", "0", "--no-stages", "--no-cpu-baseline")
+    j = run_bench("--full", "--steps", "2", "--warmup", "1", "--gpu-seconds", "0", "--no-stages", "--no-cpu-baseline")
     assert j["metric"] == METRIC and j["unit"] == "env-steps/s" and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
     assert j["higher_is_better"] is True and j["scaling"] == "weak" and j["vs_baseline"] is None and j["dtype"] == "f32" and j["data"] == "synthetic"
     assert j["value"] > 1e4 and abs(j["value"] / j["updates_per_s"] - 2.0) < 1e-9       # the gate: 2 env steps per sampled batch
@@ -58,7 +59,7 @@ def test_single_gpu_line():
 
 
 def test_two_ranks_on_one_gpu_is_functional_only():
-    j = run_bench("--gpus", "2", "--steps", "1", "--warmup", "1", "--gpu-seconds", "0", "--no-stages", "--no-cpu-baseline")
+    j = run_bench("--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--gpu-seconds", "0", "--no-stages", "--no-cpu-baseline")
     assert j["n_gpus"] == 2 and j["functional_only"] is True and j["value"] == 0.0 and "value_ungated" not in j
     f = j["functional_value"]
     assert f["value"] > 0 and f["updates_per_s"] > 0 and f["value_ungated"] > 0 and "NOT an N-GPU measurement" in f["note"]
@@ -76,7 +77,7 @@ def test_eight_ranks_on_one_gpu_config4_sizes_is_functional_only():
     """BASELINE config 4 as stated (algos/sac1/sac_ray.py:137-141,246,316-324; example/dsac.py:229-233): `bench.py --gpus 8` puts 2
     data-parallel learner ranks and 6 rollout ranks x 8192 envs with a 166 666-transition shard each on the one GPU over gloo.  Roles,
     the updates the gate owes per step under both settings, where the batches came from, pushes, and learner 0 == learner 1 bit for bit."""
-    j = run_bench("--gpus", "8", "--steps", "1", "--warmup", "0", "--gpu-seconds", "0", "--no-stages", "--no-cpu-baseline", timeout=1500)
+    j = run_bench("--full", "--gpus", "8", "--steps", "1", "--warmup", "0", "--gpu-seconds", "0", "--no-stages", "--no-cpu-baseline", timeout=1500)
     assert j["n_gpus"] == 8 and j["functional_only"] is True and j["value"] == 0.0 and "value_ungated" not in j
     c = j["config"]
     assert c["backend"] == "gloo" and c["world_size"] == 8 and c["distinct_devices"] == 1 and len(c["rank_devices"]) == 8
@@ -100,3 +101,31 @@ def test_eight_ranks_on_one_gpu_config4_sizes_is_functional_only():
     assert ps["learners_identical"] is True and len(ps["learner_weight_crc32"]) == 2
     cap = j["series"]["rollout_capacity"]["per_rank_env_steps_per_s"]
     assert cap[:2] == [None, None] and all(v and v > 0 for v in cap[2:])
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) carries the headline only, over exactly --steps timed steps; --dump-outputs writes what the last timed
+    step computed — the 4096 transitions it stored, the observations the envs act on next, the learner's main and target parameters —
+    and two runs with the same arguments write the same arrays (seeded inputs, deterministic kernels)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        j = run_bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+        assert j["metric"] == METRIC and j["unit"] == "env-steps/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert j["steps"] == 3 and j["functional_only"] is False and j["value"] > 1e4
+        assert abs(j["ms_per_step"] * 1e-3 * j["value"] - 4096) < 1e-6 * 4096
+        for k in ("cpu_baseline", "repeat_blocks", "other_gate", "roofline", "series", "free_running", "stages"):
+            assert k not in j, k
+        dumps.append({f[:-len(".npy")]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    a, b = dumps
+    shapes = {"last_step_obs1": (4096, 8), "last_step_obs2": (4096, 8), "last_step_acts": (4096, 2), "last_step_rews": (4096,),
+              "last_step_done": (4096,), "next_obs": (4096, 8)}
+    assert sorted(a) == sorted(list(shapes) + ["learner_main_params", "learner_target_params"])
+    for k, s in shapes.items():
+        assert a[k].shape == s, k
+    assert a["learner_main_params"].ndim == 1 and a["learner_main_params"].shape == a["learner_target_params"].shape
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert np.abs(a["last_step_acts"]).max() <= 1.0
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
