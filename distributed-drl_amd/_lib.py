@@ -153,6 +153,7 @@ SIGNATURES = {
     "ddrl_dqn_create": (c_int, [POINTER(_P), c_int, _P]),
     "ddrl_dqn_destroy": (c_int, [_P]),
     "ddrl_dqn_set_weights": (c_int, [_P, _P, _P]),
+    "ddrl_dqn_wide_sk": (c_int, [_P]),
     "ddrl_dqn_export": (c_int, [_P, c_int, _P, _P]),
     "ddrl_dqn_import": (c_int, [_P, c_int, _P, _P]),
     "ddrl_dqn_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -554,6 +554,8 @@ int ddrl_dqn_set_weights(ddrl_dqn_t *h, const float *flat_main_d, void *stream) 
     return DDRL_OK;
 }
 
+int ddrl_dqn_wide_sk(ddrl_dqn_t *h) { return h ? (h->sk_on ? 1 : 0) : DDRL_ERR_BAD_ARG; }
+
 int ddrl_dqn_export(ddrl_dqn_t *h, int which, float *flat_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && flat_d != nullptr, "NULL pointer");
     float *buf = which == DDRL_SAC1_MAIN ? h->main_p : which == DDRL_SAC1_TARGET ? h->target_p : which == DDRL_SAC1_ADAM_M ? h->m :

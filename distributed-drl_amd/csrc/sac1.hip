@@ -328,7 +328,7 @@ struct RowsC {
 __global__ void __launch_bounds__(64) k_rows_c(const float *base, int dz1_off, int h2_off, int w1q_off, int wmu_off, int wls_off, int save_off,
                                                int pk_h, int pk_l, int pk_a, RowsC a) {
     const int lane = threadIdx.x;
-    const int nrows = pk_a >> 16;
+    const int nrows = (int)((unsigned)pk_a >> 16);   // (the batch fills the upper half: 32 768 rows and more set the sign bit)
     if ((int)blockIdx.x == nrows) {  // (gridDim is a hidden-argument load)
         // reduce_mean over the batch: the extra last workgroup sums the per-row terms of k_rows_b in
         // a fixed order (lane-strided partial sums, then the xor-shuffle tree)
@@ -818,10 +818,11 @@ static int check_cfg(const ddrl_sac1_config_t *c) {
     return DDRL_OK;
 }
 
-// Envelope of the direct-operand path (sac1_direct.h); everything else takes the generic kernels.
+// Envelope of the direct-operand path (sac1_direct.h); everything else takes the generic kernels.  A wgrad tile of k_dg contracts
+// the whole batch inside one workgroup, DGMAX 8-deep groups per wave: 4 x 16 x 8 = 512 rows (beyond that the rows were dropped).
 static bool direct_ok(const ddrl_sac1_config_t &c) {
     return c.hidden1 % 4 == 0 && c.hidden2 % 4 == 0 && c.hidden1 <= 512 && c.hidden2 <= 32 * DNT &&
-           c.obs_dim + c.act_dim <= 12 && 2 * c.act_dim <= DFH && c.act_dim <= 4 && c.batch <= 32768 &&
+           c.obs_dim + c.act_dim <= 12 && 2 * c.act_dim <= DFH && c.act_dim <= 4 && c.batch <= 4 * DGMAX * 8 &&
            getenv("DDRL_SAC1_GENERIC") == nullptr;
 }
 
@@ -1727,7 +1728,7 @@ static void launch_rows_c(ddrl_sac1 *h, hipStream_t s) {
     const RowsC &c = h->rc;
     const float *b = h->slab;
     k_rows_c<<<c.B + 1, 64, 0, s>>>(b, (int)(c.dZ1q - b), (int)(c.H2 - b), (int)(c.W1q1 - b), (int)(c.pi.Wmu - b), (int)(c.pi.Wls - b),
-                                    (int)(c.save0 - b), c.h1 | (c.h2 << 16), c.ldh2 | (c.obs << 16), c.act | (c.B << 16), c);
+                                    (int)(c.save0 - b), c.h1 | (c.h2 << 16), c.ldh2 | (c.obs << 16), (int)((unsigned)c.act | ((unsigned)c.B << 16)), c);
 }
 
 // One stage of the update (input set `st`).  Stage ids as documented for ddrl_sac1_stage_time.

@@ -510,6 +510,9 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg);
 int ddrl_dqn_destroy(ddrl_dqn_t *h);
 /* Learner.set_weights (flat "main" vector in variable order) incl. target_init (actor_learner.py:99-101). */
 int ddrl_dqn_set_weights(ddrl_dqn_t *h, const float *flat_main_d, void *stream);
+/* 1 while the wide layer-1 wgrad runs as the stream-K kernel (k_wide_sk), 0 on the tile-per-workgroup kernel (narrow observations,
+ * DDRL_WIDE_SK=0 at create, a shape that does not split, or after a combine time-out). */
+int ddrl_dqn_wide_sk(ddrl_dqn_t *h);
 /* Flat copies of the learner's buffers; `which` = DDRL_SAC1_MAIN / TARGET / ADAM_M / ADAM_V / GRAD. */
 int ddrl_dqn_export(ddrl_dqn_t *h, int which, float *flat_d, void *stream);
 /* The inverse for MAIN (without target_init), TARGET, ADAM_M, ADAM_V: a learner resumed from its own state, or one whose

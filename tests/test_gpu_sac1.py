@@ -39,6 +39,18 @@ def _mk(ddrl, seed=0, **kw):
     return opt, learner, cfg
 
 
+def _sp():
+    """tests/_state_parity.py: start_from_other_targets / assert_targets_seen.  After set_weights the targets equal main and one update
+    moves a target by (1 - polyak) lr at most — a quarter of the n * 2e-2 * lr bars below, which then pass whatever the polyak step
+    does.  The tests that hold SAC1_TARGET to such a bar start from main != target instead (learner and oracle alike) and check that
+    the bar is at most a tenth of the targets' movement."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _state_parity
+    return _state_parity
+
+
 def _rel(a, b):
     return abs(float(a) - float(b)) / max(abs(float(b)), 1e-30)
 
@@ -279,6 +291,7 @@ def test_sacv_model_matches_oracle(ddrl, hid, batch):
             params[k] = rs.uniform(-0.05, 0.05, params[k].shape).astype(np.float32)
     model.set_weights(list(params.keys()), list(params.values()))
     o64 = sv.SacVOracle(cfg, params, torch.float64, stable=True)
+    t0 = _sp().start_from_other_targets(model, [o64], params)
     for it in range(5):
         b, eps = so.synthetic_batch(cfg, seed=40 + it)
         w = o64.step(b, eps[0])
@@ -298,6 +311,7 @@ def test_sacv_model_matches_oracle(ddrl, hid, batch):
     assert np.abs(a - b64).max() <= 5 * 2e-2 * cfg.lr
     a, b64 = model.export(_lib.SAC1_TARGET).cpu().numpy(), o64.flat("target")
     assert np.abs(a - b64).max() <= 5 * 2e-2 * cfg.lr
+    _sp().assert_targets_seen(o64, t0, 5 * 2e-2 * cfg.lr)
     assert model.opt_steps() == (5, 5)
     # get_action: the policy head of the same variables (deterministic = tanh(mu))
     obs = b["obs1"][0]
@@ -327,6 +341,7 @@ def test_ddqn_learner_matches_oracle(ddrl, obs, acts, hid, batch):
             params[k] = rs.uniform(-0.1, 0.1, params[k].shape).astype(np.float32)
     learner.set_weights(list(params.keys()), list(params.values()))
     o64 = do.DqnOracle(cfg, params, torch.float64)
+    t0 = _sp().start_from_other_targets(learner, [o64], params)
     for it in range(4):
         b = do.synthetic_batch(cfg, 10 + it)
         w = o64.step(b)
@@ -339,6 +354,7 @@ def test_ddqn_learner_matches_oracle(ddrl, obs, acts, hid, batch):
             assert np.abs(g - g64).max() <= 2e-4 * np.abs(g64).max()
     for which, name in ((_lib.SAC1_MAIN, "main"), (_lib.SAC1_TARGET, "target")):
         assert np.abs(learner.export(which).cpu().numpy() - o64.flat(name)).max() <= 4 * 2e-2 * cfg.lr
+    _sp().assert_targets_seen(o64, t0, 4 * 2e-2 * cfg.lr)
     # Actor.get_action: argmax of the same network (0.97 greedy)
     actor = dqn.Actor(Opt, "worker")
     actor.set_weights(*learner.get_weights())
@@ -369,6 +385,7 @@ def test_sqn_learner_matches_oracle(ddrl, obs, acts, hid, batch):
             params[k] = rs.uniform(-0.1, 0.1, params[k].shape).astype(np.float32)
     learner.set_weights(list(params.keys()), list(params.values()))
     o64 = do.SqnOracle(cfg, params, 0.1, torch.float64)
+    t0 = _sp().start_from_other_targets(learner, [o64], params)
     for it in range(4):
         b = do.synthetic_batch(cfg, 20 + it)
         w = o64.step(b)
@@ -381,6 +398,7 @@ def test_sqn_learner_matches_oracle(ddrl, obs, acts, hid, batch):
             assert np.abs(g - g64).max() <= 2e-4 * np.abs(g64).max()
     for which, name in ((_lib.SAC1_MAIN, "main"), (_lib.SAC1_TARGET, "target")):
         assert np.abs(learner.export(which).cpu().numpy() - o64.flat(name)).max() <= 4 * 2e-2 * cfg.lr
+    _sp().assert_targets_seen(o64, t0, 4 * 2e-2 * cfg.lr)
     actor = dqn.ActorSQN(Opt, "worker")
     actor.set_weights(*learner.get_weights())
     assert 0 <= actor.get_action(b["obs1"][0]) < acts and 0 <= actor.get_action(b["obs1"][0], True) < acts
@@ -404,6 +422,7 @@ def test_fused_envelope_shapes(ddrl, obs, act, hid, batch):
             params[k] = rs.uniform(-0.05, 0.05, params[k].shape).astype(np.float32)
     learner.set_weights(list(params.keys()), list(params.values()))
     o64 = so.Sac1Oracle(cfg, params, torch.float64)
+    t0 = _sp().start_from_other_targets(learner, [o64], params)
     for it in range(2):
         b, eps = so.synthetic_batch(cfg, seed=90 + it)
         w = o64.step(b, *eps)
@@ -419,6 +438,7 @@ def test_fused_envelope_shapes(ddrl, obs, act, hid, batch):
             assert np.abs(g - g64).max() <= 2e-4 * np.abs(g64).max()
     for which, name in ((_lib.SAC1_MAIN, "main"), (_lib.SAC1_TARGET, "target")):
         assert np.abs(learner.export(which).cpu().numpy() - o64.flat(name)).max() <= 2 * 2e-2 * cfg.lr
+    _sp().assert_targets_seen(o64, t0, 2 * 2e-2 * cfg.lr)
     assert learner.opt_steps() == (2, 2)
 
 
@@ -445,6 +465,7 @@ def test_wide_layer1_shapes(ddrl, variant, obs, acts, hid, batch, misalign):
             params[k] = rs.uniform(-0.1, 0.1, params[k].shape).astype(np.float32)
     learner.set_weights(list(params.keys()), list(params.values()))
     o64 = do.SqnOracle(cfg, params, 0.1, torch.float64) if sqn else do.DqnOracle(cfg, params, torch.float64)
+    t0 = _sp().start_from_other_targets(learner, [o64], params)
     for it in range(2):
         b = do.synthetic_batch(cfg, 30 + it)
         w = o64.step(b)
@@ -464,6 +485,7 @@ def test_wide_layer1_shapes(ddrl, variant, obs, acts, hid, batch, misalign):
             assert np.abs(g - g64).max() <= 3e-4 * np.abs(g64).max()
     for which, name in ((_lib.SAC1_MAIN, "main"), (_lib.SAC1_TARGET, "target")):
         assert np.abs(learner.export(which).cpu().numpy() - o64.flat(name)).max() <= 2 * 2e-2 * cfg.lr
+    _sp().assert_targets_seen(o64, t0, 2 * 2e-2 * cfg.lr)
     # the q output for fewer rows than the batch goes through the staged image
     x = b["obs1"][:3]
     qn = (do.q_net(o64.main, "main", torch.as_tensor(x.astype(np.float64))) if not sqn else None)
