@@ -250,6 +250,20 @@ def actor_act(cfg, params, obs, eps, deterministic=False, dtype=torch.float32):
     return (mu if deterministic else pi).numpy()
 
 
+def actor_forward(cfg, params, obs, eps, dtype=torch.float32):
+    """actor_act with its intermediates, per row: dict(mu_pre = the mu head before the tanh, log_std, std, mu = the deterministic
+    action, pi = the sampled one), NumPy arrays in `dtype`.  mu / pi come out of policy() itself (the same code actor_act runs)."""
+    p = OrderedDict((n, torch.as_tensor(np.asarray(v)).to(dtype)) for n, v in params.items() if "/pi/" in n)
+    x = torch.as_tensor(np.asarray(obs)).to(dtype).reshape(-1, cfg.obs_dim)
+    e = torch.zeros(x.shape[0], cfg.act_dim, dtype=dtype) if eps is None else torch.as_tensor(np.asarray(eps)).to(dtype)
+    mu, pi, _ = policy(p, "main", x, e, cfg)
+    h = torch.relu(_dense(x, p, "main/pi/dense"))
+    h = torch.relu(_dense(h, p, "main/pi/dense_1"))
+    log_std = LOG_STD_MIN + 0.5 * (LOG_STD_MAX - LOG_STD_MIN) * (torch.tanh(_dense(h, p, "main/pi/dense_3")) + 1)
+    return dict(mu_pre=_dense(h, p, "main/pi/dense_2").numpy(), log_std=log_std.numpy(), std=torch.exp(log_std).numpy(),
+                mu=mu.numpy(), pi=pi.numpy())
+
+
 def synthetic_batch(cfg, seed=1234, n=None):
     """SURVEY §8(d) synthetic transitions + explicit noise."""
     n = cfg.batch if n is None else n

@@ -587,7 +587,8 @@ def test_versioned_rollout_actions_match_each_versions_own_policy(n, limit, step
     case: 32 row tiles' worth of envs spread over up to 33 live versions — mostly partial row tiles.  `slots`: the forward's planner
     told the chip holds that many workgroups (DDRL_VER_WG_SLOTS), so that these env counts walk what 8192+ envs do on the real
     one — full rounds of coarse workgroups, then the surplus row tiles cut into short ones; `hidden`: other column-tile counts, 16
-    of them included — four workgroups per row tile at the least.)"""
+    of them included — four workgroups per row tile at the least.)
+    The reference path here, the row-major kernels of get_actions, is itself held to the float64 oracle in tests/test_gpu_acting.py."""
     import distributed_drl_amd as ddrl
     from distributed_drl_amd import _lib
     from distributed_drl_amd.agent import Actor, HyperParameters, Learner
@@ -896,7 +897,8 @@ def test_reference_style_nstep_rollout_stores_the_deque_windows():
 def test_get_action_as_one_launch_equals_the_batched_kernels(hidden, obs, act):
     """Actor.get_action(o) (actor_learner.py:195-197) runs as ONE launch (ddrl_actor_act_one: both layers, head, squash, noise from the
     counter): the same action as get_actions on the row with the noise elements ddrl_normal_fill yields at the same stream position —
-    within float32 summation order — stochastic and deterministic, across a set_weights, and the noise counter advances as before."""
+    within float32 summation order — stochastic and deterministic, across a set_weights, and the noise counter advances as before.
+    The reference path here, the batched kernels of get_actions, is itself held to the float64 oracle in tests/test_gpu_acting.py."""
     from distributed_drl_amd import _lib
     from distributed_drl_amd.agent import Actor, HyperParameters
     opt = HyperParameters()
