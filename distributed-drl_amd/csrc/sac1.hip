@@ -1012,6 +1012,7 @@ static int build_sacv_direct(ddrl_sac1 *h, int Bv, int B) {
     const int Kp1 = L.Kp1, Np2 = L.Np2, nt2 = (h2 + 31) / 32;
     const float *Pm = h->main_p, *Pt = h->target_p, *S = h->slab;
     DDRL_REQUIRE(L.v_W1 - L.q_W1[1] == L.q_W1[1] - L.q_W1[0], "internal: the value networks must sit at equal distances");
+    DDRL_REQUIRE(L.pi_bmu == pi_bmu_off(h1, Np2, h2, a) && L.pi_bls == pi_bls_off(h1, Np2, h2, a), "internal: policy-head bias offsets of the direct layout");
     h->fused_l1_wgrad = false;   // (direct path: the policy's layer-1 wgrad is a job of its own, no row-tile partials)
     h->sh_cur = 0;
     const long long HP = (long long)DFH * B * DNT;
@@ -1032,8 +1033,9 @@ static int build_sacv_direct(ddrl_sac1 *h, int Bv, int B) {
             F.njobs = njobs; F.tiles_n = nt2; F.act = a; F.Lp1 = h->Lp1; F.Lp2 = h->Lp2; F.h2 = h2;
             F.scale = (float)cfg->act_scale;
             F.act0 = h->act0; F.act2 = h->act2; F.logp0 = h->logp0; F.logp1 = h->logp1; F.save0 = h->save0;
-            F.php1 = nullptr; F.pbmu1 = Pm + L.pi_bmu; F.pbls1 = Pm + L.pi_bls; F.peps1 = h->in[st][6];
+            F.php1 = nullptr;
             F.pev_pack = 0;   // both phase-1 jobs take the action sampled by pi(x)
+            F.pin_pack = 0;   // ... by the main copy from eps_x
             F.noise_on = 0; F.n_each = Bv * a; F.Bv = Bv; F.noise_seed = 0;
             F.e0 = h->in[st][5]; F.e1 = h->in[st][6]; F.e2 = h->in[st][7]; F.opt = h->opt;
         };
@@ -1066,7 +1068,7 @@ static int build_sacv_direct(ddrl_sac1 *h, int Bv, int B) {
             HB.pack = pk(ns_q, 0, 0, 1) | (pk(ns_q, 0, 0, 2) << 6);
         }
         auto from_pi = [&](DFJob &j, int side) {
-            j.php = h->hp; j.pbmu = Pm + L.pi_bmu; j.pbls = Pm + L.pi_bls; j.peps = h->in[st][5]; j.side = side;
+            j.php = h->hp; j.side = side;
         };
         FB.job[0] = vj(Pm, 0, 5); from_pi(FB.job[0], 1);
         FB.job[0].H2c4 = h->H2c4 + 3 * H2C; FB.job[0].H1r4 = h->H1r4 + 3 * H1I;
@@ -1350,6 +1352,11 @@ int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cf
     }
     // ---- direct-operand path (sac1_direct.h)
     if (h->fused) {
+        if (L.pi_bmu != pi_bmu_off(h1, Np2, h2, a) || L.pi_bls != pi_bls_off(h1, Np2, h2, a)) {   // (k_dfwd<1> forms these addresses itself)
+            ddrl::set_error("internal: policy-head bias offsets of the direct layout");
+            sac1_free(h);
+            return DDRL_ERR_BAD_ARG;
+        }
         h->fused_l1_wgrad = false;   // (direct path: the policy's layer-1 wgrad is a job of its own, no row-tile partials)
         h->sh_cur = 0;
         const float *S = h->slab;
@@ -1370,8 +1377,9 @@ int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cf
                 F.njobs = njobs; F.tiles_n = nt2; F.act = a; F.Lp1 = h->Lp1; F.Lp2 = h->Lp2; F.h2 = h2;
                 F.scale = (float)cfg->act_scale;
                 F.act0 = h->act0; F.act2 = h->act2; F.logp0 = h->logp0; F.logp1 = h->logp1; F.save0 = h->save0;
-                F.php1 = h->hp + 1 * HP; F.pbmu1 = Pm + L.pi_bmu; F.pbls1 = Pm + L.pi_bls; F.peps1 = h->in[st][6];
+                F.php1 = h->hp + 1 * HP;
                 F.pev_pack = 0 | (2 << 2) | (2 << 4);   // q1(x, pi(x)) <- evaluation 0; the target Qs <- evaluation 2 (pi_targ(x2))
+                F.pin_pack = 0 | ((2 | 4) << 3) | ((2 | 4) << 6);   // evaluation 0: main copy, eps_x; evaluation 2: target copy, eps_t
                 F.noise_on = 0; F.n_each = Bv * a; F.Bv = Bv; F.noise_seed = 0;
                 F.e0 = h->in[st][5]; F.e1 = h->in[st][6]; F.e2 = h->in[st][7]; F.opt = h->opt;
             };
@@ -1412,13 +1420,11 @@ int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cf
                 HA.pack = pk(ns_pi, 0, 0, 0) | (pk(ns_pi, 1, 0, 0) << 6) | (pk(ns_pi, 1, 1, 0) << 12) | (q_late ? 0 : qxa);
                 HB.pack = pk(ns_q, 0, 0, 1) | (pk(ns_q, 1, 1, 1) << 6) | (pk(ns_q, 1, 1, 2) << 12) | (q_late ? (qxa | (1 << 30)) : 0);
             }
-            auto from_pi = [&](DFJob &j, int pev, const float *Ppi, const float *eps, int side) {
-                j.php = h->hp + pev * HP; j.pbmu = Ppi + L.pi_bmu; j.pbls = Ppi + L.pi_bls; j.peps = eps; j.side = side;
-            };
-            FB.job[0] = qj(Pm, 0, 5); from_pi(FB.job[0], 0, Pm, h->in[st][5], 1);
+            auto from_pi = [&](DFJob &j, int pev, int side) { j.php = h->hp + pev * HP; j.side = side; };
+            FB.job[0] = qj(Pm, 0, 5); from_pi(FB.job[0], 0, 1);
             FB.job[0].H2c4 = h->H2c4 + 3 * H2C; FB.job[0].H1r4 = h->H1r4 + 3 * H1I;
-            FB.job[1] = qj(Pt, 0, 6); from_pi(FB.job[1], 2, Pt, h->in[st][7], 2);
-            FB.job[2] = qj(Pt, 1, 7); from_pi(FB.job[2], 2, Pt, h->in[st][7], 0);
+            FB.job[1] = qj(Pt, 0, 6); from_pi(FB.job[1], 2, 2);
+            FB.job[2] = qj(Pt, 1, 7); from_pi(FB.job[2], 2, 0);
             // ---- backward launch 1: the three Q dgrads (slot 2 first: its dQ/da partials are what the next launch waits for)
             DGJobs &Q = h->dg_bq[st];
             Q = DGJobs{};

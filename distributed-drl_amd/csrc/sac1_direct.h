@@ -83,6 +83,15 @@ __device__ __forceinline__ int kline(const void *rec) {
     return acc;
 }
 __device__ __forceinline__ void ktouch(int v) { asm volatile("" ::"s"(v)); }
+// The zero a sum over early-requested values starts from, opaque to the compiler and pinned where the sum is written.  Those values are
+// 0 on the paths that do not load them, and the compiler folds `0.f + (loaded or 0)` into the loading block: the add, and with it a wait
+// for the first of the loads, then stands in front of every later request of the wave (one more cold round trip before the operand
+// loads of k_dg "bq" and of the `two` tiles of k_dfwd<1> were even issued).
+__device__ __forceinline__ float zero_here() {
+    float z = 0.f;
+    asm volatile("" : "+v"(z));
+    return z;
+}
 
 // ==========================================================================================
 // forward stages
@@ -98,19 +107,20 @@ struct DFJob {
     float *aug;              // [B][aug_ld] row-major [in0 | in1] rows (nullable, n-tile-0): layer-1 wgrad partial operand (policy)
     float *xr4;              // [B/4][32][4] augmented input rows (nullable, n-tile-0): A operand of the Q layer-1 wgrads
     int aug_ld;
-    // phase 1: the policy evaluation whose sampled action is this job's second input
-    const float *php, *pbmu, *pbls, *peps;
+    // phase 1: the policy evaluation whose sampled action is this job's second input (its parameter copy and noise item: DFArgs::pin_pack)
+    const float *php;
     int side;                // n-tile-0 workgroups: 1 -> act0, logp0, save0   2 -> act2, and logp1 from php1
 };
 struct DFArgs {
     int njobs, tiles_n, act, Lp1, Lp2, h2;
     float scale;
     float *act0, *act2, *logp0, *logp1, *save0;
-    const float *php1, *pbmu1, *pbls1, *peps1;  // pi_main @ x2: only its log-prob is needed (actor_learner.py:62); php1 == nullptr: no such evaluation (SAC-v)
+    const float *php1;       // pi_main @ x2 (main copy, noise item 1): only its log-prob is needed (actor_learner.py:62); nullptr: no such evaluation (SAC-v)
 #ifdef DDRL_STAMPS
     unsigned long long *st;
 #endif
     int pev_pack;            // phase 1: 2 bits per job = the policy evaluation (head-partial slot) its sampled action comes from
+    int pin_pack;            // phase 1: 3 bits per job = [1:0] the noise item of that evaluation (0 eps_x, 1 eps_x2, 2 eps_t: items 5..7 of the input set), [2] it ran on the target copy
     int noise_on, n_each;    // n_each = valid rows * act (element index of a flat [3][rows * act] fill)
     int Bv;                  // valid rows: the batch; rows up to the next multiple of 32 are padding (zero inputs, no loss terms)
     uint32_t noise_seed;
@@ -126,7 +136,7 @@ struct DFArgs {
 struct DFHead {
     const float *base;  // every offset below is relative to the slab
     int tpj, tiles_m;   // tiles per job, row tiles
-    int K, Np;          // hidden1, padded hidden2 (row stride of the k4-interleaved W2)
+    int K, Np;          // hidden1, padded hidden2 (row stride of the k4-interleaved W2); the launch packs Np - hidden2 beside them
     int B, d0;          // batch, obs_dim
     int main_off, targ_off;  // the main / target parameter buffers
     int npi, perq;           // inside a buffer: the policy, then q1 at npi, q2 at npi + perq
@@ -134,6 +144,14 @@ struct DFHead {
     int x_off;               // input set: obs1; obs2 and acts follow as consecutive 256-byte aligned items
     int pack;                // 6 bits per job: [1:0] layer-1 MFMA steps - 4 (input columns + the bias column, in pairs), [2] input is obs2, [3] target copy, [5:4] network; bit 30 (phase 1): jobs 3, 4 take the stored action
 };
+
+// Policy-head biases inside a parameter buffer of the direct layout (make_layout: [W1 ; b1] block array, k4-interleaved W2, b2, Wmu, bmu,
+// Wls, bls): phase 1 of k_dfwd forms their addresses from its preloaded scalars, so that they are requested with its first loads.
+__host__ __device__ __forceinline__ int pi_bmu_off(int K, int Np, int h2, int act) {
+    const int Kp = (K + 31) & ~31;
+    return Kp * 16 + Kp * Np + Np + h2 * act;
+}
+__host__ __device__ __forceinline__ int pi_bls_off(int K, int Np, int h2, int act) { return ((pi_bmu_off(K, Np, h2, act) + act + 3) & ~3) + h2 * act; }
 
 // One 32-unit block of the K loop: layer 1 (NS MFMA steps) -> relu -> 4 * nrq layer-2 MFMA steps.
 template <int NS>
@@ -255,7 +273,7 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     __shared__ __attribute__((aligned(16))) float tr[4][32 * 36];
     __shared__ float s_wh[DFH][32];
     const int tpj = tpj_tm & 0xffff, tiles_m = (tpj_tm >> 16) & 0xfff, njobs = (unsigned)tpj_tm >> 28;
-    const int K = K_Np & 0xfff, Np = (K_Np >> 12) & 0xfff, B = B_d0 & 0xffff, d0 = (B_d0 >> 16) & 0xff, act = B_d0 >> 24;
+    const int K = K_Np & 0xfff, Np = (K_Np >> 12) & 0xfff /* bits [28:24]: Np - hidden2 */, B = B_d0 & 0xffff, d0 = (B_d0 >> 16) & 0xff, act = B_d0 >> 24;
 #ifdef DDRL_STAMPS
     unsigned long long *const st_ = a.st;
 #endif
@@ -314,8 +332,27 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int q = 0; q < DNT / 4; ++q) hv[e][c][q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (PH == 1 && !stored) {   // block-uniform
+    // ... and, in the same wave of requests, what else the row math consumes: the head biases of that evaluation's parameter copy
+    // (wave-uniform addresses: scalar loads) and its noise rows.  Both addresses need only the preloaded scalars and the launch
+    // header: the noise items follow the inputs in the input set, the biases sit at pi_bmu_off / pi_bls_off of the copy.
+    float pbm[2][4], pbl[2][4], pep[2][4];
+    const int pin = PH == 1 ? (a.pin_pack >> (3 * ji)) & 7 : 0;
+    if (PH == 1) {   // (the biases: no branch in front — scalar loads whose values stay in SGPRs until the row math; a stored tile reads the main copy's)
+        const int h2v = Np - ((K_Np >> 24) & 31), bmu_o = pi_bmu_off(K, Np, h2v, act), bls_o = pi_bls_off(K, Np, h2v, act);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float *pb = base + ((e == 0 && (pin & 4)) ? targ_off : main_off);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int cc = c < d1 ? c : 0;
+                pbm[e][c] = pb[bmu_o + cc];
+                pbl[e][c] = pb[bls_o + cc];
+            }
+        }
+    }
+    if (PH == 1 && !stored) {   // block-uniform (pep: set here, read under the same conditions)
         const long long HPq = (long long)DFH * B * DNT;
+        const int eps_ld = (B * act + 63) & ~63, eps_off = a_off + eps_ld + 2 * ((B + 63) & ~63);  // items 5..7 of the input set
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             if (e == 0 || two) {  // block-uniform
@@ -330,6 +367,11 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
                     for (int c = 2; c < 4; ++c)
 #pragma unroll
                         for (int q = 0; q < DNT / 4; ++q) hv[e][c][q] = p0[(long long)(c < d1 ? c : 2) * B * (DNT / 4) + q];
+                }
+                const float *ep = base + eps_off + (e == 0 ? (pin & 3) : 1) * eps_ld + (long long)(m0 + l31) * d1;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    pep[e][c] = ep[c < d1 ? c : 0];
                 }
             }
         }
@@ -379,7 +421,7 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
             for (int e = 0; e < 2; ++e)
     #pragma unroll
                 for (int c = 0; c < 4; ++c) {  // n-tile order; unused slots are 0
-                    float s = 0.f;
+                    float s = zero_here();
     #pragma unroll
                     for (int q = 0; q < DNT / 4; ++q) { s += hv[e][c][q].x; s += hv[e][c][q].y; s += hv[e][c][q].z; s += hv[e][c][q].w; }
                     hs[e][c] = s;
@@ -388,10 +430,9 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float o = __shfl_xor(hs[0][c], 32);
-                const int cc = c < d1 ? c : 0;
-                mu[c] = (h ? o : hs[0][c]) + jb.pbmu[cc];
-                ls[c] = (h ? hs[0][c] : o) + jb.pbls[cc];
-                ev[c] = jb.peps[(long long)(m0 + l31) * d1 + cc];
+                mu[c] = (h ? o : hs[0][c]) + pbm[0][c];
+                ls[c] = (h ? hs[0][c] : o) + pbl[0][c];
+                ev[c] = pep[0][c];
             }
             const PolRow o = policy_row(mu, ls, ev, d1, a.scale);
     #pragma unroll
@@ -419,10 +460,9 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float o2 = __shfl_xor(hs[1][c], 32);
-                    const int cc = c < d1 ? c : 0;
-                    mu[c] = (h ? o2 : hs[1][c]) + a.pbmu1[cc];
-                    ls[c] = (h ? hs[1][c] : o2) + a.pbls1[cc];
-                    ev[c] = a.peps1[(long long)(m0 + l31) * d1 + cc];
+                    mu[c] = (h ? o2 : hs[1][c]) + pbm[1][c];
+                    ls[c] = (h ? hs[1][c] : o2) + pbl[1][c];
+                    ev[c] = pep[1][c];
                 }
                 const PolRow o1 = policy_row(mu, ls, ev, d1, a.scale);
                 if (lane < 32) a.logp1[m0 + l31] = o1.logp;
@@ -528,7 +568,7 @@ static void launch_dfwd(const DFHead &d, const DFArgs &F_, hipStream_t s) {
     const int mt = PH == 0 ? dfwd_mt(d.B, F.tiles_n) : 1;
     const int tiles_m = d.B / (32 * mt), tpj = tiles_m * F.tiles_n;
     const int grid = F.njobs * tpj + ((PH == 1 && F.do_sample) ? 1 : 0);
-    const int a1 = tpj | (tiles_m << 16) | (F.njobs << 28), a2 = d.K | (d.Np << 12), a3 = d.B | (d.d0 << 16) | (F.act << 24);
+    const int a1 = tpj | (tiles_m << 16) | (F.njobs << 28), a2 = d.K | (d.Np << 12) | ((d.Np - F.h2) << 24), a3 = d.B | (d.d0 << 16) | (F.act << 24);
     if (PH == 0 && mt == 2)
         k_dfwd<0, 2><<<grid, 256, 0, s>>>(d.base, a1, a2, a3, d.pack, d.x_off, d.main_off, d.targ_off, d.npi, d.perq, d.hp_off, F);
     else
@@ -1042,6 +1082,13 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             for (int q = 0; q < DNT / 4; ++q) qv[q] = p4[q];
         }
     }
+    // ... and, right behind them, the per-row inputs and head biases of the same prologue (addresses from the launch header alone):
+    // requested after the operand groups they would queue behind those and cost the chain a round trip of their own
+    float rew = 0.f, done = 0.f, lp0 = 0.f, lp1 = 0.f, b3_1 = 0.f, b3_2 = 0.f, b3_1t = 0.f, b3_2t = 0.f;
+    if (need_q) {  // block-uniform (the launches without Q dgrads carry no such pointers)
+        if (w == 0) { rew = jobs.rew[m0 + l31]; done = jobs.done[m0 + l31]; lp0 = jobs.logp0[m0 + l31]; lp1 = jobs.logp1[m0 + l31]; }
+        b3_1 = jobs.b3q1[0]; b3_2 = jobs.b3q2[0]; b3_1t = jobs.b3q1t[0]; b3_2t = jobs.b3q2t[0];
+    }
     // generated-operand inputs: W3 along the contraction (DGRAD_Q) or dq along it (generated wgrad operand).  The same 16
     // bytes for all 32 lanes of a half-wave: a per-lane load of them would cost the fetch path as much as a tile load,
     // so the vector is staged once per workgroup in LDS (two coalesced loads per thread) and read from there in the K loop.
@@ -1119,6 +1166,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             wm4[0] = make_float4(am[0][0], am[0][1], am[0][2], am[0][3]); wl4[0] = make_float4(al[0][0], al[0][1], al[0][2], al[0][3]);
             wm4[1] = make_float4(am[1][0], am[1][1], am[1][2], am[1][3]); wl4[1] = make_float4(al[1][0], al[1][1], al[1][2], al[1][3]);
         }
+        DST(kid, 6);   // (stamps 6 - 8: every request of the generated operand issued / row math done / head kernels staged)
         float ga[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int q = 0; q < 16; ++q)
@@ -1137,6 +1185,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             pdm[c] = c < act ? du : 0.f;
             pdl[c] = c < act ? dl * (11.0f * (1.0f - tt * tt)) : 0.f;
         }
+        DST(kid, 7);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int k = tid + 256 * u;
@@ -1145,6 +1194,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
                 else { *reinterpret_cast<float4 *>(&s_w8[k * 8]) = wm4[u]; *reinterpret_cast<float4 *>(&s_w8[k * 8 + 4]) = wl4[u]; }
             }
         }
+        DST(kid, 8);
     }
     const bool agen2 = agen && jb.nact <= 2;   // block-uniform
     ktouch(kl);
@@ -1218,10 +1268,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     if (has_gen && !need_q) __syncthreads();
     if (type == DG_DGRAD_Q) {
         if (need_q) {
-            float rew = 0.f, done = 0.f, lp0 = 0.f, lp1 = 0.f;
-            if (w == 0) { rew = jobs.rew[m0 + l31]; done = jobs.done[m0 + l31]; lp0 = jobs.logp0[m0 + l31]; lp1 = jobs.logp1[m0 + l31]; }
-            const float b3_1 = jobs.b3q1[0], b3_2 = jobs.b3q2[0], b3_1t = jobs.b3q1t[0], b3_2t = jobs.b3q2t[0];
-            float qsum = 0.f;
+            float qsum = zero_here();
 #pragma unroll
             for (int q = 0; q < DNT / 4; ++q) { qsum += qv[q].x; qsum += qv[q].y; qsum += qv[q].z; qsum += qv[q].w; }
             s_q[tid >> 5][tid & 31] = qsum;

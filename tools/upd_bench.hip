@@ -99,7 +99,7 @@ int main(int argc, char **argv) {
         if (J) {
             const int nwgs = J->total_tiles;
             for (int ji = 0; ji < J->njobs; ++ji) {
-                double ssum = 0, esum = 0, emax = 0, csum = 0, cmax = 0, psum[6] = {0}; int n = 0;
+                double ssum = 0, esum = 0, emax = 0, csum = 0, cmax = 0, psum[6] = {0}, gsum[4] = {0}; int n = 0, ngen = 0;
                 for (int b = 0; b < nwgs; ++b) {
                     const int q = nwgs >> 3, r = nwgs & 7, x = b & 7;
                     const int t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
@@ -109,9 +109,13 @@ int main(int argc, char **argv) {
                     ++n; ssum += (p[14] - rmin) / 100.0; const double e = (p[15] - rmin) / 100.0; esum += e; emax = std::max(emax, e);
                     const double c = (double)(p[5] - p[0]); csum += c; cmax = std::max(cmax, c);
                     for (int i = 1; i < 6; ++i) if (p[i] && p[i - 1]) psum[i] += (double)(p[i] - p[i - 1]);
+                    if (p[6] && p[7] && p[8]) {   // tiles with a generated A operand: the parts of their "loads" span
+                        ++ngen; gsum[0] += (double)(p[6] - p[0]); gsum[1] += (double)(p[7] - p[6]); gsum[2] += (double)(p[8] - p[7]); gsum[3] += (double)(p[1] - p[8]);
+                    }
                 }
                 if (n) printf("      job %d type %d M %4d N %4d K %4d: %3d wgs  start +%.2f us  end mean +%.2f max +%.2f us | cycles mean %.0f max %.0f | loads %.0f prol %.0f kloop %.0f bar %.0f epi %.0f\n", ji, J->job[ji].type,
                               J->job[ji].M, J->job[ji].N, J->job[ji].K, n, ssum / n, esum / n, emax, csum / n, cmax, psum[1] / n, psum[2] / n, psum[3] / n, psum[4] / n, psum[5] / n);
+                if (ngen) printf("            generated operand: requests issued %.0f  arrived + row math %.0f  head kernels staged %.0f  to loads-issued %.0f\n", gsum[0] / ngen, gsum[1] / ngen, gsum[2] / ngen, gsum[3] / ngen);
             }
         }
     }
