@@ -283,9 +283,28 @@ class Learner(_Net):
             raise RuntimeError("train / compute_gradients with a caller's batch while a dp_stepper holds a batch drawn ahead: end its "
                                "sequence with grads(last=True) first")
 
+    @staticmethod
+    def _is_window_batch(batch):
+        """The n-step driver's batch (algos/sac1/sac_ray.py:72-80): obs[B, Ln + 1, ...], acts[B, Ln, ...], rews[B, Ln], done[B, Ln]."""
+        return all(k in batch for k in ("obs", "acts", "rews", "done")) and "obs1" not in batch and np.ndim(batch["obs"]) >= 3
+
+    def _fold_windows(self, batch):
+        """A window batch (NumPy arrays or device tensors) as the learner's feed: the n-step fold on the device (ddrl_nstep_fold,
+        include/ddrl.h) with cfg.gamma — obs1 = o[0], obs2 = o[Ln], acts = a[0], rews = sum_k c_k r[k], done = 1 - prod_k (1 - d[k])."""
+        B, o, a = self.cfg.batch, self.cfg.obs_dim, self.cfg.act_dim
+        Ln = int(np.shape(batch["rews"])[-1])
+        w = [self._dev(batch[k], (B, n)) for k, n in (("obs", (Ln + 1) * o), ("acts", Ln * a), ("rews", Ln), ("done", Ln))]
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+        out = dict(obs1=e(B, o), obs2=e(B, o), acts=e(B, a), rews=e(B), done=e(B))
+        _lib.check(self._lib.ddrl_nstep_fold(*[_lib.dptr(t) for t in w], B, Ln, o, a, float(self.cfg.gamma),
+                                             *[_lib.dptr(out[k]) for k in ("obs1", "obs2", "acts", "rews", "done")], _lib.stream_ptr()))
+        return out
+
     def _args(self, batch, eps, outs):
         B, a = self.cfg.batch, self.cfg.act_dim
         self._guard_stepper()
+        if self._is_window_batch(batch):
+            batch = self._fold_windows(batch)
         if all(isinstance(batch[k], np.ndarray) for k in ("obs1", "obs2", "acts", "rews", "done")):
             if eps is None and not outs and getattr(self, "_fast_step", False):
                 if self._host_fast(batch):
@@ -325,7 +344,11 @@ class Learner(_Net):
 
     def train(self, batch, eps=None, return_outputs=False):
         """One sess.run(step_ops) (actor_learner.py:135-142).  `batch` holds obs1/obs2/acts/rews/done
-        as NumPy arrays (the reference's feed) or device tensors (no host round trip)."""
+        as NumPy arrays (the reference's feed) or device tensors (no host round trip) — or obs/acts/rews/done WINDOWS of the n-step
+        driver (sac_ray.py:72-80; a 3-D obs), which are folded into that feed on the device first (_fold_windows).  An integral
+        second positional argument is that driver's update count (sac_ray.py:171 `agent.train(batch, cnt)`), not noise: ignored."""
+        if isinstance(eps, (int, np.integer)) and not isinstance(eps, bool):
+            eps = None
         self._fast_step = True                    # train(): a host batch may take the one-call path (copy + noise + update)
         try:
             keep, ptrs, outs = self._args(batch, eps, return_outputs)
@@ -346,6 +369,8 @@ class Learner(_Net):
             self._in0 = [bufs[i] for i in range(8)]
         self._guard_stepper()
         B, a = self.cfg.batch, self.cfg.act_dim
+        if self._is_window_batch(batch):
+            batch = self._fold_windows(batch)
         keep = [self._dev(batch[k], s) for k, s in (("obs1", (B, -1)), ("obs2", (B, -1)), ("acts", (B, a)), ("rews", (B,)), ("done", (B,)))]
         _lib.check(self._lib.ddrl_sac1_fill_noise(self._h, self._noise_seed, _lib.stream_ptr()))
         return keep, [_lib.dptr(t) for t in keep] + self._in0[5:8] + [None, None, None, None]

@@ -17,6 +17,9 @@
 
 // internal (sac1.hip): put the learner's double-buffered optimizer state on copy 0
 int ddrl_sac1_internal_opt_sync(ddrl_sac1_t *h, void *stream);
+// internal (sac1.hip): sample_batch into input set `set` of the learner — ddrl_replay_sample for a transition ring, ddrl_replay_sample_nstep
+// with the learner's gamma for an n-step window ring (algos/sac1/sac_ray.py:40-51)
+int ddrl_sac1_internal_sample_into(ddrl_sac1_t *h, ddrl_replay_t *replay, int set, void *stream);
 
 struct ddrl_loop {
     ddrl_sac1_t *learner;
@@ -31,8 +34,7 @@ struct ddrl_loop {
 };
 
 static int sample_into(ddrl_loop *h, int set, void *stream) {
-    float **b = h->buf[set];
-    return ddrl_replay_sample(h->replay, h->batch, b[0], b[1], b[2], b[3], b[4], nullptr, stream);
+    return ddrl_sac1_internal_sample_into(h->learner, h->replay, set, stream);   // (h->buf[set] is the learner's input set `set`)
 }
 
 static int update_from(ddrl_loop *h, int set, void *stream) {

@@ -201,6 +201,23 @@ __global__ void __launch_bounds__(640) k_sample_wide(RingState *st, RingPtrs rin
     sample_block<640>(st, ring, out, B, idx_out, 0);
 }
 
+// n-step fold of whole windows that already lie on the device in batch order (the host `Cache` path: a sampled window batch), and the
+// fold-gather for indices drawn by a launch of their own (batches beyond the one-workgroup sampler): grid-stride forms of the
+// sampler's nstep_fold_gather.
+struct FoldSrc {
+    const float *o, *a, *r, *d;
+    int Ln, od, ad;
+    float gamma;
+};
+__global__ void __launch_bounds__(256) k_nstep_fold(FoldSrc w, BatchPtrs out, int B) {
+    nstep_fold_gather(w.o, w.a, w.r, w.d, w.Ln, w.od, w.ad, w.gamma, out.a[0], out.a[1], out.a[2], out.a[3], out.a[4], (unsigned)B,
+                      [](unsigned b) { return b; }, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u);
+}
+__global__ void __launch_bounds__(256) k_nstep_gather(FoldSrc w, BatchPtrs out, const long long *__restrict__ idx, int B) {
+    nstep_fold_gather(w.o, w.a, w.r, w.d, w.Ln, w.od, w.ad, w.gamma, out.a[0], out.a[1], out.a[2], out.a[3], out.a[4], (unsigned)B,
+                      [=](unsigned b) { return idx[b]; }, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u);
+}
+
 // Stand-alone gather for large rows (the dqn pixel shape: 2 x 112 896 B per index): one
 // workgroup per (row, array) so that >= B * n_arr workgroups fill the chip; each lane keeps four
 // independent 16-B loads in flight (HBM-bound random-row gather).
@@ -341,6 +358,10 @@ static int refresh_counts(ddrl_replay *h, hipStream_t s) {
             ddrl::set_error("high <= 0");  // the sampler drew from an empty ring (the reference's ValueError)
             return DDRL_ERR_EMPTY_BUFFER;
         }
+        if (tmp.error == DDRL_ERR_UNSUPPORTED) {
+            ddrl::set_error("a feed plan is attached to an n-step window ring: fed batches are not built for window rings (that update trained on a stale input set)");
+            return DDRL_ERR_UNSUPPORTED;
+        }
         if (tmp.error == DDRL_ERR_NOT_REPRESENTABLE) {
             ddrl::set_error("a value stored into a compact (uint8) ring array was not an integer in [0, 255]: the ring holds a clamped/truncated value there");
             return DDRL_ERR_NOT_REPRESENTABLE;
@@ -364,6 +385,25 @@ static bool has_compact(const ddrl_replay *h) {
 bool ddrl_replay_can_fuse(ddrl_replay_t *h, int64_t batch) {
     const long long bytes = batch * row_floats(h) * (long long)sizeof(float);
     return batch <= MAX_FUSED_BATCH && bytes <= MAX_FUSED_BYTES && (h->h_size > 0 || h->feed_on);
+}
+// {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]}, all float32; obs_dim / act_dim <= 0: whatever the widths give
+bool ddrl_replay_is_window_ring(ddrl_replay_t *h, int obs_dim, int act_dim) {
+    const RingPtrs &r = h->ring;
+    if (r.n_arr != 4 || has_compact(h)) return false;
+    const int Ln = r.w[2];
+    if (Ln < 1 || r.w[3] != Ln || r.w[0] % (Ln + 1) != 0 || r.w[1] % Ln != 0) return false;
+    return (obs_dim <= 0 || r.w[0] == (Ln + 1) * obs_dim) && (act_dim <= 0 || r.w[1] == Ln * act_dim);
+}
+ddrl_replay_dev::SamplerView ddrl_replay_sampler_view_nstep(ddrl_replay_t *h, float gamma) {
+    ddrl_replay_dev::SamplerView v{h->state, h->ring, h->device};
+    v.ring.fold = 1;
+    v.ring.gamma = gamma;
+    return v;
+}
+bool ddrl_replay_can_fuse_nstep(ddrl_replay_t *h, int64_t batch) {
+    const RingPtrs &r = h->ring;
+    const long long Ln = r.w[2], folded = 2 * (r.w[0] / (Ln + 1)) + r.w[1] / Ln + 2 * Ln;   // floats read per accepted index
+    return batch <= MAX_FUSED_BATCH && batch * folded * (long long)sizeof(float) <= MAX_FUSED_BYTES && h->h_size > 0 && !h->feed_on;
 }
 void ddrl_replay_note_sample(ddrl_replay_t *h) { h->h_samples += h->ring.samples_inc; }
 void ddrl_replay_note_store(ddrl_replay_t *h, long long n) {  // host mirror bookkeeping for n stores issued by another kernel (ddrl_rollout_step)
@@ -564,6 +604,76 @@ int ddrl_replay_sample_ex(ddrl_replay_t *h, int64_t batch, float *const *out_h, 
     DDRL_LAUNCH_CHECK();
     h->h_samples += h->ring.samples_inc;
     if (!fuse) return launch_gather(h, idx, batch, out, s);
+    return DDRL_OK;
+}
+
+static int fold_grid(int64_t batch, int od) {
+    long long blocks = (batch * ((od & 3) == 0 ? od / 4 : od) + 255) / 256;
+    return (int)(blocks > 4096 ? 4096 : (blocks < 1 ? 1 : blocks));
+}
+
+int ddrl_nstep_fold(const float *obs_w_d, const float *acts_w_d, const float *rews_w_d, const float *done_w_d, int64_t batch, int32_t Ln,
+                    int32_t obs_dim, int32_t act_dim, float gamma, float *obs1_d, float *obs2_d, float *acts_d, float *rews_d, float *done_d,
+                    void *stream) {
+    DDRL_REQUIRE(obs_w_d && acts_w_d && rews_w_d && done_w_d && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
+    DDRL_REQUIRE(Ln >= 1 && obs_dim >= 1 && act_dim >= 1, "Ln, obs_dim, act_dim must be positive");
+    DDRL_REQUIRE(batch > 0 && batch <= (1 << 24) && batch * (obs_dim > act_dim ? obs_dim : act_dim) < 0x7fffffffll,
+                 "batch must be in [1, 2^24] with batch * max(obs_dim, act_dim) < 2^31");
+    const FoldSrc w{obs_w_d, acts_w_d, rews_w_d, done_w_d, Ln, obs_dim, act_dim, gamma};
+    const BatchPtrs out{{obs1_d, obs2_d, acts_d, rews_d, done_d, nullptr}};
+    k_nstep_fold<<<fold_grid(batch, obs_dim), 256, 0, ddrl::as_stream(stream)>>>(w, out, (int)batch);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float *obs1_d, float *obs2_d, float *acts_d, float *rews_d,
+                             float *done_d, int64_t *idx_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
+    DDRL_REQUIRE(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
+    if (!ddrl_replay_is_window_ring(h, 0, 0)) {
+        ddrl::set_error("ddrl_replay_sample_nstep needs an n-step window ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (h->feed_on) {
+        ddrl::set_error("a feed plan is attached to this ring: fed batches are not built for n-step window rings");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    const int Ln = h->ring.w[2], od = h->ring.w[0] / (Ln + 1), ad = h->ring.w[1] / Ln;
+    DDRL_REQUIRE(batch * (od > ad ? od : ad) < 0x7fffffffll, "batch * max(obs_dim, act_dim) must be < 2^31");
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    if (h->h_size <= 0 || h->h_dirty) {
+        int rc = refresh_counts(h, s);
+        if (rc != DDRL_OK) return rc;
+        if (h->h_size <= 0) {
+            ddrl::set_error("high <= 0");  // message of the reference's ValueError
+            return DDRL_ERR_EMPTY_BUFFER;
+        }
+    }
+    const BatchPtrs out{{obs1_d, obs2_d, acts_d, rews_d, done_d, nullptr}};
+    long long *idx = reinterpret_cast<long long *>(idx_d);
+    if (batch <= MAX_FUSED_BATCH) {   // draw + fold-gather in the one workgroup
+        const SamplerView v = ddrl_replay_sampler_view_nstep(h, gamma);
+        k_sample<<<1, SAMPLE_THREADS, 0, s>>>(v.state, v.ring, out, (int)batch, idx, 1);
+        DDRL_LAUNCH_CHECK();
+        h->h_samples += h->ring.samples_inc;
+        return DDRL_OK;
+    }
+    if (!idx) {
+        if (batch > h->idx_cap) {
+            DDRL_HIP_CHECK(hipStreamSynchronize(s));
+            (void)hipFree(h->idx_buf);
+            h->idx_cap = batch;
+            DDRL_HIP_CHECK(hipMalloc(&h->idx_buf, h->idx_cap * sizeof(long long)));
+        }
+        idx = h->idx_buf;
+    }
+    k_sample_wide<<<1, 640, 0, s>>>(h->state, h->ring, out, (int)batch, idx);
+    DDRL_LAUNCH_CHECK();
+    h->h_samples += h->ring.samples_inc;
+    const FoldSrc w{h->ring.a[0], h->ring.a[1], h->ring.a[2], h->ring.a[3], Ln, od, ad, gamma};
+    k_nstep_gather<<<fold_grid(batch, od), 256, 0, s>>>(w, out, idx, (int)batch);
+    DDRL_LAUNCH_CHECK();
     return DDRL_OK;
 }
 

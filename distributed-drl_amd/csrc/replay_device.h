@@ -45,14 +45,21 @@ constexpr int MAX_ARRAYS = 6;
 // kind[j] = 1: array j is stored as uint8 (the opt-in COMPACT ring for integer-valued pixel observations, DDRL_REPLAY_U8_OBS):
 // a[j] then points at capacity * w[j] BYTES.  The surface stays float32 — store converts (a value that is not an integer in
 // [0, 255] sets the sticky DDRL_ERR_NOT_REPRESENTABLE), every gather converts back: bit-identical to the float32 ring on such data.
+// fold = 1 (a sampler's VIEW of a window ring, never the handle's own description): the gather behind the index draw is the n-step
+// fold-gather below — five learner arrays out of four window arrays, backup discount `gamma`.  Both fields sit in what was padding:
+// the struct, and every kernel argument block that embeds it, keeps its size and offsets.
 struct RingPtrs {
     float *a[MAX_ARRAYS];
     int w[MAX_ARRAYS];
     unsigned char kind[MAX_ARRAYS];
+    unsigned char fold;
     int n_arr;
+    float gamma;
     long long capacity;
     long long steps_inc, samples_inc;  // counter increments per store / per sample (sac_ray.py:68,75: num_buffers)
 };
+
+static_assert(sizeof(RingPtrs) == 112, "RingPtrs is embedded in kernel argument blocks: keep its size");
 
 struct BatchPtrs {
     float *a[MAX_ARRAYS];
@@ -117,6 +124,58 @@ __device__ __forceinline__ void gather_rows(const float *__restrict__ ring, floa
     }
 }
 
+// The n-step fold: window row i = o[0..Ln], a[0..Ln-1], r[0..Ln-1], d[0..Ln-1] (algos/sac1/sac_ray.py:40-51) becomes the transition
+//   obs1 = o[0]   obs2 = o[Ln]   acts = a[0]   rews = sum_k c_k r[k]   done = 1 - prod_k (1 - d[k]),   c_0 = 1, c_{k+1} = c_k (1 - d[k]) gamma
+// so that the update's backup rews + gamma (1 - done) v(obs2) is the n-step return cut at the first terminal.  float32, every product and
+// sum rounded on its own (no contraction: the explicit _rn forms) — a NumPy float32 loop gives the same bits.
+__device__ __forceinline__ void nstep_fold_row(const float *__restrict__ r, const float *__restrict__ d, int Ln, float gamma, float &rew, float &done) {
+    float c = 1.f, R = 0.f, g = 1.f;
+    for (int k = 0; k < Ln; ++k) {
+        R = __fadd_rn(R, __fmul_rn(c, r[k]));
+        g = __fmul_rn(c, __fsub_rn(1.f, d[k]));
+        c = __fmul_rn(g, gamma);
+    }
+    rew = R;
+    done = __fsub_rn(1.f, g);
+}
+
+// Fold-gather of B window rows (row of batch element b: idx_of(b)) into the five learner arrays: per row only o[0], o[Ln], a[0] and the
+// 2 Ln reward / done scalars are read, not the whole window.  `tid` of `nthreads` lanes: one workgroup (the sampler) or a grid.
+// B * max(od, ad) < 2^31 (host-checked for the stand-alone launches; the one-workgroup sampler has B <= MAX_FUSED_BATCH).
+template <class Idx>
+__device__ __forceinline__ void nstep_fold_gather(const float *__restrict__ ow, const float *__restrict__ aw, const float *__restrict__ rw,
+                                                  const float *__restrict__ dw, int Ln, int od, int ad, float gamma, float *__restrict__ obs1,
+                                                  float *__restrict__ obs2, float *__restrict__ acts, float *__restrict__ rews,
+                                                  float *__restrict__ done, unsigned B, Idx idx_of, unsigned tid, unsigned nthreads) {
+    if ((od & 3) == 0 && aligned16(ow, obs1) && aligned16(ow, obs2)) {
+        const unsigned o4 = (unsigned)od >> 2;
+        const long long W4 = (long long)(Ln + 1) * o4;
+        const float4 *w4 = reinterpret_cast<const float4 *>(ow);
+        for (unsigned e = tid; e < B * o4; e += nthreads) {
+            const unsigned b = e / o4, c = e - b * o4;
+            const float4 *row = w4 + (long long)idx_of(b) * W4;
+            reinterpret_cast<float4 *>(obs1)[e] = row[c];
+            reinterpret_cast<float4 *>(obs2)[e] = row[(unsigned)Ln * o4 + c];
+        }
+    } else {
+        const long long W = (long long)(Ln + 1) * od;
+        for (unsigned e = tid; e < B * (unsigned)od; e += nthreads) {
+            const unsigned b = e / (unsigned)od, c = e - b * (unsigned)od;
+            const float *row = ow + (long long)idx_of(b) * W;
+            obs1[e] = row[c];
+            obs2[e] = row[(unsigned)Ln * (unsigned)od + c];
+        }
+    }
+    for (unsigned e = tid; e < B * (unsigned)ad; e += nthreads) {
+        const unsigned b = e / (unsigned)ad, c = e - b * (unsigned)ad;
+        acts[e] = aw[(long long)idx_of(b) * Ln * ad + c];
+    }
+    for (unsigned b = tid; b < B; b += nthreads) {
+        const long long i = (long long)idx_of(b) * Ln;
+        nstep_fold_row(rw + i, dw + i, Ln, gamma, rews[b], done[b]);
+    }
+}
+
 // idxs = np.random.randint(0, size, B) (masked rejection on 32-bit draws), optionally fused with
 // the five gathers when the batch is small (the SAC1 shape: 256 x 80 B).  One workgroup: the
 // accept/reject compaction is a wave ballot + prefix count, the stream position advances by
@@ -136,6 +195,10 @@ __device__ __forceinline__ void sample_block(RingState *st, const RingPtrs &ring
     __shared__ unsigned s_idx[MAX_FUSED_BATCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (fuse_gather && st->feed.plan != nullptr) {
+        if (ring.fold) {  // fed batches are transition-shaped blocks another rank drew: not built for window rings — nothing is copied
+            if (tid == 0) st->error = DDRL_ERR_UNSUPPORTED;
+            return;
+        }
         const int pos = st->feed.pos;
         const int p = pos < st->feed.len ? st->feed.plan[pos] : -1;
         __syncthreads();  // every lane has read the position
@@ -230,6 +293,12 @@ __device__ __forceinline__ void sample_block(RingState *st, const RingPtrs &ring
     if (tid == 0) st->sample_times += ring.samples_inc;
     if (fuse_gather) {
         __syncthreads();
+        if (ring.fold) {  // a window ring {o, a, r, d} seen by a learner: w[3] = Ln, w[0] = (Ln + 1) obs, w[1] = Ln act (host-checked)
+            const int Ln = ring.w[3];
+            nstep_fold_gather(ring.a[0], ring.a[1], ring.a[2], ring.a[3], Ln, ring.w[0] / (Ln + 1), ring.w[1] / Ln, ring.gamma, out.a[0], out.a[1],
+                              out.a[2], out.a[3], out.a[4], (unsigned)B, [&](unsigned b) { return s_idx[b]; }, (unsigned)tid, (unsigned)SAMPLE_THREADS);
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < MAX_ARRAYS; ++j)
             if (j < ring.n_arr) gather_rows(ring.a[j], out.a[j], s_idx, B, ring.w[j], tid, SAMPLE_THREADS, ring.kind[j]);
@@ -249,5 +318,10 @@ struct SamplerView {
 // defined in replay.hip
 ddrl_replay_dev::SamplerView ddrl_replay_sampler_view(ddrl_replay_t *h);
 bool ddrl_replay_can_fuse(ddrl_replay_t *h, int64_t batch);
+// n-step window rings (algos/sac1/sac_ray.py:40-51): is this ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays; the sampler's
+// view of it in fold-gather mode; can_fuse for the folded batch (the bytes the fold-gather moves, not the whole windows)
+bool ddrl_replay_is_window_ring(ddrl_replay_t *h, int obs_dim, int act_dim);
+ddrl_replay_dev::SamplerView ddrl_replay_sampler_view_nstep(ddrl_replay_t *h, float gamma);
+bool ddrl_replay_can_fuse_nstep(ddrl_replay_t *h, int64_t batch);
 void ddrl_replay_note_sample(ddrl_replay_t *h);  // host mirror bookkeeping for a sample issued by another kernel
 void ddrl_replay_note_store(ddrl_replay_t *h, long long n);  // ... for n stores issued by another kernel

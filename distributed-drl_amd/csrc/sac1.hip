@@ -1951,18 +1951,55 @@ int ddrl_sac1_apply_grads(ddrl_sac1_t *h, void *stream) {
     return launch_apply(h, ddrl::as_stream(stream));
 }
 
+}  // extern "C"
+
+// The sampler's view of `replay` for this learner: a transition ring of the learner's shapes as it is; an n-step window ring
+// (algos/sac1/sac_ray.py:40-51) in fold-gather mode with the learner's gamma — its sampler hands the update kernels the folded
+// transition (include/ddrl.h: n-step fold), so nothing downstream of the input set knows the difference.
+static int learner_sampler_view(ddrl_sac1 *h, ddrl_replay_t *replay, ddrl_replay_dev::SamplerView *v, bool *nstep) {
+    *v = ddrl_replay_sampler_view(replay);
+    *nstep = false;
+    if (v->ring.n_arr == 5 && v->ring.w[0] == h->cfg.obs_dim && v->ring.w[1] == h->cfg.obs_dim && v->ring.w[2] == h->cfg.act_dim &&
+        v->ring.w[3] == 1 && v->ring.w[4] == 1)
+        return DDRL_OK;
+    DDRL_REQUIRE(ddrl_replay_is_window_ring(replay, h->cfg.obs_dim, h->cfg.act_dim),
+                 "replay row shape differs from the learner's (obs1, obs2, acts, rews, done) and is no n-step window ring of its obs / act widths");
+    *v = ddrl_replay_sampler_view_nstep(replay, (float)h->cfg.gamma);
+    *nstep = true;
+    return DDRL_OK;
+}
+static bool learner_can_fuse(ddrl_sac1 *h, ddrl_replay_t *replay, bool nstep) {
+    return nstep ? ddrl_replay_can_fuse_nstep(replay, h->cfg.batch) : ddrl_replay_can_fuse(replay, h->cfg.batch);
+}
+// sample_batch into input set `set` as a launch of its own
+static int learner_sample_launch(ddrl_sac1 *h, ddrl_replay_t *replay, bool nstep, int set, void *stream) {
+    float **b = h->in[set];
+    if (nstep) return ddrl_replay_sample_nstep(replay, h->cfg.batch, (float)h->cfg.gamma, b[0], b[1], b[2], b[3], b[4], nullptr, stream);
+    return ddrl_replay_sample(replay, h->cfg.batch, b[0], b[1], b[2], b[3], b[4], nullptr, stream);
+}
+// Internal (loop.hip): the loop's own draws (the priming draw of a graph, eager updates) into input set `set`
+int ddrl_sac1_internal_sample_into(ddrl_sac1 *h, ddrl_replay_t *replay, int set, void *stream) {
+    DDRL_REQUIRE(h != nullptr && replay != nullptr && (set == 0 || set == 1), "NULL pointer or set not in {0,1}");
+    ddrl_replay_dev::SamplerView v;
+    bool nstep;
+    const int rc = learner_sampler_view(h, replay, &v, &nstep);
+    if (rc != DDRL_OK) return rc;
+    return learner_sample_launch(h, replay, nstep, set, stream);
+}
+
+extern "C" {
+
 int ddrl_sac1_apply_grads_and_sample(ddrl_sac1_t *h, ddrl_replay_t *replay, int set, void *stream) {
     DDRL_REQUIRE(h != nullptr && replay != nullptr && (set == 0 || set == 1), "NULL pointer or set not in {0,1}");
     ddrl::DeviceGuard g(h->device);
-    const ddrl_replay_dev::SamplerView v = ddrl_replay_sampler_view(replay);
-    DDRL_REQUIRE(v.ring.n_arr == 5 && v.ring.w[0] == h->cfg.obs_dim && v.ring.w[1] == h->cfg.obs_dim && v.ring.w[2] == h->cfg.act_dim &&
-                     v.ring.w[3] == 1 && v.ring.w[4] == 1,
-                 "replay row shape differs from the learner's (obs1, obs2, acts, rews, done)");
-    if (!ddrl_replay_can_fuse(replay, h->cfg.batch)) {  // empty ring (host view) or rows too large for the one-workgroup sampler
-        float **b = h->in[set];
+    ddrl_replay_dev::SamplerView v;
+    bool nstep;
+    const int vrc = learner_sampler_view(h, replay, &v, &nstep);
+    if (vrc != DDRL_OK) return vrc;
+    if (!learner_can_fuse(h, replay, nstep)) {  // empty ring (host view) or rows too large for the one-workgroup sampler
         int rc = launch_apply(h, ddrl::as_stream(stream));
         if (rc != DDRL_OK) return rc;
-        return ddrl_replay_sample(replay, h->cfg.batch, b[0], b[1], b[2], b[3], b[4], nullptr, stream);
+        return learner_sample_launch(h, replay, nstep, set, stream);
     }
     h->ad.do_sample = 1;
     h->ad.sample_batch = h->cfg.batch;
@@ -2131,16 +2168,15 @@ int ddrl_sac1_compute_grads_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t
                  "NULL pointer, or input sets not {0,1} / not distinct");
     ddrl::DeviceGuard g(h->device);
     float **b = h->in[set_in];
-    if (!h->fused || !ddrl_replay_can_fuse(replay, h->cfg.batch)) {  // generic kernels: the sampler as its own launch
+    ddrl_replay_dev::SamplerView v;
+    bool nstep;
+    const int vrc = learner_sampler_view(h, replay, &v, &nstep);
+    if (vrc != DDRL_OK) return vrc;
+    if (!h->fused || !learner_can_fuse(h, replay, nstep)) {  // generic kernels: the sampler as its own launch
         int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
         if (rc != DDRL_OK) return rc;
-        float **o = h->in[set_out];
-        return ddrl_replay_sample(replay, h->cfg.batch, o[0], o[1], o[2], o[3], o[4], nullptr, stream);
+        return learner_sample_launch(h, replay, nstep, set_out, stream);
     }
-    const ddrl_replay_dev::SamplerView v = ddrl_replay_sampler_view(replay);
-    DDRL_REQUIRE(v.ring.n_arr == 5 && v.ring.w[0] == h->cfg.obs_dim && v.ring.w[1] == h->cfg.obs_dim && v.ring.w[2] == h->cfg.act_dim &&
-                     v.ring.w[3] == 1 && v.ring.w[4] == 1,
-                 "replay row shape differs from the learner's (obs1, obs2, acts, rews, done)");
     h->sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
     const int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
     h->sample_armed = false;
@@ -2153,15 +2189,15 @@ int ddrl_sac1_step_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t *replay,
                  "NULL pointer, or input sets not {0,1} / not distinct");
     ddrl::DeviceGuard g(h->device);
     float **b = h->in[set_in];
-    if (!h->fused || !ddrl_replay_can_fuse(replay, h->cfg.batch)) {  // generic kernels: sampler beside the Adam kernel (or on its own)
+    ddrl_replay_dev::SamplerView v;
+    bool nstep;
+    const int vrc = learner_sampler_view(h, replay, &v, &nstep);
+    if (vrc != DDRL_OK) return vrc;
+    if (!h->fused || !learner_can_fuse(h, replay, nstep)) {  // generic kernels: sampler beside the Adam kernel (or on its own)
         int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
         if (rc != DDRL_OK) return rc;
         return ddrl_sac1_apply_grads_and_sample(h, replay, set_out, stream);
     }
-    const ddrl_replay_dev::SamplerView v = ddrl_replay_sampler_view(replay);
-    DDRL_REQUIRE(v.ring.n_arr == 5 && v.ring.w[0] == h->cfg.obs_dim && v.ring.w[1] == h->cfg.obs_dim && v.ring.w[2] == h->cfg.act_dim &&
-                     v.ring.w[3] == 1 && v.ring.w[4] == 1,
-                 "replay row shape differs from the learner's (obs1, obs2, acts, rews, done)");
     h->sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
     const int rc = ddrl_sac1_step(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
     h->sample_armed = false;

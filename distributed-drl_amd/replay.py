@@ -513,6 +513,30 @@ class ReplayBufferNStep:
     def sample_batch(self):
         return {k: v.cpu().numpy() for k, v in self.sample_batch_device().items()}
 
+    def gather_device(self, idx):
+        """The four fancy-index gathers of sample_batch (sac_ray.py:76-80) for caller-supplied int64 device indices: whole windows."""
+        idx = idx.to(device=self.device, dtype=torch.int64).contiguous()
+        B = int(idx.numel())
+        outs = [torch.empty((B,) + s, dtype=torch.float32, device=self.device) for s in self.shapes]
+        ptrs = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in outs])
+        _lib.check(self._lib.ddrl_replay_gather_ex(self._h, _lib.dptr(idx), B, ptrs, _lib.stream_ptr()))
+        return dict(zip(self.names, outs))
+
+    def sample_nstep_device(self, batch_size=None, gamma=None, with_indices=False):
+        """sample_batch folded into the learner's feed on the way out (ddrl_replay_sample_nstep): dict(obs1, obs2, acts, rews, done) of
+        device tensors — obs1 = o[0], obs2 = o[Ln], acts = a[0], rews / done the n-step fold (include/ddrl.h) with discount `gamma`
+        (default opt.gamma).  Same index stream and counters as sample_batch_device; only the folded columns of a window are read."""
+        B = int(self.opt.batch_size if batch_size is None else batch_size)
+        g = float(self.opt.gamma if gamma is None else gamma)
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+        out = dict(obs1=e((B,) + self.obs_shape), obs2=e((B,) + self.obs_shape), acts=e((B,) + self.act_shape), rews=e(B), done=e(B))
+        idx = torch.empty(B, dtype=torch.int64, device=self.device) if with_indices else None
+        _lib.check(self._lib.ddrl_replay_sample_nstep(self._h, B, g, *[_lib.dptr(out[k]) for k in ("obs1", "obs2", "acts", "rews", "done")],
+                                                      _lib.dptr(idx), _lib.stream_ptr()))
+        if with_indices:
+            out["idxs"] = idx
+        return out
+
     def get_counts(self):
         c = [ctypes.c_int64() for _ in range(4)]
         _lib.check(self._lib.ddrl_replay_counts(self._h, *[ctypes.byref(x) for x in c], _lib.stream_ptr()))

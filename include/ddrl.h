@@ -152,6 +152,29 @@ int ddrl_replay_set_feed(ddrl_replay_t *h, const int32_t *plan_d, int32_t plan_l
 int ddrl_replay_take_error(ddrl_replay_t *h, int32_t *out_d, void *stream);
 int ddrl_replay_buffers_ex(ddrl_replay_t *h, float **arrays_h, int32_t *widths_h, int32_t *n_arrays_h);
 
+/* ---- n-step fold: a window of the n-step buffer (algos/sac1/sac_ray.py:40-51, drawn by sample_batch at sac_ray.py:72-80) as ONE
+ * transition of the learner's feed (algos/sac1/actor_learner.py:135-142).  The reference's learner never consumes the windows its
+ * driver draws (sac_ray.py:171 hands them to a train() that reads obs1 / obs2), so this fold is THIS library's definition of the
+ * n-step backup.  Window row = o[0..Ln], a[0..Ln-1], r[0..Ln-1], d[0..Ln-1]:
+ *     obs1 = o[0]   obs2 = o[Ln]   acts = a[0]
+ *     c = 1, R = 0;  for k in 0..Ln-1:  R = R + c * r[k];  g = c * (1 - d[k]);  c = g * gamma
+ *     rews = R      done = 1 - g
+ * in float32 with every product and sum rounded on its own (no fused multiply-add).  The update's backup
+ * rews + gamma * (1 - done) * v(obs2) is then sum_k gamma^k r[k] + gamma^Ln prod_j (1 - d[j]) v(o[Ln]), cut at the first terminal;
+ * for Ln == 1 and d in {0, 1} the fold is the identity.
+ * ddrl_nstep_fold: `batch` whole windows that lie on the device in batch order (obs_w_d[batch, (Ln+1)*obs_dim], acts_w_d[batch,
+ * Ln*act_dim], rews_w_d / done_w_d[batch, Ln]) -> the five learner arrays. */
+int ddrl_nstep_fold(const float *obs_w_d, const float *acts_w_d, const float *rews_w_d, const float *done_w_d, int64_t batch,
+                    int32_t Ln, int32_t obs_dim, int32_t act_dim, float gamma, float *obs1_d, float *obs2_d, float *acts_d,
+                    float *rews_d, float *done_d, void *stream);
+/* sample_batch of a window ring (sac_ray.py:72-80) folded on the way out: the index draw of ddrl_replay_sample_ex (same MT19937
+ * stream, same counters, same empty-ring error) followed, in the same launch for batch <= 4096, by a fold-gather that reads only
+ * o[0], o[Ln], a[0] and the 2 Ln reward / done scalars of every drawn row.  Ln, obs_dim and act_dim come from the ring's widths
+ * {(Ln+1)*obs, Ln*act, Ln, Ln}.  idx_d (nullable) receives the indices.  DDRL_ERR_UNSUPPORTED for a ring that is not of that shape,
+ * has compact (uint8) arrays, or has a feed plan attached. */
+int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float *obs1_d, float *obs2_d, float *acts_d,
+                             float *rews_d, float *done_d, int64_t *idx_d, void *stream);
+
 /* Raw ring pointers (device) for checkpointing / inspection (algos/dqn/train.py:82-90 saves
  * exactly these five arrays + (ptr,size,max_size,steps,sample_times)). */
 int ddrl_replay_buffers(ddrl_replay_t *h, float **obs1_d, float **obs2_d, float **acts_d,
@@ -285,7 +308,10 @@ int ddrl_sac1_apply_grads_and_sample(ddrl_sac1_t *h, ddrl_replay_t *replay, int 
  * update's sample_batch (example/dsac.py:39-45: np.random.randint + five gathers) into set `set_out`,
  * i.e. Learner.train of update u plus `ray.get(replay_buffer.sample_batch.remote())` of update u+1
  * (actor_learner.py:135-142).  On the fused path the sampler rides in a forward launch and the
- * optimizer in the last backward launch; otherwise == compute_grads + apply_grads_and_sample. */
+ * optimizer in the last backward launch; otherwise == compute_grads + apply_grads_and_sample.
+ * `replay` of this call and of the two beside it is a transition ring of the learner's shapes, or an n-step window ring
+ * {(Ln+1)*obs, Ln*act, Ln, Ln} (algos/sac1/sac_ray.py:40-51): the sampler then is ddrl_replay_sample_nstep with the learner's
+ * gamma — the fold-gather takes the place of the five gathers, in the same workgroup of the same launch. */
 int ddrl_sac1_step_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t *replay, int set_out, void *stream);
 /* The same without the optimizer step (data-parallel learners: all-reduce, then ddrl_sac1_apply_grads): forward + backward on
  * input set set_in while the sampler of the NEXT batch rides in a forward launch and gathers into set_out. */
@@ -375,7 +401,8 @@ int ddrl_loop_create(ddrl_loop_t **out, ddrl_sac1_t *learner, ddrl_replay_t *rep
                      uint32_t noise_seed);
 int ddrl_loop_destroy(ddrl_loop_t *h);
 /* Enqueue n_updates sample+train iterations on `stream` (graph replays + an eager remainder).
- * Returns DDRL_ERR_EMPTY_BUFFER if the ring is empty. */
+ * Returns DDRL_ERR_EMPTY_BUFFER if the ring is empty.  On an n-step window ring (algos/sac1/sac_ray.py:40-51) every draw is
+ * ddrl_replay_sample_nstep with the learner's gamma. */
 int ddrl_loop_run(ddrl_loop_t *h, int64_t n_updates, void *stream);
 
 /* ===================================================================================== */
