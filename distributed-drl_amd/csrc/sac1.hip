@@ -829,6 +829,20 @@ static bool direct_ok(const ddrl_sac1_config_t &c) {
 }  // namespace
 
 // ==========================================================================================
+// The host-side launch state: everything the launch functions toggle at LAUNCH time.  A snapshot is a copy of it and a restore an
+// assignment (ddrl_sac1_capture_begin / _abort, ddrl_sac1_step_host): an aborted capture — whose launches never ran — puts it back.
+struct LaunchState {
+    int opt_cur;         // opt + opt_cur is the current optimizer state, every optimizer step advances into the other copy
+    int sh_cur;          // which copy of the policy dgrad image is current (the optimizer epilogue writes the other one)
+    bool fuse_apply;     // this launch_grads also applies the optimizer (Adam in the wgrad epilogues)
+    bool sample_armed;   // sampler riding in k_fwd<1> (ddrl_sac1_step_and_sample; its arguments: smp_rs, smp_ring, smp_set)
+    // set by ddrl_sac1_fill_noise, consumed by the next compute_grads / apply_grads
+    bool noise_armed;
+    uint32_t noise_seed;
+    unsigned int noise_pending;
+    bool grad_imported;  // the gradient buffer was overwritten by import(GRAD): Adam must not re-sum partials
+};
+
 struct ddrl_sac1 {
     int device;
     ddrl_sac1_config_t cfg;
@@ -841,8 +855,8 @@ struct ddrl_sac1 {
     float *H1, *H2, *dZ2, *dZ1, *xa, *xp, *part;
     float *act0, *act2, *logp0, *logp1, *save0, *q1o, *q2o, *dq4, *dhead, *loss_part, *losses;
     int ldh1, ldh2, ldxa, ldxp, ldd;
-    OptState *opt;       // two copies; opt + opt_cur is current, every optimizer step advances into the other one
-    int opt_cur;
+    OptState *opt;       // two copies, see LaunchState::opt_cur
+    LaunchState ls;
     Seg *segs_d;
     L1Jobs l1a[2];
     GemmJobs g_fa, g_fb, g_bq, g_bpi, g_last;
@@ -866,31 +880,24 @@ struct ddrl_sac1 {
     float *c4_pi[2], *c4_q[3];   // c4_q[2]: V (SAC-v)
     float *c4_q2b;               // second copy of c4_q[1]: double-buffered like the policy's when part of the q2(x, a) dgrad runs in launch "mid",
                                  // where the optimizer epilogue of q2's layer-2 wgrad writes the NEXT image (copy sh_cur = current, sh_cur ^ 1 = next)
-    int mid_rest_job;            // index of that dgrad's job in dg_mid (-1: none)
+    // the jobs launch_stage re-points at launch time, as build_direct numbered them
+    int mid_rest_job;            // dg_mid: the q2(x, a) dgrad columns that run there (-1: none)
+    int bq_q2_job;               // dg_bq: the q2(x, a) dgrad
+    int mid_pi_job, mid_q2w_job; // dg_mid: the policy dgrad; q2's layer-2 wgrad
+    int pi_w2_job;               // dg_pi: the policy's layer-2 wgrad
     float *xv_r4;                // SAC-v: the [x | 1] image of V's layer-1 wgrad
     int *part_cnt;       // arrival counters of the policy layer-1 partials (one per column tile)
-    int sh_cur;          // which copy of the policy dgrad image is current (the optimizer epilogue writes the other one)
-    bool fuse_apply;     // this launch_grads also applies the optimizer (Adam in the wgrad epilogues)
-    // sampler riding in k_fwd<1> (ddrl_sac1_step_and_sample)
-    bool sample_armed;
     ddrl_replay_dev::RingState *smp_rs;
     ddrl_replay_dev::RingPtrs smp_ring;
     int smp_set;
     float *hp;           // head partials [NEVAL][DFH][B][DNT]
     bool fused_l1_wgrad;  // pi layer-1 wgrad via dgrad-epilogue partials + Adam (needs hidden1 % 4 == 0)
-    // set by ddrl_sac1_fill_noise, consumed by the next compute_grads / apply_grads
-    bool noise_armed;
-    uint32_t noise_seed;
-    unsigned int noise_pending;
-    bool grad_imported;  // the gradient buffer was overwritten by import(GRAD): Adam must not re-sum partials
-    // ddrl_sac1_capture_begin / _abort: the host-side launch state above as it stood before a caller's stream capture (every
-    // launch function toggles some of it at LAUNCH time, so an aborted capture — whose launches never ran — must put it back)
     // ddrl_sac1_step_host: the host-batch update as captured graphs — on this surface the ~8 HIP calls of an eager update (two copies, the
     // noise fill, five launches) cost more host time than the device needs for the update.  One graph per (host block, copy parity).
     struct HostGraph { const float *block; float *losses; uint32_t seed; int opt_cur, sh_cur; hipGraphExec_t exec; };
     std::vector<HostGraph> host_graphs;
     uint32_t *host_ctr_d;          // device copy of the noise counter a host block carries up (two words)
-    struct HostSnap { bool valid; int opt_cur, sh_cur; bool fuse_apply, sample_armed, noise_armed, grad_imported; uint32_t noise_seed; unsigned int noise_pending; } snap;
+    struct { bool valid; LaunchState ls; } snap;   // ddrl_sac1_capture_begin: the launch state before a caller's stream capture
 };
 
 static void refresh_shadows(ddrl_sac1 *h, hipStream_t s);
@@ -910,194 +917,295 @@ static int reset_opt(ddrl_sac1 *h, hipStream_t s) {
     OptState o{};
     o.b1p_pi = o.b1p_q = (float)h->cfg.beta1;
     o.b2p_pi = o.b2p_q = (float)h->cfg.beta2;
-    h->opt_cur = 0;
+    h->ls.opt_cur = 0;
     DDRL_HIP_CHECK(hipMemcpyAsync(h->opt, &o, sizeof(o), hipMemcpyHostToDevice, s));
     DDRL_HIP_CHECK(hipStreamSynchronize(s));
     return DDRL_OK;
 }
 
-// Job tables of the SAC-v update (example/model.py:17-76) on the generic kernels.
-static int build_sacv(ddrl_sac1 *h) {
+// ------------------------------------------------------------------------------------------
+// What differs between SAC1 (algos/sac1) and SAC-v (example/model.py:17-76), as data the two table builders walk
+// ------------------------------------------------------------------------------------------
+enum { NET_PI = 0, NET_Q1, NET_Q2, NET_V };       // the forward pack field's network ids (the value networks follow the policy at equal distances)
+enum { ACT_NONE = 0, ACT_STORED, ACT_PI };        // second input of an evaluation: none, the batch's action, an action sampled by a policy evaluation
+
+// One forward evaluation.  Its position in the list is its slot: H1 / H2 on the generic kernels, head partials on the direct ones.
+// ACT_PI evaluations run in the second forward launch (generic: observation part in k_l1, finished by k_rows_a), the others in the first.
+struct Eval {
+    int net;
+    bool x2, targ;       // reads obs2 / the target copy
+    int act;
+    // direct-operand kernels only
+    int img = -1;        // H1r4 / H2c4 slot of the images it leaves (-1: none)
+    bool r4 = false;     // leaves an H2r4 image (slot = net)
+    float *ddrl_sac1::*xr4 = nullptr;   // leaves its augmented input rows there
+    int pev = -1, side = 0;             // ACT_PI: the policy evaluation it takes its action from; DFJob::side
+};
+// A value network that is trained: its evaluation on the generic kernels, its dZ2 / dZ1 slot, its H1r4 / H2c4 slot on the direct ones
+// (H2r4 slot = net; dZ1r4 / dq / w3snap / c4_q slot = position in Variant::vn)
+struct ValueNet { int net, gen_ev, slot, img; };
+struct Variant {
+    bool sacv;
+    int nl;                          // loss terms
+    const Eval *gen, *dir;           // evaluations on the generic / the direct-operand kernels
+    int n_gen, n_dir;
+    int gen_qpi;                     // generic: the evaluation q1(x, pi(x)) (dZ slot 2), whose dgrad gives dQ/da
+    int nv;
+    ValueNet vn[3];                  // (the policy's dZ slot follows: nv + 1 generic, nv direct)
+    bool php1;                       // DFArgs::php1 = evaluation 1
+    int pev_pack, pin_pack;          // DFArgs
+    int q_ev0, q_nev;                // DGJobs: the value-head evaluations
+};
+
+// SAC1, both paths: 0 pi(x) 1 pi(x2) 2 piT(x2) 3 q1(x,a) 4 q2(x,a) | 5 q1(x,pi) 6 q1T(x2,piT) 7 q2T(x2,piT)
+static const Eval EV_SAC1[8] = {
+    {NET_PI, false, false, ACT_NONE, 0, true, &ddrl_sac1::xp_r4},   // [x | 1] as an x4 image: A operand of the policy's layer-1 wgrad
+    {NET_PI, true, false, ACT_NONE},
+    {NET_PI, true, true, ACT_NONE},
+    {NET_Q1, false, false, ACT_STORED, 1, true, &ddrl_sac1::xa_r4},
+    {NET_Q2, false, false, ACT_STORED, 2, true},
+    {NET_Q1, false, false, ACT_PI, 3, false, nullptr, 0, 1},
+    {NET_Q1, true, true, ACT_PI, -1, false, nullptr, 2, 2},
+    {NET_Q2, true, true, ACT_PI, -1, false, nullptr, 2, 0},
+};
+// SAC-v, generic kernels: 0 pi(x) 1 q1(x,a) 2 q2(x,a) | 3 q1(x,pi) 4 q2(x,pi) | 5 v(x) 6 v_targ(x2)
+static const Eval EV_SACV_GEN[7] = {
+    {NET_PI, false, false, ACT_NONE}, {NET_Q1, false, false, ACT_STORED}, {NET_Q2, false, false, ACT_STORED},
+    {NET_Q1, false, false, ACT_PI}, {NET_Q2, false, false, ACT_PI}, {NET_V, false, false, ACT_NONE}, {NET_V, true, true, ACT_NONE},
+};
+// SAC-v, direct-operand kernels: 0 pi(x) 1 q1(x,a) 2 q2(x,a) 3 v(x) 4 v_targ(x2) | 5 q1(x,pi) 6 q2(x,pi)
+static const Eval EV_SACV_DIR[7] = {
+    {NET_PI, false, false, ACT_NONE, 0, true, &ddrl_sac1::xp_r4},
+    {NET_Q1, false, false, ACT_STORED, 1, true, &ddrl_sac1::xa_r4},
+    {NET_Q2, false, false, ACT_STORED, 2, true},
+    {NET_V, false, false, ACT_NONE, 4, true, &ddrl_sac1::xv_r4},
+    {NET_V, true, true, ACT_NONE},
+    {NET_Q1, false, false, ACT_PI, 3, false, nullptr, 0, 1},   // both take the action sampled by pi(x), by the main copy from eps_x
+    {NET_Q2, false, false, ACT_PI, -1, false, nullptr, 0, 0},
+};
+static const Variant VARIANTS[2] = {
+    {false, 3, EV_SAC1, EV_SAC1, 8, 8, 5, 2, {{NET_Q1, 3, 0, 1}, {NET_Q2, 4, 1, 2}},
+     true, 0 | (2 << 2) | (2 << 4),            // q1(x, pi(x)) <- evaluation 0; the target Qs <- evaluation 2 (pi_targ(x2))
+     0 | ((2 | 4) << 3) | ((2 | 4) << 6),      // evaluation 0: main copy, eps_x; evaluation 2: target copy, eps_t
+     3, 5},
+    {true, 4, EV_SACV_GEN, EV_SACV_DIR, 7, 7, 3, 3, {{NET_Q1, 1, 0, 1}, {NET_Q2, 2, 1, 2}, {NET_V, 5, 3, 4}}, false, 0, 0, 1, 6},
+};
+static const Variant &variant_of(const ddrl_sac1 *h) { return VARIANTS[h->cfg.variant == DDRL_SAC_V ? 1 : 0]; }
+
+struct NetOff { long long W1, b1, W2, b2, W3, b3; };   // a network's tensors inside a parameter buffer (the policy: no W3 / b3)
+static NetOff net_off(const Layout &L, int net) {
+    if (net == NET_PI) return NetOff{L.pi_W1, L.pi_b1, L.pi_W2, L.pi_b2, -1, -1};
+    if (net == NET_V) return NetOff{L.v_W1, L.v_b1, L.v_W2, L.v_b2, L.v_W3, L.v_b3};
+    const int q = net - NET_Q1;
+    return NetOff{L.q_W1[q], L.q_b1[q], L.q_W2[q], L.q_b2[q], L.q_W3[q], L.q_b3[q]};
+}
+
+// rows of every row-indexed buffer.  Direct-operand path: a whole number of 32-row tiles; rows past the batch are padding (zero
+// inputs, no loss terms, zero upstream gradients) and means run over the batch's rows
+static int rows_of(const ddrl_sac1 *h) { return h->fused ? rup32(h->cfg.batch) : h->cfg.batch; }
+
+// Element i of a buffer that only the generic path allocates.  The row tables are filled on the direct path too (it reads rc.nl and
+// launches none of them): there the buffer is null and the offset alone is kept, as an integer.
+static float *at(float *p, long long i) { return reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)i * sizeof(float)); }
+
+// ---- job tables of the update on the generic kernels (gemm_core.h) ----
+static int build_generic(ddrl_sac1 *h) {
+    const Variant &V = variant_of(h);
     const ddrl_sac1_config_t *cfg = &h->cfg;
     const Layout &L = h->L;
     const int B = cfg->batch, o = cfg->obs_dim, a = cfg->act_dim, h1 = cfg->hidden1, h2 = cfg->hidden2;
     const float *Pm = h->main_p, *Pt = h->target_p;
     const int ldh1 = h->ldh1, ldh2 = h->ldh2;
     const long long BH1 = (long long)B * ldh1, BH2 = (long long)B * ldh2, BZ1 = (long long)B * h1, BZ2 = (long long)B * h2;
-    h->fused = false;
-    // evaluations: 0 pi(x) 1 q1(x,a) 2 q2(x,a) | 3 q1(x,pi) 4 q2(x,pi) (observation part here, finished by k_rows_a_v) | 5 v(x) 6 v_targ(x2)
+    // ---- layer-1 jobs (one table per input set) and the forward layer-2 GEMMs
     for (int st = 0; st < 2; ++st) {
         float *x = h->in[st][0], *x2 = h->in[st][1], *ac = h->in[st][2];
-        auto l1 = [&](const float *in0, int d0, const float *in1, int d1, const float *W, const float *b, int ev, int pre) {
-            return L1Job{in0, in1, W, b, h->H1 + ev * BH1, nullptr, d0, d1, B, h1, ldh1, 0, pre};
-        };
         L1Jobs &J = h->l1a[st];
-        J.njobs = 7;
+        J.njobs = V.n_gen;
         J.noise_on = 0; J.act = a; J.n_each = B * a; J.noise_seed = 0;
         J.e0 = h->in[st][5]; J.e1 = h->in[st][6]; J.e2 = h->in[st][7]; J.opt = h->opt;
-        J.job[0] = l1(x, o, nullptr, 0, Pm + L.pi_W1, Pm + L.pi_b1, 0, 0);
-        J.job[1] = l1(x, o, ac, a, Pm + L.q_W1[0], Pm + L.q_b1[0], 1, 0);
-        J.job[2] = l1(x, o, ac, a, Pm + L.q_W1[1], Pm + L.q_b1[1], 2, 0);
-        J.job[3] = l1(x, o, nullptr, a, Pm + L.q_W1[0], Pm + L.q_b1[0], 3, 1);
-        J.job[4] = l1(x, o, nullptr, a, Pm + L.q_W1[1], Pm + L.q_b1[1], 4, 1);
-        J.job[5] = l1(x, o, nullptr, 0, Pm + L.v_W1, Pm + L.v_b1, 5, 0);
-        J.job[6] = l1(x2, o, nullptr, 0, Pt + L.v_W1, Pt + L.v_b1, 6, 0);
-        J.job[0].aug_out = h->xp; J.job[0].aug_ld = h->ldxp;  // [x | 1]     : pi and v layer-1 wgrads
-        J.job[1].aug_out = h->xa; J.job[1].aug_ld = h->ldxa;  // [x | a | 1] : Q layer-1 wgrads
-        h->rav[st] = RowsAV{h->H2, net_pi(Pm, L), net_q(Pm, L, 0), net_q(Pm, L, 1), net_v(Pm, L), net_v(Pt, L), h->in[st][5],
-                            h->act0, h->logp0, h->save0, h->q1o, h->q2o, h->vo, h->vto, h->H1,
-                            Pm + L.q_W1[0] + (long long)o * h1, Pm + L.q_W1[1] + (long long)o * h1, B, h2, ldh2, a, h1, ldh1,
-                            (float)cfg->act_scale};
-        h->rbv[st] = RowsBV{h->H2, net_q(Pm, L, 0), net_q(Pm, L, 1), net_v(Pm, L), h->in[st][3], h->in[st][4], h->logp0, h->q1o, h->q2o,
-                            h->vo, h->vto, h->dZ2, h->dq4, h->loss_part, B, h2, ldh2, (float)cfg->alpha, (float)cfg->gamma};
+        for (int ev = 0; ev < V.n_gen; ++ev) {
+            const Eval &e = V.gen[ev];
+            const NetOff n = net_off(L, e.net);
+            const float *P = e.targ ? Pt : Pm;
+            J.job[ev] = L1Job{e.x2 ? x2 : x, e.act == ACT_STORED ? ac : nullptr, P + n.W1, P + n.b1, h->H1 + ev * BH1, nullptr,
+                              o, e.act != ACT_NONE ? a : 0, B, h1, ldh1, 0, e.act == ACT_PI ? 1 : 0};
+            if (ev == 0) { J.job[ev].aug_out = h->xp; J.job[ev].aug_ld = h->ldxp; }                                    // [x | 1]     : pi (and v) layer-1 wgrads
+            if (e.net == NET_Q1 && e.act == ACT_STORED) { J.job[ev].aug_out = h->xa; J.job[ev].aug_ld = h->ldxa; }    // [x | a | 1] : Q layer-1 wgrads
+            if (st == 0)
+                gemm_add(e.act == ACT_PI ? h->g_fb : h->g_fa,
+                         gemm_fwd(h->H1 + ev * BH1, ldh1, P + n.W2, P + n.b2, h->H2 + ev * BH2, ldh2, B, h1, h2));
+        }
     }
-    auto fwd = [&](const float *P, long long W2, long long b2, int ev) {
-        return gemm_fwd(h->H1 + ev * BH1, ldh1, P + W2, P + b2, h->H2 + ev * BH2, ldh2, B, h1, h2);
-    };
-    gemm_add(h->g_fa, fwd(Pm, L.pi_W2, L.pi_b2, 0));
-    gemm_add(h->g_fa, fwd(Pm, L.q_W2[0], L.q_b2[0], 1));
-    gemm_add(h->g_fa, fwd(Pm, L.q_W2[1], L.q_b2[1], 2));
-    gemm_add(h->g_fa, fwd(Pm, L.v_W2, L.v_b2, 5));
-    gemm_add(h->g_fa, fwd(Pt, L.v_W2, L.v_b2, 6));
-    gemm_add(h->g_fb, fwd(Pm, L.q_W2[0], L.q_b2[0], 3));
-    gemm_add(h->g_fb, fwd(Pm, L.q_W2[1], L.q_b2[1], 4));
+    // ---- backward GEMM launches.  dZ2 / dZ1 slots: 0 q1(x,a), 1 q2(x,a), 2 q1(x,pi), 3 v(x) (SAC-v), then the policy.
+    // Every bias gradient rides as the "ones column" row of its kernel's wgrad.
     float *G = h->grad;
-    // value backward: dZ2 / dZ1 slots 0 q1(x,a) 1 q2(x,a) 2 q1(x,pi) 3 v(x)
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 2 * BZ2, Pm + L.q_W2[0], h->H1 + 3 * BH1, ldh1, h->dZ1 + 2 * BZ1, B, h1, h2));
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 0 * BZ2, Pm + L.q_W2[0], h->H1 + 1 * BH1, ldh1, h->dZ1 + 0 * BZ1, B, h1, h2));
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 1 * BZ2, Pm + L.q_W2[1], h->H1 + 2 * BH1, ldh1, h->dZ1 + 1 * BZ1, B, h1, h2));
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 3 * BZ2, Pm + L.v_W2, h->H1 + 5 * BH1, ldh1, h->dZ1 + 3 * BZ1, B, h1, h2));
-    for (int q = 0; q < 2; ++q) {
-        gemm_add(h->g_bq, gemm_wgrad(h->H1 + (1 + q) * BH1, ldh1, h1, h->dZ2 + q * BZ2, h2, h2, G + L.q_W2[q], h2, B));
-        gemm_add(h->g_bq, gemm_wgrad(h->H2 + (1 + q) * BH2, ldh2, h2, h->dq4 + (long long)q * B * 4, 4, 1, G + L.q_W3[q], 1, B));
+    const int pi_slot = V.nv + 1;
+    // launch "bwd Q": needs dZ2 of the value networks, dq4
+    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 2 * BZ2, Pm + L.q_W2[0], h->H1 + V.gen_qpi * BH1, ldh1, h->dZ1 + 2 * BZ1, B, h1, h2));
+    for (int q = 0; q < V.nv; ++q) {
+        const ValueNet &vn = V.vn[q];
+        gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + vn.slot * BZ2, Pm + net_off(L, vn.net).W2, h->H1 + vn.gen_ev * BH1, ldh1, h->dZ1 + vn.slot * BZ1, B, h1, h2));
     }
-    gemm_add(h->g_bq, gemm_wgrad(h->H1 + 5 * BH1, ldh1, h1, h->dZ2 + 3 * BZ2, h2, h2, G + L.v_W2, h2, B));
-    gemm_add(h->g_bq, gemm_wgrad(h->H2 + 5 * BH2, ldh2, h2, h->dq4 + (long long)2 * B * 4, 4, 1, G + L.v_W3, 1, B));
-    // policy backward (dZ2 / dZ1 slot 4) + the layer-1 wgrads of the value networks
+    for (int q = 0; q < V.nv; ++q) {
+        const ValueNet &vn = V.vn[q];
+        const NetOff n = net_off(L, vn.net);
+        gemm_add(h->g_bq, gemm_wgrad(h->H1 + vn.gen_ev * BH1, ldh1, h1, h->dZ2 + vn.slot * BZ2, h2, h2, G + n.W2, h2, B));           // W2, b2
+        gemm_add(h->g_bq, gemm_wgrad(h->H2 + vn.gen_ev * BH2, ldh2, h2, h->dq4 + (long long)q * B * 4, 4, 1, G + n.W3, 1, B));      // W3, b3
+    }
+    // launch "bwd pi": needs the policy's dZ2, dhead (k_rows_c) and the value networks' dZ1 (launch above)
     {
-        GemmJob j = gemm_dgrad(h->dZ2 + 4 * BZ2, Pm + L.pi_W2, h->H1 + 0 * BH1, ldh1, h->dZ1 + 4 * BZ1, B, h1, h2);
+        GemmJob j = gemm_dgrad(h->dZ2 + pi_slot * BZ2, Pm + L.pi_W2, h->H1, ldh1, h->dZ1 + pi_slot * BZ1, B, h1, h2);
         h->fused_l1_wgrad = (h1 % 4 == 0) && (o + 1 <= 12) && (L.pi_W1 % 4 == 0);
         if (h->fused_l1_wgrad) { j.part_x = h->xp; j.part = h->part; j.part_nk = o + 1; j.part_ldx = h->ldxp; }
         gemm_add(h->g_bpi, j);
     }
-    gemm_add(h->g_bpi, gemm_wgrad(h->H1 + 0 * BH1, ldh1, h1, h->dZ2 + 4 * BZ2, h2, h2, G + L.pi_W2, h2, B));
-    gemm_add(h->g_bpi, gemm_wgrad(h->H2, ldh2, h2, h->dhead, h->ldd, a, G + L.pi_Wmu, a, B));
-    gemm_add(h->g_bpi, gemm_wgrad(h->H2, ldh2, h2, h->dhead + a, h->ldd, a, G + L.pi_Wls, a, B));
-    for (int q = 0; q < 2; ++q)
-        gemm_add(h->g_bpi, gemm_wgrad(h->xa, h->ldxa, o + a, h->dZ1 + q * BZ1, h1, h1, G + L.q_W1[q], h1, B));
-    gemm_add(h->g_bpi, gemm_wgrad(h->xp, h->ldxp, o, h->dZ1 + 3 * BZ1, h1, h1, G + L.v_W1, h1, B));
-    if (!h->fused_l1_wgrad) gemm_add(h->g_last, gemm_wgrad(h->xp, h->ldxp, o, h->dZ1 + 4 * BZ1, h1, h1, G + L.pi_W1, h1, B));
-    h->rc = RowsC{h->H2, h->dZ1 + 2 * BZ1, Pm + L.q_W1[0], net_pi(Pm, L), h->save0, h->dhead, h->dZ2 + 4 * BZ2,
-                  h->loss_part, h->losses, B, h1, h2, ldh2, o, a, h->ldd, h->rows_b_blocks, (float)cfg->alpha,
-                  (float)cfg->act_scale, 4};
-    h->ad = AdamArgs{h->main_p, h->target_p, h->m, h->v, h->grad, h->opt, h->opt + 1, L.total_int, L.n_pi_int, 0,
-                     (float)cfg->lr, (float)cfg->beta1, (float)cfg->beta2, (float)cfg->adam_eps,
-                     (float)cfg->polyak, (float)(1.0 - cfg->polyak),
-                     h->part, L.pi_W1 / 4, (long long)(o + 1) * h1 / 4, (long long)(o + 1) * h1 / 4,
-                     h->fused_l1_wgrad ? (B + 31) / 32 : 0, 0u};
-    h->noise_armed = false; h->noise_seed = 0; h->noise_pending = 0; h->grad_imported = false;
-    h->fuse_apply = false; h->sample_armed = false;
+    gemm_add(h->g_bpi, gemm_wgrad(h->H1, ldh1, h1, h->dZ2 + pi_slot * BZ2, h2, h2, G + L.pi_W2, h2, B));     // W2, b2
+    gemm_add(h->g_bpi, gemm_wgrad(h->H2, ldh2, h2, h->dhead, h->ldd, a, G + L.pi_Wmu, a, B));                 // Wmu, bmu
+    gemm_add(h->g_bpi, gemm_wgrad(h->H2, ldh2, h2, h->dhead + a, h->ldd, a, G + L.pi_Wls, a, B));             // Wls, bls
+    for (int q = 0; q < V.nv; ++q) {                                                                          // value W1, b1
+        const ValueNet &vn = V.vn[q];
+        const bool v = vn.net == NET_V;
+        gemm_add(h->g_bpi, gemm_wgrad(v ? h->xp : h->xa, v ? h->ldxp : h->ldxa, v ? o : o + a, h->dZ1 + vn.slot * BZ1, h1, h1, G + net_off(L, vn.net).W1, h1, B));
+    }
+    // launch "last" (only when the fused form is unavailable): needs the policy's dZ1
+    if (!h->fused_l1_wgrad) gemm_add(h->g_last, gemm_wgrad(h->xp, h->ldxp, o, h->dZ1 + pi_slot * BZ1, h1, h1, G + L.pi_W1, h1, B));   // pi W1, b1
     return DDRL_OK;
 }
 
-// Job tables of the SAC-v update on the direct-operand kernels (sac1_direct.h).  B = rows of every image (whole 32-row
-// tiles), Bv = the batch.  Evaluations (head-partial slots): 0 pi(x) 1 q1(x,a) 2 q2(x,a) 3 v(x) 4 v_targ(x2) |
-// phase 1: 5 q1(x,pi) 6 q2(x,pi).  Image slots — H1r4 / H2c4: 0 pi 1 q1(x,a) 2 q2(x,a) 3 q1(x,pi) 4 v;  H2r4: 0 pi 1 q1 2 q2 3 v;
-// dZ1r4: 0 q1 1 q2 2 v.  Network ids of the forward pack field: 0 policy, 1 q1, 2 q2, 3 v (the value networks follow the
-// policy at equal distances in a parameter buffer).
-static int build_sacv_direct(ddrl_sac1 *h, int Bv, int B) {
+// Tile counts against the 256 CUs (profiles/r05_update_experiments.txt: a launch pays +1.2 ... +2.1 us where its tile count
+// crosses a multiple of 256 and is flat in between): the three Q dgrads are 3 x 104 = 312 tiles at config 2 — 56 over.  Only the
+// last launch reads the dZ1 of the stored-action dgrads (the Q layer-1 wgrads), so the q2(x, a) dgrad is cut by COLUMN tiles: the
+// first `keep` stay in launch "bq" (= 256 tiles), the rest run in launch "mid" (which the two Q-head wgrads leave for launch
+// "pi": 464 - 20 + 56 = 500 <= 512; "pi": 190 + 20 = 210 <= 256).  A column sub-range of a dgrad is a job of its own — operand B,
+// the relu mask and the output image start n_off columns further — with the same arithmetic per tile: bit-identical results.
+// Returns the column tiles that stay (all of them: no split).  SAC1 only.  DDRL_BQ_SPLIT=0: never split.
+static int bq_keep(int tm, int h1, int h2) {
+    const int ct = (h1 + 31) / 32, T = tm * ct, ncu = 256;
+    static const int want = getenv("DDRL_BQ_SPLIT") ? atoi(getenv("DDRL_BQ_SPLIT")) : 1;
+    const int rm_tiles = 2 * ((h2 + 1 + 31) / 32);                                  // the two Q-head wgrads (one column tile each)
+    const int mid_now = T + tm * ((h2 + 31) / 32) + 2 * ((h1 + 1 + 31) / 32) * ((h2 + 31) / 32) + rm_tiles;
+    const int pi_now = ((h1 + 1 + 31) / 32) * ((h2 + 31) / 32) + rm_tiles + 3 * ct + 1;
+    if (want && 3 * T > ncu && 2 * T < ncu) {
+        const int k = (ncu - 2 * T) / tm, moved = (ct - k) * tm;
+        if (k >= 1 && k < ct && mid_now - rm_tiles + moved <= 2 * ncu && pi_now + rm_tiles <= ncu) return k;
+    }
+    return ct;
+}
+
+// ---- job tables of the update on the direct-operand kernels (sac1_direct.h).  B = rows of every image (whole 32-row tiles), Bv = the
+// batch.  Image slots — H1r4 / H2c4: 0 pi(x) 1 q1(x,a) 2 q2(x,a) 3 q1(x,pi) 4 v(x);  H2r4: 0 pi 1 q1 2 q2 3 v;  dZ1r4: the value
+// networks, then the policy.
+static int build_direct(ddrl_sac1 *h, int Bv, int B) {
+    const Variant &V = variant_of(h);
     const ddrl_sac1_config_t *cfg = &h->cfg;
     const Layout &L = h->L;
     const int o = cfg->obs_dim, a = cfg->act_dim, h1 = cfg->hidden1, h2 = cfg->hidden2;
-    const int Kp1 = L.Kp1, Np2 = L.Np2, nt2 = (h2 + 31) / 32;
+    const int Kp1 = L.Kp1, Np2 = L.Np2, nt2 = (h2 + 31) / 32, ct = (h1 + 31) / 32;
     const float *Pm = h->main_p, *Pt = h->target_p, *S = h->slab;
-    DDRL_REQUIRE(L.v_W1 - L.q_W1[1] == L.q_W1[1] - L.q_W1[0], "internal: the value networks must sit at equal distances");
-    DDRL_REQUIRE(L.pi_bmu == pi_bmu_off(h1, Np2, h2, a) && L.pi_bls == pi_bls_off(h1, Np2, h2, a), "internal: policy-head bias offsets of the direct layout");
+    DDRL_REQUIRE(!V.sacv || L.v_W1 - L.q_W1[1] == L.q_W1[1] - L.q_W1[0], "internal: the value networks must sit at equal distances");
+    DDRL_REQUIRE(L.pi_bmu == pi_bmu_off(h1, Np2, h2, a) && L.pi_bls == pi_bls_off(h1, Np2, h2, a),   // (k_dfwd<1> forms these addresses itself)
+                 "internal: policy-head bias offsets of the direct layout");
     h->fused_l1_wgrad = false;   // (direct path: the policy's layer-1 wgrad is a job of its own, no row-tile partials)
-    h->sh_cur = 0;
     const long long HP = (long long)DFH * B * DNT;
     const long long H1I = (long long)B * h->Lp1, H2C = (long long)Np2 * B, H2R = (long long)B * h->Lp2;
-    auto steps = [](int D) { return D + 1 <= 8 ? 4 : 4 + (D + 1 - 8 + 1) / 2; };
-    const long long vW1[3] = {L.q_W1[0], L.q_W1[1], L.v_W1}, vW2[3] = {L.q_W2[0], L.q_W2[1], L.v_W2}, vb2[3] = {L.q_b2[0], L.q_b2[1], L.v_b2};
-    const long long vW3[3] = {L.q_W3[0], L.q_W3[1], L.v_W3};
+    auto steps = [](int D) { return D + 1 <= 8 ? 4 : 4 + (D + 1 - 8 + 1) / 2; };  // input columns + the bias column, two per MFMA step
+    const int ns_pi = steps(o) - 4, ns_q = steps(o + a) - 4;
+    // SAC1: Q1(x, a), Q2(x, a) need nothing from the policy: they run in phase 1 beside the policy-dependent evaluations (k_dfwd:
+    // "stored") when the tile counts allow the per-XCD split, else in phase 0 as before.  DDRL_QXA_PHASE=0 forces phase 0.
+    const int tpj_f = (B / 32) * nt2;
+    static const int qxa_phase = getenv("DDRL_QXA_PHASE") ? atoi(getenv("DDRL_QXA_PHASE")) : 1;
+    const bool q_late = !V.sacv && qxa_phase == 1 && (3 * tpj_f) % 8 == 0 && (2 * tpj_f) % 8 == 0;
+    // SAC1: the column tiles of the q2(x, a) dgrad that stay in launch "bq"
+    const int keep = V.sacv ? ct : bq_keep(B / 32, h1, h2);
+    const bool split = keep < ct;
+    if (!V.sacv) h->bq_cols = keep;
     for (int st = 0; st < 2; ++st) {
-        auto head = [&](DFHead &d) {
-            d = DFHead{};
-            d.base = S; d.tiles_m = B / 32; d.tpj = (B / 32) * nt2; d.K = h1; d.Np = Np2; d.B = B; d.d0 = o;
-            d.x_off = (int)(h->in[st][0] - S);
-            d.main_off = (int)(Pm - S); d.targ_off = (int)(Pt - S); d.npi = (int)L.q_W1[0]; d.perq = (int)(L.q_W1[1] - L.q_W1[0]);
-            d.hp_off = (int)(h->hp - S);
-        };
-        auto args = [&](DFArgs &F, int njobs) {
-            F = DFArgs{};
-            F.njobs = njobs; F.tiles_n = nt2; F.act = a; F.Lp1 = h->Lp1; F.Lp2 = h->Lp2; F.h2 = h2;
-            F.scale = (float)cfg->act_scale;
-            F.act0 = h->act0; F.act2 = h->act2; F.logp0 = h->logp0; F.logp1 = h->logp1; F.save0 = h->save0;
-            F.php1 = nullptr;
-            F.pev_pack = 0;   // both phase-1 jobs take the action sampled by pi(x)
-            F.pin_pack = 0;   // ... by the main copy from eps_x
-            F.noise_on = 0; F.n_each = Bv * a; F.Bv = Bv; F.noise_seed = 0;
-            F.e0 = h->in[st][5]; F.e1 = h->in[st][6]; F.e2 = h->in[st][7]; F.opt = h->opt;
-        };
-        auto vj = [&](const float *P, int q, int ev) {   // a value network (q = 0, 1: Q; 2: V)
-            DFJob j{};
-            j.b2 = P + vb2[q]; j.wh0 = P + vW3[q]; j.wh1 = j.wh0; j.nh = 1; j.hsplit = 1; j.hstride = 1;
-            j.hp = h->hp + ev * HP;
-            return j;
-        };
-        const int ns_pi = steps(o) - 4, ns_q = steps(o + a) - 4;
         DFHead &HA = h->fh_a[st], &HB = h->fh_b[st];
         DFArgs &FA = h->f_a[st], &FB = h->f_b[st];
-        head(HA); args(FA, 5);
-        {
+        HA = DFHead{};
+        HA.base = S; HA.tiles_m = B / 32; HA.tpj = (B / 32) * nt2; HA.K = h1; HA.Np = Np2; HA.B = B; HA.d0 = o;
+        HA.x_off = (int)(h->in[st][0] - S);
+        HA.main_off = (int)(Pm - S); HA.targ_off = (int)(Pt - S); HA.npi = (int)L.q_W1[0]; HA.perq = (int)(L.q_W1[1] - L.q_W1[0]);
+        HA.hp_off = (int)(h->hp - S);
+        HB = HA;
+        FA = DFArgs{};
+        FA.tiles_n = nt2; FA.act = a; FA.Lp1 = h->Lp1; FA.Lp2 = h->Lp2; FA.h2 = h2;
+        FA.scale = (float)cfg->act_scale;
+        FA.act0 = h->act0; FA.act2 = h->act2; FA.logp0 = h->logp0; FA.logp1 = h->logp1; FA.save0 = h->save0;
+        FA.php1 = V.php1 ? h->hp + 1 * HP : nullptr;
+        FA.pev_pack = V.pev_pack; FA.pin_pack = V.pin_pack;
+        FA.noise_on = 0; FA.n_each = Bv * a; FA.Bv = Bv; FA.noise_seed = 0;
+        FA.e0 = h->in[st][5]; FA.e1 = h->in[st][6]; FA.e2 = h->in[st][7]; FA.opt = h->opt;
+        FB = FA;
+        // evaluation `ev` as the next job of a forward launch.  Pack field of a job: steps | obs2 << 2 | target << 3 | network << 4
+        auto put = [&](DFHead &H, DFArgs &F, int ev) {
+            const Eval &e = V.dir[ev];
+            const NetOff n = net_off(L, e.net);
+            const float *P = e.targ ? Pt : Pm;
+            const bool pi = e.net == NET_PI;
             DFJob j{};
-            j.b2 = Pm + L.pi_b2; j.wh0 = Pm + L.pi_Wmu; j.wh1 = Pm + L.pi_Wls; j.nh = 2 * a; j.hsplit = a; j.hstride = a; j.hp = h->hp;
-            j.H2c4 = h->H2c4; j.H2r4 = h->H2r4; j.H1r4 = h->H1r4; j.xr4 = h->xp_r4;
-            FA.job[0] = j;
-        }
-        FA.job[1] = vj(Pm, 0, 1); FA.job[1].H2c4 = h->H2c4 + 1 * H2C; FA.job[1].H2r4 = h->H2r4 + 1 * H2R; FA.job[1].H1r4 = h->H1r4 + 1 * H1I;
-        FA.job[1].xr4 = h->xa_r4;
-        FA.job[2] = vj(Pm, 1, 2); FA.job[2].H2c4 = h->H2c4 + 2 * H2C; FA.job[2].H2r4 = h->H2r4 + 2 * H2R; FA.job[2].H1r4 = h->H1r4 + 2 * H1I;
-        FA.job[3] = vj(Pm, 2, 3); FA.job[3].H2c4 = h->H2c4 + 4 * H2C; FA.job[3].H2r4 = h->H2r4 + 3 * H2R; FA.job[3].H1r4 = h->H1r4 + 4 * H1I;
-        FA.job[3].xr4 = h->xv_r4;
-        FA.job[4] = vj(Pt, 2, 4);
-        head(HB); args(FB, 2);
-        {
-            auto pk = [](int ns, int x2, int targ, int net) { return ns | (x2 << 2) | (targ << 3) | (net << 4); };
-            HA.pack = pk(ns_pi, 0, 0, 0) | (pk(ns_q, 0, 0, 1) << 6) | (pk(ns_q, 0, 0, 2) << 12) | (pk(ns_pi, 0, 0, 3) << 18) | (pk(ns_pi, 1, 1, 3) << 24);
-            HB.pack = pk(ns_q, 0, 0, 1) | (pk(ns_q, 0, 0, 2) << 6);
-        }
-        auto from_pi = [&](DFJob &j, int side) {
-            j.php = h->hp; j.side = side;
+            j.b2 = P + n.b2; j.wh0 = P + (pi ? L.pi_Wmu : n.W3); j.wh1 = pi ? P + L.pi_Wls : j.wh0;
+            j.nh = pi ? 2 * a : 1; j.hsplit = pi ? a : 1; j.hstride = pi ? a : 1;
+            j.hp = h->hp + ev * HP;
+            if (e.img >= 0) { j.H2c4 = h->H2c4 + e.img * H2C; j.H1r4 = h->H1r4 + e.img * H1I; }
+            if (e.r4) j.H2r4 = h->H2r4 + e.net * H2R;
+            if (e.xr4) j.xr4 = h->*e.xr4;
+            if (e.pev >= 0) { j.php = h->hp + e.pev * HP; j.side = e.side; }
+            const int ns = (e.net == NET_Q1 || e.net == NET_Q2) ? ns_q : ns_pi;
+            H.pack |= (ns | ((e.x2 ? 1 : 0) << 2) | ((e.targ ? 1 : 0) << 3) | (e.net << 4)) << (6 * F.njobs);
+            F.job[F.njobs++] = j;
         };
-        FB.job[0] = vj(Pm, 0, 5); from_pi(FB.job[0], 1);
-        FB.job[0].H2c4 = h->H2c4 + 3 * H2C; FB.job[0].H1r4 = h->H1r4 + 3 * H1I;
-        FB.job[1] = vj(Pm, 1, 6); from_pi(FB.job[1], 0);
-        // ---- backward launch 1: the four value dgrads (slot 2 first: its dQ/da partials are what the next launch waits for)
+        for (int ev = 0; ev < V.n_dir; ++ev) {
+            const int act = V.dir[ev].act;
+            if (act == ACT_PI) put(HB, FB, ev);
+            else if (!(q_late && act == ACT_STORED)) put(HA, FA, ev);
+        }
+        if (q_late) {
+            for (int ev = 0; ev < V.n_dir; ++ev)
+                if (V.dir[ev].act == ACT_STORED) put(HB, FB, ev);
+            HB.pack |= 1 << 30;
+        }
+        // ---- backward launch 1: the value dgrads (slot 2 first: its dQ/da partials are what the next launch waits for)
         DGJobs &Q = h->dg_bq[st];
         Q = DGJobs{};
-        Q.hp = h->hp; Q.B = B; Q.Bv = Bv; Q.sacv = 1; Q.q_ev0 = 1; Q.q_nev = 6;
-        Q.b3q1 = Pm + L.q_b3[0]; Q.b3q2 = Pm + L.q_b3[1]; Q.b3q1t = Pm + L.v_b3; Q.b3q2t = Pt + L.v_b3;
+        Q.hp = h->hp; Q.B = B; Q.Bv = Bv; Q.sacv = V.sacv ? 1 : 0; Q.q_ev0 = V.q_ev0; Q.q_nev = V.q_nev;
+        Q.b3q1 = Pm + L.q_b3[0]; Q.b3q2 = Pm + L.q_b3[1];
+        if (V.sacv) { Q.b3q1t = Pm + L.v_b3; Q.b3q2t = Pt + L.v_b3; Q.vo = h->vo; Q.vto = h->vto; }
+        else { Q.b3q1t = Pt + L.q_b3[0]; Q.b3q2t = Pt + L.q_b3[1]; }
         Q.rew = h->in[st][3]; Q.done = h->in[st][4]; Q.logp0 = h->logp0; Q.logp1 = h->logp1;
-        Q.q1o = h->q1o; Q.q2o = h->q2o; Q.vo = h->vo; Q.vto = h->vto; Q.dq = h->dq; Q.loss_part = h->loss_part;
+        Q.q1o = h->q1o; Q.q2o = h->q2o; Q.dq = h->dq; Q.loss_part = h->loss_part;
         Q.alpha = (float)cfg->alpha; Q.gamma = (float)cfg->gamma;
         auto dq_job = [&](int slot, int img, int q, float *C) {
             DGJob j{};
             j.type = DG_DGRAD_Q; j.M = B; j.N = h1; j.K = h2; j.slot = slot;
             j.A = h->H2c4 + img * H2C; j.lda = B; j.B = h->c4_q[q]; j.ldb = Kp1;
-            j.gw = Pm + vW3[q]; j.gdq = nullptr; j.gconst = -1.0f / (float)Bv;
+            j.gw = Pm + net_off(L, V.vn[q].net).W3; j.gdq = nullptr; j.gconst = -1.0f / (float)Bv;
             j.mask = h->H1r4 + img * H1I; j.ldmask = h->Lp1; j.C = C; j.ldc = h->Lp1; j.adam_off = -1;
             return j;
         };
         {
-            DGJob j = dq_job(2, 3, 0, nullptr);
+            DGJob j = dq_job(2, 3, 0, nullptr);   // q1(x, pi(x))
             j.wa = Pm + L.q_W1[0]; j.wa_d0 = o; j.da_part = h->da_part; j.nact = a;
             dg_add(Q, j);
         }
-        // (the W3 snapshots for the next launch's generated wgrad operands: one per value network)
-        { DGJob j = dq_job(0, 1, 0, h->dZ1r4); j.gw_snap = h->w3snap; dg_add(Q, j); }
-        { DGJob j = dq_job(1, 2, 1, h->dZ1r4 + H1I); j.gw_snap = h->w3snap + 512; dg_add(Q, j); }
-        { DGJob j = dq_job(3, 4, 2, h->dZ1r4 + 2 * H1I); j.gw_snap = h->w3snap + 1024; dg_add(Q, j); }
+        for (int q = 0; q < V.nv; ++q) {
+            const ValueNet &vn = V.vn[q];
+            DGJob j = dq_job(vn.slot, vn.img, q, h->dZ1r4 + q * H1I);
+            j.gw_snap = h->w3snap + 512 * q;   // (the W3 snapshots for the next launch's generated wgrad operands: one per value network)
+            if (vn.net != NET_Q2) { dg_add(Q, j); continue; }
+            if (split) j.N = keep * 32;
+            h->bq_q2_job = Q.njobs;
+            dg_add(Q, j);
+            if (split && st == 0) {   // the rest of the columns: a job of launch "mid" (rew / done of the input set patched at launch)
+                const long long noff = (long long)keep * 32 * 4;
+                DGJob r = dq_job(vn.slot, vn.img, q, h->dZ1r4 + q * H1I + noff);
+                r.N = h1 - keep * 32;
+                r.B = h->c4_q[q] + noff;
+                r.mask = h->H1r4 + vn.img * H1I + noff;
+                h->bq_rest = r;
+            }
+        }
     }
     float *G = h->grad;
     const AdamCtx ctx{0, h->main_p, h->target_p, h->m, h->v, G, h->opt, nullptr, L.n_pi_int,
@@ -1115,61 +1223,230 @@ static int build_sacv_direct(ddrl_sac1 *h, int Bv, int B) {
         j.type = DG_WGRAD_RM; j.M = M; j.N = N; j.K = B; j.A = A; j.lda = lda; j.B = Bm; j.ldb = ldb; j.adam_off = off; j.ldc = N;
         return j;
     };
-    const int img1[3] = {1, 2, 4}, img2r[3] = {1, 2, 3};   // H1r4 / H2r4 slots of q1(x,a), q2(x,a), v(x)
-    {   // ---- backward launch 2: the policy dgrad with its A operand generated in the tile (see the SAC1 tables), the policy-head backward
-        // tiles beside it, layer-2 + head wgrads of the three value networks
+    auto head_wgrad = [&](int q) {   // a value network's head: W3, b3
+        return wgrad_rm(h->H2r4 + V.vn[q].net * H2R, h->Lp2, h2 + 1, h->dq + (long long)q * B, 1, 1, net_off(L, V.vn[q].net).W3);
+    };
+    {   // ---- backward launch 2: the policy dgrad — its A operand (dZ2 of the policy trunk) generated in the tile from the dQ/da
+        // partials (k_dg, bgen = 3), so it does not wait for the policy-head backward tiles, which run beside it and write the
+        // images the policy wgrads of launch 3 contract over —, the value layer-2 + head wgrads (optimizer in the epilogue)
         DGJobs &M = h->dg_mid;
         M = DGJobs{};
         M.B = B; M.Bv = Bv; M.ad = ctx;
         DGJob d{};
-        d.type = DG_DGRAD; d.M = B; d.N = h1; d.K = h2; d.A = h->H2c4; d.lda = B; d.B = h->c4_pi[0]; d.ldb = Kp1;
-        d.bgen = 3; d.dap = h->da_part; d.nparts = (h1 + 31) / 32; d.save0 = h->save0; d.wmu = Pm + L.pi_Wmu; d.wls = Pm + L.pi_Wls;
+        d.type = DG_DGRAD; d.M = B; d.N = h1; d.K = h2; d.A = h->H2c4; d.lda = B; d.B = h->c4_pi[0]; d.ldb = Kp1;   // (B: launch_stage picks the copy)
+        d.bgen = 3; d.dap = h->da_part; d.nparts = ct; d.save0 = h->save0; d.wmu = Pm + L.pi_Wmu; d.wls = Pm + L.pi_Wls;
         d.nact = a; d.alpha = (float)cfg->alpha; d.scale = (float)cfg->act_scale;
-        d.mask = h->H1r4; d.ldmask = h->Lp1; d.C = h->dZ1r4 + 3 * H1I; d.ldc = h->Lp1; d.adam_off = -1;
+        d.mask = h->H1r4; d.ldmask = h->Lp1; d.C = h->dZ1r4 + V.nv * H1I; d.ldc = h->Lp1; d.adam_off = -1;
+        h->mid_pi_job = M.njobs;
         dg_add(M, d);
         DGJob rc{};
         rc.type = DG_ROWS_C; rc.M = B; rc.N = h2; rc.K = 0; rc.nact = a; rc.adam_off = -1;
-        rc.h2c4 = h->H2c4; rc.dap = h->da_part; rc.nparts = (h1 + 31) / 32; rc.save0 = h->save0;
+        rc.h2c4 = h->H2c4; rc.dap = h->da_part; rc.nparts = ct; rc.save0 = h->save0;
         rc.wmu = Pm + L.pi_Wmu; rc.wls = Pm + L.pi_Wls; rc.dz_c4 = h->dzpi_c4; rc.dz_r4 = h->dzpi_r4; rc.dhead_r4 = h->dhead_r4;
         rc.ld_r4 = h->Lp2; rc.alpha = (float)cfg->alpha; rc.scale = (float)cfg->act_scale;
         dg_add(M, rc);
-        for (int q = 0; q < 3; ++q) {
-            DGJob j = wgrad_j4(h->H1r4 + img1[q] * H1I, h->H2r4 + img2r[q] * H2R, vW2[q], vb2[q], h->c4_q[q]);
+        for (int q = 0; q < V.nv; ++q) {
+            const ValueNet &vn = V.vn[q];
+            const NetOff n = net_off(L, vn.net);
+            DGJob j = wgrad_j4(h->H1r4 + vn.img * H1I, h->H2r4 + vn.net * H2R, n.W2, n.b2, h->c4_q[q]);
             j.bgen = 1; j.gw = h->w3snap + 512 * q; j.gdq = h->dq + (long long)q * B;   // (W3 as the previous launch saw it)
+            if (vn.net == NET_Q2) h->mid_q2w_job = M.njobs;
             dg_add(M, j);
         }
-        for (int q = 0; q < 3; ++q) dg_add(M, wgrad_rm(h->H2r4 + img2r[q] * H2R, h->Lp2, h2 + 1, h->dq + (long long)q * B, 1, 1, vW3[q]));
+        h->mid_rest_job = -1;
+        if (!split) {
+            for (int q = 0; q < V.nv; ++q) dg_add(M, head_wgrad(q));
+        } else {
+            // the remaining column tiles of the q2(x, a) dgrad (see launch 1): its prologue needs the launch header of the Q dgrads
+            const DGJobs &Q0 = h->dg_bq[0];
+            M.hp = Q0.hp; M.sacv = 0; M.q_ev0 = Q0.q_ev0; M.q_nev = Q0.q_nev;
+            M.b3q1 = Q0.b3q1; M.b3q2 = Q0.b3q2; M.b3q1t = Q0.b3q1t; M.b3q2t = Q0.b3q2t;
+            M.rew = Q0.rew; M.done = Q0.done; M.logp0 = Q0.logp0; M.logp1 = Q0.logp1;   // (rew / done: launch_stage sets the input set's)
+            M.q1o = Q0.q1o; M.q2o = Q0.q2o; M.dq = Q0.dq; M.loss_part = Q0.loss_part;
+            M.alpha = Q0.alpha; M.gamma = Q0.gamma;
+            h->mid_rest_job = M.njobs;
+            dg_add(M, h->bq_rest);
+        }
     }
-    {   // ---- backward launch 3: policy wgrads (layer 2, heads, layer 1), layer-1 wgrads of the value networks, loss means, optimizer bookkeeping
+    {   // ---- backward launch 3: the wgrads that need launch 2's outputs — policy layer 2 / heads / layer 1, value layer 1 —, loss means,
+        // optimizer bookkeeping.  No hand-off inside the launch: every tile is a plain GEMM tile with its Adam epilogue.
         DGJobs &P = h->dg_pi;
         P = DGJobs{};
         P.B = B; P.Bv = Bv; P.ad = ctx;
-        dg_add(P, wgrad_j4(h->H1r4, h->dzpi_r4, L.pi_W2, L.pi_b2, h->c4_pi[1]));
+        h->pi_w2_job = P.njobs;
+        dg_add(P, wgrad_j4(h->H1r4, h->dzpi_r4, L.pi_W2, L.pi_b2, h->c4_pi[1]));   // (launch_stage picks the shadow copy)
         dg_add(P, wgrad_rm(h->H2r4, h->Lp2, h2 + 1, h->dhead_r4, 32, a, L.pi_Wmu));
         dg_add(P, wgrad_rm(h->H2r4, h->Lp2, h2 + 1, h->dhead_r4 + (long long)a * 4, 32, a, L.pi_Wls));
-        for (int q = 0; q < 3; ++q) {
-            DGJob j = wgrad_rm(q < 2 ? h->xa_r4 : h->xv_r4, 32, (q < 2 ? o + a : o) + 1, h->dZ1r4 + q * H1I, h->Lp1, h1, vW1[q]);
+        for (int q = 0; q <= V.nv; ++q) {   // [W1 ; b1] of the value networks, then of the policy: they live in the layer-1 block layout
+            const int net = q < V.nv ? V.vn[q].net : NET_PI;
+            const bool xa = net == NET_Q1 || net == NET_Q2;
+            DGJob j = wgrad_rm(xa ? h->xa_r4 : (net == NET_V ? h->xv_r4 : h->xp_r4), 32, (xa ? o + a : o) + 1, h->dZ1r4 + q * H1I, h->Lp1, h1, net_off(L, net).W1);
             j.type = DG_WGRAD_W1Y;
             dg_add(P, j);
         }
-        {
-            DGJob j = wgrad_rm(h->xp_r4, 32, o + 1, h->dZ1r4 + 3 * H1I, h->Lp1, h1, L.pi_W1);
-            j.type = DG_WGRAD_W1Y;
-            dg_add(P, j);
-        }
+        if (split)   // the Q-head wgrads (+ Adam + polyak of W3, b3), moved here from launch "mid": nothing reads the head
+                     // kernels between the two launches (the Q layer-2 wgrads of "mid" use the W3 snapshot)
+            for (int q = 0; q < V.nv; ++q) dg_add(P, head_wgrad(q));
         DGJob ls{};
-        ls.type = DG_LOSS; ls.M = 1; ls.N = 1; ls.K = 0; ls.adam_off = -1; ls.loss_part = h->loss_part; ls.losses = h->losses; ls.nl = 4;
+        ls.type = DG_LOSS; ls.M = 1; ls.N = 1; ls.K = 0; ls.adam_off = -1; ls.loss_part = h->loss_part; ls.losses = h->losses; ls.nl = V.nl;
         ls.nparts = -1;   // + the optimizer's books
         dg_add(P, ls);
     }
-    h->rc = RowsC{};
-    h->rc.nl = 4;
+    return DDRL_OK;
+}
+
+// ---- row kernels of the generic path
+static void build_rows(ddrl_sac1 *h) {
+    const Variant &V = variant_of(h);
+    const ddrl_sac1_config_t *cfg = &h->cfg;
+    const Layout &L = h->L;
+    const int B = rows_of(h), o = cfg->obs_dim, a = cfg->act_dim, h1 = cfg->hidden1, h2 = cfg->hidden2;
+    const float *Pm = h->main_p, *Pt = h->target_p;
+    const int ldh1 = h->ldh1, ldh2 = h->ldh2;
+    const long long BZ1 = (long long)B * h1, BZ2 = (long long)B * h2;
+    for (int st = 0; st < 2; ++st) {
+        float **in = h->in[st];
+        if (V.sacv) {
+            h->rav[st] = RowsAV{h->H2, net_pi(Pm, L), net_q(Pm, L, 0), net_q(Pm, L, 1), net_v(Pm, L), net_v(Pt, L), in[5],
+                                h->act0, h->logp0, h->save0, h->q1o, h->q2o, h->vo, h->vto, h->H1,
+                                Pm + L.q_W1[0] + (long long)o * h1, Pm + L.q_W1[1] + (long long)o * h1, B, h2, ldh2, a, h1, ldh1,
+                                (float)cfg->act_scale};
+            h->rbv[st] = RowsBV{h->H2, net_q(Pm, L, 0), net_q(Pm, L, 1), net_v(Pm, L), in[3], in[4], h->logp0, h->q1o, h->q2o,
+                                h->vo, h->vto, h->dZ2, h->dq4, h->loss_part, B, h2, ldh2, (float)cfg->alpha, (float)cfg->gamma};
+        } else {
+            h->ra[st] = RowsA{h->H2, net_pi(Pm, L), net_pi(Pt, L), net_q(Pm, L, 0), net_q(Pm, L, 1), in[5], in[6], in[7],
+                              h->act0, h->act2, h->logp0, h->logp1, h->save0, h->q1o, h->q2o,
+                              h->H1, Pm + L.q_W1[0] + (long long)o * h1, Pt + L.q_W1[0] + (long long)o * h1,
+                              Pt + L.q_W1[1] + (long long)o * h1, B, h2, ldh2, a, h1, ldh1, (float)cfg->act_scale};
+            h->rb[st] = RowsB{h->H2, net_q(Pm, L, 0), net_q(Pm, L, 1), net_q(Pt, L, 0), net_q(Pt, L, 1), in[3], in[4],
+                              h->logp0, h->logp1, h->q1o, h->q2o, h->dZ2, h->dq4, h->loss_part, B, h2, ldh2,
+                              (float)cfg->alpha, (float)cfg->gamma};
+        }
+    }
+    h->rc = RowsC{h->H2, at(h->dZ1, 2 * BZ1), Pm + L.q_W1[0], net_pi(Pm, L), h->save0, h->dhead, at(h->dZ2, (V.nv + 1) * BZ2),
+                  h->loss_part, h->losses, B, h1, h2, ldh2, o, a, h->ldd, h->rows_b_blocks, (float)cfg->alpha,
+                  (float)cfg->act_scale, V.nl};
+}
+
+// ---- create, step 2: the kernel path, the parameter layout and the leading dimensions
+static void init_shape(ddrl_sac1 *h) {
+    const ddrl_sac1_config_t &c = h->cfg;
+    h->fused = direct_ok(c);
+    h->L = make_layout(c, false, h->fused);
+    h->Lp1 = rup32(c.hidden1 + 1); h->Lp2 = rup32(c.hidden2 + 1);  // activation images keep room for the ones column
+    // activations carry one extra physical column of ones (the bias-gradient row of the wgrads)
+    h->ldh1 = (int)pad4(c.hidden1 + 1); h->ldh2 = (int)pad4(c.hidden2 + 1);
+    h->ldxa = (int)pad4(c.obs_dim + c.act_dim + 1); h->ldxp = (int)pad4(c.obs_dim + 1); h->ldd = (int)pad4(2 * c.act_dim);
+    h->rows_b_blocks = rows_of(h);  // per-row loss terms
+    h->mid_rest_job = -1;           // (no Q dgrad columns in launch "mid" unless build_direct splits them off)
+}
+
+// ---- create, step 3: ONE slab for every buffer of the learner (parameters, optimizer state, activations, job tables): a single
+// large allocation is mapped with large page fragments, so the ~30 buffers a stage touches share a handful of TLB entries instead
+// of missing on one 4 KB page each.  The plan is sizes and offsets only; bind_slab points the handle's members into a base address.
+struct SlabPlan {
+    struct Item { float **p; size_t off; };
+    std::vector<Item> items;
+    size_t floats = 0, cnt_off = 0, opt_off = 0, segs_off = 0;
+    size_t reserve(size_t cnt) { const size_t off = floats; floats += (cnt + 63) & ~(size_t)63; return off; }  // 256-B aligned
+    void add(float *&p, size_t cnt) { items.push_back(Item{&p, reserve(cnt)}); }
+};
+static SlabPlan plan_slab(ddrl_sac1 *h) {
+    const ddrl_sac1_config_t &c = h->cfg;
+    const size_t B = (size_t)rows_of(h), o = c.obs_dim, a = c.act_dim, h1 = c.hidden1, h2 = c.hidden2;
+    const size_t NT = (size_t)h->L.total_int, Kp1 = h->L.Kp1, Np2 = h->L.Np2, Lp1 = h->Lp1, Lp2 = h->Lp2;
+    SlabPlan p;
+    p.add(h->main_p, NT); p.add(h->target_p, NT); p.add(h->m, NT); p.add(h->v, NT); p.add(h->grad, NT);
+    for (int st = 0; st < 2; ++st) {   // (ddrl_sac1_step_host takes input set 0 as one contiguous span)
+        const size_t cnt[8] = {B * o, B * o, B * a, B, B, B * a, B * a, B * a};
+        for (int i = 0; i < 8; ++i) p.add(h->in[st][i], cnt[i]);
+    }
+    p.add(h->part, ((B + 31) / 32) * (o + 1) * h1);
+    if (!h->fused) {
+        p.add(h->H1, NEVAL * B * h->ldh1); p.add(h->H2, NEVAL * B * h->ldh2);
+        p.add(h->dZ2, 5 * B * h2); p.add(h->dZ1, 5 * B * h1);
+    } else {
+        // image slots: SAC1 — H1r4 / H2c4: pi(x) q1(x,a) q2(x,a) q1(x,pi); H2r4: pi q1 q2; dZ1r4: q1 q2.  SAC-v adds V to each.
+        const size_t xv = c.variant == DDRL_SAC_V ? 1 : 0;
+        p.add(h->H1r4, (4 + xv) * B * Lp1); p.add(h->H2c4, (4 + xv) * Np2 * B); p.add(h->H2r4, (3 + xv) * B * Lp2);
+        p.add(h->dZ1r4, (3 + xv) * B * Lp1) /* q1 q2 (v) + the policy's (last slot) */; p.add(h->dzpi_c4, Np2 * B); p.add(h->dzpi_r4, B * Lp2);
+        p.add(h->dhead_r4, B * 32); p.add(h->xa_r4, B * 32); p.add(h->xv_r4, B * 32); p.add(h->xp_r4, B * 32); p.add(h->da_part, 16 * B * 4);
+        p.add(h->dq, 3 * B + 256); p.add(h->w3snap, 3 * 512);
+        for (int i = 0; i < 2; ++i) p.add(h->c4_pi[i], Np2 * Kp1);
+        for (size_t i = 0; i < 2 + xv; ++i) p.add(h->c4_q[i], Np2 * Kp1);
+        p.add(h->c4_q2b, Np2 * Kp1);
+    }
+    p.add(h->xa, B * h->ldxa); p.add(h->xp, B * h->ldxp);
+    p.add(h->act0, B * a); p.add(h->act2, B * a); p.add(h->logp0, B); p.add(h->logp1, B); p.add(h->save0, B * a * 4);
+    p.add(h->q1o, B); p.add(h->q2o, B); p.add(h->vo, B); p.add(h->vto, B); p.add(h->dq4, 3 * B * 4); p.add(h->dhead, B * h->ldd);
+    p.add(h->loss_part, (size_t)h->rows_b_blocks * 4); p.add(h->losses, 4);
+    p.add(h->hp, (size_t)NEVAL * DFH * B * DNT);
+    p.cnt_off = p.reserve(64);
+    p.opt_off = p.reserve((2 * sizeof(OptState) + 3) / 4);
+    p.segs_off = p.reserve((h->L.segs.size() * sizeof(Seg) + 3) / 4);
+    (void)p.reserve(2048);  // readable guard behind the last buffer (unclamped tile loads, see OpPre)
+    return p;
+}
+static void bind_slab(ddrl_sac1 *h, const SlabPlan &p, float *base) {
+    h->slab = base;
+    for (const auto &it : p.items) *it.p = base + it.off;
+    h->opt = reinterpret_cast<OptState *>(base + p.opt_off);
+    h->part_cnt = reinterpret_cast<int *>(base + p.cnt_off);
+    h->segs_d = reinterpret_cast<Seg *>(base + p.segs_off);
+}
+static int alloc_slab(ddrl_sac1 *h, const SlabPlan &p) {
+    float *base = nullptr;
+    hipError_t e = hipMalloc((void **)&base, p.floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(base, 0, p.floats * sizeof(float));
+    if (e != hipSuccess) {
+        ddrl::set_error("hipMalloc of %zu bytes failed in ddrl_sac1_create: %s", p.floats * sizeof(float), hipGetErrorString(e));
+        if (base) (void)hipFree(base);
+        return DDRL_ERR_NOMEM;
+    }
+    bind_slab(h, p, base);
+    DDRL_HIP_CHECK(hipMemcpy(h->segs_d, h->L.segs.data(), h->L.segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
+    return reset_opt(h, nullptr);
+}
+
+// ---- create, step 4: the physical ones columns (never overwritten: kernels write columns < h1 / h2 / obs(+act) only)
+static int fill_ones(ddrl_sac1 *h) {
+    const ddrl_sac1_config_t &c = h->cfg;
+    const int B = rows_of(h), o = c.obs_dim, a = c.act_dim, h1 = c.hidden1, h2 = c.hidden2;
+    if (!h->fused) {
+        k_fill_col<<<(NEVAL * B + 255) / 256, 256>>>(h->H1, (long long)NEVAL * B, h->ldh1, h1, 1.0f);
+        k_fill_col<<<(NEVAL * B + 255) / 256, 256>>>(h->H2, (long long)NEVAL * B, h->ldh2, h2, 1.0f);
+    } else {  // x4 images [row/4][ld][4]: "column" c of every row = four consecutive floats per row group
+        const int xv = c.variant == DDRL_SAC_V ? 1 : 0;
+        k_fill_col4<<<((4 + xv) * B / 4 + 255) / 256, 256>>>(h->H1r4, (long long)(4 + xv) * B / 4, h->Lp1, h1);
+        k_fill_col4<<<((3 + xv) * B / 4 + 255) / 256, 256>>>(h->H2r4, (long long)(3 + xv) * B / 4, h->Lp2, h2);
+        k_fill_col4<<<(B / 4 + 255) / 256, 256>>>(h->xa_r4, (long long)B / 4, 32, o + a);
+        k_fill_col4<<<(B / 4 + 255) / 256, 256>>>(h->xv_r4, (long long)B / 4, 32, o);
+        k_fill_col4<<<(B / 4 + 255) / 256, 256>>>(h->xp_r4, (long long)B / 4, 32, o);
+    }
+    k_fill_col<<<(B + 255) / 256, 256>>>(h->xa, B, h->ldxa, o + a, 1.0f);
+    k_fill_col<<<(B + 255) / 256, 256>>>(h->xp, B, h->ldxp, o, 1.0f);
+    DDRL_LAUNCH_CHECK();
+    DDRL_HIP_CHECK(hipDeviceSynchronize());
+    return DDRL_OK;
+}
+
+// ---- create, step 5: the job tables of the kernel path, the flat optimizer step and the launch state.  Pointer arithmetic over the
+// bound slab only: nothing here touches the device.
+static int build_tables(ddrl_sac1 *h) {
+    const Variant &V = variant_of(h);
+    const ddrl_sac1_config_t *cfg = &h->cfg;
+    const Layout &L = h->L;
+    const int B = rows_of(h), o = cfg->obs_dim, h1 = cfg->hidden1;
+    const int rc = h->fused ? build_direct(h, cfg->batch, B) : build_generic(h);
+    if (rc != DDRL_OK) return rc;
+    if (h->fused && V.sacv) h->rc.nl = V.nl;   // (the direct path reads the loss count only; SAC1 has always filled its row tables there too)
+    else build_rows(h);
     h->ad = AdamArgs{h->main_p, h->target_p, h->m, h->v, h->grad, h->opt, h->opt + 1, L.total_int, L.n_pi_int, 0,
                      (float)cfg->lr, (float)cfg->beta1, (float)cfg->beta2, (float)cfg->adam_eps,
                      (float)cfg->polyak, (float)(1.0 - cfg->polyak),
-                     h->part, L.pi_W1 / 4, (long long)(o + 1) * h1 / 4, (long long)(o + 1) * h1 / 4, 0, 0u};
-    h->noise_armed = false; h->noise_seed = 0; h->noise_pending = 0; h->grad_imported = false;
-    h->fuse_apply = false; h->sample_armed = false;
+                     h->part, L.pi_W1 / 4, (long long)(o + 1) * h1 / 4, (long long)(o + 1) * h1 / 4,
+                     h->fused_l1_wgrad ? (B + 31) / 32 : 0, 0u};
+    h->ls = LaunchState{};
     return DDRL_OK;
 }
 
@@ -1186,404 +1463,18 @@ int ddrl_sac1_param_counts(const ddrl_sac1_config_t *cfg, int64_t *n_pi, int64_t
 
 int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) {
     DDRL_REQUIRE(out != nullptr, "out is NULL");
-    int rc = check_cfg(cfg);
+    int rc = check_cfg(cfg);                                                      // 1. check
     if (rc != DDRL_OK) return rc;
     ddrl::DeviceGuard g(device);
     if (!g.ok) { ddrl::set_error("cannot select device %d", device); return DDRL_ERR_HIP; }
     ddrl_sac1 *h = new ddrl_sac1();  // value-initialised: every pointer/job table starts zeroed
-    h->mid_rest_job = -1;            // (no Q dgrad columns in launch "mid" unless the SAC1 direct build below splits them off)
     h->device = device;
     h->cfg = *cfg;
-    h->fused = direct_ok(*cfg);
-    h->L = make_layout(*cfg, false, h->fused);
-    const Layout &L = h->L;
-    // direct-operand path: every row-indexed buffer holds a whole number of 32-row tiles; rows past the batch are padding
-    // (zero inputs, no loss terms, zero upstream gradients) and means run over the Bv valid rows
-    const int Bv = cfg->batch, B = h->fused ? (int)rup32(Bv) : Bv;
-    const int o = cfg->obs_dim, a = cfg->act_dim, h1 = cfg->hidden1, h2 = cfg->hidden2;
-    const size_t NT = (size_t)L.total_int;
-    const int Kp1 = L.Kp1, Np2 = L.Np2;
-    h->Lp1 = rup32(h1 + 1); h->Lp2 = rup32(h2 + 1);  // activation images keep room for the ones column
-    // ONE slab for every buffer of the learner (parameters, optimizer state, activations, job
-    // tables): a single large allocation is mapped with large page fragments, so the ~30 buffers a
-    // stage touches share a handful of TLB entries instead of missing on one 4 KB page each.
-    h->rows_b_blocks = B;  // per-row loss terms
-    size_t slab_floats = 0;
-    auto reserve = [&](size_t cnt) { size_t off = slab_floats; slab_floats += (cnt + 63) & ~(size_t)63; return off; };  // 256-B aligned
-    struct Item { float **p; size_t off; };
-    std::vector<Item> items;
-#define ALLOC(ptr, cnt) items.push_back(Item{&h->ptr, reserve((size_t)(cnt))})
-    // activations carry one extra physical column of ones (the bias-gradient row of the wgrads)
-    h->ldh1 = (int)pad4(h1 + 1); h->ldh2 = (int)pad4(h2 + 1);
-    h->ldxa = (int)pad4(o + a + 1); h->ldxp = (int)pad4(o + 1); h->ldd = (int)pad4(2 * a);
-    ALLOC(main_p, NT); ALLOC(target_p, NT); ALLOC(m, NT); ALLOC(v, NT); ALLOC(grad, NT);
-    for (int st = 0; st < 2; ++st) {
-        const size_t cnt[8] = {(size_t)B * o, (size_t)B * o, (size_t)B * a, (size_t)B, (size_t)B, (size_t)B * a, (size_t)B * a, (size_t)B * a};
-        for (int i = 0; i < 8; ++i) items.push_back(Item{&h->in[st][i], reserve(cnt[i])});
-    }
-    ALLOC(part, (size_t)((B + 31) / 32) * (o + 1) * h1);
-    if (!h->fused) {
-        ALLOC(H1, (size_t)NEVAL * B * h->ldh1); ALLOC(H2, (size_t)NEVAL * B * h->ldh2);
-        ALLOC(dZ2, (size_t)5 * B * h2); ALLOC(dZ1, (size_t)5 * B * h1);
-    } else {
-        // image slots: SAC1 — H1r4 / H2c4: pi(x) q1(x,a) q2(x,a) q1(x,pi); H2r4: pi q1 q2; dZ1r4: q1 q2.  SAC-v adds V to each.
-        const int xv = cfg->variant == DDRL_SAC_V ? 1 : 0;
-        ALLOC(H1r4, (size_t)(4 + xv) * B * h->Lp1); ALLOC(H2c4, (size_t)(4 + xv) * Np2 * B); ALLOC(H2r4, (size_t)(3 + xv) * B * h->Lp2);
-        ALLOC(dZ1r4, (size_t)(3 + xv) * B * h->Lp1) /* q1 q2 (v) + the policy's (last slot) */; ALLOC(dzpi_c4, (size_t)Np2 * B); ALLOC(dzpi_r4, (size_t)B * h->Lp2);
-        ALLOC(dhead_r4, (size_t)B * 32); ALLOC(xa_r4, (size_t)B * 32); ALLOC(xv_r4, (size_t)B * 32); ALLOC(xp_r4, (size_t)B * 32); ALLOC(da_part, (size_t)16 * B * 4);
-        ALLOC(dq, (size_t)3 * B + 256); ALLOC(w3snap, (size_t)3 * 512);
-        for (int i = 0; i < 2; ++i) items.push_back(Item{&h->c4_pi[i], reserve((size_t)Np2 * Kp1)});
-        for (int i = 0; i < 2 + xv; ++i) items.push_back(Item{&h->c4_q[i], reserve((size_t)Np2 * Kp1)});
-        items.push_back(Item{&h->c4_q2b, reserve((size_t)Np2 * Kp1)});
-    }
-    ALLOC(xa, (size_t)B * h->ldxa); ALLOC(xp, (size_t)B * h->ldxp);
-    ALLOC(act0, B * a); ALLOC(act2, B * a); ALLOC(logp0, B); ALLOC(logp1, B); ALLOC(save0, (size_t)B * a * 4);
-    ALLOC(q1o, B); ALLOC(q2o, B); ALLOC(vo, B); ALLOC(vto, B); ALLOC(dq4, (size_t)3 * B * 4); ALLOC(dhead, (size_t)B * h->ldd);
-    ALLOC(loss_part, (size_t)h->rows_b_blocks * 4); ALLOC(losses, 4);
-    const int nt2 = (h2 + 31) / 32;
-    ALLOC(hp, (size_t)NEVAL * DFH * B * DNT);
-#undef ALLOC
-    const size_t cnt_off = reserve(64);
-    const size_t opt_off = reserve((2 * sizeof(OptState) + 3) / 4);
-    const size_t segs_off = reserve((L.segs.size() * sizeof(Seg) + 3) / 4);
-    (void)reserve(2048);  // readable guard behind the last buffer (unclamped tile loads, see OpPre)
-    hipError_t e = hipMalloc((void **)&h->slab, slab_floats * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(h->slab, 0, slab_floats * sizeof(float));
-    if (e != hipSuccess) {
-        ddrl::set_error("hipMalloc of %zu bytes failed in ddrl_sac1_create: %s", slab_floats * sizeof(float), hipGetErrorString(e));
-        sac1_free(h);
-        return DDRL_ERR_NOMEM;
-    }
-    for (auto &it : items) *it.p = h->slab + it.off;
-    h->opt = reinterpret_cast<OptState *>(h->slab + opt_off);
-    h->part_cnt = reinterpret_cast<int *>(h->slab + cnt_off);
-    h->segs_d = reinterpret_cast<Seg *>(h->slab + segs_off);
-    DDRL_HIP_CHECK(hipMemcpy(h->segs_d, L.segs.data(), L.segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
-    rc = reset_opt(h, nullptr);
+    init_shape(h);                                                                // 2. layout
+    rc = alloc_slab(h, plan_slab(h));                                             // 3. plan and allocate the slab
+    if (rc == DDRL_OK) rc = fill_ones(h);                                         // 4. the ones columns
+    if (rc == DDRL_OK) rc = build_tables(h);                                      // 5. the tables
     if (rc != DDRL_OK) { sac1_free(h); return rc; }
-
-    // the physical ones columns (never overwritten: kernels write columns < h1 / h2 / obs(+act) only)
-    if (!h->fused) {
-        k_fill_col<<<(NEVAL * B + 255) / 256, 256>>>(h->H1, (long long)NEVAL * B, h->ldh1, h1, 1.0f);
-        k_fill_col<<<(NEVAL * B + 255) / 256, 256>>>(h->H2, (long long)NEVAL * B, h->ldh2, h2, 1.0f);
-    } else {  // x4 images [row/4][ld][4]: "column" c of every row = four consecutive floats per row group
-        const int xv = cfg->variant == DDRL_SAC_V ? 1 : 0;
-        k_fill_col4<<<((4 + xv) * B / 4 + 255) / 256, 256>>>(h->H1r4, (long long)(4 + xv) * B / 4, h->Lp1, h1);
-        k_fill_col4<<<((3 + xv) * B / 4 + 255) / 256, 256>>>(h->H2r4, (long long)(3 + xv) * B / 4, h->Lp2, h2);
-        k_fill_col4<<<(B / 4 + 255) / 256, 256>>>(h->xa_r4, (long long)B / 4, 32, o + a);
-        k_fill_col4<<<(B / 4 + 255) / 256, 256>>>(h->xv_r4, (long long)B / 4, 32, o);
-        k_fill_col4<<<(B / 4 + 255) / 256, 256>>>(h->xp_r4, (long long)B / 4, 32, o);
-    }
-    k_fill_col<<<(B + 255) / 256, 256>>>(h->xa, B, h->ldxa, o + a, 1.0f);
-    k_fill_col<<<(B + 255) / 256, 256>>>(h->xp, B, h->ldxp, o, 1.0f);
-    DDRL_LAUNCH_CHECK();
-    DDRL_HIP_CHECK(hipDeviceSynchronize());
-
-    if (cfg->variant == DDRL_SAC_V) {
-        rc = h->fused ? build_sacv_direct(h, Bv, B) : build_sacv(h);
-        if (rc != DDRL_OK) { sac1_free(h); return rc; }
-        *out = h;
-        return DDRL_OK;
-    }
-    const float *Pm = h->main_p, *Pt = h->target_p;
-    const int ldh1 = h->ldh1, ldh2 = h->ldh2;
-    const long long BH1 = (long long)B * ldh1, BH2 = (long long)B * ldh2, BZ1 = (long long)B * h1, BZ2 = (long long)B * h2;
-    if (!h->fused) {
-    // ---- layer-1 jobs (one table per input set).  evals: 0 pi(x) 1 pi(x2) 2 piT(x2) 3 q1(x,a) 4 q2(x,a) |
-    // 5 q1(x,pi) 6 q1T(x2,piT) 7 q2T(x2,piT): observation part only here, finished by k_rows_a
-    for (int st = 0; st < 2; ++st) {
-        float *x = h->in[st][0], *x2 = h->in[st][1], *ac = h->in[st][2];
-        auto l1 = [&](const float *in0, int d0, const float *in1, int d1, const float *W, const float *b, int ev, int pre) {
-            return L1Job{in0, in1, W, b, h->H1 + ev * BH1, nullptr, d0, d1, B, h1, ldh1, 0, pre};
-        };
-        L1Jobs &J = h->l1a[st];
-        J.njobs = 8;
-        J.noise_on = 0; J.act = a; J.n_each = B * a; J.noise_seed = 0;
-        J.e0 = h->in[st][5]; J.e1 = h->in[st][6]; J.e2 = h->in[st][7]; J.opt = h->opt;
-        J.job[0] = l1(x, o, nullptr, 0, Pm + L.pi_W1, Pm + L.pi_b1, 0, 0);
-        J.job[1] = l1(x2, o, nullptr, 0, Pm + L.pi_W1, Pm + L.pi_b1, 1, 0);
-        J.job[2] = l1(x2, o, nullptr, 0, Pt + L.pi_W1, Pt + L.pi_b1, 2, 0);
-        J.job[3] = l1(x, o, ac, a, Pm + L.q_W1[0], Pm + L.q_b1[0], 3, 0);
-        J.job[4] = l1(x, o, ac, a, Pm + L.q_W1[1], Pm + L.q_b1[1], 4, 0);
-        J.job[5] = l1(x, o, nullptr, a, Pm + L.q_W1[0], Pm + L.q_b1[0], 5, 1);
-        J.job[6] = l1(x2, o, nullptr, a, Pt + L.q_W1[0], Pt + L.q_b1[0], 6, 1);
-        J.job[7] = l1(x2, o, nullptr, a, Pt + L.q_W1[1], Pt + L.q_b1[1], 7, 1);
-        J.job[0].aug_out = h->xp; J.job[0].aug_ld = h->ldxp;  // [x | 1]      : A operand of the pi layer-1 wgrad
-        J.job[3].aug_out = h->xa; J.job[3].aug_ld = h->ldxa;  // [x | a | 1]  : A operand of the Q layer-1 wgrads
-    }
-    // ---- forward layer-2 GEMMs
-    auto fwd = [&](const float *P, long long W2, long long b2, int ev) {
-        return gemm_fwd(h->H1 + ev * BH1, ldh1, P + W2, P + b2, h->H2 + ev * BH2, ldh2, B, h1, h2);
-    };
-    gemm_add(h->g_fa, fwd(Pm, L.pi_W2, L.pi_b2, 0));
-    gemm_add(h->g_fa, fwd(Pm, L.pi_W2, L.pi_b2, 1));
-    gemm_add(h->g_fa, fwd(Pt, L.pi_W2, L.pi_b2, 2));
-    gemm_add(h->g_fa, fwd(Pm, L.q_W2[0], L.q_b2[0], 3));
-    gemm_add(h->g_fa, fwd(Pm, L.q_W2[1], L.q_b2[1], 4));
-    gemm_add(h->g_fb, fwd(Pm, L.q_W2[0], L.q_b2[0], 5));
-    gemm_add(h->g_fb, fwd(Pt, L.q_W2[0], L.q_b2[0], 6));
-    gemm_add(h->g_fb, fwd(Pt, L.q_W2[1], L.q_b2[1], 7));
-    // ---- backward GEMM launches.  dZ2 / dZ1 slots: 0 q1(x,a), 1 q2(x,a), 2 q1(x,pi), 3 pi.
-    // Every bias gradient rides as the "ones column" row of its kernel's wgrad.
-    float *G = h->grad;
-    // launch "bwd Q": needs dZ2[0..2], dq4
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 2 * BZ2, Pm + L.q_W2[0], h->H1 + 5 * BH1, ldh1, h->dZ1 + 2 * BZ1, B, h1, h2));
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 0 * BZ2, Pm + L.q_W2[0], h->H1 + 3 * BH1, ldh1, h->dZ1 + 0 * BZ1, B, h1, h2));
-    gemm_add(h->g_bq, gemm_dgrad(h->dZ2 + 1 * BZ2, Pm + L.q_W2[1], h->H1 + 4 * BH1, ldh1, h->dZ1 + 1 * BZ1, B, h1, h2));
-    for (int q = 0; q < 2; ++q) {
-        gemm_add(h->g_bq, gemm_wgrad(h->H1 + (3 + q) * BH1, ldh1, h1, h->dZ2 + q * BZ2, h2, h2, G + L.q_W2[q], h2, B));       // W2, b2
-        gemm_add(h->g_bq, gemm_wgrad(h->H2 + (3 + q) * BH2, ldh2, h2, h->dq4 + (long long)q * B * 4, 4, 1, G + L.q_W3[q], 1, B));  // W3, b3
-    }
-    // launch "bwd pi": needs dZ2[3], dhead (k_rows_c) and dZ1[0..1] (launch above)
-    {
-        GemmJob j = gemm_dgrad(h->dZ2 + 3 * BZ2, Pm + L.pi_W2, h->H1 + 0 * BH1, ldh1, h->dZ1 + 3 * BZ1, B, h1, h2);
-        h->fused_l1_wgrad = (h1 % 4 == 0) && (o + 1 <= 12) && (L.pi_W1 % 4 == 0);
-        if (h->fused_l1_wgrad) { j.part_x = h->xp; j.part = h->part; j.part_nk = o + 1; j.part_ldx = h->ldxp; }
-        gemm_add(h->g_bpi, j);
-    }
-    gemm_add(h->g_bpi, gemm_wgrad(h->H1 + 0 * BH1, ldh1, h1, h->dZ2 + 3 * BZ2, h2, h2, G + L.pi_W2, h2, B));     // W2, b2
-    gemm_add(h->g_bpi, gemm_wgrad(h->H2, ldh2, h2, h->dhead, h->ldd, a, G + L.pi_Wmu, a, B));                      // Wmu, bmu
-    gemm_add(h->g_bpi, gemm_wgrad(h->H2, ldh2, h2, h->dhead + a, h->ldd, a, G + L.pi_Wls, a, B));                  // Wls, bls
-    for (int q = 0; q < 2; ++q)
-        gemm_add(h->g_bpi, gemm_wgrad(h->xa, h->ldxa, o + a, h->dZ1 + q * BZ1, h1, h1, G + L.q_W1[q], h1, B));    // Q W1, b1
-    // launch "last" (only when the fused form is unavailable): needs dZ1[3]
-    if (!h->fused_l1_wgrad) gemm_add(h->g_last, gemm_wgrad(h->xp, h->ldxp, o, h->dZ1 + 3 * BZ1, h1, h1, G + L.pi_W1, h1, B));               // pi W1, b1
-
-    }
-    // ---- direct-operand path (sac1_direct.h)
-    if (h->fused) {
-        if (L.pi_bmu != pi_bmu_off(h1, Np2, h2, a) || L.pi_bls != pi_bls_off(h1, Np2, h2, a)) {   // (k_dfwd<1> forms these addresses itself)
-            ddrl::set_error("internal: policy-head bias offsets of the direct layout");
-            sac1_free(h);
-            return DDRL_ERR_BAD_ARG;
-        }
-        h->fused_l1_wgrad = false;   // (direct path: the policy's layer-1 wgrad is a job of its own, no row-tile partials)
-        h->sh_cur = 0;
-        const float *S = h->slab;
-        const long long HP = (long long)DFH * B * DNT;
-        const long long H1I = (long long)B * h->Lp1, H2C = (long long)Np2 * B, H2R = (long long)B * h->Lp2;
-        // image slots — H1r4: 0 pi(x) 1 q1(x,a) 2 q2(x,a) 3 q1(x,pi);  H2c4: same;  H2r4: 0 pi(x) 1 q1(x,a) 2 q2(x,a)
-        auto steps = [](int D) { return D + 1 <= 8 ? 4 : 4 + (D + 1 - 8 + 1) / 2; };  // input columns + the bias column, two per MFMA step
-        for (int st = 0; st < 2; ++st) {
-            auto head = [&](DFHead &d) {
-                d = DFHead{};
-                d.base = S; d.tiles_m = B / 32; d.tpj = (B / 32) * nt2; d.K = h1; d.Np = Np2; d.B = B; d.d0 = o;
-                d.x_off = (int)(h->in[st][0] - S);
-                d.main_off = (int)(Pm - S); d.targ_off = (int)(Pt - S); d.npi = (int)L.q_W1[0]; d.perq = (int)(L.q_W1[1] - L.q_W1[0]);
-                d.hp_off = (int)(h->hp - S);
-            };
-            auto args = [&](DFArgs &F, int njobs) {
-                F = DFArgs{};
-                F.njobs = njobs; F.tiles_n = nt2; F.act = a; F.Lp1 = h->Lp1; F.Lp2 = h->Lp2; F.h2 = h2;
-                F.scale = (float)cfg->act_scale;
-                F.act0 = h->act0; F.act2 = h->act2; F.logp0 = h->logp0; F.logp1 = h->logp1; F.save0 = h->save0;
-                F.php1 = h->hp + 1 * HP;
-                F.pev_pack = 0 | (2 << 2) | (2 << 4);   // q1(x, pi(x)) <- evaluation 0; the target Qs <- evaluation 2 (pi_targ(x2))
-                F.pin_pack = 0 | ((2 | 4) << 3) | ((2 | 4) << 6);   // evaluation 0: main copy, eps_x; evaluation 2: target copy, eps_t
-                F.noise_on = 0; F.n_each = Bv * a; F.Bv = Bv; F.noise_seed = 0;
-                F.e0 = h->in[st][5]; F.e1 = h->in[st][6]; F.e2 = h->in[st][7]; F.opt = h->opt;
-            };
-            auto pij = [&](const float *P, int ev) {
-                DFJob j{};
-                j.b2 = P + L.pi_b2; j.wh0 = P + L.pi_Wmu; j.wh1 = P + L.pi_Wls; j.nh = 2 * a; j.hsplit = a; j.hstride = a;
-                j.hp = h->hp + ev * HP;
-                return j;
-            };
-            auto qj = [&](const float *P, int q, int ev) {
-                DFJob j{};
-                j.b2 = P + L.q_b2[q]; j.wh0 = P + L.q_W3[q]; j.wh1 = j.wh0; j.nh = 1; j.hsplit = 1; j.hstride = 1;
-                j.hp = h->hp + ev * HP;
-                return j;
-            };
-            const int ns_pi = steps(o) - 4, ns_q = steps(o + a) - 4;
-            DFHead &HA = h->fh_a[st], &HB = h->fh_b[st];
-            DFArgs &FA = h->f_a[st], &FB = h->f_b[st];
-            // Q1(x, a), Q2(x, a) need nothing from the policy: they run in phase 1 beside the policy-dependent evaluations (k_dfwd:
-            // "stored") when the tile counts allow the per-XCD split, else in phase 0 as before.  DDRL_QXA_PHASE=0 forces phase 0.
-            const int tpj_f = (B / 32) * nt2;
-            static const int qxa_phase = getenv("DDRL_QXA_PHASE") ? atoi(getenv("DDRL_QXA_PHASE")) : 1;
-            const bool q_late = qxa_phase == 1 && (3 * tpj_f) % 8 == 0 && (2 * tpj_f) % 8 == 0;
-            head(HA); args(FA, q_late ? 3 : 5);
-            FA.job[0] = pij(Pm, 0); FA.job[0].H2c4 = h->H2c4; FA.job[0].H2r4 = h->H2r4; FA.job[0].H1r4 = h->H1r4;
-            FA.job[0].xr4 = h->xp_r4;   // [x | 1] as an x4 image: A operand of the policy's layer-1 wgrad
-            FA.job[1] = pij(Pm, 1);
-            FA.job[2] = pij(Pt, 2);
-            DFJob qa1 = qj(Pm, 0, 3); qa1.H2c4 = h->H2c4 + 1 * H2C; qa1.H2r4 = h->H2r4 + 1 * H2R; qa1.H1r4 = h->H1r4 + 1 * H1I;
-            qa1.xr4 = h->xa_r4;
-            DFJob qa2 = qj(Pm, 1, 4); qa2.H2c4 = h->H2c4 + 2 * H2C; qa2.H2r4 = h->H2r4 + 2 * H2R; qa2.H1r4 = h->H1r4 + 2 * H1I;
-            if (!q_late) { FA.job[3] = qa1; FA.job[4] = qa2; }
-            head(HB); args(FB, q_late ? 5 : 3);
-            if (q_late) { FB.job[3] = qa1; FB.job[4] = qa2; }
-            {   // pack field of a job: steps | obs2 << 2 | target << 3 | network << 4
-                auto pk = [](int ns, int x2, int targ, int net) { return ns | (x2 << 2) | (targ << 3) | (net << 4); };
-                const int qxa = (pk(ns_q, 0, 0, 1) << 18) | (pk(ns_q, 0, 0, 2) << 24);
-                HA.pack = pk(ns_pi, 0, 0, 0) | (pk(ns_pi, 1, 0, 0) << 6) | (pk(ns_pi, 1, 1, 0) << 12) | (q_late ? 0 : qxa);
-                HB.pack = pk(ns_q, 0, 0, 1) | (pk(ns_q, 1, 1, 1) << 6) | (pk(ns_q, 1, 1, 2) << 12) | (q_late ? (qxa | (1 << 30)) : 0);
-            }
-            auto from_pi = [&](DFJob &j, int pev, int side) { j.php = h->hp + pev * HP; j.side = side; };
-            FB.job[0] = qj(Pm, 0, 5); from_pi(FB.job[0], 0, 1);
-            FB.job[0].H2c4 = h->H2c4 + 3 * H2C; FB.job[0].H1r4 = h->H1r4 + 3 * H1I;
-            FB.job[1] = qj(Pt, 0, 6); from_pi(FB.job[1], 2, 2);
-            FB.job[2] = qj(Pt, 1, 7); from_pi(FB.job[2], 2, 0);
-            // ---- backward launch 1: the three Q dgrads (slot 2 first: its dQ/da partials are what the next launch waits for)
-            DGJobs &Q = h->dg_bq[st];
-            Q = DGJobs{};
-            Q.hp = h->hp; Q.B = B; Q.Bv = Bv; Q.sacv = 0; Q.q_ev0 = 3; Q.q_nev = 5;
-            Q.b3q1 = Pm + L.q_b3[0]; Q.b3q2 = Pm + L.q_b3[1]; Q.b3q1t = Pt + L.q_b3[0]; Q.b3q2t = Pt + L.q_b3[1];
-            Q.rew = h->in[st][3]; Q.done = h->in[st][4]; Q.logp0 = h->logp0; Q.logp1 = h->logp1;
-            Q.q1o = h->q1o; Q.q2o = h->q2o; Q.dq = h->dq; Q.loss_part = h->loss_part;
-            Q.alpha = (float)cfg->alpha; Q.gamma = (float)cfg->gamma;
-            auto dq_job = [&](int slot, int img, int q, float *C) {
-                DGJob j{};
-                j.type = DG_DGRAD_Q; j.M = B; j.N = h1; j.K = h2; j.slot = slot;
-                j.A = h->H2c4 + img * H2C; j.lda = B; j.B = h->c4_q[q]; j.ldb = Kp1;
-                j.gw = Pm + L.q_W3[q]; j.gdq = nullptr; j.gconst = -1.0f / (float)Bv;
-                j.mask = h->H1r4 + img * H1I; j.ldmask = h->Lp1; j.C = C; j.ldc = h->Lp1; j.adam_off = -1;
-                return j;
-            };
-            {
-                DGJob j = dq_job(2, 3, 0, nullptr);
-                j.wa = Pm + L.q_W1[0]; j.wa_d0 = o; j.da_part = h->da_part; j.nact = a;
-                dg_add(Q, j);
-            }
-            // (the W3 snapshots for the next launch's generated wgrad operands)
-            { DGJob j = dq_job(0, 1, 0, h->dZ1r4); j.gw_snap = h->w3snap; dg_add(Q, j); }
-            // Tile counts against the 256 CUs (profiles/r05_update_experiments.txt: a launch pays +1.2 ... +2.1 us where its tile count
-            // crosses a multiple of 256 and is flat in between): the three Q dgrads are 3 x 104 = 312 tiles at config 2 — 56 over.  Only the
-            // last launch reads the dZ1 of the stored-action dgrads (the Q layer-1 wgrads), so the q2(x, a) dgrad is cut by COLUMN tiles: the
-            // first `bq_cols` stay here (launch = 256 tiles), the rest run in launch "mid" (which the two Q-head wgrads leave for launch
-            // "pi": 464 - 20 + 56 = 500 <= 512; "pi": 190 + 20 = 210 <= 256).  A column sub-range of a dgrad is a job of its own — operand B,
-            // the relu mask and the output image start n_off columns further — with the same arithmetic per tile: bit-identical results.
-            {
-                const int tm = B / 32, ct = (h1 + 31) / 32, T = tm * ct, ncu = 256;
-                static const int want = getenv("DDRL_BQ_SPLIT") ? atoi(getenv("DDRL_BQ_SPLIT")) : 1;
-                int keep = ct;   // column tiles of the q2(x, a) dgrad that stay in this launch
-                const int rm_tiles = 2 * ((h2 + 1 + 31) / 32);                                  // the two Q-head wgrads (one column tile each)
-                const int mid_now = T + tm * ((h2 + 31) / 32) + 2 * ((h1 + 1 + 31) / 32) * ((h2 + 31) / 32) + rm_tiles;
-                const int pi_now = ((h1 + 1 + 31) / 32) * ((h2 + 31) / 32) + rm_tiles + 3 * ct + 1;
-                if (want && 3 * T > ncu && 2 * T < ncu) {
-                    const int k = (ncu - 2 * T) / tm, moved = (ct - k) * tm;
-                    if (k >= 1 && k < ct && mid_now - rm_tiles + moved <= 2 * ncu && pi_now + rm_tiles <= ncu) keep = k;
-                }
-                h->bq_cols = keep;
-                DGJob j = dq_job(1, 2, 1, h->dZ1r4 + H1I);
-                j.gw_snap = h->w3snap + 512;
-                if (keep < ct) j.N = keep * 32;
-                dg_add(Q, j);
-                if (keep < ct && st == 0) {   // the rest of the columns: a job of launch "mid" (rew / done of the input set patched at launch)
-                    const long long noff = (long long)keep * 32 * 4;
-                    DGJob r = dq_job(1, 2, 1, h->dZ1r4 + H1I + noff);
-                    r.N = h1 - keep * 32;
-                    r.B = h->c4_q[1] + noff;
-                    r.mask = h->H1r4 + 2 * H1I + noff;
-                    h->bq_rest = r;
-                }
-            }
-        }
-        float *G = h->grad;
-        const AdamCtx ctx{0, h->main_p, h->target_p, h->m, h->v, G, h->opt, nullptr, L.n_pi_int,
-                          (float)cfg->lr, (float)cfg->beta1, (float)cfg->beta2, (float)cfg->adam_eps,
-                          (float)cfg->polyak, (float)(1.0 - cfg->polyak), 0u};
-        auto wgrad_j4 = [&](const float *A, const float *Bm, long long w_off, long long b_off, float *shadow) {
-            DGJob j{};
-            j.type = DG_WGRAD_J4; j.M = h1 + 1; j.N = h2; j.K = B;
-            j.A = A; j.lda = h->Lp1; j.B = Bm; j.ldb = h->Lp2;
-            j.adam_off = w_off; j.ldc = Np2; j.bias_off = b_off; j.bias_row = h1; j.shadow = shadow; j.ld_sh = Kp1;
-            return j;
-        };
-        auto wgrad_rm = [&](const float *A, int lda, int M, const float *Bm, int ldb, int N, long long off) {
-            DGJob j{};
-            j.type = DG_WGRAD_RM; j.M = M; j.N = N; j.K = B; j.A = A; j.lda = lda; j.B = Bm; j.ldb = ldb; j.adam_off = off; j.ldc = N;
-            return j;
-        };
-        {   // ---- backward launch 2: the policy dgrad — its A operand (dZ2 of the policy trunk) generated in the tile from the dQ/da
-            // partials (k_dg, bgen = 3), so it does not wait for the policy-head backward tiles, which run beside it and write the
-            // images the policy wgrads of launch 3 contract over —, the Q layer-2 + head wgrads (optimizer in the epilogue)
-            DGJobs &M = h->dg_mid;
-            M = DGJobs{};
-            M.B = B; M.Bv = Bv; M.ad = ctx;
-            DGJob d{};
-            d.type = DG_DGRAD; d.M = B; d.N = h1; d.K = h2; d.A = h->H2c4; d.lda = B; d.B = h->c4_pi[0]; d.ldb = Kp1;   // (B: launch_stage picks the copy)
-            d.bgen = 3; d.dap = h->da_part; d.nparts = (h1 + 31) / 32; d.save0 = h->save0; d.wmu = Pm + L.pi_Wmu; d.wls = Pm + L.pi_Wls;
-            d.nact = a; d.alpha = (float)cfg->alpha; d.scale = (float)cfg->act_scale;
-            d.mask = h->H1r4; d.ldmask = h->Lp1; d.C = h->dZ1r4 + 2 * H1I; d.ldc = h->Lp1; d.adam_off = -1;
-            dg_add(M, d);
-            DGJob rc{};
-            rc.type = DG_ROWS_C; rc.M = B; rc.N = h2; rc.K = 0; rc.nact = a; rc.adam_off = -1;
-            rc.h2c4 = h->H2c4; rc.dap = h->da_part; rc.nparts = (h1 + 31) / 32; rc.save0 = h->save0;
-            rc.wmu = Pm + L.pi_Wmu; rc.wls = Pm + L.pi_Wls; rc.dz_c4 = h->dzpi_c4; rc.dz_r4 = h->dzpi_r4; rc.dhead_r4 = h->dhead_r4;
-            rc.ld_r4 = h->Lp2; rc.alpha = (float)cfg->alpha; rc.scale = (float)cfg->act_scale;
-            dg_add(M, rc);
-            for (int q = 0; q < 2; ++q) {
-                DGJob j = wgrad_j4(h->H1r4 + (1 + q) * H1I, h->H2r4 + (1 + q) * H2R, L.q_W2[q], L.q_b2[q], h->c4_q[q]);
-                j.bgen = 1; j.gw = h->w3snap + 512 * q; j.gdq = h->dq + (long long)q * B;   // (W3 as the previous launch saw it)
-                dg_add(M, j);
-            }
-            const bool split = h->bq_cols < (h1 + 31) / 32;
-            h->mid_rest_job = -1;
-            if (!split) {
-                for (int q = 0; q < 2; ++q) dg_add(M, wgrad_rm(h->H2r4 + (1 + q) * H2R, h->Lp2, h2 + 1, h->dq + (long long)q * B, 1, 1, L.q_W3[q]));
-            } else {
-                // the remaining column tiles of the q2(x, a) dgrad (see launch 1): its prologue needs the launch header of the Q dgrads
-                const DGJobs &Q0 = h->dg_bq[0];
-                M.hp = Q0.hp; M.sacv = 0; M.q_ev0 = Q0.q_ev0; M.q_nev = Q0.q_nev;
-                M.b3q1 = Q0.b3q1; M.b3q2 = Q0.b3q2; M.b3q1t = Q0.b3q1t; M.b3q2t = Q0.b3q2t;
-                M.rew = Q0.rew; M.done = Q0.done; M.logp0 = Q0.logp0; M.logp1 = Q0.logp1;   // (rew / done: launch_stage sets the input set's)
-                M.q1o = Q0.q1o; M.q2o = Q0.q2o; M.dq = Q0.dq; M.loss_part = Q0.loss_part;
-                M.alpha = Q0.alpha; M.gamma = Q0.gamma;
-                h->mid_rest_job = M.njobs;
-                dg_add(M, h->bq_rest);
-            }
-        }
-        {   // ---- backward launch 3: the wgrads that need launch 2's outputs — policy layer 2 / heads / layer 1, Q layer 1 —, loss means,
-            // optimizer bookkeeping.  No hand-off inside the launch any more: every tile is a plain GEMM tile with its Adam epilogue.
-            DGJobs &P = h->dg_pi;
-            P = DGJobs{};
-            P.B = B; P.Bv = Bv; P.ad = ctx;
-            dg_add(P, wgrad_j4(h->H1r4, h->dzpi_r4, L.pi_W2, L.pi_b2, h->c4_pi[1]));   // job 0: launch_stage picks the shadow copy
-            dg_add(P, wgrad_rm(h->H2r4, h->Lp2, h2 + 1, h->dhead_r4, 32, a, L.pi_Wmu));
-            dg_add(P, wgrad_rm(h->H2r4, h->Lp2, h2 + 1, h->dhead_r4 + (long long)a * 4, 32, a, L.pi_Wls));
-            for (int q = 0; q < 2; ++q) {
-                DGJob j = wgrad_rm(h->xa_r4, 32, o + a + 1, h->dZ1r4 + q * H1I, h->Lp1, h1, L.q_W1[q]);
-                j.type = DG_WGRAD_W1Y;   // [W1 ; b1] lives in the layer-1 block layout
-                dg_add(P, j);
-            }
-            {
-                DGJob j = wgrad_rm(h->xp_r4, 32, o + 1, h->dZ1r4 + 2 * H1I, h->Lp1, h1, L.pi_W1);
-                j.type = DG_WGRAD_W1Y;
-                dg_add(P, j);
-            }
-            if (h->bq_cols < (h1 + 31) / 32)   // the Q-head wgrads (+ Adam + polyak of W3, b3), moved here from launch "mid": nothing reads the head
-                                               // kernels between the two launches (the Q layer-2 wgrads of "mid" use the W3 snapshot)
-                for (int q = 0; q < 2; ++q) dg_add(P, wgrad_rm(h->H2r4 + (1 + q) * H2R, h->Lp2, h2 + 1, h->dq + (long long)q * B, 1, 1, L.q_W3[q]));
-            DGJob ls{};
-            ls.type = DG_LOSS; ls.M = 1; ls.N = 1; ls.K = 0; ls.adam_off = -1; ls.loss_part = h->loss_part; ls.losses = h->losses; ls.nl = 3;
-            ls.nparts = -1;   // + the optimizer's books
-            dg_add(P, ls);
-        }
-    }
-
-    // ---- row kernels
-    for (int st = 0; st < 2; ++st) {
-        h->ra[st] = RowsA{h->H2, net_pi(Pm, L), net_pi(Pt, L), net_q(Pm, L, 0), net_q(Pm, L, 1),
-                          h->in[st][5], h->in[st][6], h->in[st][7],
-                          h->act0, h->act2, h->logp0, h->logp1, h->save0, h->q1o, h->q2o,
-                          h->H1, Pm + L.q_W1[0] + (long long)o * h1, Pt + L.q_W1[0] + (long long)o * h1,
-                          Pt + L.q_W1[1] + (long long)o * h1, B, h2, ldh2, a, h1, ldh1, (float)cfg->act_scale};
-        h->rb[st] = RowsB{h->H2, net_q(Pm, L, 0), net_q(Pm, L, 1), net_q(Pt, L, 0), net_q(Pt, L, 1), h->in[st][3], h->in[st][4],
-                          h->logp0, h->logp1, h->q1o, h->q2o, h->dZ2, h->dq4, h->loss_part, B, h2, ldh2,
-                          (float)cfg->alpha, (float)cfg->gamma};
-    }
-    h->rc = RowsC{h->H2, h->dZ1 + 2 * BZ1, Pm + L.q_W1[0], net_pi(Pm, L), h->save0, h->dhead, h->dZ2 + 3 * BZ2,
-                  h->loss_part, h->losses, B, h1, h2, ldh2, o, a, h->ldd, h->rows_b_blocks, (float)cfg->alpha,
-                  (float)cfg->act_scale, 3};
-    h->ad = AdamArgs{h->main_p, h->target_p, h->m, h->v, h->grad, h->opt, h->opt + 1, L.total_int, L.n_pi_int, 0,
-                     (float)cfg->lr, (float)cfg->beta1, (float)cfg->beta2, (float)cfg->adam_eps,
-                     (float)cfg->polyak, (float)(1.0 - cfg->polyak),
-                     h->part, L.pi_W1 / 4, (long long)(o + 1) * h1 / 4, (long long)(o + 1) * h1 / 4,
-                     h->fused_l1_wgrad ? (B + 31) / 32 : 0, 0u};
-    h->noise_armed = false; h->noise_seed = 0; h->noise_pending = 0; h->grad_imported = false;
-    h->fuse_apply = false; h->sample_armed = false;
     *out = h;
     return DDRL_OK;
 }
@@ -1610,7 +1501,7 @@ int ddrl_sac1_export(ddrl_sac1_t *h, int which, float *flat_d, void *stream) {
     float *buf = which_buf(h, which);
     DDRL_REQUIRE(buf != nullptr, "unknown buffer id");
     ddrl::DeviceGuard g(h->device);
-    if (which == DDRL_SAC1_GRAD && h->fused_l1_wgrad && !h->grad_imported) {
+    if (which == DDRL_SAC1_GRAD && h->fused_l1_wgrad && !h->ls.grad_imported) {
         // the pi layer-1 gradient exists only as row-tile partials until Adam runs: materialise it
         const long long n = (long long)(h->cfg.obs_dim + 1) * h->cfg.hidden1;
         if (h->fused)
@@ -1634,7 +1525,7 @@ int ddrl_sac1_grad_buffer(ddrl_sac1_t *h, float **grad_d, int64_t *n) {
 int ddrl_sac1_grad_finalize(ddrl_sac1_t *h, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     ddrl::DeviceGuard g(h->device);
-    if (h->fused_l1_wgrad && !h->grad_imported) {  // the pi layer-1 gradient exists only as row-tile partials: sum them into the buffer
+    if (h->fused_l1_wgrad && !h->ls.grad_imported) {  // the pi layer-1 gradient exists only as row-tile partials: sum them into the buffer
         const long long n = (long long)(h->cfg.obs_dim + 1) * h->cfg.hidden1;
         if (h->fused)
             k_reduce_parts_w1y<<<(unsigned)((n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->part, h->grad + h->L.pi_W1, h->cfg.obs_dim + 1,
@@ -1643,7 +1534,7 @@ int ddrl_sac1_grad_finalize(ddrl_sac1_t *h, void *stream) {
             k_reduce_parts<<<(unsigned)((n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->part, h->grad + h->L.pi_W1, n, n, h->ad.nparts);
         DDRL_LAUNCH_CHECK();
     }
-    h->grad_imported = true;  // apply_grads takes the buffer as it is (e.g. after an in-place all-reduce)
+    h->ls.grad_imported = true;  // apply_grads takes the buffer as it is (e.g. after an in-place all-reduce)
     return DDRL_OK;
 }
 
@@ -1655,7 +1546,7 @@ int ddrl_sac1_import(ddrl_sac1_t *h, int which, const float *flat_d, void *strea
     k_pack<<<dim3(64, (unsigned)h->L.segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_d, buf, nullptr, 1);
     if (which == DDRL_SAC1_MAIN) refresh_shadows(h, ddrl::as_stream(stream));
     DDRL_LAUNCH_CHECK();
-    if (which == DDRL_SAC1_GRAD) h->grad_imported = true;
+    if (which == DDRL_SAC1_GRAD) h->ls.grad_imported = true;
     return DDRL_OK;
 }
 
@@ -1679,7 +1570,7 @@ int ddrl_sac1_opt_steps(ddrl_sac1_t *h, int64_t *t_pi_h, int64_t *t_q_h, void *s
     ddrl::DeviceGuard g(h->device);
     OptState o;
     hipStream_t s = ddrl::as_stream(stream);
-    DDRL_HIP_CHECK(hipMemcpyAsync(&o, h->opt + h->opt_cur, sizeof(o), hipMemcpyDeviceToHost, s));
+    DDRL_HIP_CHECK(hipMemcpyAsync(&o, h->opt + h->ls.opt_cur, sizeof(o), hipMemcpyDeviceToHost, s));
     DDRL_HIP_CHECK(hipStreamSynchronize(s));
     if (t_pi_h) *t_pi_h = o.t_pi;
     if (t_q_h) *t_q_h = o.t_q;
@@ -1691,7 +1582,7 @@ int ddrl_sac1_opt_state_get(ddrl_sac1_t *h, int64_t *t_pi_h, int64_t *t_q_h, uin
     ddrl::DeviceGuard g(h->device);
     OptState o;
     hipStream_t s = ddrl::as_stream(stream);
-    DDRL_HIP_CHECK(hipMemcpyAsync(&o, h->opt + h->opt_cur, sizeof(o), hipMemcpyDeviceToHost, s));
+    DDRL_HIP_CHECK(hipMemcpyAsync(&o, h->opt + h->ls.opt_cur, sizeof(o), hipMemcpyDeviceToHost, s));
     DDRL_HIP_CHECK(hipStreamSynchronize(s));
     if (t_pi_h) *t_pi_h = o.t_pi;
     if (t_q_h) *t_q_h = o.t_q;
@@ -1710,10 +1601,26 @@ int ddrl_sac1_opt_state_set(ddrl_sac1_t *h, int64_t t_pi, int64_t t_q, uint64_t 
     for (int64_t i = 0; i < t_q; ++i) { o.b1p_q *= b1; o.b2p_q *= b2; }
     o.t_pi = t_pi; o.t_q = t_q; o.noise_ctr = noise_ctr;
     hipStream_t s = ddrl::as_stream(stream);
-    h->opt_cur = 0;
+    h->ls.opt_cur = 0;
     DDRL_HIP_CHECK(hipMemcpyAsync(h->opt, &o, sizeof(o), hipMemcpyHostToDevice, s));
     DDRL_HIP_CHECK(hipStreamSynchronize(s));
     return DDRL_OK;
+}
+
+// Direct path: copy `copy` of the dgrad image of q2's layer-2 kernel (double-buffered only when mid_rest_job >= 0: see c4_q2b)
+static float *q2_image(const ddrl_sac1 *h, int copy) { return copy ? h->c4_q2b : h->c4_q[1]; }
+
+// Direct path: the main layer-2 kernels a stepped parameter buffer holds (offsets in it) and the current dgrad image of each
+struct Shadows { int n; long long w2[4]; float *img[4]; };
+static Shadows current_shadows(const ddrl_sac1 *h) {
+    const Variant &V = variant_of(h);
+    Shadows sh{};
+    sh.w2[sh.n] = h->L.pi_W2; sh.img[sh.n++] = h->c4_pi[h->ls.sh_cur];
+    for (int q = 0; q < V.nv; ++q) {
+        sh.w2[sh.n] = net_off(h->L, V.vn[q].net).W2;
+        sh.img[sh.n++] = (V.vn[q].net == NET_Q2 && h->mid_rest_job >= 0) ? q2_image(h, h->ls.sh_cur) : h->c4_q[q];
+    }
+    return sh;
 }
 
 // Direct path: the dgrad images [h2/4][h1][4] of the main layer-2 kernels, regenerated from the k4-interleaved parameters
@@ -1722,12 +1629,10 @@ static void refresh_shadows(ddrl_sac1 *h, hipStream_t s) {
     if (!h->fused) return;
     const Layout &L = h->L;
     const int h1 = h->cfg.hidden1, h2 = h->cfg.hidden2;
+    const Shadows sh = current_shadows(h);
     ShadowJobs sj{};
-    int n = 0;
-    sj.j4[n] = h->main_p + L.pi_W2; sj.c4[n++] = h->c4_pi[h->sh_cur];
-    for (int q = 0; q < 2; ++q) { sj.j4[n] = h->main_p + L.q_W2[q]; sj.c4[n++] = (q == 1 && h->mid_rest_job >= 0 && h->sh_cur) ? h->c4_q2b : h->c4_q[q]; }
-    if (h->cfg.variant == DDRL_SAC_V) { sj.j4[n] = h->main_p + L.v_W2; sj.c4[n++] = h->c4_q[2]; }
-    k_shadow<<<dim3((h1 + 31) / 32, (h2 / 4 + 7) / 8, n), 256, 0, s>>>(sj, h1, h2, L.Np2, L.Kp1);   // one launch for all networks
+    for (int i = 0; i < sh.n; ++i) { sj.j4[i] = h->main_p + sh.w2[i]; sj.c4[i] = sh.img[i]; }
+    k_shadow<<<dim3((h1 + 31) / 32, (h2 / 4 + 7) / 8, sh.n), 256, 0, s>>>(sj, h1, h2, L.Np2, L.Kp1);   // one launch for all networks
 }
 
 static void launch_rows_c(ddrl_sac1 *h, hipStream_t s) {
@@ -1744,11 +1649,11 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
     const dim3 l1grid((c.hidden1 + 255) / 256, (B + L1_ROWS - 1) / L1_ROWS, 1);
     if (h->fused) {
         switch (stage) {
-            case 2: h->f_a[st].opt = h->opt + h->opt_cur; launch_dfwd<0>(h->fh_a[st], h->f_a[st], s); break;
+            case 2: h->f_a[st].opt = h->opt + h->ls.opt_cur; launch_dfwd<0>(h->fh_a[st], h->f_a[st], s); break;
             case 5: {
                 DFArgs &F = h->f_b[st];
-                F.do_sample = h->sample_armed ? 1 : 0;
-                if (h->sample_armed) {
+                F.do_sample = h->ls.sample_armed ? 1 : 0;
+                if (h->ls.sample_armed) {
                     F.rs = h->smp_rs; F.ring = h->smp_ring; F.sample_batch = h->cfg.batch;
                     float **b = h->in[h->smp_set];
                     F.sout = ddrl_replay_dev::BatchPtrs{{b[0], b[1], b[2], b[3], b[4], nullptr}};
@@ -1758,43 +1663,42 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
             }
             case 7: {
                 DGJobs &J = h->dg_bq[st];
-                if (h->mid_rest_job >= 0) J.job[2].B = h->sh_cur ? h->c4_q2b : h->c4_q[1];   // q2(x, a) dgrad: the current image of q2's layer-2 kernel
+                if (h->mid_rest_job >= 0) J.job[h->bq_q2_job].B = q2_image(h, h->ls.sh_cur);   // q2(x, a) dgrad: the current image of q2's layer-2 kernel
                 launch_dg(J, s, 2);
                 break;
             }
             case 8: {
                 DGJobs &J = h->dg_mid;
-                J.ad.on = h->fuse_apply ? 1 : 0;
-                J.ad.opt = h->opt + h->opt_cur;
-                J.job[0].B = h->c4_pi[h->sh_cur];           // the policy dgrad reads this update's image of the policy's layer-2 kernel ...
+                J.ad.on = h->ls.fuse_apply ? 1 : 0;
+                J.ad.opt = h->opt + h->ls.opt_cur;
+                J.job[h->mid_pi_job].B = h->c4_pi[h->ls.sh_cur];          // the policy dgrad reads this update's image of the policy's layer-2 kernel ...
                 J.rew = h->dg_bq[st].rew; J.done = h->dg_bq[st].done;   // (read by the Q dgrad columns that run here, if any)
                 if (h->mid_rest_job >= 0) {
-                    // those columns read the CURRENT image of q2's layer-2 kernel while the optimizer epilogue of q2's layer-2 wgrad (job 3 of
-                    // this launch) writes the next one: two copies, like the policy's (found by the graph == eager test: with one copy the
+                    // those columns read the CURRENT image of q2's layer-2 kernel while the optimizer epilogue of q2's layer-2 wgrad (in
+                    // this launch too) writes the next one: two copies, like the policy's (found by the graph == eager test: with one copy the
                     // dgrad saw a half-stepped kernel)
-                    float *cur = h->sh_cur ? h->c4_q2b : h->c4_q[1], *nxt = h->sh_cur ? h->c4_q[1] : h->c4_q2b;
-                    J.job[h->mid_rest_job].B = cur + (long long)h->bq_cols * 32 * 4;
-                    J.job[3].shadow = J.ad.on ? nxt : nullptr;
+                    J.job[h->mid_rest_job].B = q2_image(h, h->ls.sh_cur) + (long long)h->bq_cols * 32 * 4;
+                    J.job[h->mid_q2w_job].shadow = J.ad.on ? q2_image(h, h->ls.sh_cur ^ 1) : nullptr;
                 }
                 launch_dg(J, s, 3);
                 break;
             }
             case 9: {
                 DGJobs &J = h->dg_pi;
-                J.ad.on = h->fuse_apply ? 1 : 0;
-                J.ad.opt = h->opt + h->opt_cur;
-                J.job[0].shadow = h->c4_pi[h->sh_cur ^ 1];  // ... the optimizer epilogue of the policy's layer-2 wgrad writes the next one
-                J.ad.opt_next = h->opt + (h->opt_cur ^ 1);  // the optimizer bookkeeping rides in this launch (its loss tile)
-                J.ad.noise_adv = h->noise_pending;
+                J.ad.on = h->ls.fuse_apply ? 1 : 0;
+                J.ad.opt = h->opt + h->ls.opt_cur;
+                J.job[h->pi_w2_job].shadow = h->c4_pi[h->ls.sh_cur ^ 1];  // ... the optimizer epilogue of the policy's layer-2 wgrad writes the next one
+                J.ad.opt_next = h->opt + (h->ls.opt_cur ^ 1);  // the optimizer bookkeeping rides in this launch (its loss tile)
+                J.ad.noise_adv = h->ls.noise_pending;
                 launch_dg(J, s, 4);
-                if (J.ad.on) { h->opt_cur ^= 1; h->sh_cur ^= 1; }
+                if (J.ad.on) { h->ls.opt_cur ^= 1; h->ls.sh_cur ^= 1; }
                 break;
             }
             case 11: {
                 const long long blocks = (h->L.total_int / 4 + 255) / 256;
                 h->ad.adam_blocks = (int)blocks;
-                h->ad.opt = h->opt + h->opt_cur; h->ad.opt_next = h->opt + (h->opt_cur ^ 1);
-                h->opt_cur ^= 1;
+                h->ad.opt = h->opt + h->ls.opt_cur; h->ad.opt_next = h->opt + (h->ls.opt_cur ^ 1);
+                h->ls.opt_cur ^= 1;
                 const int nparts = h->ad.nparts;
                 if (nparts > 0) {  // the policy's layer-1 gradient exists as row-tile partials: sum them into the (block-layout) gradient first
                     const int nk = h->cfg.obs_dim + 1, N = h->cfg.hidden1;
@@ -1802,12 +1706,9 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
                 }
                 h->ad.nparts = 0;
                 {   // the dgrad images of the main layer-2 kernels (what refresh_shadows would rewrite in a launch of its own) ride in the flat step
-                    const Layout &L = h->L;
-                    int n = 0;
-                    h->ad.sh_off4[n] = L.pi_W2 >> 2; h->ad.sh_dst[n++] = h->c4_pi[h->sh_cur];
-                    for (int q = 0; q < 2; ++q) { h->ad.sh_off4[n] = L.q_W2[q] >> 2; h->ad.sh_dst[n++] = (q == 1 && h->mid_rest_job >= 0 && h->sh_cur) ? h->c4_q2b : h->c4_q[q]; }
-                    if (h->cfg.variant == DDRL_SAC_V) { h->ad.sh_off4[n] = L.v_W2 >> 2; h->ad.sh_dst[n++] = h->c4_q[2]; }
-                    h->ad.n_sh = n; h->ad.sh_K = h->cfg.hidden1; h->ad.sh_N = h->cfg.hidden2; h->ad.sh_Np = L.Np2; h->ad.sh_ld = L.Kp1;
+                    const Shadows sh = current_shadows(h);
+                    for (int i = 0; i < sh.n; ++i) { h->ad.sh_off4[i] = sh.w2[i] >> 2; h->ad.sh_dst[i] = sh.img[i]; }
+                    h->ad.n_sh = sh.n; h->ad.sh_K = h->cfg.hidden1; h->ad.sh_N = h->cfg.hidden2; h->ad.sh_Np = h->L.Np2; h->ad.sh_ld = h->L.Kp1;
                 }
                 k_adam_polyak<<<(unsigned)(blocks + (h->ad.do_sample ? 1 : 0)), 256, 0, s>>>(h->ad);
                 h->ad.nparts = nparts; h->ad.n_sh = 0;
@@ -1818,7 +1719,7 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
         return;
     }
     switch (stage) {
-        case 1: h->l1a[st].opt = h->opt + h->opt_cur; k_l1<<<dim3(l1grid.x, l1grid.y, h->l1a[st].njobs), 256, 0, s>>>(h->l1a[st]); break;
+        case 1: h->l1a[st].opt = h->opt + h->ls.opt_cur; k_l1<<<dim3(l1grid.x, l1grid.y, h->l1a[st].njobs), 256, 0, s>>>(h->l1a[st]); break;
         case 2: launch_gemm(h->g_fa, s); break;
         case 3:
             if (c.variant == DDRL_SAC_V) k_rows_a_v<<<(B * 5 + 3) / 4, 256, 0, s>>>(h->rav[st]);
@@ -1836,8 +1737,8 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
         case 11: {
             const long long blocks = (h->L.total_int / 4 + 255) / 256;
             h->ad.adam_blocks = (int)blocks;
-            h->ad.opt = h->opt + h->opt_cur; h->ad.opt_next = h->opt + (h->opt_cur ^ 1);
-            h->opt_cur ^= 1;
+            h->ad.opt = h->opt + h->ls.opt_cur; h->ad.opt_next = h->opt + (h->ls.opt_cur ^ 1);
+            h->ls.opt_cur ^= 1;
             k_adam_polyak<<<(unsigned)(blocks + (h->ad.do_sample ? 1 : 0)), 256, 0, s>>>(h->ad);
             break;
         }
@@ -1864,16 +1765,16 @@ static int launch_grads(ddrl_sac1 *h, const float *obs1, const float *obs2, cons
         for (int i = 0; i < 8; ++i) { sa.src[i] = src[i]; sa.dst[i] = h->in[0][i]; sa.n[i] = n[i]; }
         k_stage<<<dim3((unsigned)((B * c.obs_dim + 255) / 256), 8), 256, 0, s>>>(sa);
     }
-    h->l1a[st].noise_on = h->noise_armed ? 1 : 0;
-    h->l1a[st].noise_seed = h->noise_seed;
-    h->f_a[st].noise_on = h->noise_armed ? 1 : 0;
-    h->f_a[st].noise_seed = h->noise_seed;
-    h->noise_pending = h->noise_armed ? (unsigned)(3 * B * c.act_dim) : 0u;
-    h->noise_armed = false;
-    h->grad_imported = false;
+    h->l1a[st].noise_on = h->ls.noise_armed ? 1 : 0;
+    h->l1a[st].noise_seed = h->ls.noise_seed;
+    h->f_a[st].noise_on = h->ls.noise_armed ? 1 : 0;
+    h->f_a[st].noise_seed = h->ls.noise_seed;
+    h->ls.noise_pending = h->ls.noise_armed ? (unsigned)(3 * B * c.act_dim) : 0u;
+    h->ls.noise_armed = false;
+    h->ls.grad_imported = false;
     for (int stage = 1; stage <= 10; ++stage) launch_stage(h, stage, st, s);
     DDRL_LAUNCH_CHECK();
-    if (h->fuse_apply) h->noise_pending = 0;  // consumed by the optimizer bookkeeping of the last stage
+    if (h->ls.fuse_apply) h->ls.noise_pending = 0;  // consumed by the optimizer bookkeeping of the last stage
     if (losses_d) DDRL_HIP_CHECK(hipMemcpyAsync(losses_d, h->losses, (size_t)h->rc.nl * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (q1_d || q2_d || logp_d) {
         k_copy3<<<(B + 255) / 256, 256, 0, s>>>(h->q1o, h->q2o, h->logp0, q1_d, q2_d, logp_d, B);
@@ -1883,10 +1784,10 @@ static int launch_grads(ddrl_sac1 *h, const float *obs1, const float *obs2, cons
 }
 
 static int launch_apply(ddrl_sac1 *h, hipStream_t s) {
-    h->ad.noise_adv = h->noise_pending;
-    h->noise_pending = 0;
+    h->ad.noise_adv = h->ls.noise_pending;
+    h->ls.noise_pending = 0;
     const int nparts = h->ad.nparts;
-    if (h->grad_imported) h->ad.nparts = 0;  // use the imported (e.g. all-reduced) gradient as is
+    if (h->ls.grad_imported) h->ad.nparts = 0;  // use the imported (e.g. all-reduced) gradient as is
     launch_stage(h, 11, 0, s);
     h->ad.nparts = nparts;
     DDRL_LAUNCH_CHECK();
@@ -1908,8 +1809,8 @@ int ddrl_sac1_fill_noise(ddrl_sac1_t *h, uint32_t seed, void *stream) {
     // first kernel (k_l1) from hash(seed, device counter + i) and its Adam kernel advances the counter.
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     (void)stream;
-    h->noise_armed = true;
-    h->noise_seed = seed;
+    h->ls.noise_armed = true;
+    h->ls.noise_seed = seed;
     return DDRL_OK;
 }
 
@@ -2017,11 +1918,11 @@ int ddrl_sac1_step(ddrl_sac1_t *h, const float *obs1_d, const float *obs2_d, con
                    float *losses_d, float *q1_d, float *q2_d, float *logp_pi_d, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     // fused path: the optimizer runs in the epilogues of the last GEMM launch — no Adam kernel
-    h->fuse_apply = h->fused;
+    h->ls.fuse_apply = h->fused;
     int rc = ddrl_sac1_compute_grads(h, obs1_d, obs2_d, acts_d, rews_d, done_d, eps_x_d, eps_x2_d, eps_t_d, losses_d,
                                      q1_d, q2_d, logp_pi_d, stream);
-    const bool applied = h->fuse_apply;
-    h->fuse_apply = false;
+    const bool applied = h->ls.fuse_apply;
+    h->ls.fuse_apply = false;
     if (rc != DDRL_OK || applied) return rc;
     return ddrl_sac1_apply_grads(h, stream);
 }
@@ -2081,37 +1982,33 @@ int ddrl_sac1_step_host(ddrl_sac1_t *h, float *block_h, int64_t n_floats, uint32
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cap);
     if (!graphs_on || !h->fused || s == nullptr || cap != hipStreamCaptureStatusNone) return issue();   // (the legacy null stream cannot be captured)
-    if (h->noise_armed || h->sample_armed) return issue();   // a request armed through another call belongs to THIS update only: not into a graph
+    if (h->ls.noise_armed || h->ls.sample_armed) return issue();   // a request armed through another call belongs to THIS update only: not into a graph
     for (auto &hg : h->host_graphs)
-        if (hg.block == block_h && hg.losses == losses_d && hg.seed == noise_seed && hg.opt_cur == h->opt_cur && hg.sh_cur == h->sh_cur) {
+        if (hg.block == block_h && hg.losses == losses_d && hg.seed == noise_seed && hg.opt_cur == h->ls.opt_cur && hg.sh_cur == h->ls.sh_cur) {
             DDRL_HIP_CHECK(hipGraphLaunch(hg.exec, s));
-            h->opt_cur ^= 1; h->sh_cur ^= 1;   // what the recorded launches did to the host-side state when they were recorded
+            h->ls.opt_cur ^= 1; h->ls.sh_cur ^= 1;   // what the recorded launches did to the host-side state when they were recorded
             return DDRL_OK;
         }
     if (h->host_graphs.size() >= 16) return issue();   // (a caller that keeps changing blocks: eager)
     resolve();
     if (!block_dev) return issue();                    // pageable memory: the copies are not capturable
-    ddrl_sac1::HostGraph hg{block_h, losses_d, noise_seed, h->opt_cur, h->sh_cur, nullptr};
+    ddrl_sac1::HostGraph hg{block_h, losses_d, noise_seed, h->ls.opt_cur, h->ls.sh_cur, nullptr};
     hipGraph_t graph = nullptr;
     // the recorded launches advance the host-side launch state without running: kept if the graph then runs once, put back if not
-    const ddrl_sac1::HostSnap before{true, h->opt_cur, h->sh_cur, h->fuse_apply, h->sample_armed, h->noise_armed, h->grad_imported, h->noise_seed, h->noise_pending};
-    auto put_back = [&]() {
-        h->opt_cur = before.opt_cur; h->sh_cur = before.sh_cur; h->fuse_apply = before.fuse_apply; h->sample_armed = before.sample_armed;
-        h->noise_armed = before.noise_armed; h->grad_imported = before.grad_imported; h->noise_seed = before.noise_seed; h->noise_pending = before.noise_pending;
-    };
+    const LaunchState before = h->ls;
     DDRL_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     const int rc = issue();
     const hipError_t e2 = hipStreamEndCapture(s, &graph);
     if (rc != DDRL_OK || e2 != hipSuccess || graph == nullptr) {
         if (graph) (void)hipGraphDestroy(graph);
         (void)hipGetLastError();
-        put_back();
+        h->ls = before;
         if (rc != DDRL_OK) return rc;                  // the update itself was refused (arguments): the same eagerly
         return issue();                                // the capture was refused: nothing ran — this update goes eagerly
     }
     const hipError_t e3 = hipGraphInstantiate(&hg.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
-    if (e3 != hipSuccess) { (void)hipGetLastError(); put_back(); return issue(); }
+    if (e3 != hipSuccess) { (void)hipGetLastError(); h->ls = before; return issue(); }
     h->host_graphs.push_back(hg);
     DDRL_HIP_CHECK(hipGraphLaunch(hg.exec, s));   // (the capture recorded the update — host state advanced once — now it runs once)
     return DDRL_OK;
@@ -2125,20 +2022,20 @@ __global__ void k_opt_copy(const OptState *src, OptState *dst) { *dst = *src; }
 // captured graph starts and ends on the same copy whatever the number of updates it holds.
 int ddrl_sac1_internal_opt_sync(ddrl_sac1 *h, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
-    if (h->opt_cur == 0 && !(h->fused && h->sh_cur != 0)) return DDRL_OK;
+    if (h->ls.opt_cur == 0 && !(h->fused && h->ls.sh_cur != 0)) return DDRL_OK;
     ddrl::DeviceGuard g(h->device);
-    if (h->opt_cur != 0) {
+    if (h->ls.opt_cur != 0) {
         k_opt_copy<<<1, 1, 0, ddrl::as_stream(stream)>>>(h->opt + 1, h->opt);
         DDRL_LAUNCH_CHECK();
-        h->opt_cur = 0;
+        h->ls.opt_cur = 0;
     }
-    if (h->fused && h->sh_cur != 0) {  // same for the double-buffered dgrad image of the policy's layer-2 kernel
+    if (h->fused && h->ls.sh_cur != 0) {  // same for the double-buffered dgrad image of the policy's layer-2 kernel
         DDRL_HIP_CHECK(hipMemcpyAsync(h->c4_pi[0], h->c4_pi[1], (size_t)h->L.Np2 * h->L.Kp1 * sizeof(float), hipMemcpyDeviceToDevice,
                                       ddrl::as_stream(stream)));
         if (h->mid_rest_job >= 0)      // ... and of q2's, when it is double-buffered too
             DDRL_HIP_CHECK(hipMemcpyAsync(h->c4_q[1], h->c4_q2b, (size_t)h->L.Np2 * h->L.Kp1 * sizeof(float), hipMemcpyDeviceToDevice,
                                           ddrl::as_stream(stream)));
-        h->sh_cur = 0;
+        h->ls.sh_cur = 0;
     }
     return DDRL_OK;
 }
@@ -2149,16 +2046,15 @@ int ddrl_sac1_graph_sync(ddrl_sac1_t *h, void *stream) { return ddrl_sac1_intern
 
 int ddrl_sac1_capture_begin(ddrl_sac1_t *h) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
-    h->snap = ddrl_sac1::HostSnap{true, h->opt_cur, h->sh_cur, h->fuse_apply, h->sample_armed, h->noise_armed, h->grad_imported, h->noise_seed, h->noise_pending};
+    h->snap.valid = true;
+    h->snap.ls = h->ls;
     return DDRL_OK;
 }
 
 int ddrl_sac1_capture_abort(ddrl_sac1_t *h) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     DDRL_REQUIRE(h->snap.valid, "ddrl_sac1_capture_abort without ddrl_sac1_capture_begin");
-    const ddrl_sac1::HostSnap &s = h->snap;
-    h->opt_cur = s.opt_cur; h->sh_cur = s.sh_cur; h->fuse_apply = s.fuse_apply; h->sample_armed = s.sample_armed;
-    h->noise_armed = s.noise_armed; h->grad_imported = s.grad_imported; h->noise_seed = s.noise_seed; h->noise_pending = s.noise_pending;
+    h->ls = h->snap.ls;
     h->snap.valid = false;
     return DDRL_OK;
 }
@@ -2177,9 +2073,9 @@ int ddrl_sac1_compute_grads_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t
         if (rc != DDRL_OK) return rc;
         return learner_sample_launch(h, replay, nstep, set_out, stream);
     }
-    h->sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
+    h->ls.sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
     const int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
-    h->sample_armed = false;
+    h->ls.sample_armed = false;
     if (rc == DDRL_OK) ddrl_replay_note_sample(replay);
     return rc;
 }
@@ -2198,9 +2094,9 @@ int ddrl_sac1_step_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t *replay,
         if (rc != DDRL_OK) return rc;
         return ddrl_sac1_apply_grads_and_sample(h, replay, set_out, stream);
     }
-    h->sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
+    h->ls.sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
     const int rc = ddrl_sac1_step(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
-    h->sample_armed = false;
+    h->ls.sample_armed = false;
     if (rc == DDRL_OK) ddrl_replay_note_sample(replay);
     return rc;
 }

@@ -113,7 +113,13 @@ EDGE_CASES = [
 # path equivalence off the headline shape (tests/test_gpu_learner_state.py, part C)
 PATH_CASES = [Case("paths-sac1-generic", "sac1", 5, 3, (70, 45), 37, fused=0, **HYPER_H),
               Case("paths-sac1-direct-ragged", "sac1", 5, 3, (72, 44), 37, fused=1, **HYPER_J),
-              Case("paths-sacv-generic", "sacv", 8, 2, (50, 34), 20, fused=0, **HYPER_I)]
+              Case("paths-sacv-generic", "sacv", 8, 2, (50, 34), 20, fused=0, **HYPER_I),
+              # SAC-v on the direct-operand kernels (the shape of sacv-direct-b37-h64x48)
+              Case("paths-sacv-direct", "sacv", 8, 2, (64, 48), 37, fused=1, **HYPER_H),
+              # the smallest SAC1 shape where the q2(x, a) dgrad is cut by column tiles AND Q(x, a) is evaluated late: 8 row tiles of a
+              # ragged batch x 11 column tiles = 88 tiles per dgrad (3 x 88 > 256 > 2 x 88), 10 of the 11 column tiles stay in launch
+              # "bq" (bq_cols = 10 < 11), the last runs in launch "mid" beside q2's layer-2 wgrad, whose dgrad image is double-buffered
+              Case("paths-sac1-direct-split", "sac1", 5, 3, (324, 36), 225, fused=1, **HYPER_J)]
 
 DEAD = slice(8, 24)      # the block of layer-1 units switched off by the "dead" edge, in pi and in q1
 DEAD_BIAS = -50.0
