@@ -3,12 +3,20 @@
 // per call with no host work per update.  Built on the public C-ABI only: the replay gathers
 // straight into one of the learner's two input sets, the noise comes from the learner's device
 // counter, and because every cursor / RNG state / optimizer state lives on the device the
-// sequence for `updates_per_graph` updates is captured ONCE into a hipGraph and replayed (an
-// eager launch stream would be host-bound at ~3.5 us per kernel, MI355X guide
-// "graph-replay-floor").  Consecutive updates alternate between the learner's two input sets, so
-// the sampler of update u+1 never overwrites what update u still reads; optionally
-// (DDRL_LOOP_FORK=1) the sampler runs on a forked graph branch and overlaps the previous update —
-// the job of the reference's `Cache` prefetch process (algos/sac1/sac1.py:103-130).
+// sequence of updates is captured ONCE into hipGraphs and replayed (an eager launch stream would
+// be host-bound at ~3.5 us per kernel, MI355X guide "graph-replay-floor").
+// A FAMILY of lengths is captured — `updates_per_graph` and every power of two below it — and a
+// call consumes its updates greedily: full-size replays, then the binary decomposition of the
+// rest, so after the capture no update runs eagerly (a caller that cuts its updates at every push
+// leaves a different remainder each call).  Consecutive updates alternate between the learner's
+// two input sets, so the sampler of update u+1 never overwrites what update u still reads: it
+// rides in update u's forward launch, and that chain carries on ACROSS the replays of one call —
+// only a call's first replay opens with a stand-alone sampler launch, and only its last one ends
+// without a draw (the caller may store into the ring before the next call).  bench.py at N = 1:
+// 92.30 -> 91.38 ms per 2048-update step (profiles/loop_graph_family_before_after.txt).  Optionally
+// (DDRL_LOOP_FORK) the sampler runs on a forked graph branch of the full-size graph and overlaps
+// the previous update — the job of the reference's `Cache` prefetch process
+// (algos/sac1/sac1.py:103-130).
 #include "ddrl_common.h"
 
 #include <cstdlib>
@@ -28,7 +36,18 @@ struct ddrl_loop {
     uint32_t seed;
     float *buf[2][8];
     int batch;
-    hipGraphExec_t exec;
+    // One captured length.  exec[pre][start][tail]:
+    //   pre   0: head-sampled — opens with a stand-alone sampler launch;  1: pre-sampled — the replay before it drew its first batch
+    //   start the input set of its first update
+    //   tail  1: the last update draws the first batch of the replay that follows (into the set its own last update does not read)
+    // INPUT-SET PARITY: both starting sets are captured where a replay can meet them, nothing is tracked across calls.  A
+    // head-sampled graph starts on set 0 whatever ran before it (its sampler is stream-ordered behind every earlier reader of set 0,
+    // as the single graph's always was); a pre-sampled graph starts where the replay before it left its draw, which is set 1 only
+    // behind an odd number of odd-length replays — an odd `per_graph`, the length-1 graph being the last of any call.  Variants
+    // that no call can reach stay nullptr (variant_needed).  Eager updates keep alternating on `parity` among themselves.
+    struct Graph { int len; hipGraphExec_t exec[2][2][2]; };
+    std::vector<Graph> family;  // per_graph, then the powers of two below it, descending
+    bool chain;                 // the sampler chain runs across replays (off under DDRL_LOOP_FORK: every replay head-sampled, no tail draw)
     bool captured;
     int parity;  // input set of the next eager update
 };
@@ -60,23 +79,43 @@ static int grads_from(ddrl_loop *h, int set, void *stream) {
                                    stream);
 }
 
-// Capture `per_graph` updates.  Default: one branch; the sampler of update u+1 rides inside update u
-// (ddrl_sac1_step_and_sample: an extra workgroup of a forward launch on the fused path, of the Adam
+static int fork_mode() {
+    const char *fk = getenv("DDRL_LOOP_FORK");
+    return !fk ? 0 : (strcmp(fk, "all") == 0 ? 2 : 1);
+}
+
+static bool variant_needed(const ddrl_loop *h, int len, int pre, int start, int tail) {
+    if (!h->chain) return !pre && !start && !tail;
+    if (start && (!pre || (h->per_graph & 1) == 0)) return false;
+    if (tail && len == 1 && h->per_graph != 1) return false;   // the length-1 remainder ends its call
+    return true;
+}
+
+static void destroy_family(ddrl_loop *h) {
+    for (auto &g : h->family)
+        for (int v = 0; v < 8; ++v)
+            if (g.exec[v >> 2][(v >> 1) & 1][v & 1]) (void)hipGraphExecDestroy(g.exec[v >> 2][(v >> 1) & 1][v & 1]);
+    h->family.clear();
+    h->captured = false;
+}
+
+// Capture `n` updates as variant (pre, start, tail) of ddrl_loop::Graph.  mode 0: one branch; the sampler of update u+1 rides
+// inside update u (ddrl_sac1_step_and_sample: an extra workgroup of a forward launch on the fused path, of the Adam
 // kernel otherwise).
 // Experimental overlap modes (bit-identical results, both measured SLOWER on MI355X — a kernel
 // starting or ending on another branch costs the kernel running beside it more than it hides):
 //   DDRL_LOOP_FORK=adam  sampler of update u+1 beside the Adam/polyak kernel of update u (105 us)
 //   DDRL_LOOP_FORK=all   sampler of update u+1 anywhere beside update u (99 us)
-static int capture(ddrl_loop *h, hipStream_t main_s) {
-    const char *fk = getenv("DDRL_LOOP_FORK");
-    const int mode = !fk ? 0 : (strcmp(fk, "all") == 0 ? 2 : 1);
+static int capture(ddrl_loop *h, hipStream_t main_s, int n, int mode, int pre, int start, int tail, hipGraphExec_t *exec) {
     hipStream_t side = nullptr;
-    DDRL_HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    const int n = h->per_graph;
-    std::vector<hipEvent_t> e_smp(n + 1), e_upd(n + 1), e_grad(n + 1);
-    hipEvent_t e_fork;
-    DDRL_HIP_CHECK(hipEventCreateWithFlags(&e_fork, hipEventDisableTiming));
-    for (int i = 0; i <= n; ++i) {
+    const int n_ev = mode != 0 ? n + 1 : 0;   // the fork modes' branch events
+    std::vector<hipEvent_t> e_smp(n_ev), e_upd(n_ev), e_grad(n_ev);
+    hipEvent_t e_fork = nullptr;
+    if (mode != 0) {
+        DDRL_HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        DDRL_HIP_CHECK(hipEventCreateWithFlags(&e_fork, hipEventDisableTiming));
+    }
+    for (int i = 0; i < n_ev; ++i) {
         DDRL_HIP_CHECK(hipEventCreateWithFlags(&e_smp[i], hipEventDisableTiming));
         DDRL_HIP_CHECK(hipEventCreateWithFlags(&e_upd[i], hipEventDisableTiming));
         DDRL_HIP_CHECK(hipEventCreateWithFlags(&e_grad[i], hipEventDisableTiming));
@@ -90,15 +129,17 @@ static int capture(ddrl_loop *h, hipStream_t main_s) {
 #define HE(x) do { if (e == hipSuccess && rc == DDRL_OK) e = (x); } while (0)
 #define RC(x) do { if (e == hipSuccess && rc == DDRL_OK) rc = (x); } while (0)
     if (mode == 0) {
-        // sample(0) as a kernel; sample(i+1) rides inside the Adam kernel of update i.  No store can
-        // interleave inside one graph, so this equals the sequential sample -> update order.
-        RC(sample_into(h, 0, (void *)main_s));
+        // sample(0) as a kernel (head-sampled) or drawn by the replay before (pre-sampled); sample(i+1) rides inside update i,
+        // the last update's only in a tail-sampling graph.  No store can interleave inside one graph, nor between two replays
+        // of one ddrl_loop_run call, so this equals the sequential sample -> update order.
+        if (!pre) RC(sample_into(h, start, (void *)main_s));
         for (int i = 0; i < n; ++i) {
+            const int set = (start + i) & 1;
             RC(ddrl_sac1_fill_noise(h->learner, h->seed, (void *)main_s));
-            if (i + 1 < n) {
-                RC(ddrl_sac1_step_and_sample(h->learner, i & 1, h->replay, (i + 1) & 1, (void *)main_s));
+            if (i + 1 < n || tail) {
+                RC(ddrl_sac1_step_and_sample(h->learner, set, h->replay, set ^ 1, (void *)main_s));
             } else {
-                float **b = h->buf[i & 1];
+                float **b = h->buf[set];
                 RC(ddrl_sac1_step(h->learner, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr,
                                   (void *)main_s));
             }
@@ -134,17 +175,45 @@ static int capture(ddrl_loop *h, hipStream_t main_s) {
 #undef RC
     // every side-branch node is an ancestor of a main-stream node: the branch is joined
     hipError_t e2 = hipStreamEndCapture(main_s, &graph);
-    for (int i = 0; i <= n; ++i) { (void)hipEventDestroy(e_smp[i]); (void)hipEventDestroy(e_upd[i]); (void)hipEventDestroy(e_grad[i]); }
-    (void)hipEventDestroy(e_fork);
-    (void)hipStreamDestroy(side);
+    for (int i = 0; i < n_ev; ++i) { (void)hipEventDestroy(e_smp[i]); (void)hipEventDestroy(e_upd[i]); (void)hipEventDestroy(e_grad[i]); }
+    if (e_fork) (void)hipEventDestroy(e_fork);
+    if (side) (void)hipStreamDestroy(side);
     if (rc != DDRL_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess || e2 != hipSuccess) {
         ddrl::set_error("graph capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
         if (graph) (void)hipGraphDestroy(graph);
         return DDRL_ERR_HIP;
     }
-    DDRL_HIP_CHECK(hipGraphInstantiate(&h->exec, graph, nullptr, nullptr, 0));
+    const hipError_t e3 = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
+    if (e3 != hipSuccess) {
+        *exec = nullptr;
+        ddrl::set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e3));
+        return DDRL_ERR_HIP;
+    }
+    return DDRL_OK;
+}
+
+// The whole family, or nothing: a failure destroys the graphs already built.  The fork modes shape the per_graph-sized graph only.
+// COST: the lengths sum to < 3 x per_graph and each has up to 4 variants (8 where per_graph is odd), so the one-time capture holds
+// up to 12 x per_graph updates (24 x where odd) of five kernel nodes each, against per_graph before: 450 updates in 26 graphs at 50,
+// where the first capturing call takes what it took with the single graph (26.5 ms).  It grows linearly: ~33 000 updates /
+// ~164 000 nodes at the accepted maximum of 4096, a size nothing here runs at.
+static int capture_family(ddrl_loop *h, hipStream_t main_s) {
+    const int mode = fork_mode();
+    h->chain = mode == 0;
+    h->family.clear();
+    h->family.push_back(ddrl_loop::Graph{h->per_graph, {}});
+    int p = 1;
+    while (p * 2 < h->per_graph) p *= 2;
+    for (; p >= 1 && p < h->per_graph; p >>= 1) h->family.push_back(ddrl_loop::Graph{p, {}});
+    for (auto &g : h->family)
+        for (int v = 0; v < 8; ++v) {
+            const int pre = v >> 2, start = (v >> 1) & 1, tail = v & 1;
+            if (!variant_needed(h, g.len, pre, start, tail)) continue;
+            const int rc = capture(h, main_s, g.len, g.len == h->per_graph ? mode : 0, pre, start, tail, &g.exec[pre][start][tail]);
+            if (rc != DDRL_OK) { destroy_family(h); return rc; }
+        }
     h->captured = true;
     return DDRL_OK;
 }
@@ -157,7 +226,7 @@ int ddrl_loop_create(ddrl_loop_t **out, ddrl_sac1_t *learner, ddrl_replay_t *rep
     DDRL_REQUIRE(updates_per_graph >= 0 && updates_per_graph <= 4096, "updates_per_graph must be in [0, 4096]");
     ddrl_loop *h = new ddrl_loop();
     h->learner = learner; h->replay = replay; h->per_graph = updates_per_graph; h->seed = noise_seed;
-    h->exec = nullptr; h->captured = false; h->parity = 0;
+    h->chain = false; h->captured = false; h->parity = 0;
     int rc = ddrl_sac1_input_buffers(learner, 0, h->buf[0]);
     if (rc == DDRL_OK) rc = ddrl_sac1_input_buffers(learner, 1, h->buf[1]);
     if (rc != DDRL_OK) { delete h; return rc; }
@@ -168,7 +237,7 @@ int ddrl_loop_create(ddrl_loop_t **out, ddrl_sac1_t *learner, ddrl_replay_t *rep
 
 int ddrl_loop_destroy(ddrl_loop_t *h) {
     if (!h) return DDRL_OK;
-    if (h->exec) (void)hipGraphExecDestroy(h->exec);
+    destroy_family(h);
     delete h;
     return DDRL_OK;
 }
@@ -177,7 +246,7 @@ int ddrl_loop_run(ddrl_loop_t *h, int64_t n_updates, void *stream) {
     DDRL_REQUIRE(h != nullptr && n_updates >= 0, "bad handle / n_updates");
     hipStream_t s = ddrl::as_stream(stream);
     int64_t left = n_updates;
-    if (h->per_graph > 0 && left >= h->per_graph) {
+    if (h->per_graph > 0 && (h->captured || left >= h->per_graph)) {   // (the first call of at least per_graph updates captures)
         if (!h->captured) {
             // one eager update first: surfaces EMPTY_BUFFER / argument errors outside the capture
             int rc = one_update(h, stream);
@@ -189,18 +258,29 @@ int ddrl_loop_run(ddrl_loop_t *h, int64_t n_updates, void *stream) {
                 DDRL_HIP_CHECK(hipDeviceSynchronize());
                 cs = own;
             }
-            rc = capture(h, cs);
+            rc = capture_family(h, cs);
             if (own) (void)hipStreamDestroy(own);
             if (rc != DDRL_OK) return rc;
         }
-        if (left >= h->per_graph) {  // eager updates since the last replay may have left the optimizer state on copy 1
+        if (left > 0) {  // eager updates since the last replay may have left the optimizer state on copy 1
             const int rc2 = ddrl_sac1_internal_opt_sync(h->learner, stream);
             if (rc2 != DDRL_OK) return rc2;
         }
-        while (left >= h->per_graph) {
-            DDRL_HIP_CHECK(hipGraphLaunch(h->exec, s));
-            left -= h->per_graph;
-        }
+        // Greedy: per_graph-sized replays, then each power of two at most once (left < per_graph <= 2 x the largest of them).
+        // The first replay of the call is head-sampled; each replay that another one follows draws that one's first batch.
+        bool first = true;
+        int set = 0;
+        for (const auto &g : h->family)
+            while (left >= g.len) {
+                const int pre = (!first && h->chain) ? 1 : 0, tail = (h->chain && left > g.len) ? 1 : 0;
+                if (!pre) set = 0;
+                hipGraphExec_t exec = g.exec[pre][set][tail];
+                DDRL_REQUIRE(exec != nullptr, "no captured graph for this replay (internal)");
+                DDRL_HIP_CHECK(hipGraphLaunch(exec, s));
+                set ^= g.len & 1;
+                left -= g.len;
+                first = false;
+            }
     }
     for (; left > 0; --left) {
         int rc = one_update(h, stream);
