@@ -77,6 +77,7 @@ SIGNATURES = {
     "ddrl_replay_gather_ex": (c_int, [_P, _P, c_int64, POINTER(_P), _P]),
     "ddrl_nstep_fold": (c_int, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P]),
     "ddrl_replay_sample_nstep": (c_int, [_P, c_int64, c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "ddrl_replay_sample_many_nstep": (c_int, [_P, c_int64, c_int64, c_float, POINTER(_P), _P]),
     "ddrl_replay_buffers_ex": (c_int, [_P, POINTER(_P), POINTER(c_int32), POINTER(c_int32)]),
     "ddrl_replay_counts": (c_int, [_P, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), _P]),
     "ddrl_replay_buffers": (c_int, [_P, POINTER(_P), POINTER(_P), POINTER(_P), POINTER(_P), POINTER(_P)]),

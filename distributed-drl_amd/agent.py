@@ -411,6 +411,8 @@ class Learner(_Net):
         _lib.check(lib.ddrl_sac1_grad_buffer(self._h, ctypes.byref(gp), ctypes.byref(gn)))
         g = _view(gp.value, (int(gn.value),), torch.device("cuda", torch.cuda.current_device()))
         B, h, rh, seed, nul = int(self.cfg.batch), self._h, ring._h, self._noise_seed, ctypes.c_void_p(None)
+        from .replay import ReplayBufferNStep
+        windows = isinstance(ring, ReplayBufferNStep)    # an n-step window ring: the priming draw folds, like the sampler in the launches
         state = self._dp_state = {"cur": 0, "primed": False}   # (train(host batch) looks at `primed` before it writes into input set 0)
 
         def grads(last=False):
@@ -418,7 +420,10 @@ class Learner(_Net):
             s, cur = sp(), state["cur"]
             if not state["primed"]:
                 i = ins[cur]
-                _lib.check(lib.ddrl_replay_sample(rh, B, i[0], i[1], i[2], i[3], i[4], nul, s))
+                if windows:
+                    _lib.check(lib.ddrl_replay_sample_nstep(rh, B, float(self.cfg.gamma), i[0], i[1], i[2], i[3], i[4], nul, s))
+                else:
+                    _lib.check(lib.ddrl_replay_sample(rh, B, i[0], i[1], i[2], i[3], i[4], nul, s))
             _lib.check(lib.ddrl_sac1_fill_noise(h, seed, s))
             if last:
                 _lib.check(lib.ddrl_sac1_compute_grads(h, *ins[cur], nul, nul, nul, nul, s))

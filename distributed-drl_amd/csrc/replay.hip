@@ -358,10 +358,6 @@ static int refresh_counts(ddrl_replay *h, hipStream_t s) {
             ddrl::set_error("high <= 0");  // the sampler drew from an empty ring (the reference's ValueError)
             return DDRL_ERR_EMPTY_BUFFER;
         }
-        if (tmp.error == DDRL_ERR_UNSUPPORTED) {
-            ddrl::set_error("a feed plan is attached to an n-step window ring: fed batches are not built for window rings (that update trained on a stale input set)");
-            return DDRL_ERR_UNSUPPORTED;
-        }
         if (tmp.error == DDRL_ERR_NOT_REPRESENTABLE) {
             ddrl::set_error("a value stored into a compact (uint8) ring array was not an integer in [0, 255]: the ring holds a clamped/truncated value there");
             return DDRL_ERR_NOT_REPRESENTABLE;
@@ -403,7 +399,7 @@ ddrl_replay_dev::SamplerView ddrl_replay_sampler_view_nstep(ddrl_replay_t *h, fl
 bool ddrl_replay_can_fuse_nstep(ddrl_replay_t *h, int64_t batch) {
     const RingPtrs &r = h->ring;
     const long long Ln = r.w[2], folded = 2 * (r.w[0] / (Ln + 1)) + r.w[1] / Ln + 2 * Ln;   // floats read per accepted index
-    return batch <= MAX_FUSED_BATCH && batch * folded * (long long)sizeof(float) <= MAX_FUSED_BYTES && h->h_size > 0 && !h->feed_on;
+    return batch <= MAX_FUSED_BATCH && batch * folded * (long long)sizeof(float) <= MAX_FUSED_BYTES && (h->h_size > 0 || h->feed_on);
 }
 void ddrl_replay_note_sample(ddrl_replay_t *h) { h->h_samples += h->ring.samples_inc; }
 void ddrl_replay_note_store(ddrl_replay_t *h, long long n) {  // host mirror bookkeeping for n stores issued by another kernel (ddrl_rollout_step)
@@ -626,32 +622,10 @@ int ddrl_nstep_fold(const float *obs_w_d, const float *acts_w_d, const float *re
     return DDRL_OK;
 }
 
-int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float *obs1_d, float *obs2_d, float *acts_d, float *rews_d,
-                             float *done_d, int64_t *idx_d, void *stream) {
-    DDRL_REQUIRE(h != nullptr && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
-    DDRL_REQUIRE(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
-    if (!ddrl_replay_is_window_ring(h, 0, 0)) {
-        ddrl::set_error("ddrl_replay_sample_nstep needs an n-step window ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays");
-        return DDRL_ERR_UNSUPPORTED;
-    }
-    if (h->feed_on) {
-        ddrl::set_error("a feed plan is attached to this ring: fed batches are not built for n-step window rings");
-        return DDRL_ERR_UNSUPPORTED;
-    }
+// The folded draw of `batch` rows of a window ring: one workgroup (draw + fold-gather) up to MAX_FUSED_BATCH rows, the wide draw and a
+// grid fold-gather beyond.  The ring is a window ring and (unless a feed is attached) known to hold rows.
+static int launch_sample_nstep(ddrl_replay *h, int64_t batch, float gamma, const BatchPtrs &out, long long *idx, hipStream_t s) {
     const int Ln = h->ring.w[2], od = h->ring.w[0] / (Ln + 1), ad = h->ring.w[1] / Ln;
-    DDRL_REQUIRE(batch * (od > ad ? od : ad) < 0x7fffffffll, "batch * max(obs_dim, act_dim) must be < 2^31");
-    ddrl::DeviceGuard g(h->device);
-    hipStream_t s = ddrl::as_stream(stream);
-    if (h->h_size <= 0 || h->h_dirty) {
-        int rc = refresh_counts(h, s);
-        if (rc != DDRL_OK) return rc;
-        if (h->h_size <= 0) {
-            ddrl::set_error("high <= 0");  // message of the reference's ValueError
-            return DDRL_ERR_EMPTY_BUFFER;
-        }
-    }
-    const BatchPtrs out{{obs1_d, obs2_d, acts_d, rews_d, done_d, nullptr}};
-    long long *idx = reinterpret_cast<long long *>(idx_d);
     if (batch <= MAX_FUSED_BATCH) {   // draw + fold-gather in the one workgroup
         const SamplerView v = ddrl_replay_sampler_view_nstep(h, gamma);
         k_sample<<<1, SAMPLE_THREADS, 0, s>>>(v.state, v.ring, out, (int)batch, idx, 1);
@@ -674,6 +648,73 @@ int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float
     const FoldSrc w{h->ring.a[0], h->ring.a[1], h->ring.a[2], h->ring.a[3], Ln, od, ad, gamma};
     k_nstep_gather<<<fold_grid(batch, od), 256, 0, s>>>(w, out, idx, (int)batch);
     DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+// argument checks shared by the two folded draws; `what` names the caller in the refusal
+static int check_sample_nstep(ddrl_replay *h, int64_t rows, const char *what) {
+    if (!ddrl_replay_is_window_ring(h, 0, 0)) {
+        ddrl::set_error("%s needs an n-step window ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays", what);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    const int Ln = h->ring.w[2], od = h->ring.w[0] / (Ln + 1), ad = h->ring.w[1] / Ln;
+    DDRL_REQUIRE(rows * (od > ad ? od : ad) < 0x7fffffffll, "batch * max(obs_dim, act_dim) must be < 2^31");
+    return DDRL_OK;
+}
+
+static int require_rows(ddrl_replay *h, hipStream_t s) {
+    if (h->h_size <= 0 || h->h_dirty) {
+        int rc = refresh_counts(h, s);
+        if (rc != DDRL_OK) return rc;
+        if (h->h_size <= 0) {
+            ddrl::set_error("high <= 0");  // message of the reference's ValueError
+            return DDRL_ERR_EMPTY_BUFFER;
+        }
+    }
+    return DDRL_OK;
+}
+
+int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float *obs1_d, float *obs2_d, float *acts_d, float *rews_d,
+                             float *done_d, int64_t *idx_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
+    DDRL_REQUIRE(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
+    int rc = check_sample_nstep(h, batch, "ddrl_replay_sample_nstep");
+    if (rc != DDRL_OK) return rc;
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    if (h->feed_on) {   // the plan decides per call: a fed batch is copied, a -1 entry draws and folds (an empty ring: the sticky error)
+        DDRL_REQUIRE(ddrl_replay_can_fuse_nstep(h, batch), "a feed plan is attached: the batch must fit the one-workgroup sampler");
+    } else if ((rc = require_rows(h, s)) != DDRL_OK) {
+        return rc;
+    }
+    const BatchPtrs out{{obs1_d, obs2_d, acts_d, rews_d, done_d, nullptr}};
+    return launch_sample_nstep(h, batch, gamma, out, reinterpret_cast<long long *>(idx_d), s);
+}
+
+int ddrl_replay_sample_many_nstep(ddrl_replay_t *h, int64_t batch, int64_t count, float gamma, float *const *out_h, void *stream) {
+    DDRL_REQUIRE(h != nullptr && out_h != nullptr, "NULL pointer");
+    DDRL_REQUIRE(batch > 0 && count > 0 && batch * count <= (1 << 24), "batch, count must be positive with batch * count <= 2^24");
+    int rc = check_sample_nstep(h, batch * count, "ddrl_replay_sample_many_nstep");
+    if (rc != DDRL_OK) return rc;
+    if (h->feed_on) {
+        ddrl::set_error("a feed plan is attached to this ring");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    BatchPtrs out{};
+    for (int j = 0; j < 5; ++j) {
+        DDRL_REQUIRE(out_h[j] != nullptr, "NULL output pointer");
+        out.a[j] = out_h[j];
+    }
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    if ((rc = require_rows(h, s)) != DDRL_OK) return rc;
+    // `count` consecutive folded sample_batch(batch) calls consume the index stream exactly like one draw of batch * count
+    // (the ring size cannot change in between: nothing else is ordered between them on this stream)
+    rc = launch_sample_nstep(h, batch * count, gamma, out, nullptr, s);
+    if (rc != DDRL_OK || count == 1) return rc;
+    k_add_samples<<<1, 1, 0, s>>>(h->state, (count - 1) * h->ring.samples_inc);
+    DDRL_LAUNCH_CHECK();
+    h->h_samples += (count - 1) * h->ring.samples_inc;
     return DDRL_OK;
 }
 

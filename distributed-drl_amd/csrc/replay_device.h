@@ -17,8 +17,9 @@ constexpr int MAX_FEED = 16;
 // Batches drawn on OTHER ranks' shards (partition.py): the learner's sampler follows a per-update plan held in
 // device memory — entry -1 = draw from the local ring, entry (r << 24 | i) = take batch i of region r, a block of
 // `count[r]` batches [obs1 | obs2 | acts | rews | done] (each array [count*B, w]) that shard owner r drew with its own
-// index stream and sent in one message.  Lives in the ring state so that a captured graph follows a new plan
-// without re-capture.
+// index stream and sent in one message.  A window ring's sampler (fold view) is fed the same transition-shaped blocks: its
+// owners fold on their own GPU (ddrl_replay_sample_many_nstep), a fed entry is copied as a finished batch and only -1
+// entries run the fold-gather.  Lives in the ring state so that a captured graph follows a new plan without re-capture.
 struct Feed {
     const int *plan;
     int pos, len, batch, n_regions;
@@ -195,10 +196,6 @@ __device__ __forceinline__ void sample_block(RingState *st, const RingPtrs &ring
     __shared__ unsigned s_idx[MAX_FUSED_BATCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (fuse_gather && st->feed.plan != nullptr) {
-        if (ring.fold) {  // fed batches are transition-shaped blocks another rank drew: not built for window rings — nothing is copied
-            if (tid == 0) st->error = DDRL_ERR_UNSUPPORTED;
-            return;
-        }
         const int pos = st->feed.pos;
         const int p = pos < st->feed.len ? st->feed.plan[pos] : -1;
         __syncthreads();  // every lane has read the position
@@ -211,19 +208,30 @@ __device__ __forceinline__ void sample_block(RingState *st, const RingPtrs &ring
             }
             const float *src = st->feed.base[r];
             const long long rows = (long long)st->feed.count[r] * B;
+            // batch i of the region's next array ([rows, w]) -> dst[B, w]; float4 where both sides and the row counts allow
+            auto copy_fed = [&](float *dst, int w) {
+                const int n = B * w;
+                const float *sj = src + (long long)i * n;
+                if ((n & 3) == 0 && ((rows * w) & 3) == 0 && ((((unsigned long long)dst) | ((unsigned long long)src)) & 15ull) == 0) {
+                    for (int e = tid; e < (n >> 2); e += SAMPLE_THREADS)
+                        reinterpret_cast<float4 *>(dst)[e] = reinterpret_cast<const float4 *>(sj)[e];
+                } else {
+                    for (int e = tid; e < n; e += SAMPLE_THREADS) dst[e] = sj[e];
+                }
+                src += rows * w;
+            };
+            if (ring.fold) {  // a window ring's regions hold FOLDED blocks (the owner folded): the five learner arrays {od, od, ad, 1, 1}
+                const int Ln = ring.w[3], od = ring.w[0] / (Ln + 1), ad = ring.w[1] / Ln;
+                copy_fed(out.a[0], od);
+                copy_fed(out.a[1], od);
+                copy_fed(out.a[2], ad);
+                copy_fed(out.a[3], 1);
+                copy_fed(out.a[4], 1);
+                return;
+            }
 #pragma unroll
             for (int j = 0; j < MAX_ARRAYS; ++j)
-                if (j < ring.n_arr) {
-                    const int w = ring.w[j], n = B * w;
-                    const float *sj = src + (long long)i * n;
-                    if ((n & 3) == 0 && ((rows * w) & 3) == 0 && ((((unsigned long long)out.a[j]) | ((unsigned long long)src)) & 15ull) == 0) {
-                        for (int e = tid; e < (n >> 2); e += SAMPLE_THREADS)
-                            reinterpret_cast<float4 *>(out.a[j])[e] = reinterpret_cast<const float4 *>(sj)[e];
-                    } else {
-                        for (int e = tid; e < n; e += SAMPLE_THREADS) out.a[j][e] = sj[e];
-                    }
-                    src += rows * w;
-                }
+                if (j < ring.n_arr) copy_fed(out.a[j], ring.w[j]);
             return;
         }
     }

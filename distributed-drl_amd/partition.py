@@ -181,8 +181,14 @@ class PartitionedRun:
     broadcasts the flat parameter vector and the rollout ranks adopt it."""
 
     def __init__(self, opt, roles, make_replay, make_rollout, make_learner, seed=0, push_freq=None, device=None, updates_per_graph=16,
-                 force_dp=False, dp_updates_per_graph=None, free_steps=0):
-        """free_steps = K > 0: the FREE-RUNNING mode (example/dsac.py:229-236: rollouts and learners are launched and left running, no
+                 force_dp=False, dp_updates_per_graph=None, free_steps=0, nstep=None):
+        """nstep=True: the run of the n-step driver (algos/sac1/sac_ray.py, the reference's one driver that is both n-step and sharded) —
+        make_replay returns a ReplayBufferNStep, make_rollout a RolloutDeviceNStep.  A shard owner FOLDS on its own GPU (the folded
+        sample_many, discount opt.gamma — the learner's own) and sends the same transition-shaped blocks as ever; a learner's sampler
+        sees its window ring in fold view, copies fed batches as they are and fold-gathers local draws; a dedicated learner's feed
+        ring is an empty one-slot window ring.  Lock-step mode only.  Default (None): what this rank's shard is; a rank without
+        a shard adopts what the owners hold (the ranks compare at construction; a disagreement raises ValueError on every rank).
+        free_steps = K > 0: the FREE-RUNNING mode (example/dsac.py:229-236: rollouts and learners are launched and left running, no
         gate between them, dsac.py:76-150).  A step is then K vector steps on every rollout rank beside the learners' n updates, and
         nothing on a rollout rank's env stream ever waits for the learners of the SAME step:
           * blocks: an owner draws and sends, behind its K vector steps of step s, the batches of step s + 1; a learner posts the
@@ -205,6 +211,21 @@ class PartitionedRun:
         self.schedule = Schedule(roles, seed)
         self.push_freq = int(getattr(opt, "push_freq", 300) if push_freq is None else push_freq)
         self.rb = make_replay() if roles.my_shard is not None else None
+        from .replay import ReplayBufferNStep
+        # every rank must run the same kind of run: what the shards are and what the callers said is compared across the ranks (a
+        # rank without a shard that was not told adopts the rest's answer); a disagreement raises on EVERY rank
+        mine = [isinstance(self.rb, ReplayBufferNStep) if self.rb is not None else None, None if nstep is None else bool(nstep)]
+        said = [mine]
+        if dist.is_initialized() and roles.world > 1:
+            said = [None] * roles.world
+            dist.all_gather_object(said, mine)               # collective: every rank calls it
+        kinds = sorted(set(v for pair in said for v in pair if v is not None))
+        if len(kinds) > 1:
+            raise ValueError("the ranks disagree on window rings / nstep: (shard is a window ring, nstep argument) per rank = %s" % (said,))
+        mine = kinds[0] if kinds else False
+        self.nstep = bool(mine)
+        if self.nstep and self.free_steps > 0:
+            raise ValueError("free-running mode (free_steps=%d) is not built for n-step window rings: use lock-step mode (free_steps=0)" % self.free_steps)
         self.learner = make_learner() if roles.is_learner else None
         from .agent import param_specs
         self.n_params = int(sum(int(np.prod(sh)) for _, sh in param_specs(opt.obs_dim, opt.act_dim, opt.hidden_sizes[0], opt.hidden_sizes[1],
@@ -219,9 +240,17 @@ class PartitionedRun:
         self.feed_ring, self.loop, self.batch_buf = None, None, None
         if self.learner is not None:
             # the ring whose sampler the learner drives: its own shard, or (dedicated learner rank) an empty one-row ring
-            # that only ever follows the feed plan
+            # that only ever follows the feed plan — of the run's own kind: a window ring's sampler is fed folded blocks
             from .replay import ReplayBufferSAC1
-            self.feed_ring = self.rb if self.rb is not None else ReplayBufferSAC1(opt.obs_dim, opt.act_dim, 1)
+            if self.rb is not None:
+                self.feed_ring = self.rb
+            elif self.nstep:
+                import copy
+                one = copy.copy(opt)
+                one.buffer_size = 1
+                self.feed_ring = ReplayBufferNStep(one)
+            else:
+                self.feed_ring = ReplayBufferSAC1(opt.obs_dim, opt.act_dim, 1)
             self.batch_buf = torch.empty(self.nf, dtype=torch.float32, device=self.device)
             if self.lgroup is None:
                 self.loop = _Loop(self.learner, self.feed_ring, updates_per_graph)
@@ -306,7 +335,9 @@ class PartitionedRun:
             k = sum(1 for p in plans if p[li][1] == me)
             if k == 0:
                 continue
-            blk = self.rb.sample_many(self.B, k, self._buf(self.send_bufs, l, k))
+            buf = self._buf(self.send_bufs, l, k)
+            # (a window ring's owner folds here, with the discount the learner folds its local draws with: the block does not carry it)
+            blk = self.rb.sample_many(self.B, k, buf, gamma=self.opt.gamma) if self.nstep else self.rb.sample_many(self.B, k, buf)
             self.sends.append(_send(blk, l))
             self.stats["sent_batches"] += k
             self.stats["sent_blocks"] += 1

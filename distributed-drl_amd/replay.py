@@ -18,7 +18,43 @@ import torch
 from . import _lib
 
 
-class ReplayBuffer:
+def _block_ptrs(flat, rows, obs_dim, act_dim):
+    """The five array bases of a packed block [obs1 | obs2 | acts | rews | done], each array [rows, w], inside `flat`."""
+    ptrs, off = (ctypes.c_void_p * 5)(), 0
+    for j, w in enumerate((obs_dim, obs_dim, act_dim, 1, 1)):
+        ptrs[j] = flat.data_ptr() + 4 * off
+        off += rows * w
+    assert flat.numel() >= off and flat.dtype == torch.float32 and flat.is_cuda and flat.is_contiguous()
+    return ptrs, off
+
+
+class _Fed:
+    """The learner side of the sharded replay, for every ring class (a handle in self._h): the sampler's feed plan and its
+    sticky device-side error."""
+
+    def set_feed(self, plan, batch_size, regions):
+        """Attach a per-update feed plan (int32 device tensor: -1 = local draw, r << 24 | i = batch i of regions[r]) to
+        this ring's sampler; regions = [(packed block tensor, batches in it)].  plan=None detaches."""
+        if plan is None:
+            _lib.check(self._lib.ddrl_replay_set_feed(self._h, None, 0, 0, 0, None, None, _lib.stream_ptr()))
+            self._feed_keep = None
+            return
+        assert plan.dtype == torch.int32 and plan.is_cuda and plan.is_contiguous()
+        n = len(regions)
+        base, cnt = (ctypes.c_void_p * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+        for r, (t, k) in enumerate(regions):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
+            base[r], cnt[r] = t.data_ptr(), int(k)
+        _lib.check(self._lib.ddrl_replay_set_feed(self._h, _lib.dptr(plan), int(plan.numel()), int(batch_size), n, base, cnt, _lib.stream_ptr()))
+        self._feed_keep = (plan, [t for t, _ in regions])   # the kernels read these until the next set_feed
+
+    def take_error(self, out):
+        """Move the sampler's sticky device-side error into out[0] (int32 device tensor) and clear it; no sync."""
+        assert out.dtype == torch.int32 and out.is_cuda
+        _lib.check(self._lib.ddrl_replay_take_error(self._h, _lib.dptr(out), _lib.stream_ptr()))
+
+
+class ReplayBuffer(_Fed):
     """A simple FIFO experience replay buffer for SAC agents (example/dsac.py:14-48)."""
 
     _default_batch = 32
@@ -262,36 +298,11 @@ class ReplayBuffer:
         as one block [obs1 | obs2 | acts | rews | done], each array [count * B, w] (ddrl_replay_sample_many): what a
         shard owner sends a remote learner for one step (partition.py)."""
         B, K = int(batch_size), int(count)
-        ptrs, off = (ctypes.c_void_p * 5)(), 0
-        for j, w in enumerate((self.obs_dim, self.obs_dim, self.act_dim, 1, 1)):
-            ptrs[j] = flat.data_ptr() + 4 * off
-            off += K * B * w
-        assert flat.numel() >= off and flat.dtype == torch.float32 and flat.is_cuda and flat.is_contiguous()
+        ptrs, off = _block_ptrs(flat, K * B, self.obs_dim, self.act_dim)
         self._pf_order_store(True)
         _lib.check(self._lib.ddrl_replay_sample_many(self._h, B, K, ptrs, _lib.stream_ptr()))
         self._pf_order_store(False)
         return flat[:off]
-
-    def set_feed(self, plan, batch_size, regions):
-        """Attach a per-update feed plan (int32 device tensor: -1 = local draw, r << 24 | i = batch i of regions[r]) to
-        this ring's sampler; regions = [(packed block tensor, batches in it)].  plan=None detaches."""
-        if plan is None:
-            _lib.check(self._lib.ddrl_replay_set_feed(self._h, None, 0, 0, 0, None, None, _lib.stream_ptr()))
-            self._feed_keep = None
-            return
-        assert plan.dtype == torch.int32 and plan.is_cuda and plan.is_contiguous()
-        n = len(regions)
-        base, cnt = (ctypes.c_void_p * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
-        for r, (t, k) in enumerate(regions):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
-            base[r], cnt[r] = t.data_ptr(), int(k)
-        _lib.check(self._lib.ddrl_replay_set_feed(self._h, _lib.dptr(plan), int(plan.numel()), int(batch_size), n, base, cnt, _lib.stream_ptr()))
-        self._feed_keep = (plan, [t for t, _ in regions])   # the kernels read these until the next set_feed
-
-    def take_error(self, out):
-        """Move the sampler's sticky device-side error into out[0] (int32 device tensor) and clear it; no sync."""
-        assert out.dtype == torch.int32 and out.is_cuda
-        _lib.check(self._lib.ddrl_replay_take_error(self._h, _lib.dptr(out), _lib.stream_ptr()))
 
     def get_counts(self):
         """example/dsac.py:47-48: number of store() calls so far."""
@@ -434,13 +445,15 @@ class ReplayBufferDQN(ReplayBuffer):
                                                     int(infos[4]), _lib.stream_ptr()))
 
 
-class ReplayBufferNStep:
+class ReplayBufferNStep(_Fed):
     """The n-step window buffer of algos/sac1/sac_ray.py:34-82: `ReplayBuffer(opt)` with
     opt.buffer_size slots, each holding (opt.Ln + 1) observation frames and opt.Ln (action, reward,
     done) triples; `store(o_queue, a_r_d_queue, worker_index)` takes the rollout's two deques
     (sac_ray.py:53-70), `sample_batch()` returns dict(obs, acts, rews, done) of whole windows
     (sac_ray.py:72-80) and the counters advance by opt.num_buffers per call.  Float observations
-    only (the reference's packed-string CNN frames are out of scope)."""
+    only (the reference's packed-string CNN frames are out of scope).
+    Sharded (partition.py): a shard owner folds on its own GPU — sample_many() hands out transition-shaped blocks — and a
+    learner's ring follows a feed plan of such blocks (set_feed): regions of a window ring hold FOLDED batches."""
 
     def __init__(self, opt, device=None, seed=None):
         _lib.require_gpu()
@@ -536,6 +549,17 @@ class ReplayBufferNStep:
         if with_indices:
             out["idxs"] = idx
         return out
+
+    def sample_many(self, batch_size, count, flat, gamma=None):
+        """`count` consecutive sample_nstep_device(batch_size) draws folded into the packed float32 device buffer `flat` as one block
+        [obs1 | obs2 | acts | rews | done], each array [count * B, w] (ddrl_replay_sample_many_nstep): the layout of
+        ReplayBuffer.sample_many, so what a shard owner sends a remote learner for one step is the same message on both kinds of
+        ring.  The block does not record `gamma` (default opt.gamma): the learner it feeds must fold with the same value."""
+        B, K = int(batch_size), int(count)
+        g = float(self.opt.gamma if gamma is None else gamma)
+        ptrs, off = _block_ptrs(flat, K * B, self.obs_dim, self.act_dim)
+        _lib.check(self._lib.ddrl_replay_sample_many_nstep(self._h, B, K, g, ptrs, _lib.stream_ptr()))
+        return flat[:off]
 
     def get_counts(self):
         c = [ctypes.c_int64() for _ in range(4)]

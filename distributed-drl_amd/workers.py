@@ -739,7 +739,11 @@ class RolloutDeviceNStep:
     """worker_rollout of the n-step driver (algos/sac1/sac_ray.py:179-262) for `opt.num_envs` envs per launch:
     Wrapper'd env.step (action noise, action repeat 3, observation noise, reward scale), the per-env window
     queues, and `replay_buffer[random shard].store(o_queue, a_r_d_queue)` for every env whose queues are full —
-    one masked row store per vector step.  `replay_buffers` is a ReplayBufferNStep or a list of them."""
+    one masked row store per vector step.  `replay_buffers` is a ReplayBufferNStep or a list of them.
+    ps=None (a rollout rank of partition.py): nothing is pulled — the worker still owns an Actor, which takes the learner's
+    broadcasts through actor.set_weights_flat, as RolloutDevice's does, and acts with it once filling_steps > opt.start_steps
+    (until then, and for ever with the default start_steps inside a short run, on random actions as before; earlier versions
+    had no Actor without a server and stayed on random actions throughout)."""
 
     WRAPPER_REPEAT = 3  # the literal in sac_ray.py:189 (opt.action_repeat only scales the episode limit)
 
@@ -753,7 +757,7 @@ class RolloutDeviceNStep:
         n = int(opt.num_envs)
         self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23)
         self.limit_steps = -(-int(opt.max_ep_len) // int(opt.action_repeat))   # ep_len * action_repeat >= max_ep_len (sac_ray.py:252)
-        self.actor = Actor(opt, job="worker", max_rows=n, index=worker_index) if ps is not None else None
+        self.actor = Actor(opt, job="worker", max_rows=n, index=worker_index)
         self.span = ps.span(self.actor.keys) if ps is not None else None
         self._layout = getattr(ps, "layout", 0)
         self.version = -1
@@ -770,7 +774,7 @@ class RolloutDeviceNStep:
         self.adopt = getattr(opt, "adopt", "episode")
         self._versions = False
         self._learning = bool(getattr(opt, "weights_file", ""))   # steps > start_steps seen (sticky): pulls happen from then on
-        if self.adopt == "episode" and self.actor is not None and n % 32 == 0:
+        if self.adopt == "episode" and n % 32 == 0:
             try:
                 self.actor.enable_versions(min(2048, min(n, self.limit_steps) + 2))
                 self._versions = True
@@ -779,13 +783,18 @@ class RolloutDeviceNStep:
 
     pull = RolloutDevice.pull
 
-    def step(self):
+    def step(self, n_steps=1):
+        """n_steps vector steps, back to back."""
+        for _ in range(int(n_steps)):
+            self._step_once()
+
+    def _step_once(self):
         """One vector step = num_envs iterations of sac_ray.py:208-262."""
         env, opt = self.env, self.opt
         if self._versions:
             self.pull()              # what the server holds now is what an env ending its episode in this step would pull
         self.o.copy_(env.obs)
-        if self.actor is not None and (self.filling_steps > opt.start_steps or getattr(opt, "weights_file", "")):
+        if self.filling_steps > opt.start_steps or getattr(opt, "weights_file", ""):
             if self._versions:
                 self.actor.get_actions_versioned(self.o, self.limit_steps, out=self.act)
             else:

@@ -139,6 +139,11 @@ int ddrl_replay_sample_many(ddrl_replay_t *h, int64_t batch, int64_t count, floa
  * follow plan_d[0..plan_len) (DEVICE int32): -1 = draw from this ring as usual; (r << 24 | i) = copy batch i of
  * region r instead, consuming no local draw.  Region r is a block that ddrl_replay_sample_many produced on the
  * owning rank: region_base_h[r] (device) -> [obs1 | obs2 | ...] with each array [region_count_h[r]*batch, w_j].
+ * On an n-step window ring (a learner's sampler sees it in fold view: ddrl_replay_sample_nstep, the learner's launches, ddrl_loop_*)
+ * the regions hold FOLDED blocks — [obs1 | obs2 | acts | rews | done] with widths {obs, obs, act, 1, 1}, what
+ * ddrl_replay_sample_many_nstep produced on the owning rank: a fed entry is copied as a finished transition batch and only -1
+ * entries run the fold-gather on the local windows.  A folded block carries no record of its discount: the owner's `gamma` and the
+ * learner's must be the same value (the Python layer passes opt.gamma on both sides).
  * The plan position restarts at 0 on every call; plan_d and the regions must stay valid while attached.
  * plan_d == NULL detaches.  n_regions <= 16.  A plan entry that is out of range (wrong batch, region or batch index)
  * or a local draw from an empty ring cannot fail the call that launched it (it may run inside a captured graph): it
@@ -170,10 +175,19 @@ int ddrl_nstep_fold(const float *obs_w_d, const float *acts_w_d, const float *re
 /* sample_batch of a window ring (sac_ray.py:72-80) folded on the way out: the index draw of ddrl_replay_sample_ex (same MT19937
  * stream, same counters, same empty-ring error) followed, in the same launch for batch <= 4096, by a fold-gather that reads only
  * o[0], o[Ln], a[0] and the 2 Ln reward / done scalars of every drawn row.  Ln, obs_dim and act_dim come from the ring's widths
- * {(Ln+1)*obs, Ln*act, Ln, Ln}.  idx_d (nullable) receives the indices.  DDRL_ERR_UNSUPPORTED for a ring that is not of that shape,
- * has compact (uint8) arrays, or has a feed plan attached. */
+ * {(Ln+1)*obs, Ln*act, Ln, Ln}.  idx_d (nullable) receives the indices.  DDRL_ERR_UNSUPPORTED for a ring that is not of that shape
+ * or has compact (uint8) arrays.  With a feed plan attached (ddrl_replay_set_feed) the call follows the plan — a fed entry copies a
+ * folded batch and leaves idx_d alone — and the batch must fit the one-workgroup sampler, the rule of ddrl_replay_sample_ex. */
 int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float *obs1_d, float *obs2_d, float *acts_d,
                              float *rews_d, float *done_d, int64_t *idx_d, void *stream);
+/* `count` consecutive folded sample_batch(batch) calls of a window ring in one launch sequence — ddrl_replay_sample_many for the
+ * n-step driver: out_h[0..4] = obs1, obs2, acts, rews, done, each [count*batch, w] with w = obs, obs, act, 1, 1 and batch i in rows
+ * [i*batch, (i+1)*batch); the arrays may start at any float offset (a packed block).  Consumes the index stream like one draw of
+ * batch * count and advances sample_times by count * samples_inc.  A shard owner folds on its own GPU with it and sends the
+ * transition-shaped block (a fifth of the bytes of whole windows at Ln = 8); the block carries no record of `gamma` — the learner
+ * that is fed it must fold its local draws with the same value.  DDRL_ERR_UNSUPPORTED for a ring that is no float32 window ring
+ * or has a feed plan attached; DDRL_ERR_EMPTY_BUFFER ("high <= 0") for an empty one. */
+int ddrl_replay_sample_many_nstep(ddrl_replay_t *h, int64_t batch, int64_t count, float gamma, float *const *out_h, void *stream);
 
 /* Raw ring pointers (device) for checkpointing / inspection (algos/dqn/train.py:82-90 saves
  * exactly these five arrays + (ptr,size,max_size,steps,sample_times)). */
