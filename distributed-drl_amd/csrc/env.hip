@@ -530,18 +530,7 @@ __global__ void __launch_bounds__(64) k_env_step_pi(RolloutArgs a) {
     }
     // the last block to finish advances the ring cursor (every block has read rs->ptr before its ticket)
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned ticket = atomicAdd(&a.rs->done_counter, 1u);
-        s_last = ticket == gridDim.x - 1 ? 1 : 0;
-        if (ticket == gridDim.x - 1) {
-            const long long cap = a.ring.capacity;
-            a.rs->ptr = (s_ptr + n) % cap;
-            const long long sz = a.rs->size + n;
-            a.rs->size = sz > cap ? cap : sz;
-            a.rs->steps += n * a.ring.steps_inc;
-            a.rs->done_counter = 0;
-        }
-    }
+    if (threadIdx.x == 0) s_last = ddrl_replay_dev::ring_commit(a.rs, a.ring, s_ptr, n) ? 1 : 0;
     if (!a.vcnt) return;
     __syncthreads();
     if (!s_last) return;   // block-uniform

@@ -58,17 +58,10 @@ __global__ void __launch_bounds__(256) k_store(RingState *st, RingPtrs ring, Sto
                 const float f[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
                 unsigned u[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const unsigned b = (unsigned)(int)fminf(fmaxf(f[k], 0.f), 255.f);
-                    bad |= !((float)b == f[k]);
-                    u[k >> 2] |= b << (8 * (k & 3));
-                }
+                for (int k = 0; k < 16; ++k) u[k >> 2] |= to_u8(f[k], bad) << (8 * (k & 3));
                 *reinterpret_cast<uint4 *>(d8 + dof) = make_uint4(u[0], u[1], u[2], u[3]);
             } else {
-                const float f = src[so];
-                const unsigned b = (unsigned)(int)fminf(fmaxf(f, 0.f), 255.f);
-                bad |= !((float)b == f);
-                d8[dof] = (unsigned char)b;
+                d8[dof] = (unsigned char)to_u8(src[so], bad);
             }
         }
         if (bad) st->error = DDRL_ERR_NOT_REPRESENTABLE;
@@ -100,17 +93,7 @@ __global__ void __launch_bounds__(256) k_store(RingState *st, RingPtrs ring, Sto
     }
     // last block to finish advances the cursor (every block has read st->ptr before its ticket)
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned total_blocks = gridDim.x * gridDim.y;
-        const unsigned ticket = atomicAdd(&st->done_counter, 1u);
-        if (ticket == total_blocks - 1) {
-            st->ptr = (ptr + n) % cap;
-            const long long sz = st->size + n;
-            st->size = sz > cap ? cap : sz;
-            st->steps += n * ring.steps_inc;
-            st->done_counter = 0;
-        }
-    }
+    if (threadIdx.x == 0) ring_commit(st, ring, ptr, n);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -162,17 +145,7 @@ __global__ void __launch_bounds__(256) k_store_masked(RingState *st, RingPtrs ri
         else dst[row * wv + c] = src[e];
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned total_blocks = gridDim.x * gridDim.y;
-        const unsigned ticket = atomicAdd(&st->done_counter, 1u);
-        if (ticket == total_blocks - 1) {
-            st->ptr = (ptr + total) % cap;
-            const long long sz = st->size + total;
-            st->size = sz > cap ? cap : sz;
-            st->steps += total * ring.steps_inc;
-            st->done_counter = 0;
-        }
-    }
+    if (threadIdx.x == 0) ring_commit(st, ring, ptr, total);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -305,13 +278,8 @@ __global__ void __launch_bounds__(256) k_rows_import(RingState *st, RingPtrs rin
     bool bad = false;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const float f = src[e];
-        if (ring.kind[j] == 1) {
-            const unsigned b = (unsigned)(int)fminf(fmaxf(f, 0.f), 255.f);
-            bad |= !((float)b == f);
-            r8[off + e] = (unsigned char)b;
-        } else {
-            ring.a[j][off + e] = f;
-        }
+        if (ring.kind[j] == 1) r8[off + e] = (unsigned char)to_u8(f, bad);
+        else ring.a[j][off + e] = f;
     }
     if (bad) st->error = DDRL_ERR_NOT_REPRESENTABLE;
 }
@@ -368,18 +336,28 @@ static int refresh_counts(ddrl_replay *h, hipStream_t s) {
     return DDRL_OK;
 }
 
-ddrl_replay_dev::SamplerView ddrl_replay_sampler_view(ddrl_replay_t *h) { return ddrl_replay_dev::SamplerView{h->state, h->ring, h->device}; }
-static long long row_floats(const ddrl_replay *h) {
+ddrl_replay_dev::SamplerView ddrl_replay_sampler_view(ddrl_replay_t *h, bool fold, float gamma) {
+    ddrl_replay_dev::SamplerView v{h->state, h->ring, h->device};
+    v.ring.fold = fold ? 1 : 0;
+    v.ring.gamma = fold ? gamma : 0.f;
+    return v;
+}
+// floats gathered per accepted index: the whole row of a plain view; o[0], o[Ln], a[0] and the 2 Ln reward / done scalars of a fold view
+static long long view_floats(const RingPtrs &r) {
+    if (r.fold) {
+        const long long Ln = r.w[2];
+        return 2 * (r.w[0] / (Ln + 1)) + r.w[1] / Ln + 2 * Ln;
+    }
     long long t = 0;
-    for (int j = 0; j < h->ring.n_arr; ++j) t += h->ring.w[j];
+    for (int j = 0; j < r.n_arr; ++j) t += r.w[j];
     return t;
 }
 static bool has_compact(const ddrl_replay *h) {
     for (int j = 0; j < h->ring.n_arr; ++j) if (h->ring.kind[j]) return true;
     return false;
 }
-bool ddrl_replay_can_fuse(ddrl_replay_t *h, int64_t batch) {
-    const long long bytes = batch * row_floats(h) * (long long)sizeof(float);
+bool ddrl_replay_can_fuse(ddrl_replay_t *h, const ddrl_replay_dev::SamplerView &v, int64_t batch) {
+    const long long bytes = batch * view_floats(v.ring) * (long long)sizeof(float);
     return batch <= MAX_FUSED_BATCH && bytes <= MAX_FUSED_BYTES && (h->h_size > 0 || h->feed_on);
 }
 // {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]}, all float32; obs_dim / act_dim <= 0: whatever the widths give
@@ -390,22 +368,137 @@ bool ddrl_replay_is_window_ring(ddrl_replay_t *h, int obs_dim, int act_dim) {
     if (Ln < 1 || r.w[3] != Ln || r.w[0] % (Ln + 1) != 0 || r.w[1] % Ln != 0) return false;
     return (obs_dim <= 0 || r.w[0] == (Ln + 1) * obs_dim) && (act_dim <= 0 || r.w[1] == Ln * act_dim);
 }
-ddrl_replay_dev::SamplerView ddrl_replay_sampler_view_nstep(ddrl_replay_t *h, float gamma) {
-    ddrl_replay_dev::SamplerView v{h->state, h->ring, h->device};
-    v.ring.fold = 1;
-    v.ring.gamma = gamma;
-    return v;
-}
-bool ddrl_replay_can_fuse_nstep(ddrl_replay_t *h, int64_t batch) {
-    const RingPtrs &r = h->ring;
-    const long long Ln = r.w[2], folded = 2 * (r.w[0] / (Ln + 1)) + r.w[1] / Ln + 2 * Ln;   // floats read per accepted index
-    return batch <= MAX_FUSED_BATCH && batch * folded * (long long)sizeof(float) <= MAX_FUSED_BYTES && (h->h_size > 0 || h->feed_on);
-}
 void ddrl_replay_note_sample(ddrl_replay_t *h) { h->h_samples += h->ring.samples_inc; }
-void ddrl_replay_note_store(ddrl_replay_t *h, long long n) {  // host mirror bookkeeping for n stores issued by another kernel (ddrl_rollout_step)
+void ddrl_replay_note_store(ddrl_replay_t *h, long long n) {  // host mirror bookkeeping for n stores (ddrl_replay_store_ex, ddrl_rollout_step)
     h->h_ptr = (h->h_ptr + n) % h->ring.capacity;
     h->h_size = (h->h_size + n > h->ring.capacity) ? h->ring.capacity : h->h_size + n;
     h->h_steps += n * h->ring.steps_inc;
+}
+
+// A draw needs rows: the mirror may lag behind graph replays / masked stores, so ask the device before reporting empty
+static int require_rows(ddrl_replay *h, hipStream_t s) {
+    if (h->h_size <= 0 || h->h_dirty) {
+        int rc = refresh_counts(h, s);
+        if (rc != DDRL_OK) return rc;
+        if (h->h_size <= 0) {
+            ddrl::set_error("high <= 0");  // message of the reference's ValueError
+            return DDRL_ERR_EMPTY_BUFFER;
+        }
+    }
+    return DDRL_OK;
+}
+
+// Device scratch that holds at least `need` elements (its old contents are not kept): the launches that read the old block are waited for
+template <class T>
+static int grow(T *&buf, long long &cap, long long need, hipStream_t s) {
+    if (need <= cap) return DDRL_OK;
+    DDRL_HIP_CHECK(hipStreamSynchronize(s));
+    (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    DDRL_HIP_CHECK(hipMalloc(&buf, need * sizeof(T)));
+    cap = need;
+    return DDRL_OK;
+}
+
+// The source table of a store and its widest row in vector elements (the grid's size); false: a source is NULL
+static bool store_srcs(const ddrl_replay *h, const float *const *src_h, StoreSrc &srcs, int &widest) {
+    srcs = StoreSrc{};
+    widest = 1;
+    for (int j = 0; j < h->ring.n_arr; ++j) {
+        if (src_h[j] == nullptr) return false;
+        srcs.a[j] = src_h[j];
+        const int wv = (h->ring.w[j] & 3) == 0 ? h->ring.w[j] / 4 : h->ring.w[j];
+        if (wv > widest) widest = wv;
+    }
+    return true;
+}
+
+static int launch_gather(ddrl_replay *h, const long long *idx, int64_t B, BatchPtrs out, hipStream_t s) {
+    int widest = 1;
+    for (int j = 0; j < h->ring.n_arr; ++j) widest = h->ring.w[j] > widest ? h->ring.w[j] : widest;
+    if (widest <= 64 && B >= 4096) {  // many small rows
+        long long blocks = (B * ((widest & 3) == 0 ? widest / 4 : widest) + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        k_gather_small<<<dim3((unsigned)blocks, (unsigned)h->ring.n_arr), 256, 0, s>>>(h->ring, out, idx, (int)B);
+        DDRL_LAUNCH_CHECK();
+        return DDRL_OK;
+    }
+    k_gather<<<dim3((unsigned)B, (unsigned)h->ring.n_arr), 256, 0, s>>>(h->ring, out, idx, (int)B);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+static int fold_grid(int64_t batch, int od) {
+    long long blocks = (batch * ((od & 3) == 0 ? od / 4 : od) + 255) / 256;
+    return (int)(blocks > 4096 ? 4096 : (blocks < 1 ? 1 : blocks));
+}
+
+// The one place a draw is launched: `batch` indices of view `v` (a plain ring, or a window ring's fold view), gathered into `out`
+// (NULL: indices only) and written to `idx` (nullable).
+//   draw + gather in one workgroup (k_sample, fuse 1): a plain batch <= MAX_FUSED_BATCH rows and <= MAX_FUSED_BYTES, a folded one
+//     <= MAX_FUSED_BATCH rows whatever its bytes.  The only form that follows a feed plan (the entry points refuse the others then).
+//   otherwise: the draw — 640-thread form from 2048 indices on — into `idx` or the handle's scratch, then the view's gather launch.
+// The thresholds were measured one by one: they are not meant to agree.
+static int launch_draw(ddrl_replay *h, const SamplerView &v, int64_t batch, const BatchPtrs *out, long long *idx, hipStream_t s) {
+    const RingPtrs &r = v.ring;
+    const bool fuse = out && batch <= MAX_FUSED_BATCH && (r.fold || batch * view_floats(r) * (long long)sizeof(float) <= MAX_FUSED_BYTES);
+    const BatchPtrs o = out ? *out : BatchPtrs{};
+    if (!fuse && !idx) {
+        const int rc = grow(h->idx_buf, h->idx_cap, batch, s);
+        if (rc != DDRL_OK) return rc;
+        idx = h->idx_buf;
+    }
+    if (!fuse && batch >= 2048) k_sample_wide<<<1, 640, 0, s>>>(v.state, r, o, (int)batch, idx);
+    else k_sample<<<1, SAMPLE_THREADS, 0, s>>>(v.state, r, o, (int)batch, idx, fuse ? 1 : 0);
+    DDRL_LAUNCH_CHECK();
+    h->h_samples += r.samples_inc;
+    if (fuse || !out) return DDRL_OK;
+    if (!r.fold) return launch_gather(h, idx, batch, o, s);
+    const int Ln = r.w[2], od = r.w[0] / (Ln + 1), ad = r.w[1] / Ln;
+    const FoldSrc w{r.a[0], r.a[1], r.a[2], r.a[3], Ln, od, ad, r.gamma};
+    k_nstep_gather<<<fold_grid(batch, od), 256, 0, s>>>(w, o, idx, (int)batch);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+int ddrl_replay_draw(ddrl_replay_t *h, const SamplerView &v, int64_t batch, const BatchPtrs &out, int64_t *idx_d, void *stream) {
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    if (h->feed_on) {   // the plan decides per call: a fed batch is copied, a -1 entry draws (an empty ring: the sticky error)
+        DDRL_REQUIRE(ddrl_replay_can_fuse(h, v, batch), "a feed plan is attached: the batch must fit the one-workgroup sampler");
+    } else {
+        const int rc = require_rows(h, s);
+        if (rc != DDRL_OK) return rc;
+    }
+    return launch_draw(h, v, batch, &out, reinterpret_cast<long long *>(idx_d), s);
+}
+
+// `count` consecutive sample_batch(batch) calls through view `v` consume the index stream exactly like one draw of batch * count
+// (the ring size cannot change in between: nothing else is ordered between them on this stream); the counter takes the other calls
+static int sample_many(ddrl_replay *h, const SamplerView &v, int64_t batch, int64_t count, float *const *out_h, void *stream) {
+    BatchPtrs out;
+    DDRL_REQUIRE(batch_ptrs(out, out_h, v.ring.fold ? 5 : v.ring.n_arr), "NULL output pointer");
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    int rc = require_rows(h, s);
+    if (rc == DDRL_OK) rc = launch_draw(h, v, batch * count, &out, nullptr, s);
+    if (rc != DDRL_OK || count == 1) return rc;
+    k_add_samples<<<1, 1, 0, s>>>(h->state, (count - 1) * h->ring.samples_inc);
+    DDRL_LAUNCH_CHECK();
+    h->h_samples += (count - 1) * h->ring.samples_inc;
+    return DDRL_OK;
+}
+
+// argument checks shared by the two folded draws; `what` names the caller in the refusal
+static int check_sample_nstep(ddrl_replay *h, int64_t rows, const char *what) {
+    if (!ddrl_replay_is_window_ring(h, 0, 0)) {
+        ddrl::set_error("%s needs an n-step window ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays", what);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    const int Ln = h->ring.w[2], od = h->ring.w[0] / (Ln + 1), ad = h->ring.w[1] / Ln;
+    DDRL_REQUIRE(rows * (od > ad ? od : ad) < 0x7fffffffll, "batch * max(obs_dim, act_dim) must be < 2^31");
+    return DDRL_OK;
 }
 
 extern "C" {
@@ -441,7 +534,7 @@ int ddrl_replay_create_typed(ddrl_replay_t **out, int device, int64_t capacity, 
     h->idx_cap = 1 << 16;
     if (e == hipSuccess) e = hipMalloc(&h->idx_buf, h->idx_cap * sizeof(long long));
     if (e != hipSuccess) {
-        ddrl::set_error("hipMalloc failed for a ring of %lld rows x %lld floats: %s", (long long)capacity, row_floats(h),
+        ddrl::set_error("hipMalloc failed for a ring of %lld rows x %lld floats: %s", (long long)capacity, view_floats(h->ring),
                         hipGetErrorString(e));
         ddrl_replay_destroy(h);
         return DDRL_ERR_NOMEM;
@@ -490,14 +583,9 @@ int ddrl_replay_store_ex(ddrl_replay_t *h, const float *const *src_h, int64_t n,
     DDRL_REQUIRE(h != nullptr && src_h != nullptr, "NULL pointer");
     DDRL_REQUIRE(n >= 0, "n must be >= 0");
     if (n == 0) return DDRL_OK;
-    StoreSrc srcs{};
-    int widest = 1;
-    for (int j = 0; j < h->ring.n_arr; ++j) {
-        DDRL_REQUIRE(src_h[j] != nullptr, "NULL source array");
-        srcs.a[j] = src_h[j];
-        const int wv = (h->ring.w[j] & 3) == 0 ? h->ring.w[j] / 4 : h->ring.w[j];
-        if (wv > widest) widest = wv;
-    }
+    StoreSrc srcs;
+    int widest;
+    DDRL_REQUIRE(store_srcs(h, src_h, srcs, widest), "NULL source array");
     ddrl::DeviceGuard g(h->device);
     const long long rows = n > h->ring.capacity ? h->ring.capacity : n;
     long long blocks = (rows * widest + 255) / 256;
@@ -505,9 +593,7 @@ int ddrl_replay_store_ex(ddrl_replay_t *h, const float *const *src_h, int64_t n,
     if (blocks < 1) blocks = 1;
     k_store<<<dim3((unsigned)blocks, (unsigned)h->ring.n_arr), 256, 0, ddrl::as_stream(stream)>>>(h->state, h->ring, srcs, n);
     DDRL_LAUNCH_CHECK();
-    h->h_ptr = (h->h_ptr + n) % h->ring.capacity;
-    h->h_size = (h->h_size + n > h->ring.capacity) ? h->ring.capacity : h->h_size + n;
-    h->h_steps += n * h->ring.steps_inc;
+    ddrl_replay_note_store(h, n);
     return DDRL_OK;
 }
 
@@ -516,22 +602,13 @@ int ddrl_replay_store_masked_ex(ddrl_replay_t *h, const float *const *src_h, con
     DDRL_REQUIRE(n >= 0 && n < 0x7fffffffll, "n must be in [0, 2^31)");
     DDRL_REQUIRE(!has_compact(h), "masked store into a compact (uint8) ring is not built");
     if (n == 0) return DDRL_OK;
-    StoreSrc srcs{};
-    int widest = 1;
-    for (int j = 0; j < h->ring.n_arr; ++j) {
-        DDRL_REQUIRE(src_h[j] != nullptr, "NULL source array");
-        srcs.a[j] = src_h[j];
-        const int wv = (h->ring.w[j] & 3) == 0 ? h->ring.w[j] / 4 : h->ring.w[j];
-        if (wv > widest) widest = wv;
-    }
+    StoreSrc srcs;
+    int widest;
+    DDRL_REQUIRE(store_srcs(h, src_h, srcs, widest), "NULL source array");
     ddrl::DeviceGuard g(h->device);
     hipStream_t s = ddrl::as_stream(stream);
-    if (n + 1 > h->rank_cap) {
-        DDRL_HIP_CHECK(hipStreamSynchronize(s));
-        (void)hipFree(h->rank_buf);
-        h->rank_cap = n + 1;
-        DDRL_HIP_CHECK(hipMalloc(&h->rank_buf, h->rank_cap * sizeof(int)));
-    }
+    const int grc = grow(h->rank_buf, h->rank_cap, n + 1, s);
+    if (grc != DDRL_OK) return grc;
     k_mask_scan<<<1, 256, 0, s>>>(mask_d, n, h->rank_buf);
     long long blocks = (n * widest + 255) / 256;
     if (blocks > 2048) blocks = 2048;
@@ -548,174 +625,48 @@ int ddrl_replay_store(ddrl_replay_t *h, const float *obs_d, const float *act_d, 
     return ddrl_replay_store_ex(h, src, n, stream);
 }
 
-static int launch_gather(ddrl_replay *h, const long long *idx, int64_t B, BatchPtrs out, hipStream_t s) {
-    int widest = 1;
-    for (int j = 0; j < h->ring.n_arr; ++j) widest = h->ring.w[j] > widest ? h->ring.w[j] : widest;
-    if (widest <= 64 && B >= 4096) {  // many small rows
-        long long blocks = (B * ((widest & 3) == 0 ? widest / 4 : widest) + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        k_gather_small<<<dim3((unsigned)blocks, (unsigned)h->ring.n_arr), 256, 0, s>>>(h->ring, out, idx, (int)B);
-        DDRL_LAUNCH_CHECK();
-        return DDRL_OK;
-    }
-    k_gather<<<dim3((unsigned)B, (unsigned)h->ring.n_arr), 256, 0, s>>>(h->ring, out, idx, (int)B);
-    DDRL_LAUNCH_CHECK();
-    return DDRL_OK;
-}
-
 int ddrl_replay_sample_ex(ddrl_replay_t *h, int64_t batch, float *const *out_h, int64_t *idx_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && out_h != nullptr, "NULL pointer");
     DDRL_REQUIRE(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
-    BatchPtrs out{};
-    for (int j = 0; j < h->ring.n_arr; ++j) {
-        DDRL_REQUIRE(out_h[j] != nullptr, "NULL output pointer");
-        out.a[j] = out_h[j];
-    }
-    ddrl::DeviceGuard g(h->device);
-    hipStream_t s = ddrl::as_stream(stream);
-    if (h->feed_on) {
-        DDRL_REQUIRE(ddrl_replay_can_fuse(h, batch), "a feed plan is attached: the batch must fit the one-workgroup sampler");
-    } else if (h->h_size <= 0 || h->h_dirty) {
-        // the mirror may lag behind graph replays / masked stores: ask the device before reporting empty
-        int rc = refresh_counts(h, s);
-        if (rc != DDRL_OK) return rc;
-        if (h->h_size <= 0) {
-            ddrl::set_error("high <= 0");  // message of the reference's ValueError
-            return DDRL_ERR_EMPTY_BUFFER;
-        }
-    }
-    const int fuse = ddrl_replay_can_fuse(h, batch) ? 1 : 0;
-    long long *idx = reinterpret_cast<long long *>(idx_d);
-    if (!fuse && !idx) {
-        if (batch > h->idx_cap) {
-            DDRL_HIP_CHECK(hipStreamSynchronize(s));
-            (void)hipFree(h->idx_buf);
-            h->idx_cap = batch;
-            DDRL_HIP_CHECK(hipMalloc(&h->idx_buf, h->idx_cap * sizeof(long long)));
-        }
-        idx = h->idx_buf;
-    }
-    if (!fuse && batch >= 2048) k_sample_wide<<<1, 640, 0, s>>>(h->state, h->ring, out, (int)batch, idx);
-    else k_sample<<<1, SAMPLE_THREADS, 0, s>>>(h->state, h->ring, out, (int)batch, idx, fuse);
-    DDRL_LAUNCH_CHECK();
-    h->h_samples += h->ring.samples_inc;
-    if (!fuse) return launch_gather(h, idx, batch, out, s);
-    return DDRL_OK;
-}
-
-static int fold_grid(int64_t batch, int od) {
-    long long blocks = (batch * ((od & 3) == 0 ? od / 4 : od) + 255) / 256;
-    return (int)(blocks > 4096 ? 4096 : (blocks < 1 ? 1 : blocks));
+    BatchPtrs out;
+    DDRL_REQUIRE(batch_ptrs(out, out_h, h->ring.n_arr), "NULL output pointer");
+    return ddrl_replay_draw(h, ddrl_replay_sampler_view(h), batch, out, idx_d, stream);
 }
 
 int ddrl_nstep_fold(const float *obs_w_d, const float *acts_w_d, const float *rews_w_d, const float *done_w_d, int64_t batch, int32_t Ln,
                     int32_t obs_dim, int32_t act_dim, float gamma, float *obs1_d, float *obs2_d, float *acts_d, float *rews_d, float *done_d,
                     void *stream) {
-    DDRL_REQUIRE(obs_w_d && acts_w_d && rews_w_d && done_w_d && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
+    BatchPtrs out;
+    DDRL_REQUIRE(obs_w_d && acts_w_d && rews_w_d && done_w_d && batch_ptrs(out, obs1_d, obs2_d, acts_d, rews_d, done_d), "NULL pointer");
     DDRL_REQUIRE(Ln >= 1 && obs_dim >= 1 && act_dim >= 1, "Ln, obs_dim, act_dim must be positive");
     DDRL_REQUIRE(batch > 0 && batch <= (1 << 24) && batch * (obs_dim > act_dim ? obs_dim : act_dim) < 0x7fffffffll,
                  "batch must be in [1, 2^24] with batch * max(obs_dim, act_dim) < 2^31");
     const FoldSrc w{obs_w_d, acts_w_d, rews_w_d, done_w_d, Ln, obs_dim, act_dim, gamma};
-    const BatchPtrs out{{obs1_d, obs2_d, acts_d, rews_d, done_d, nullptr}};
     k_nstep_fold<<<fold_grid(batch, obs_dim), 256, 0, ddrl::as_stream(stream)>>>(w, out, (int)batch);
     DDRL_LAUNCH_CHECK();
     return DDRL_OK;
 }
 
-// The folded draw of `batch` rows of a window ring: one workgroup (draw + fold-gather) up to MAX_FUSED_BATCH rows, the wide draw and a
-// grid fold-gather beyond.  The ring is a window ring and (unless a feed is attached) known to hold rows.
-static int launch_sample_nstep(ddrl_replay *h, int64_t batch, float gamma, const BatchPtrs &out, long long *idx, hipStream_t s) {
-    const int Ln = h->ring.w[2], od = h->ring.w[0] / (Ln + 1), ad = h->ring.w[1] / Ln;
-    if (batch <= MAX_FUSED_BATCH) {   // draw + fold-gather in the one workgroup
-        const SamplerView v = ddrl_replay_sampler_view_nstep(h, gamma);
-        k_sample<<<1, SAMPLE_THREADS, 0, s>>>(v.state, v.ring, out, (int)batch, idx, 1);
-        DDRL_LAUNCH_CHECK();
-        h->h_samples += h->ring.samples_inc;
-        return DDRL_OK;
-    }
-    if (!idx) {
-        if (batch > h->idx_cap) {
-            DDRL_HIP_CHECK(hipStreamSynchronize(s));
-            (void)hipFree(h->idx_buf);
-            h->idx_cap = batch;
-            DDRL_HIP_CHECK(hipMalloc(&h->idx_buf, h->idx_cap * sizeof(long long)));
-        }
-        idx = h->idx_buf;
-    }
-    k_sample_wide<<<1, 640, 0, s>>>(h->state, h->ring, out, (int)batch, idx);
-    DDRL_LAUNCH_CHECK();
-    h->h_samples += h->ring.samples_inc;
-    const FoldSrc w{h->ring.a[0], h->ring.a[1], h->ring.a[2], h->ring.a[3], Ln, od, ad, gamma};
-    k_nstep_gather<<<fold_grid(batch, od), 256, 0, s>>>(w, out, idx, (int)batch);
-    DDRL_LAUNCH_CHECK();
-    return DDRL_OK;
-}
-
-// argument checks shared by the two folded draws; `what` names the caller in the refusal
-static int check_sample_nstep(ddrl_replay *h, int64_t rows, const char *what) {
-    if (!ddrl_replay_is_window_ring(h, 0, 0)) {
-        ddrl::set_error("%s needs an n-step window ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays", what);
-        return DDRL_ERR_UNSUPPORTED;
-    }
-    const int Ln = h->ring.w[2], od = h->ring.w[0] / (Ln + 1), ad = h->ring.w[1] / Ln;
-    DDRL_REQUIRE(rows * (od > ad ? od : ad) < 0x7fffffffll, "batch * max(obs_dim, act_dim) must be < 2^31");
-    return DDRL_OK;
-}
-
-static int require_rows(ddrl_replay *h, hipStream_t s) {
-    if (h->h_size <= 0 || h->h_dirty) {
-        int rc = refresh_counts(h, s);
-        if (rc != DDRL_OK) return rc;
-        if (h->h_size <= 0) {
-            ddrl::set_error("high <= 0");  // message of the reference's ValueError
-            return DDRL_ERR_EMPTY_BUFFER;
-        }
-    }
-    return DDRL_OK;
-}
-
 int ddrl_replay_sample_nstep(ddrl_replay_t *h, int64_t batch, float gamma, float *obs1_d, float *obs2_d, float *acts_d, float *rews_d,
                              float *done_d, int64_t *idx_d, void *stream) {
-    DDRL_REQUIRE(h != nullptr && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
+    BatchPtrs out;
+    DDRL_REQUIRE(h != nullptr && batch_ptrs(out, obs1_d, obs2_d, acts_d, rews_d, done_d), "NULL pointer");
     DDRL_REQUIRE(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
-    int rc = check_sample_nstep(h, batch, "ddrl_replay_sample_nstep");
+    const int rc = check_sample_nstep(h, batch, "ddrl_replay_sample_nstep");
     if (rc != DDRL_OK) return rc;
-    ddrl::DeviceGuard g(h->device);
-    hipStream_t s = ddrl::as_stream(stream);
-    if (h->feed_on) {   // the plan decides per call: a fed batch is copied, a -1 entry draws and folds (an empty ring: the sticky error)
-        DDRL_REQUIRE(ddrl_replay_can_fuse_nstep(h, batch), "a feed plan is attached: the batch must fit the one-workgroup sampler");
-    } else if ((rc = require_rows(h, s)) != DDRL_OK) {
-        return rc;
-    }
-    const BatchPtrs out{{obs1_d, obs2_d, acts_d, rews_d, done_d, nullptr}};
-    return launch_sample_nstep(h, batch, gamma, out, reinterpret_cast<long long *>(idx_d), s);
+    return ddrl_replay_draw(h, ddrl_replay_sampler_view(h, true, gamma), batch, out, idx_d, stream);
 }
 
 int ddrl_replay_sample_many_nstep(ddrl_replay_t *h, int64_t batch, int64_t count, float gamma, float *const *out_h, void *stream) {
     DDRL_REQUIRE(h != nullptr && out_h != nullptr, "NULL pointer");
     DDRL_REQUIRE(batch > 0 && count > 0 && batch * count <= (1 << 24), "batch, count must be positive with batch * count <= 2^24");
-    int rc = check_sample_nstep(h, batch * count, "ddrl_replay_sample_many_nstep");
+    const int rc = check_sample_nstep(h, batch * count, "ddrl_replay_sample_many_nstep");
     if (rc != DDRL_OK) return rc;
     if (h->feed_on) {
         ddrl::set_error("a feed plan is attached to this ring");
         return DDRL_ERR_UNSUPPORTED;
     }
-    BatchPtrs out{};
-    for (int j = 0; j < 5; ++j) {
-        DDRL_REQUIRE(out_h[j] != nullptr, "NULL output pointer");
-        out.a[j] = out_h[j];
-    }
-    ddrl::DeviceGuard g(h->device);
-    hipStream_t s = ddrl::as_stream(stream);
-    if ((rc = require_rows(h, s)) != DDRL_OK) return rc;
-    // `count` consecutive folded sample_batch(batch) calls consume the index stream exactly like one draw of batch * count
-    // (the ring size cannot change in between: nothing else is ordered between them on this stream)
-    rc = launch_sample_nstep(h, batch * count, gamma, out, nullptr, s);
-    if (rc != DDRL_OK || count == 1) return rc;
-    k_add_samples<<<1, 1, 0, s>>>(h->state, (count - 1) * h->ring.samples_inc);
-    DDRL_LAUNCH_CHECK();
-    h->h_samples += (count - 1) * h->ring.samples_inc;
-    return DDRL_OK;
+    return sample_many(h, ddrl_replay_sampler_view(h, true, gamma), batch, count, out_h, stream);
 }
 
 int ddrl_replay_sample_indices(ddrl_replay_t *h, int64_t batch, int64_t *idx_d, void *stream) {
@@ -724,20 +675,9 @@ int ddrl_replay_sample_indices(ddrl_replay_t *h, int64_t batch, int64_t *idx_d, 
     DDRL_REQUIRE(!h->feed_on, "a feed plan is attached to this ring");
     ddrl::DeviceGuard g(h->device);
     hipStream_t s = ddrl::as_stream(stream);
-    if (h->h_size <= 0 || h->h_dirty) {
-        int rc = refresh_counts(h, s);
-        if (rc != DDRL_OK) return rc;
-        if (h->h_size <= 0) {
-            ddrl::set_error("high <= 0");  // message of the reference's ValueError
-            return DDRL_ERR_EMPTY_BUFFER;
-        }
-    }
-    BatchPtrs none{};
-    if (batch >= 2048) k_sample_wide<<<1, 640, 0, s>>>(h->state, h->ring, none, (int)batch, reinterpret_cast<long long *>(idx_d));
-    else k_sample<<<1, SAMPLE_THREADS, 0, s>>>(h->state, h->ring, none, (int)batch, reinterpret_cast<long long *>(idx_d), 0);
-    DDRL_LAUNCH_CHECK();
-    h->h_samples += h->ring.samples_inc;
-    return DDRL_OK;
+    const int rc = require_rows(h, s);
+    if (rc != DDRL_OK) return rc;
+    return launch_draw(h, ddrl_replay_sampler_view(h), batch, nullptr, reinterpret_cast<long long *>(idx_d), s);
 }
 
 int ddrl_replay_sample(ddrl_replay_t *h, int64_t batch, float *obs1_d, float *obs2_d, float *acts_d,
@@ -751,15 +691,7 @@ int ddrl_replay_sample_many(ddrl_replay_t *h, int64_t batch, int64_t count, floa
     DDRL_REQUIRE(h != nullptr && out_h != nullptr, "NULL pointer");
     DDRL_REQUIRE(batch > 0 && count > 0 && batch * count <= (1 << 24), "batch, count must be positive with batch * count <= 2^24");
     DDRL_REQUIRE(!h->feed_on, "a feed plan is attached to this ring");
-    // `count` consecutive sample_batch(batch) calls consume the index stream exactly like one draw of batch * count
-    // (the ring size cannot change in between: nothing else is ordered between them on this stream)
-    const int rc = ddrl_replay_sample_ex(h, batch * count, out_h, nullptr, stream);
-    if (rc != DDRL_OK || count == 1) return rc;
-    ddrl::DeviceGuard g(h->device);
-    k_add_samples<<<1, 1, 0, ddrl::as_stream(stream)>>>(h->state, (count - 1) * h->ring.samples_inc);
-    DDRL_LAUNCH_CHECK();
-    h->h_samples += (count - 1) * h->ring.samples_inc;
-    return DDRL_OK;
+    return sample_many(h, ddrl_replay_sampler_view(h), batch, count, out_h, stream);
 }
 
 int ddrl_replay_set_feed(ddrl_replay_t *h, const int32_t *plan_d, int32_t plan_len, int32_t batch, int32_t n_regions,
@@ -786,11 +718,8 @@ int ddrl_replay_set_feed(ddrl_replay_t *h, const int32_t *plan_d, int32_t plan_l
 int ddrl_replay_gather_ex(ddrl_replay_t *h, const int64_t *idx_d, int64_t batch, float *const *out_h, void *stream) {
     DDRL_REQUIRE(h != nullptr && idx_d != nullptr && out_h != nullptr, "NULL handle, index or output pointer");
     DDRL_REQUIRE(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
-    BatchPtrs out{};
-    for (int j = 0; j < h->ring.n_arr; ++j) {
-        DDRL_REQUIRE(out_h[j] != nullptr, "NULL output pointer");
-        out.a[j] = out_h[j];
-    }
+    BatchPtrs out;
+    DDRL_REQUIRE(batch_ptrs(out, out_h, h->ring.n_arr), "NULL output pointer");
     ddrl::DeviceGuard g(h->device);
     return launch_gather(h, reinterpret_cast<const long long *>(idx_d), batch, out, ddrl::as_stream(stream));
 }

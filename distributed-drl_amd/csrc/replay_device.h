@@ -65,6 +65,35 @@ static_assert(sizeof(RingPtrs) == 112, "RingPtrs is embedded in kernel argument 
 struct BatchPtrs {
     float *a[MAX_ARRAYS];
 };
+// The output table of a draw / gather / fold from `n` pointers, or from the five learner arrays; false: one of them is NULL
+static inline bool batch_ptrs(BatchPtrs &out, float *const *p, int n) {
+    out = BatchPtrs{};
+    for (int j = 0; j < n; ++j) {
+        if (p[j] == nullptr) return false;
+        out.a[j] = p[j];
+    }
+    return true;
+}
+static inline bool batch_ptrs(BatchPtrs &out, float *obs1, float *obs2, float *acts, float *rews, float *done) {
+    float *const p[5] = {obs1, obs2, acts, rews, done};
+    return batch_ptrs(out, p, 5);
+}
+
+// The cursor commit of a launch that stored `n` rows from cursor `ptr` (read by every block before its ticket): the last block to
+// finish advances ptr / size / steps and resets the ticket counter.  One lane per block calls it, behind the block's barrier;
+// true in the block that committed.
+__device__ __forceinline__ bool ring_commit(RingState *st, const RingPtrs &ring, long long ptr, long long n) {
+    const unsigned total_blocks = gridDim.x * gridDim.y;
+    const unsigned ticket = atomicAdd(&st->done_counter, 1u);
+    if (ticket != total_blocks - 1) return false;
+    const long long cap = ring.capacity;
+    st->ptr = (ptr + n) % cap;
+    const long long sz = st->size + n;
+    st->size = sz > cap ? cap : sz;
+    st->steps += n * ring.steps_inc;
+    st->done_counter = 0;
+    return true;
+}
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
     y ^= (y >> 11);
@@ -97,6 +126,14 @@ __device__ __forceinline__ void mt_twist_lds(const uint32_t *mt, uint32_t *nw, i
 
 __device__ __forceinline__ bool aligned16(const void *a, const void *b) {
     return ((reinterpret_cast<unsigned long long>(a) | reinterpret_cast<unsigned long long>(b)) & 15ull) == 0;
+}
+
+// float32 -> the byte a compact (uint8) array holds: clamped to [0, 255] and truncated; `bad` is raised when the value does not
+// survive the round trip (not an integer in [0, 255], NaN) — the caller turns it into the sticky DDRL_ERR_NOT_REPRESENTABLE
+__device__ __forceinline__ unsigned to_u8(float f, bool &bad) {
+    const unsigned b = (unsigned)(int)fminf(fmaxf(f, 0.f), 255.f);
+    bad |= !((float)b == f);
+    return b;
 }
 
 __device__ __forceinline__ void gather_rows(const float *__restrict__ ring, float *__restrict__ out,
@@ -324,12 +361,16 @@ struct SamplerView {
 }  // namespace ddrl_replay_dev
 
 // defined in replay.hip
-ddrl_replay_dev::SamplerView ddrl_replay_sampler_view(ddrl_replay_t *h);
-bool ddrl_replay_can_fuse(ddrl_replay_t *h, int64_t batch);
-// n-step window rings (algos/sac1/sac_ray.py:40-51): is this ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays; the sampler's
-// view of it in fold-gather mode; can_fuse for the folded batch (the bytes the fold-gather moves, not the whole windows)
+// the sampler's view of a ring; fold = true: of an n-step window ring in fold-gather mode with backup discount `gamma`
+ddrl_replay_dev::SamplerView ddrl_replay_sampler_view(ddrl_replay_t *h, bool fold = false, float gamma = 0.f);
+// can the one-workgroup sampler draw AND gather `batch` rows of this view (so that it can ride in another kernel's launch): batch and
+// gathered bytes under the caps — the bytes the view's gather moves per index, not the whole windows of a fold view
+bool ddrl_replay_can_fuse(ddrl_replay_t *h, const ddrl_replay_dev::SamplerView &v, int64_t batch);
+// n-step window rings (algos/sac1/sac_ray.py:40-51): is this ring {o[(Ln+1) obs], a[Ln act], r[Ln], d[Ln]} of float32 arrays
 bool ddrl_replay_is_window_ring(ddrl_replay_t *h, int obs_dim, int act_dim);
-ddrl_replay_dev::SamplerView ddrl_replay_sampler_view_nstep(ddrl_replay_t *h, float gamma);
-bool ddrl_replay_can_fuse_nstep(ddrl_replay_t *h, int64_t batch);
+// sample_batch(batch) through view `v` into `out` (and idx_d, nullable) as launches of its own: ddrl_replay_sample_ex / _sample_nstep
+// behind their argument checks
+int ddrl_replay_draw(ddrl_replay_t *h, const ddrl_replay_dev::SamplerView &v, int64_t batch, const ddrl_replay_dev::BatchPtrs &out,
+                     int64_t *idx_d, void *stream);
 void ddrl_replay_note_sample(ddrl_replay_t *h);  // host mirror bookkeeping for a sample issued by another kernel
 void ddrl_replay_note_store(ddrl_replay_t *h, long long n);  // ... for n stores issued by another kernel

@@ -1854,38 +1854,37 @@ int ddrl_sac1_apply_grads(ddrl_sac1_t *h, void *stream) {
 
 }  // extern "C"
 
-// The sampler's view of `replay` for this learner: a transition ring of the learner's shapes as it is; an n-step window ring
-// (algos/sac1/sac_ray.py:40-51) in fold-gather mode with the learner's gamma — its sampler hands the update kernels the folded
-// transition (include/ddrl.h: n-step fold), so nothing downstream of the input set knows the difference.
-static int learner_sampler_view(ddrl_sac1 *h, ddrl_replay_t *replay, ddrl_replay_dev::SamplerView *v, bool *nstep) {
+// The sampler step of an update call.  *v: the sampler's view of `replay` for this learner — a transition ring of the learner's shapes as
+// it is; an n-step window ring (algos/sac1/sac_ray.py:40-51) in fold-gather mode with the learner's gamma (v->ring.fold): its sampler
+// hands the update kernels the folded transition (include/ddrl.h: n-step fold), so nothing downstream of the input set knows the
+// difference.  *rides: the sampler can go as one extra workgroup of an update launch (`kernels_take_it`: this kernel path has such a
+// launch) — the caller arms it there; else it goes behind the update as a launch of its own (learner_sample_alone).
+static int learner_sampler(ddrl_sac1 *h, ddrl_replay_t *replay, bool kernels_take_it, ddrl_replay_dev::SamplerView *v, bool *rides) {
     *v = ddrl_replay_sampler_view(replay);
-    *nstep = false;
-    if (v->ring.n_arr == 5 && v->ring.w[0] == h->cfg.obs_dim && v->ring.w[1] == h->cfg.obs_dim && v->ring.w[2] == h->cfg.act_dim &&
-        v->ring.w[3] == 1 && v->ring.w[4] == 1)
-        return DDRL_OK;
-    DDRL_REQUIRE(ddrl_replay_is_window_ring(replay, h->cfg.obs_dim, h->cfg.act_dim),
-                 "replay row shape differs from the learner's (obs1, obs2, acts, rews, done) and is no n-step window ring of its obs / act widths");
-    *v = ddrl_replay_sampler_view_nstep(replay, (float)h->cfg.gamma);
-    *nstep = true;
+    *rides = false;
+    if (!(v->ring.n_arr == 5 && v->ring.w[0] == h->cfg.obs_dim && v->ring.w[1] == h->cfg.obs_dim && v->ring.w[2] == h->cfg.act_dim &&
+          v->ring.w[3] == 1 && v->ring.w[4] == 1)) {
+        DDRL_REQUIRE(ddrl_replay_is_window_ring(replay, h->cfg.obs_dim, h->cfg.act_dim),
+                     "replay row shape differs from the learner's (obs1, obs2, acts, rews, done) and is no n-step window ring of its obs / act widths");
+        *v = ddrl_replay_sampler_view(replay, true, (float)h->cfg.gamma);
+    }
+    *rides = kernels_take_it && ddrl_replay_can_fuse(replay, *v, h->cfg.batch);
     return DDRL_OK;
 }
-static bool learner_can_fuse(ddrl_sac1 *h, ddrl_replay_t *replay, bool nstep) {
-    return nstep ? ddrl_replay_can_fuse_nstep(replay, h->cfg.batch) : ddrl_replay_can_fuse(replay, h->cfg.batch);
-}
-// sample_batch into input set `set` as a launch of its own
-static int learner_sample_launch(ddrl_sac1 *h, ddrl_replay_t *replay, bool nstep, int set, void *stream) {
-    float **b = h->in[set];
-    if (nstep) return ddrl_replay_sample_nstep(replay, h->cfg.batch, (float)h->cfg.gamma, b[0], b[1], b[2], b[3], b[4], nullptr, stream);
-    return ddrl_replay_sample(replay, h->cfg.batch, b[0], b[1], b[2], b[3], b[4], nullptr, stream);
+// sample_batch into input set `set` as a launch of its own (check_cfg keeps batch * max(obs_dim, act_dim) far below the draw's 2^31)
+static int learner_sample_alone(ddrl_sac1 *h, ddrl_replay_t *replay, const ddrl_replay_dev::SamplerView &v, int set, void *stream) {
+    ddrl_replay_dev::BatchPtrs out;
+    ddrl_replay_dev::batch_ptrs(out, h->in[set], 5);
+    return ddrl_replay_draw(replay, v, h->cfg.batch, out, nullptr, stream);
 }
 // Internal (loop.hip): the loop's own draws (the priming draw of a graph, eager updates) into input set `set`
 int ddrl_sac1_internal_sample_into(ddrl_sac1 *h, ddrl_replay_t *replay, int set, void *stream) {
     DDRL_REQUIRE(h != nullptr && replay != nullptr && (set == 0 || set == 1), "NULL pointer or set not in {0,1}");
     ddrl_replay_dev::SamplerView v;
-    bool nstep;
-    const int rc = learner_sampler_view(h, replay, &v, &nstep);
+    bool rides;
+    const int rc = learner_sampler(h, replay, false, &v, &rides);
     if (rc != DDRL_OK) return rc;
-    return learner_sample_launch(h, replay, nstep, set, stream);
+    return learner_sample_alone(h, replay, v, set, stream);
 }
 
 extern "C" {
@@ -1894,19 +1893,19 @@ int ddrl_sac1_apply_grads_and_sample(ddrl_sac1_t *h, ddrl_replay_t *replay, int 
     DDRL_REQUIRE(h != nullptr && replay != nullptr && (set == 0 || set == 1), "NULL pointer or set not in {0,1}");
     ddrl::DeviceGuard g(h->device);
     ddrl_replay_dev::SamplerView v;
-    bool nstep;
-    const int vrc = learner_sampler_view(h, replay, &v, &nstep);
+    bool rides;
+    const int vrc = learner_sampler(h, replay, true, &v, &rides);
     if (vrc != DDRL_OK) return vrc;
-    if (!learner_can_fuse(h, replay, nstep)) {  // empty ring (host view) or rows too large for the one-workgroup sampler
+    if (!rides) {  // empty ring (host view) or rows too large for the one-workgroup sampler
         int rc = launch_apply(h, ddrl::as_stream(stream));
         if (rc != DDRL_OK) return rc;
-        return learner_sample_launch(h, replay, nstep, set, stream);
+        return learner_sample_alone(h, replay, v, set, stream);
     }
     h->ad.do_sample = 1;
     h->ad.sample_batch = h->cfg.batch;
     h->ad.rs = v.state;
     h->ad.ring = v.ring;
-    h->ad.sout = ddrl_replay_dev::BatchPtrs{{h->in[set][0], h->in[set][1], h->in[set][2], h->in[set][3], h->in[set][4], nullptr}};
+    ddrl_replay_dev::batch_ptrs(h->ad.sout, h->in[set], 5);
     const int rc = launch_apply(h, ddrl::as_stream(stream));
     h->ad.do_sample = 0;
     if (rc == DDRL_OK) ddrl_replay_note_sample(replay);
@@ -2065,13 +2064,13 @@ int ddrl_sac1_compute_grads_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t
     ddrl::DeviceGuard g(h->device);
     float **b = h->in[set_in];
     ddrl_replay_dev::SamplerView v;
-    bool nstep;
-    const int vrc = learner_sampler_view(h, replay, &v, &nstep);
+    bool rides;
+    const int vrc = learner_sampler(h, replay, h->fused, &v, &rides);
     if (vrc != DDRL_OK) return vrc;
-    if (!h->fused || !learner_can_fuse(h, replay, nstep)) {  // generic kernels: the sampler as its own launch
+    if (!rides) {  // generic kernels: the sampler as its own launch
         int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
         if (rc != DDRL_OK) return rc;
-        return learner_sample_launch(h, replay, nstep, set_out, stream);
+        return learner_sample_alone(h, replay, v, set_out, stream);
     }
     h->ls.sample_armed = true; h->smp_rs = v.state; h->smp_ring = v.ring; h->smp_set = set_out;
     const int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
@@ -2086,10 +2085,10 @@ int ddrl_sac1_step_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t *replay,
     ddrl::DeviceGuard g(h->device);
     float **b = h->in[set_in];
     ddrl_replay_dev::SamplerView v;
-    bool nstep;
-    const int vrc = learner_sampler_view(h, replay, &v, &nstep);
+    bool rides;
+    const int vrc = learner_sampler(h, replay, h->fused, &v, &rides);
     if (vrc != DDRL_OK) return vrc;
-    if (!h->fused || !learner_can_fuse(h, replay, nstep)) {  // generic kernels: sampler beside the Adam kernel (or on its own)
+    if (!rides) {  // generic kernels: sampler beside the Adam kernel (or on its own)
         int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
         if (rc != DDRL_OK) return rc;
         return ddrl_sac1_apply_grads_and_sample(h, replay, set_out, stream);

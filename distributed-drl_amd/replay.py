@@ -28,9 +28,40 @@ def _block_ptrs(flat, rows, obs_dim, act_dim):
     return ptrs, off
 
 
-class _Fed:
-    """The learner side of the sharded replay, for every ring class (a handle in self._h): the sampler's feed plan and its
-    sticky device-side error."""
+def _packed_offsets(B, obs_dim, act_dim):
+    """Float offsets of the five arrays [obs1 | obs2 | acts | rews | done] of ONE batch in a packed host / device block, every piece
+    16-byte aligned; the sixth entry is the block's length."""
+    offs = [0]
+    for n in (B * obs_dim, B * obs_dim, B * act_dim, B, B):
+        offs.append((offs[-1] + n + 3) & ~3)
+    return offs
+
+
+class _Ring:
+    """What every ring class shares (a handle in self._h, the library in self._lib): the handle's lifetime, the sampler's seed and
+    MT19937 state, the counters, and the learner side of the sharded replay — the sampler's feed plan and its sticky device-side
+    error."""
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.ddrl_replay_destroy(h)
+
+    # -- np.random.seed(s) of the reference's buffer process ---------------------------------
+    def seed(self, s):
+        _lib.check(self._lib.ddrl_replay_seed(self._h, int(s) & 0xFFFFFFFF, _lib.stream_ptr()))
+
+    def mt_state(self):
+        key = np.empty(624, dtype=np.uint32)
+        pos = ctypes.c_int32()
+        _lib.check(self._lib.ddrl_replay_mt_state(self._h, ctypes.c_void_p(key.ctypes.data), ctypes.byref(pos),
+                                                  _lib.stream_ptr()))
+        return key, int(pos.value)
+
+    def _counts(self):
+        c = [ctypes.c_int64() for _ in range(4)]
+        _lib.check(self._lib.ddrl_replay_counts(self._h, *[ctypes.byref(x) for x in c], _lib.stream_ptr()))
+        return tuple(int(x.value) for x in c)  # (ptr, size, steps, sample_times)
 
     def set_feed(self, plan, batch_size, regions):
         """Attach a per-update feed plan (int32 device tensor: -1 = local draw, r << 24 | i = batch i of regions[r]) to
@@ -54,7 +85,7 @@ class _Fed:
         _lib.check(self._lib.ddrl_replay_take_error(self._h, _lib.dptr(out), _lib.stream_ptr()))
 
 
-class ReplayBuffer(_Fed):
+class ReplayBuffer(_Ring):
     """A simple FIFO experience replay buffer for SAC agents (example/dsac.py:14-48)."""
 
     _default_batch = 32
@@ -78,15 +109,9 @@ class ReplayBuffer(_Fed):
         if seed is not None:
             self.seed(seed)
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.ddrl_replay_destroy(h)
-
-    # -- np.random.seed(s) of the reference's buffer process ---------------------------------
     def seed(self, s):
         self._pf_order_store(True)
-        _lib.check(self._lib.ddrl_replay_seed(self._h, int(s) & 0xFFFFFFFF, _lib.stream_ptr()))
+        super().seed(s)
         self._pf_order_store(False)
 
     # -- reference surface ---------------------------------------------------------------------
@@ -161,17 +186,10 @@ class ReplayBuffer(_Fed):
         if B <= 0 or depth <= 0:
             return
         assert 1 <= hold < depth
-        o, a = self.obs_dim, self.act_dim
-        offs = [0]
-        for n in (B * o, B * o, B * a, B, B):
-            offs.append((offs[-1] + n + 3) & ~3)
+        o = self.obs_dim
+        offs = _packed_offsets(B, o, self.act_dim)
         host = [torch.empty(offs[5], dtype=torch.float32).pin_memory() for _ in range(depth)]
-        views = []
-        for h in host:
-            v = h.numpy()
-            views.append(dict(obs1=v[offs[0]:offs[0] + B * o].reshape(B, o), obs2=v[offs[1]:offs[1] + B * o].reshape(B, o),
-                              acts=v[offs[2]:offs[2] + B * a] if self._acts_1d else v[offs[2]:offs[2] + B * a].reshape(B, a),
-                              rews=v[offs[3]:offs[3] + B], done=v[offs[4]:offs[4] + B]))
+        views = [self._packed_views(h.numpy(), offs, B) for h in host]
         # the gather writes straight into the page-locked blocks (their device-side addresses: posted PCIe writes, no copy launch
         # behind the gather, no device staging buffers) — rows of megabytes (config 5) keep a device block and a copy down
         direct = B * o < (1 << 18)
@@ -247,9 +265,7 @@ class ReplayBuffer(_Fed):
         if B * o >= (1 << 22):    # rows of megabytes (config 5): the gather's own aligned per-array buffers
             d = self.sample_batch_device(B, fresh=True)
             return {k: v.cpu().numpy() for k, v in d.items()}
-        offs = [0]
-        for n in (B * o, B * o, B * a, B, B):
-            offs.append((offs[-1] + n + 3) & ~3)               # every piece 16-byte aligned
+        offs = _packed_offsets(B, o, a)
         # ... gathered straight into a page-locked block of this buffer (its device-side address: no device staging block, no copy
         # launch), of which the caller gets a fresh copy: 38 -> ~20 us per call
         st = self.__dict__.setdefault("_plain_host", {}).get(B)
@@ -263,10 +279,7 @@ class ReplayBuffer(_Fed):
         _lib.check(self._lib.ddrl_replay_sample(self._h, B, p[0], p[1], p[2], p[3], p[4], None, _lib.stream_ptr()))
         self._pf_order_store(False)
         torch.cuda.current_stream().synchronize()
-        h = st[1].copy()
-        return dict(obs1=h[offs[0]:offs[0] + B * o].reshape(B, o), obs2=h[offs[1]:offs[1] + B * o].reshape(B, o),
-                    acts=h[offs[2]:offs[2] + B * a] if self._acts_1d else h[offs[2]:offs[2] + B * a].reshape(B, a),
-                    rews=h[offs[3]:offs[3] + B], done=h[offs[4]:offs[4] + B])
+        return self._packed_views(st[1].copy(), offs, B)
 
     def sample_batch_device(self, batch_size=None, fresh=False, with_indices=False):
         B = int(self._default_batch if batch_size is None else batch_size)
@@ -314,6 +327,13 @@ class ReplayBuffer(_Fed):
             t = torch.as_tensor(np.asarray(t, dtype=np.float32))
         return t.to(device=self.device, dtype=torch.float32).contiguous()
 
+    def _packed_views(self, v, offs, B):
+        """dict(obs1, obs2, acts, rews, done) of views over the packed block `v` (NumPy float32, laid out by _packed_offsets)."""
+        o, a = self.obs_dim, self.act_dim
+        return dict(obs1=v[offs[0]:offs[0] + B * o].reshape(B, o), obs2=v[offs[1]:offs[1] + B * o].reshape(B, o),
+                    acts=v[offs[2]:offs[2] + B * a] if self._acts_1d else v[offs[2]:offs[2] + B * a].reshape(B, a),
+                    rews=v[offs[3]:offs[3] + B], done=v[offs[4]:offs[4] + B])
+
     def _buffers(self, B, fresh):
         if not fresh and B in self._out:
             return self._out[B]
@@ -323,11 +343,6 @@ class ReplayBuffer(_Fed):
         if not fresh:
             self._out[B] = out
         return out
-
-    def _counts(self):
-        c = [ctypes.c_int64() for _ in range(4)]
-        _lib.check(self._lib.ddrl_replay_counts(self._h, *[ctypes.byref(x) for x in c], _lib.stream_ptr()))
-        return tuple(int(x.value) for x in c)  # (ptr, size, steps, sample_times)
 
     @property
     def ptr(self):
@@ -371,13 +386,6 @@ class ReplayBuffer(_Fed):
     def check(self):
         """Surface the ring's sticky device-side error now (an empty-ring draw inside a graph, a value a compact array cannot hold)."""
         self._counts()
-
-    def mt_state(self):
-        key = np.empty(624, dtype=np.uint32)
-        pos = ctypes.c_int32()
-        _lib.check(self._lib.ddrl_replay_mt_state(self._h, ctypes.c_void_p(key.ctypes.data), ctypes.byref(pos),
-                                                  _lib.stream_ptr()))
-        return key, int(pos.value)
 
 
 class ReplayBufferSAC1(ReplayBuffer):
@@ -445,7 +453,7 @@ class ReplayBufferDQN(ReplayBuffer):
                                                     int(infos[4]), _lib.stream_ptr()))
 
 
-class ReplayBufferNStep(_Fed):
+class ReplayBufferNStep(_Ring):
     """The n-step window buffer of algos/sac1/sac_ray.py:34-82: `ReplayBuffer(opt)` with
     opt.buffer_size slots, each holding (opt.Ln + 1) observation frames and opt.Ln (action, reward,
     done) triples; `store(o_queue, a_r_d_queue, worker_index)` takes the rollout's two deques
@@ -475,14 +483,6 @@ class ReplayBufferNStep(_Fed):
         self._h = h
         if seed is not None:
             self.seed(seed)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.ddrl_replay_destroy(h)
-
-    def seed(self, s):
-        _lib.check(self._lib.ddrl_replay_seed(self._h, int(s) & 0xFFFFFFFF, _lib.stream_ptr()))
 
     def store(self, o_queue, a_r_d_queue, worker_index=None):
         """One window (sac_ray.py:53-70): o_queue = Ln+1 tuples (o,), a_r_d_queue = Ln tuples (a, r, d)."""
@@ -562,9 +562,7 @@ class ReplayBufferNStep(_Fed):
         return flat[:off]
 
     def get_counts(self):
-        c = [ctypes.c_int64() for _ in range(4)]
-        _lib.check(self._lib.ddrl_replay_counts(self._h, *[ctypes.byref(x) for x in c], _lib.stream_ptr()))
-        ptr, size, steps, samples = (int(x.value) for x in c)
+        _, size, steps, samples = self._counts()
         return samples, steps, size
 
     def rings(self):
@@ -572,13 +570,6 @@ class ReplayBufferNStep(_Fed):
         _lib.check(self._lib.ddrl_replay_buffers_ex(self._h, p, None, None))
         return {"buffer_" + n[0]: _view(p[j], (self.max_size,) + s, self.device)
                 for j, (n, s) in enumerate(zip(self.names, self.shapes))}
-
-    def mt_state(self):
-        key = np.empty(624, dtype=np.uint32)
-        pos = ctypes.c_int32()
-        _lib.check(self._lib.ddrl_replay_mt_state(self._h, ctypes.c_void_p(key.ctypes.data), ctypes.byref(pos),
-                                                  _lib.stream_ptr()))
-        return key, int(pos.value)
 
 
 def _view(ptr, shape, device):

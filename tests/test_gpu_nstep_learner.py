@@ -88,10 +88,13 @@ def test_fold_kernel_with_outputs_off_the_16_byte_grid(ddrl):
 
 
 # ---- 2. draw + fold-gather in one launch == fold of the plain gather at the same indices ------------------------------------------
-@pytest.mark.parametrize("stores,B,obs_dim,num_buffers", [(100, 256, 8, 1), (100, 37, 5, 2), (37, 37, 8, 1), (1, 37, 8, 2), (100, 5000, 8, 1)])
+@pytest.mark.parametrize("stores,B,obs_dim,num_buffers", [(100, 256, 8, 1), (100, 37, 5, 2), (37, 37, 8, 1), (1, 37, 8, 2), (100, 5000, 8, 1),
+                                                                  (100, 4096, 8, 1), (100, 4097, 8, 1), (100, 65537, 5, 1)])
 def test_sample_nstep_device_equals_fold_of_the_gather(ddrl, stores, B, obs_dim, num_buffers):
     """Capacity 64: 100 stores wrap it, 37 fill it partly, 1 is the no-draw case of np.random.randint(0, 1, B); batch 5000 is beyond the
-    one-workgroup sampler (index draw and fold-gather as two launches).  Same indices, MT19937 state and counters as sample_batch_device."""
+    one-workgroup sampler (index draw and fold-gather as two launches): 4096 is its last batch, 4097 the first of the wide draw, and
+    65537 indices outgrow the handle's index scratch of 65536 in the gamma-0.5 draw, which passes no index buffer.  Same indices, MT19937
+    state and counters as sample_batch_device."""
     Ln = 8
     opt = _opt(Ln=Ln, batch=B, obs_dim=obs_dim, cap=64, num_buffers=num_buffers)
     win = nf.windows(np.random.RandomState(stores + B), stores, Ln, obs_dim, 2, terminal="every")

@@ -206,6 +206,35 @@ def test_large_row_gather_path(ddrl):
     np.testing.assert_array_equal(g["acts"].cpu().numpy(), ora.acts_buf[idx.cpu().numpy()])
 
 
+@pytest.mark.parametrize("with_indices", [False, True])
+@pytest.mark.parametrize("B", [2047, 2048, 65537])
+def test_wide_rows_draw_then_gather(ddrl, B, with_indices):
+    """Rows too wide for the one-workgroup draw + gather (42 x 4 B x 2 per index: 2047 rows are 687 KB): the draw is a launch of its
+    own — the 256-thread form below 2048 indices, the 640-thread form from 2048 on — behind it the row gather (the small-row form from
+    4096 rows on); 65537 indices outgrow the handle's index scratch of 65536 when the caller passes no index buffer.  Indices, rows,
+    MT19937 state and counters bit for bit those of the oracle."""
+    from oracle.replay_oracle import ReplayBufferOracle
+    obs_dim, cap, n = 40, 1000, 700
+    buf, ora = ddrl.ReplayBufferSAC1(obs_dim, 2, cap, seed=11), ReplayBufferOracle(obs_dim, 2, cap, seed=11)
+    rs = np.random.RandomState(B)
+    o, o2 = rs.randn(n, obs_dim).astype(np.float32), rs.randn(n, obs_dim).astype(np.float32)
+    a, r, d = rs.uniform(-1, 1, (n, 2)).astype(np.float32), rs.randn(n).astype(np.float32), (rs.rand(n) < 0.1).astype(np.float32)
+    buf.store_batch(*(torch.from_numpy(x).cuda() for x in (o, a, r, o2, d)))
+    for name, src in (("obs1_buf", o), ("obs2_buf", o2), ("acts_buf", a), ("rews_buf", r), ("done_buf", d)):
+        getattr(ora, name)[:n] = src   # (n sequential stores into an empty ring of more than n rows)
+    ora.ptr, ora.size, ora.steps = n, n, n
+    for it in range(2):
+        g = _cpu(buf.sample_batch_device(B, with_indices=with_indices))
+        w = ora.sample_batch(B)
+        if with_indices:
+            np.testing.assert_array_equal(g["idxs"], ora.last_idxs, err_msg="draw %d" % it)
+        for k in ("obs1", "obs2", "acts", "rews", "done"):
+            np.testing.assert_array_equal(g[k], w[k], err_msg="draw %d %s" % (it, k))
+    key, pos = buf.mt_state()
+    assert pos == ora.rng.pos and (key == ora.rng.key).all()
+    assert buf.get_counts() == ora.get_counts() == (2, n, n)
+
+
 def test_parameter_server_golden(ddrl, golden_dir, tmp_path):
     import pickle
     log = json.load(open(os.path.join(golden_dir, "ps_trace.json")))
@@ -733,6 +762,45 @@ def test_nstep_ring_random_walk(ddrl, seed):
             rings = buf.rings()
             for k in ("buffer_o", "buffer_a", "buffer_r", "buffer_d"):
                 np.testing.assert_array_equal(rings[k].cpu().numpy().reshape(getattr(ora, k).shape), getattr(ora, k), err_msg="op %d %s" % (op, k))
+
+
+def test_masked_store_of_more_rows_than_slots_from_a_cursor_off_zero(ddrl):
+    """One masked store that selects 33 of 40 windows for a ring of 7 slots whose cursor stands at 5: the selected rows that a later one
+    of the same batch overwrites are skipped inside the launch, the last 7 land behind the cursor in row order, and the cursor commit
+    counts all 33."""
+    from oracle.replay_oracle import NStepReplayOracle
+    rs = np.random.RandomState(4)
+
+    class Opt:
+        obs_shape, act_shape = (3,), (1,)
+        Ln, buffer_size, batch_size, num_buffers = 2, 7, 4, 1
+    buf, ora = ddrl.ReplayBufferNStep(Opt, seed=2), NStepReplayOracle(Opt, seed=2)
+
+    def windows(n):
+        return (rs.randn(n, 3, 3).astype(np.float32), rs.uniform(-1, 1, (n, 2, 1)).astype(np.float32), rs.randn(n, 2).astype(np.float32),
+                (rs.rand(n, 2) < 0.1).astype(np.float32))
+
+    def ora_store(o, a, r, d, rows):
+        for i in rows:
+            ora.store([(o[i, k],) for k in range(3)], [(a[i, k], r[i, k], d[i, k]) for k in range(2)], 0)
+
+    w = windows(5)
+    buf.store_batch(*(torch.from_numpy(x).cuda() for x in w))
+    ora_store(*w, range(5))
+    w = windows(40)
+    mask = np.ones(40, dtype=np.uint8)
+    mask[[0, 3, 9, 17, 18, 30, 39]] = 0
+    assert mask.sum() == 33
+    buf.store_masked(*(torch.from_numpy(x).cuda() for x in w), torch.from_numpy(mask).cuda())
+    ora_store(*w, np.nonzero(mask)[0])
+    assert buf.get_counts() == ora.get_counts() == (0, 38, 7)
+    assert buf._counts()[0] == ora.ptr == 38 % 7
+    rings = buf.rings()
+    for k in ("buffer_o", "buffer_a", "buffer_r", "buffer_d"):
+        np.testing.assert_array_equal(rings[k].cpu().numpy().reshape(getattr(ora, k).shape), getattr(ora, k), err_msg=k)
+    got, want = buf.sample_batch(), ora.sample_batch()
+    for k in want:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
 
 
 def test_prefetch_hands_out_the_same_batches_in_the_same_order():
