@@ -129,6 +129,7 @@ SIGNATURES = {
     "ddrl_actor_get_weights": (c_int, [_P, _P, _P]),
     "ddrl_actor_act": (c_int, [_P, _P, _P, c_int64, c_int, _P, _P]),
     "ddrl_actor_act_one": (c_int, [_P, _P, c_uint32, c_uint64, c_int, _P, _P]),
+    "ddrl_policy_eval": (c_int, [POINTER(Sac1Config), _P, c_int32, c_uint32, c_uint32, c_int32, _P, _P, _P, _P]),
     "ddrl_env_create": (c_int, [POINTER(_P), c_int, c_int64, c_uint32, c_int32]),
     "ddrl_env_destroy": (c_int, [_P]),
     "ddrl_env_reset": (c_int, [_P, _P, _P, _P]),
@@ -179,6 +180,10 @@ class DdrlError(RuntimeError):
     pass
 
 
+class DdrlUnsupported(DdrlError):
+    """DDRL_ERR_UNSUPPORTED: the call has no kernel for this shape (callers with another path catch this one)."""
+
+
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
     global _lib
@@ -216,7 +221,7 @@ def check(rc):
         raise ValueError("ddrl: " + msg)
     if rc == DDRL_ERR_NOMEM:
         raise MemoryError("ddrl: " + msg)
-    raise DdrlError("ddrl error %d: %s" % (rc, msg))
+    raise (DdrlUnsupported if rc == DDRL_ERR_UNSUPPORTED else DdrlError)("ddrl error %d: %s" % (rc, msg))
 
 
 def require_gpu():

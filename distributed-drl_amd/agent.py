@@ -517,6 +517,11 @@ class Model(Learner):
         return self._actor
 
     def get_action(self, o, deterministic=False):
+        if deterministic:
+            # the evaluation action (test_agent) is Actor.get_action's one launch for the one row (ddrl_actor_act_one), not the batched
+            # kernels' chain of three: the arithmetic the on-device evaluation episodes repeat (csrc/eval.hip), so that test_agent returns
+            # the same float from a host env and from an env.DeviceLunarLander.  Sampled actions (the rollout) go as they did.
+            return self._policy().get_action(o, True)
         a = self._policy().get_actions(torch.as_tensor(np.asarray(o, dtype=np.float32)).reshape(1, -1), deterministic=deterministic)
         return a[0].cpu().numpy()
 
@@ -529,6 +534,9 @@ class Model(Learner):
         return super().train(batch, eps=eps, return_outputs=return_outputs)
 
     def test_agent(self, test_env, args, n=10):
+        if getattr(test_env, "on_device", False):   # env.DeviceLunarLander: the n episodes as one launch
+            test_ret = _device_episodes(self._policy(), test_env, n, int(args.max_ep_len))
+            return sum(test_ret) / len(test_ret)
         test_ret = []
         for _ in range(n):
             o, r, d, ep_ret, ep_len = test_env.reset(), 0, False, 0, 0
@@ -538,6 +546,29 @@ class Model(Learner):
                 ep_len += 1
             test_ret.append(ep_ret)
         return sum(test_ret) / len(test_ret)
+
+
+def _device_episodes(actor, test_env, n, max_ep_len):
+    """The episodes of Actor.test / Model.test_agent on an env.DeviceLunarLander: `actor.evaluate` from the env's episode count
+    on, which then advances by n.  -> the n returns as Python floats, in episode order (what the host loop's `ep_ret`s are).
+    Outside the kernel's envelope (DDRL_ERR_UNSUPPORTED: a hidden width > 512) a host LunarLander of the same seed, positioned
+    at the same episode, is stepped instead."""
+    if int(test_env.max_ep_len) != int(max_ep_len):
+        raise ValueError("the test env's max_ep_len (%d) must equal the agent's (%d): the device plays whole episodes"
+                         % (test_env.max_ep_len, max_ep_len))
+    try:
+        rets = [float(x) for x in actor.evaluate(n, test_env.seed, test_env.episodes_played, max_ep_len)["ret"]]
+    except _lib.DdrlUnsupported:
+        host, rets = test_env.host_env(), []
+        for _ in range(n):
+            o, d, ep_ret, ep_len = host.reset(), False, 0, 0
+            while not (d or (ep_len == max_ep_len)):
+                o, r, d, _ = host.step(actor.get_action(o, True))
+                ep_ret += r
+                ep_len += 1
+            rets.append(ep_ret)
+    test_env.episodes_played += n
+    return rets
 
 
 class Actor(_Net):
@@ -645,18 +676,41 @@ class Actor(_Net):
         torch.cuda.current_stream().synchronize()
         return hov[0].copy()
 
+    def evaluate(self, n=25, seed=0, first_episode=0, max_ep_len=None, trace=False):
+        """n deterministic evaluation episodes on the device as ONE launch (ddrl_policy_eval, csrc/eval.hip): episode e is the
+        (first_episode + e)-th episode a host `LunarLander(seed, max_ep_len)` plays, acted on with this actor's current weights
+        by get_action(o, deterministic=True)'s arithmetic.  -> dict(ret float64 [n], len int32 [n]) NumPy, and with trace=True
+        `trace` float32 [n, max_ep_len, 12]: per step obs[8] acted on, act[2], rew, ended; zero rows past an episode's end.
+        One weight snapshot, one launch, one synchronisation; the actor's weights and noise counter are untouched."""
+        n = int(n)
+        max_ep_len = int(self.opt.max_ep_len if max_ep_len is None else max_ep_len)
+        flat = self._flat_get()
+        ret = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+        ln = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        tr = torch.empty(max(n, 1), max(max_ep_len, 1), 12, dtype=torch.float32, device=self.device) if trace else None
+        _lib.check(self._lib.ddrl_policy_eval(ctypes.byref(self.cfg), _lib.dptr(flat), n, int(seed) & 0xFFFFFFFF, int(first_episode),
+                                              max_ep_len, _lib.dptr(ret), _lib.dptr(ln), _lib.dptr(tr), _lib.stream_ptr()))
+        torch.cuda.current_stream().synchronize()
+        out = {"ret": ret.cpu().numpy(), "len": ln.cpu().numpy()}
+        if trace:
+            out["trace"] = tr.cpu().numpy()
+        return out
+
     def test(self, test_env, replay_buffer=None, n=25):
         """Deterministic evaluation episodes (actor_learner.py:199-218); returns the mean return.  With opt.summary_dir set the
         reference's TensorBoard scalar goes out too: "Reward" = sum(rew) / 25 at step sample_times (actor_learner.py:210-216;
         the divisor is the reference's constant, whatever n is)."""
-        rew = []
-        for _ in range(n):
-            o, r, d, ep_ret, ep_len = test_env.reset(), 0, False, 0, 0
-            while not (d or (ep_len == self.opt.max_ep_len)):
-                o, r, d, _ = test_env.step(self.get_action(o, True))
-                ep_ret += r
-                ep_len += 1
-            rew.append(ep_ret)
+        if getattr(test_env, "on_device", False):   # env.DeviceLunarLander: the n episodes as one launch
+            rew = _device_episodes(self, test_env, n, int(self.opt.max_ep_len))
+        else:
+            rew = []
+            for _ in range(n):
+                o, r, d, ep_ret, ep_len = test_env.reset(), 0, False, 0, 0
+                while not (d or (ep_len == self.opt.max_ep_len)):
+                    o, r, d, _ = test_env.step(self.get_action(o, True))
+                    ep_ret += r
+                    ep_len += 1
+                rew.append(ep_ret)
         logdir = getattr(self.opt, "summary_dir", None)
         if logdir and self.job == "main":   # the reference creates its FileWriter for job == "main" only (actor_learner.py:176-179)
             if getattr(self, "_writer", None) is None:

@@ -129,6 +129,39 @@ class LunarLander:
         return o2[0].cpu().numpy().astype(np.float64), float(r[0].item()), ended, {}
 
 
+class DeviceLunarLander:
+    """The test env of an on-device evaluation: a MARKER, not a steppable env.  It holds what names the episodes a host
+    `LunarLander(seed, max_ep_len)` would play one after another — the seed and how many episodes have been played — and
+    `Actor.test` / `Model.test_agent` given one run their episodes as one launch (`Actor.evaluate`, csrc/eval.hip) and advance
+    the count.  reset / action_space exist so that nothing breaks on attribute access at construction; step raises."""
+
+    on_device = True
+
+    def __init__(self, seed=0, max_ep_len=1000):
+        self.seed, self.max_ep_len = int(seed) & 0xFFFFFFFF, int(max_ep_len)
+        self.episodes_played = 0
+        self.action_space = _ActionSpace(self)
+        self.observation_space = _ObsSpace()
+
+    def reset(self):
+        return np.zeros(8, np.float64)
+
+    def step(self, a):
+        raise RuntimeError("DeviceLunarLander is not steppable: its episodes run on the device (Actor.evaluate / Actor.test / "
+                           "Model.test_agent); use env.make(name) for an env to step from the host")
+
+    def host_env(self):
+        """A host `LunarLander` of the same seed positioned at the next episode this env would play (the fallback of a policy
+        outside ddrl_policy_eval's envelope)."""
+        host = LunarLander(self.seed, self.max_ep_len)
+        if self.episodes_played:
+            s = host._vec.get_state()
+            s[13] = float(self.episodes_played)   # EPI (csrc/env_device.h): the episode index names the env's random stream
+            host._vec.set_state(s)
+            host._vec.reset()
+        return host
+
+
 class Wrapper(object):
     """algos/sac1/hyperparams.py:107-134 on a host env: uniform action noise added IN PLACE to the caller's action (`action +=`),
     the action repeated `action_repeat` times with the rewards summed and scaled — except that a terminal inside the repeat returns
@@ -167,8 +200,9 @@ class Wrapper(object):
         return self._noisy(obs_), self.reward_scale * r, done_, info_
 
 
-def make(env_name="LunarLanderContinuous-v2", **kw):
-    """gym.make stand-in (example/dsac.py:78)."""
+def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
+    """gym.make stand-in (example/dsac.py:78).  on_device=True: the test-env marker whose episodes `Actor.test` /
+    `Model.test_agent` run as one launch (DeviceLunarLander)."""
     if "LunarLander" not in env_name:
         raise ValueError("only the LunarLanderContinuous-v2 stand-in is built (SURVEY §8(a) A7): %r" % env_name)
-    return LunarLander(**kw)
+    return DeviceLunarLander(**kw) if on_device else LunarLander(**kw)

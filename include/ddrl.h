@@ -448,6 +448,20 @@ int ddrl_actor_act(ddrl_actor_t *h, const float *obs_d, const float *eps_d, int6
  * width > 512 or act_dim > 4.  Same threading / capture rules as ddrl_actor_act. */
 int ddrl_actor_act_one(ddrl_actor_t *h, const float *obs_d, uint32_t noise_seed, uint64_t noise_ctr, int deterministic, float *act_d,
                        void *stream);
+/* The test worker's evaluation episodes as ONE launch: Actor.test (actor_learner.py:199-218) and Model.test_agent
+ * (example/model.py:106-118) — n deterministic episodes of get_action(o, deterministic) + env.step(a) — with one workgroup per
+ * episode and no host round trip per step.  pi_flat_d is the policy in the flat external order ddrl_actor_get_weights writes
+ * (W1[obs][h1], b1, W2[h1][h2], b2, Wmu, bmu, Wls, bls); no actor handle is involved.  Episode e of the call plays the lander's
+ * stream (env_seed, env id 0, episode first_episode + e): exactly the episodes ONE ddrl_env_create(n_envs = 1, env_seed, max_ep_len)
+ * env plays one after the other from its (first_episode + 1)-th on.  The policy row is ddrl_actor_act_one's arithmetic in its
+ * summation order (deterministic), the env step is ddrl_env_step's: actions, rewards and lengths equal those of that host loop bit
+ * for bit.  ret_d[n] = the float64 sum of the float32 step rewards in step order, len_d[n] = steps played, trace_d (NULL, or
+ * [n][max_ep_len][12] 16-byte aligned) = per step the observation acted on [8], the action [2], the reward, ended (0 / 1); rows past
+ * an episode's end are written as zeros.  Stream-ordered on the CURRENT device: no host synchronisation, no allocation.
+ * DDRL_ERR_BAD_ARG unless obs_dim == 8, act_dim == 2, n_episodes >= 1, max_ep_len >= 1 (and max_ep_len, first_episode + n_episodes
+ * exact in float32: <= 2^24); DDRL_ERR_UNSUPPORTED outside ddrl_actor_act_one's envelope (a hidden width > 512). */
+int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int32_t n_episodes, uint32_t env_seed, uint32_t first_episode,
+                     int32_t max_ep_len, double *ret_d, int32_t *len_d, float *trace_d, void *stream);
 
 /* ===================================================================================== */
 /* Batched lander environment — stands where gym's LunarLanderContinuous-v2 env.step /     */
