@@ -205,6 +205,13 @@ constexpr int DPRE = 1;    // operand blocks of k_dfwd requested before its K lo
 #endif
 constexpr int DGP0 = DDRL_DGP0;    // 8-deep operand groups of k_dg requested before its K loop
 constexpr int DGMID = DDRL_DGMID;   // k_dg: the group behind whose MFMAs the epilogue operands are requested
+#ifndef DDRL_DGST
+#define DDRL_DGST 5
+#endif
+// k_dg, tiles that step the optimizer: the group in front of whose MFMAs the state is requested.  With DGP0 = 2 that is right
+// behind the request of group DGST + 2: group 7, the last one a wave has of a 256-deep contraction (the batch).
+constexpr int DGST10 = DDRL_DGST;
+template <int V> struct DGKind { static constexpr int value = V; };
 struct DSrc {
     const float *W1, *W2p;
     int Np, b0, nb, n0;
@@ -1122,6 +1129,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     // only the first DGP groups are requested up front; group g + DGP is requested when group g's MFMAs are issued (the
     // fetch path then works beside the matrix pipe, and the first MFMA does not queue behind the whole stream)
     constexpr int DGP = DGP0 < GMAX ? DGP0 : GMAX;
+    constexpr int DGST = GMAX <= 10 ? DGST10 : GMAX - DGP - 1;   // (deeper contractions: behind the last group's request)
 #pragma unroll
     for (int g = 0; g < DGP; ++g) fetch_group(g);
     // ---- policy dgrad with a GENERATED A operand (bgen = 3): A[row][k] = dZ2 of the policy trunk = (H2[row][k] > 0) * sum_a (dmu[row][a]
@@ -1200,11 +1208,25 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     ktouch(kl);
     DST(kid, 1);
     // ---- epilogue operands: requested from inside the K loop (behind the MFMAs of the first groups), so that the first
-    // MFMA does not queue behind up to 16 more wave-loads per wave.  (A wave's loads return in order, so the optimizer state —
-    // cold, from the fabric — still holds up the operand groups requested behind it: +2.8 k / +4.1 k cycles of K loop in the
-    // two optimizer launches against the same launches without the step.  Measured alternative: a fifth "helper" wave per
+    // MFMA does not queue behind up to 16 more wave-loads per wave.  A wave's loads return in order, and the optimizer state is
+    // cold (it comes over the fabric): whatever waits behind it in the K loop waits a round trip.  That cost did not depend on
+    // WHERE the state was requested (DGMID 1 - 8: flat), because of how the waits were counted, not because of the queue: the
+    // requests sat in branches (job type, do_adam) inside the one K loop of all job types, and where paths with different
+    // numbers of loads in flight join, the compiler's wait counts assume the shortest one — the very next MFMA group waited for
+    // all but the four newest loads (vmcnt(5) / (4) where the stepping J4 path had 13 behind the operand it needed), i.e. for
+    // the whole state wherever it stood; and the four bias-correction powers were used where they were loaded, a vmcnt(0) in the
+    // middle of the loop of EVERY tile of a stepping launch, dgrads included, which never use them.
+    // So the tiles that step the optimizer run a K loop of their own per epilogue mapping (k_loop_step, KIND 1 - 3 below: no load
+    // of theirs under a branch, the waits count exactly: vmcnt(13) there now), request the state behind the last operand group
+    // of a 256-deep contraction (DGST) and first use it, and the powers, behind the combine barrier; the other tiles keep the
+    // loop they had and no longer load the powers.  (All four kinds through ONE generic loop: the compiler then turns the
+    // generated-operand branches of the dgrads into selects, +0.9 k cycles of K loop in launch "bq".)  tools/upd_bench, us per
+    // update: 43.9 -> 42.7 (K loop of the stepping J4 tiles 16.6 k -> 14.7 k cycles in launch "mid", 11.4 k -> 9.8 k in "pi";
+    // their epilogue 2.8 k -> 3.3 k; the policy dgrad beside them 9.7 k -> 9.1 k); DGST 3 / 4 / 5 / 6 / 7: 43.0 - 43.4 against
+    // 44.1, flat — with exact waits the position hardly matters, the rest of the K loop's excess is the arrival of its own
+    // operands (profiles/optstate_queue_before_after.txt).  Closed before that: a fifth "helper" wave per
     // workgroup that fetches the state into LDS before the combine barrier — the dispatcher then fits one 5-wave workgroup
-    // per CU at 131 VGPRs (59.5 us per update), and capping the kernel at 128 VGPRs spills (55.7 us) against 52.5 us.)
+    // per CU at 131 VGPRs (59.5 us per update), and capping the kernel at 128 VGPRs spills (55.7 us) against 52.5 us.
     const bool is_dgrad = type == DG_DGRAD_Q || type == DG_DGRAD;
     float4 mk = make_float4(1.f, 1.f, 1.f, 1.f);
     float wa_v = 0.f;  // staged into LDS after the K loop
@@ -1213,6 +1235,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     const bool do_adam = jobs.ad.on && (type == DG_WGRAD_J4 || rm_like) && jb.adam_off >= 0;
     const bool narrow = rm_like && hot_N <= 8;   // block-uniform
     float al_pi = 0.f, al_q = 0.f;
+    float b1p_pi = 0.f, b2p_pi = 0.f, b1p_q = 0.f, b2p_q = 0.f;   // stepping tiles: the powers as loaded, al_pi / al_q from them in the epilogue
     // optimizer state of this tile: J4 — thread (col r, row group cg) owns rows 4cg..4cg+3 of column r as one float4;
     // RM — thread owns elements (o >> 5, o & 31), o = tid + 256 q
     float4 j_m, j_v, j_p, j_t;
@@ -1221,41 +1244,44 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     bool okv[4];
     long long j_idx = 0, b_idx = 0;
     bool j_ok = false, b_ok = false;
-    auto epilogue_operands = [&]() {
-        if (is_dgrad) mk = *reinterpret_cast<const float4 *>(jb.mask + ((long long)(m0 / 4 + cg) * jb.ldmask + n0 + r) * 4);  // mapping C: (col r, row group cg)
-        if (has_da) {
-            const int c = tid >> 5, col = n0 + (tid & 31);
-            const bool ok = c < jb.nact && col < jb.N;
-            const float v = jb.wa[ok ? w1y_index(jb.wa_d0 + c, col) : 0];
-            wa_v = ok ? v : 0.f;
+    // KIND 0: a tile that does not step the optimizer (dgrads; wgrads of the split API) — 1 / 2 / 3: a stepping J4 / element-addressed /
+    // narrow element-addressed tile (block-uniform, chosen once in front of the K loop)
+    auto epilogue_operands = [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        if (KIND == 0) {
+            if (is_dgrad) mk = *reinterpret_cast<const float4 *>(jb.mask + ((long long)(m0 / 4 + cg) * jb.ldmask + n0 + r) * 4);  // mapping C: (col r, row group cg)
+            if (has_da) {
+                const int c = tid >> 5, col = n0 + (tid & 31);
+                const bool ok = c < jb.nact && col < jb.N;
+                const float v = jb.wa[ok ? w1y_index(jb.wa_d0 + c, col) : 0];
+                wa_v = ok ? v : 0.f;
+            }
+        } else {
+            b1p_pi = jobs.ad.opt->b1p_pi; b2p_pi = jobs.ad.opt->b2p_pi; b1p_q = jobs.ad.opt->b1p_q; b2p_q = jobs.ad.opt->b2p_q;
         }
-        if (jobs.ad.on) {
-            const float b1p_pi = jobs.ad.opt->b1p_pi, b2p_pi = jobs.ad.opt->b2p_pi, b1p_q = jobs.ad.opt->b1p_q, b2p_q = jobs.ad.opt->b2p_q;
-            al_pi = jobs.ad.lr * sqrtf(1.0f - b2p_pi) / (1.0f - b1p_pi);
-            al_q = jobs.ad.lr * sqrtf(1.0f - b2p_q) / (1.0f - b1p_q);
-        }
-        if (type == DG_WGRAD_J4) {
+        if (KIND == 1 || (KIND == 0 && type == DG_WGRAD_J4)) {
             j_ok = m0 + 4 * cg < jb.bias_row && n0 + r < jb.N;
             j_idx = jb.adam_off + ((long long)(m0 / 4 + cg) * jb.ldc + n0 + r) * 4;
             b_ok = m0 + 4 * cg == jb.bias_row && n0 + r < jb.N;  // (hidden1 % 4 == 0: the bias row opens a group)
             b_idx = jb.bias_off + n0 + r;
-            if (do_adam) {
+            if (KIND == 1) {
                 const long long ic = j_ok ? j_idx : jb.adam_off;
                 j_m = *reinterpret_cast<const float4 *>(jobs.ad.m + ic); j_v = *reinterpret_cast<const float4 *>(jobs.ad.v + ic);
                 j_p = *reinterpret_cast<const float4 *>(jobs.ad.p + ic); j_t = *reinterpret_cast<const float4 *>(jobs.ad.t + ic);
                 const long long bc = b_ok ? b_idx : jb.bias_off;
                 bm = jobs.ad.m[bc]; bv = jobs.ad.v[bc]; bp = jobs.ad.p[bc]; bt = jobs.ad.t[bc];
             }
-        } else if (rm_like) {
+        } else if (KIND >= 2 || (KIND == 0 && rm_like)) {
             // narrow outputs (the head kernels: N = act or 1 column): 32 rows x 8 columns = one element per thread instead of four —
-            // a quarter of the optimizer-state loads queued in front of the operand groups that follow them
+            // a quarter of the optimizer-state loads
+            const bool nar = KIND == 3 || (KIND == 0 && narrow);   // block-uniform
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                if (narrow && q > 0) { okv[q] = false; continue; }   // block-uniform
+                if (nar && q > 0) { okv[q] = false; continue; }
                 const int o = tid + 256 * q;
-                const int gi = m0 + (narrow ? (o >> 3) : (o >> 5)), gj = n0 + (narrow ? (o & 7) : (o & 31));
+                const int gi = m0 + (nar ? (o >> 3) : (o >> 5)), gj = n0 + (nar ? (o & 7) : (o & 31));
                 okv[q] = gi < jb.M && gj < jb.N;
-                if (do_adam) {
+                if (KIND >= 2) {
                     const long long idx = !okv[q] ? jb.adam_off : jb.adam_off + (type == DG_WGRAD_W1Y ? w1y_index(gi, gj) : (long long)gi * jb.ldc + gj);
                     am[q] = jobs.ad.m[idx]; av[q] = jobs.ad.v[idx]; ap[q] = jobs.ad.p[idx]; at[q] = jobs.ad.t[idx];
                 }
@@ -1327,6 +1353,36 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     floatx16 acc;
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    // the tiles that step the optimizer (wgrads: a plain or a generated B operand): one loop per epilogue mapping, no load under a branch
+    auto k_loop_step = [&](auto kind) {
+#pragma unroll
+        for (int g = 0; g < GMAX; ++g) {
+            if (g + DGP < GMAX) {
+                fetch_group(g + DGP);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (g == DGST) {
+                epilogue_operands(kind);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (g < ng) {
+                float4 av4 = a4[g], bv4 = b4[g];
+                if (jb.bgen) {
+                    const float4 d4 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
+                    bv4 = make_float4(bv4.x > 0.f ? d4.x * gwn : 0.f, bv4.y > 0.f ? d4.y * gwn : 0.f, bv4.z > 0.f ? d4.z * gwn : 0.f, bv4.w > 0.f ? d4.w * gwn : 0.f);
+                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.x, bv4.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.y, bv4.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.z, bv4.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.w, bv4.w, acc, 0, 0, 0);
+            }
+        }
+    };
+    if (do_adam) {   // block-uniform
+        if (type == DG_WGRAD_J4) k_loop_step(DGKind<1>{});
+        else if (!narrow) k_loop_step(DGKind<2>{});
+        else k_loop_step(DGKind<3>{});
+    } else {
 #pragma unroll
     for (int g = 0; g < GMAX; ++g) {
         if (g + DGP < GMAX) {
@@ -1334,7 +1390,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             __builtin_amdgcn_sched_barrier(0);
         }
         if (g == DGMID) {
-            epilogue_operands();
+            epilogue_operands(DGKind<0>{});
             __builtin_amdgcn_sched_barrier(0);
         }
         if (g < ng) {
@@ -1377,6 +1433,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.w, bv4.w, acc, 0, 0, 0);
         }
     }
+    }
     // ---- split-K combine.  D layout: col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)
     DST(kid, 3);
     if (has_da && tid < 128) s_wa[tid >> 5][tid & 31] = wa_v;
@@ -1410,6 +1467,10 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
         }
         DST(kid, 5); DRT(kid, 15);
         return;
+    }
+    if (do_adam) {  // block-uniform
+        al_pi = jobs.ad.lr * sqrtf(1.0f - b2p_pi) / (1.0f - b1p_pi);
+        al_q = jobs.ad.lr * sqrtf(1.0f - b2p_q) / (1.0f - b1p_q);
     }
     if (type == DG_WGRAD_J4) {
         // gradient tile rows = hidden-1 index (the contraction axis of the forward), cols = hidden-2 index
