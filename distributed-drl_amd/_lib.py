@@ -55,7 +55,7 @@ class DqnConfig(ctypes.Structure):
 _P = c_void_p  # device pointers and opaque handles cross as void*
 
 # name -> (restype, argtypes).  Must list every symbol include/ddrl.h declares
-# (tests/test_boundary.py checks header <-> table <-> library).
+# (tests/test_workers_cpu.py checks header <-> table <-> library).
 SIGNATURES = {
     "ddrl_version": (c_int, []),
     "ddrl_last_error": (c_char_p, []),

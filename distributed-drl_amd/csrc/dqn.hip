@@ -271,6 +271,25 @@ __global__ void __launch_bounds__(256) k_dqn_gather_rows(const float *__restrict
     for (; e < w4; e += 256) d4[e] = s4[e];
 }
 
+// the same out of a compact (uint8) ring array: one 16-byte load of 16 pixels -> four float4 stores (width % 16 == 0; exact conversion)
+__global__ void __launch_bounds__(256) k_dqn_gather_rows_u8(const unsigned char *__restrict__ ring, const long long *__restrict__ ridx, float *__restrict__ x1, int width, int ldx) {
+    const uint4 *s16 = reinterpret_cast<const uint4 *>(ring + ridx[blockIdx.x] * (long long)width);
+    float4 *d4 = reinterpret_cast<float4 *>(x1 + (long long)blockIdx.x * ldx);
+    auto put = [&](int e, const uint4 v) {
+        const unsigned d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            d4[4 * e + j] = make_float4((float)(d[j] & 255u), (float)((d[j] >> 8) & 255u), (float)((d[j] >> 16) & 255u), (float)(d[j] >> 24));
+    };
+    const int w16 = width >> 4, tid = threadIdx.x;
+    int e = tid;
+    for (; e + 3 * 256 < w16; e += 4 * 256) {
+        const uint4 a0 = s16[e], a1 = s16[e + 256], a2 = s16[e + 512], a3 = s16[e + 768];
+        put(e, a0); put(e + 256, a1); put(e + 512, a2); put(e + 768, a3);
+    }
+    for (; e < w16; e += 256) put(e, s16[e]);
+}
+
 __global__ void __launch_bounds__(256) k_dqn_stage(const float *o1, const float *o2, const float *ac, const float *r, const float *d,
                                                    float *x1, float *x2, float *acts, float *rew, float *done, int B, int obs, int ldx) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -586,8 +605,10 @@ int ddrl_dqn_import(ddrl_dqn_t *h, int which, const float *flat_d, void *stream)
 // The launches of one update.  ev != nullptr: an event after every stage (DDRL_DQN_STAGES + 1 events, ev[0] first) for
 // ddrl_dqn_step_timed; the update itself is the same either way.
 // ridx != nullptr: obs1_d / obs2_d are the replay ring's observation arrays and batch row r is their row ridx[r] (ddrl_dqn_step_ring).
+// u8 (with ridx, 16-byte aligned arrays, obs_dim % 16 == 0): those arrays are the BYTES of a compact ring — the layer-1 forward reads them as
+// they lie, the gradient's obs1 copy is converted by its gather.
 static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d, const float *acts_d, const float *rews_d, const float *done_d,
-                           float *loss_d, float *q_d, hipStream_t s, hipEvent_t *ev, const long long *ridx = nullptr) {
+                           float *loss_d, float *q_d, hipStream_t s, hipEvent_t *ev, const long long *ridx = nullptr, bool u8 = false) {
     const int B = h->cfg.batch, o = h->cfg.obs_dim;
     int e = 0;
     if (int prc = dqn_poison_check(h, s, false)) return prc;   // a stream-K combine of an EARLIER step gave up waiting for its partner
@@ -608,6 +629,7 @@ static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2
             f.ev[k].lda = in_place ? o : h->ldx;
             f.ev[k].ridx = ridx;
         }
+        f.a_u8 = u8 ? 1 : 0;   // (lda = obs_dim is then the row stride in bytes)
         launch_wide_fwd(f, s);
     } else {
         launch_gemm(h->g_f1, s);
@@ -629,7 +651,8 @@ static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2
         // ring rows (ridx): the gradient contracts over the batch rows, so it reads a gathered copy of obs1 (the one array of the
         // batch that is still materialised: 58 MB of the 231)
         const bool direct = in_place && !ridx;
-        if (ridx) k_dqn_gather_rows<<<B, 256, 0, s>>>(obs1_d, ridx, h->x1, o, h->ldx);
+        if (ridx && u8) k_dqn_gather_rows_u8<<<B, 256, 0, s>>>(reinterpret_cast<const unsigned char *>(obs1_d), ridx, h->x1, o, h->ldx);
+        else if (ridx) k_dqn_gather_rows<<<B, 256, 0, s>>>(obs1_d, ridx, h->x1, o, h->ldx);
         for (int nn = 0; nn < h->nnet; ++nn) {
             if (h->sk_on) {
                 SkArgs g = h->sk[nn];
@@ -684,8 +707,17 @@ int ddrl_dqn_step_ring(ddrl_dqn_t *h, ddrl_replay_t *replay, float *loss_d, floa
     }
     DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == o && rv.ring.w[1] == o && rv.ring.w[2] == 1 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
                  "the ring must be (obs1[obs_dim], obs2[obs_dim], acts, rews, done) of this learner's observation width");
-    if (rv.ring.kind[0] || rv.ring.kind[1]) {
-        ddrl::set_error("ddrl_dqn_step_ring reads float32 observation rows: a compact (uint8) ring goes through ddrl_replay_sample + ddrl_dqn_step");
+    // a compact (uint8) ring: both observation arrays as bytes, whole 16-byte chunks per row (the layer-1 forward's LDS-DMA and the
+    // gradient's gather load 16 bytes at a time); what this does not take goes through ddrl_replay_sample + ddrl_dqn_step
+    const bool u8 = rv.ring.kind[0] == 1 && rv.ring.kind[1] == 1;
+    if (!u8 && (rv.ring.kind[0] || rv.ring.kind[1])) {
+        ddrl::set_error("ddrl_dqn_step_ring reads both observation arrays as float32 rows or both as uint8 rows: this ring has one compact (uint8) "
+                        "and one float32 observation array; use ddrl_replay_sample + ddrl_dqn_step");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (u8 && (o % 16 != 0 || !al16(rv.ring.a[0]) || !al16(rv.ring.a[1]))) {
+        ddrl::set_error("ddrl_dqn_step_ring reads a compact (uint8) ring in 16-byte chunks: obs_dim must be a multiple of 16 (and the arrays 16-byte "
+                        "aligned); use ddrl_replay_sample + ddrl_dqn_step");
         return DDRL_ERR_UNSUPPORTED;
     }
     ddrl::DeviceGuard g(h->device);
@@ -694,7 +726,7 @@ int ddrl_dqn_step_ring(ddrl_dqn_t *h, ddrl_replay_t *replay, float *loss_d, floa
     int rc = ddrl_replay_sample_indices(replay, B, reinterpret_cast<int64_t *>(idx), stream);   // np.random.randint(0, size, B); sample_times += 1
     if (rc != DDRL_OK) return rc;
     k_dqn_gather3<<<(B + 255) / 256, 256, 0, s>>>(rv.ring.a[2], rv.ring.a[3], rv.ring.a[4], idx, h->acts, h->rew, h->done, reinterpret_cast<long long *>(idx_out_d), B);
-    return dqn_step_launch(h, rv.ring.a[0], rv.ring.a[1], h->acts, h->rew, h->done, loss_d, q_d, s, nullptr, idx);
+    return dqn_step_launch(h, rv.ring.a[0], rv.ring.a[1], h->acts, h->rew, h->done, loss_d, q_d, s, nullptr, idx, u8);
 }
 
 int ddrl_dqn_step_timed(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d, const float *acts_d, const float *rews_d, const float *done_d,

@@ -5,6 +5,7 @@
 // replaces it for both GEMMs of the layer:
 //
 //   k_wide<true>   forward, split K: partial pre-activations P[ev][s] = X[ev][:, Ks] * W1[ev][Ks, :]
+//                  (U8 instance: the X rows are the bytes of a compact replay ring, converted at the LDS read; same partials, bit for bit)
 //   k_wide_reduce  H1[ev] = relu(sum_s P[ev][s] + b1) in split order (deterministic)
 //   k_wide<false>  [dW1 ; db1] = [X | 1]^T dZ1, the whole batch as K, one tile per workgroup (shapes that do not split evenly)
 //   k_wide_sk      the same product as equal shares of the stage sequence over all resident workgroups (config 5: below)
@@ -41,6 +42,8 @@ struct WideEval {
     // quarters of sample_batch(512)'s 231 MB gather never happen (ddrl_dqn_step_ring).  (The same for the K rows of the weight
     // gradient was built and measured: ring-row numbers in LDS, one lookup per 1 KB piece — the kernel, already at 256 VGPRs, went
     // from 134 to 163 us with 189 spilled SGPRs; the gradient contracts a gathered copy of obs1 instead.)
+    // a_u8 (forward, WideArgs): A points at BYTES — the uint8 array of a compact ring, row ridx[r] starting ridx[r] * lda bytes in (lda in
+    // bytes, % 16 == 0) — and the U8 instance of k_wide converts them where it reads its LDS image.
     const long long *ridx;
 };
 struct WideArgs {
@@ -53,6 +56,7 @@ struct WideArgs {
     // column tiles come in two classes: cnt[0] tiles of nu[0] units, then cnt[1] tiles of nu[1] units; S[c] K ranges each
     int nu[2], cnt[2], S[2], wg0[3];
     int Smax, Mp, Np, ldo, total;
+    int a_u8;           // forward: the A rows are uint8 (k_wide<true, 4, 32, true>); K % 16 == 0
 #ifdef WD_STAMPS
     long long *stamps;  // diagnostic builds (tools/wide_bench.hip): [workgroup][wave][8] accumulated phase cycles
 #endif
@@ -63,7 +67,7 @@ struct WideArgs {
 // (it cannot tell the two LDS buffers apart), which serialises the stage being loaded with the stage being computed.  The
 // compiler does not count these loads: the kernel waits for them by hand (wide_dma_wait) before the barrier that publishes them.
 // M0 (the LDS-DMA base) is compiler-reserved: saved, set and restored inside the one statement.
-__device__ __forceinline__ void glds16(const float *src, unsigned lds) {
+__device__ __forceinline__ void glds16(const void *src, unsigned lds) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(src), "s"(lds) : "memory");
@@ -73,12 +77,21 @@ __device__ __forceinline__ unsigned lds_addr(const float *p) {
     return (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) const float *)p;
 }
 
-template <bool FWD, int WV, int WD_KB>   // the product instance is <., 4, 32>: 4 waves, 32 k per LDS stage (8-wave 256-row tiles and 16-k stages measured no better)
+// U8 (forward only): the A rows are bytes.  A stage's A image is then [rows][32 bytes] = 4 KB: ONE 1 KB piece per wave and stage instead of
+// four (1 + NU LDS-DMA instructions per wave and stage instead of 4 + NU), and that piece is the wave's own 32 rows x 2 chunks of 16 bytes.
+// A lane reads a whole chunk (k = 16 q .. 16 q + 15 of its row) with one ds_read_b128 per two 8-deep groups and takes dword 2 (g & 1) + h of
+// it: the four bytes k = 8 g + 4 h + {0..3}, converted exactly (v_cvt_f32_ubyte0..3).  k -> (stage, g, h, j), the B image, the split-K plan and
+// the MFMA order are the float instance's, so every accumulator sees the same operands in the same order: the same partials, bit for bit.
+// Unswizzled, rows r and r + 8 of a wave would sit on the same banks and ds_read_b128's 16-lane groups {0-3, 12-15, 20-27}, {4-11, 16-19,
+// 28-31} hold each residue mod 8 twice, once from rows < 16 and once from rows >= 16: chunk q of row r lives in slot q ^ ((r >> 4) & 1).
+template <bool FWD, int WV, int WD_KB, bool U8 = false>   // the product instances are <., 4, 32>: 4 waves, 32 k per LDS stage (8-wave 256-row tiles and 16-k stages measured no better)
 __global__ void __launch_bounds__(64 * WV, 2) k_wide(WideArgs a) {
     static_assert(WD_KB == 32 || !FWD, "the forward A image is cut for 128-byte rows");
-    constexpr int ROWS = 32 * WV, AOP = ROWS * WD_KB, WD_BOP = WD_KB * WD_BW, NG = WD_KB / 8;
+    static_assert(!U8 || (FWD && WV == 4 && WD_KB == 32), "the byte A image is one 1 KB piece of 32 rows x 32 bytes per wave");
+    constexpr int ROWS = 32 * WV, AOP = (U8 ? ROWS * WD_KB / 4 : ROWS * WD_KB), WD_BOP = WD_KB * WD_BW, NG = WD_KB / 8;   // AOP: floats of LDS per A image
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float *sA = wsm;             // [2][AOP]  forward: [rows][8 float4 slots], chunk q of row r in slot q ^ ((r >> 1) & 7)   wgrad: [32 k][rows]
+                                 //           U8 forward: [rows][2 slots of 16 bytes], chunk q of row r in slot q ^ ((r >> 4) & 1)
     float *sB = wsm + 2 * AOP;   // [2][32 k][160 columns]
     int L;
     {   // contiguous run of the workgroup order per XCD (block b runs on XCD b % 8)
@@ -102,10 +115,11 @@ __global__ void __launch_bounds__(64 * WV, 2) k_wide(WideArgs a) {
     // fills 1 KB of LDS in lane order from per-lane source addresses, so the images are cut into 1 KB pieces of 64 float4:
     //   forward A   piece I = rows 8I..8I+7 x 8 slots; the lane that fills slot p of row r loads chunk p ^ ((r >> 1) & 7) (the
     //               swizzle sits on the SOURCE address and on the read; the destination is linear)
+    //   U8 forward A  piece I = rows 32I..32I+31 x 2 slots of 16 bytes (wave I's own rows); slot p of row r loads chunk p ^ ((r >> 4) & 1)
     //   wgrad A     piece I = 1 KB of the [32 k][rows] image (4 waves: k rows 2I, 2I + 1)
     //   B           piece I = float4 64 I .. 64 I + 63 of the [32 k][160 columns] image (1.6 k rows)
     // What lies outside the matrices comes from a 16-byte block of zeros, the gradient's bias row from {1, 0, 0, 0}.
-    constexpr int APW = (AOP / 256) / WV, BPW = (WD_BOP / 256) / WV;   // pieces per wave and stage: 4 of A, 5 of B
+    constexpr int APW = (AOP / 256) / WV, BPW = (WD_BOP / 256) / WV;   // pieces per wave and stage: 4 of A (bytes: 1), 5 of B
     static_assert(APW * WV * 256 == AOP && BPW * WV * 256 == WD_BOP, "the LDS images are dealt to the waves in whole 1 KB pieces");
     static_assert(WV == 4 && WD_KB == 32, "a B image of 32 k x 32 NU columns is 4 NU pieces: NU per wave of four");
     const float *const ones_blk = a.consts, *const zero_blk = a.consts + 4;
@@ -115,7 +129,13 @@ __global__ void __launch_bounds__(64 * WV, 2) k_wide(WideArgs a) {
 #pragma unroll
     for (int i = 0; i < APW; ++i) {
         const int I = APW * w + i;
-        if (FWD) {
+        if (U8) {
+            const int row = 32 * I + (lane >> 1), q = (lane & 1) ^ ((row >> 4) & 1);
+            ak[i] = 16 * q;
+            const long long rr = (E.ridx && m0 + row < a.a_rows) ? E.ridx[m0 + row] : m0 + row;
+            // (a byte address kept in the float-pointer table: only ever advanced by whole dwords, k % 16 == 0, and handed to the DMA)
+            pa[i] = m0 + row < a.a_rows ? reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(E.A) + rr * E.lda + 16 * q) : nullptr;
+        } else if (FWD) {
             const int row = 8 * I + (lane >> 3), q = (lane & 7) ^ ((row >> 1) & 7);
             ak[i] = 4 * q;
             const long long rr = (E.ridx && m0 + row < a.a_rows) ? E.ridx[m0 + row] : m0 + row;
@@ -139,7 +159,8 @@ __global__ void __launch_bounds__(64 * WV, 2) k_wide(WideArgs a) {
 #pragma unroll
         for (int g = 0; g < APW; ++g) {
             const float *src;
-            if (FWD) src = (pa[g] && k + ak[g] < a.K) ? pa[g] + k : zero_blk;   // K % 4 == 0
+            if (U8) src = (pa[g] && k + ak[g] < a.K) ? pa[g] + (k >> 2) : zero_blk;   // K % 16 == 0: a chunk lies inside K or outside as a whole
+            else if (FWD) src = (pa[g] && k + ak[g] < a.K) ? pa[g] + k : zero_blk;   // K % 4 == 0
             else src = amode == 2 ? ones_blk : (amode == 1 && k + ak[g] < a.K) ? pa[g] + (long long)k * E.lda : zero_blk;
             glds16(src, dA + 1024 * g);
         }
@@ -153,10 +174,15 @@ __global__ void __launch_bounds__(64 * WV, 2) k_wide(WideArgs a) {
     const int sw = (l31 >> 1) & 7;
     auto compute = [&](const float *cA, const float *cB, auto nu_c) {
         constexpr int NUC = decltype(nu_c)::value;
+        uint4 t8 = make_uint4(0u, 0u, 0u, 0u);   // U8: the 16-byte chunk that holds this and the next 8-deep group
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             float av[4], bv[NUC][4];
-            if (FWD) {
+            if (U8) {
+                if ((g & 1) == 0) t8 = *reinterpret_cast<const uint4 *>(cA + (32 * w + l31) * (WD_KB / 4) + ((((g >> 1) ^ (l31 >> 4)) & 1) << 2));
+                const unsigned d = (g & 1) ? (h ? t8.w : t8.z) : (h ? t8.y : t8.x);
+                av[0] = (float)(d & 255u); av[1] = (float)((d >> 8) & 255u); av[2] = (float)((d >> 16) & 255u); av[3] = (float)(d >> 24);
+            } else if (FWD) {
                 const float4 t = *reinterpret_cast<const float4 *>(cA + (32 * w + l31) * WD_KB + (((2 * g + h) ^ sw) << 2));
                 av[0] = t.x; av[1] = t.y; av[2] = t.z; av[3] = t.w;
             } else {
@@ -528,7 +554,7 @@ static bool wide_applies(int obs, int h1) { return obs >= 1024 && obs % 4 == 0 &
 // Tiling of an [M x N] output over K: column tiles in two classes, K ranges per class proportional to the class's units,
 // at most `slots` workgroups (forward: all resident, 2 per CU; split = false: one K range, any number of workgroups).
 static void wide_plan(WideArgs &a, int nev, int M, int N, int K, bool split, int waves, int slots, int kb = 32, int max_nu = WD_NB) {
-    a.nev = nev; a.M = M; a.N = N; a.K = K; a.rows = 32 * waves; a.kb = kb;
+    a.nev = nev; a.M = M; a.N = N; a.K = K; a.rows = 32 * waves; a.kb = kb; a.a_u8 = 0;
     const int units = (N + 31) / 32, ntiles = (units + max_nu - 1) / max_nu, base = units / ntiles, rem = units % ntiles;
     a.nu[0] = base + 1; a.cnt[0] = rem; a.nu[1] = base; a.cnt[1] = ntiles - rem;
     a.m_tiles = (M + a.rows - 1) / a.rows;
@@ -550,24 +576,26 @@ static void wide_plan(WideArgs &a, int nev, int M, int N, int K, bool split, int
     a.total = a.wg0[2];
 }
 static size_t wide_part_floats(const WideArgs &a) { return (size_t)a.nev * a.Smax * a.Mp * a.Np; }
-template <bool FWD, int WV, int KB>
+template <bool FWD, int WV, int KB, bool U8 = false>
 static hipError_t wide_launch(const WideArgs &a, hipStream_t s, bool prepare_only) {
-    constexpr size_t lds = (size_t)2 * (32 * WV * KB + KB * WD_BW) * sizeof(float);   // 4 waves, 32-k stages: 72 KB (two workgroups per CU)
-    if (prepare_only) return hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide<FWD, WV, KB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    k_wide<FWD, WV, KB><<<a.total, 64 * WV, lds, s>>>(a);
+    constexpr size_t lds = (size_t)2 * (32 * WV * KB / (U8 ? 4 : 1) + KB * WD_BW) * sizeof(float);   // 4 waves, 32-k stages: 72 KB (two workgroups per CU); byte A rows: 48 KB
+    if (prepare_only) return hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide<FWD, WV, KB, U8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    k_wide<FWD, WV, KB, U8><<<a.total, 64 * WV, lds, s>>>(a);
     return hipSuccess;
 }
 // once per device, outside any stream capture (ddrl_dqn_create)
 static hipError_t wide_prepare() {
     WideArgs z{};
     hipError_t e = wide_launch<true, 4, 32>(z, nullptr, true);
+    if (e == hipSuccess) e = wide_launch<true, 4, 32, true>(z, nullptr, true);
     if (e == hipSuccess) e = wide_launch<false, 4, 32>(z, nullptr, true);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_wide_sk), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)((size_t)2 * (128 * 32 + 32 * WD_BW) * sizeof(float)));
     return e;
 }
 static void launch_wide_fwd(const WideArgs &a, hipStream_t s) {
-    (void)wide_launch<true, 4, 32>(a, s, false);
+    if (a.a_u8) (void)wide_launch<true, 4, 32, true>(a, s, false);
+    else (void)wide_launch<true, 4, 32>(a, s, false);
     const long long n = (long long)a.nev * a.M * (a.N >> 2);
     k_wide_reduce<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(a);
 }

@@ -150,12 +150,19 @@ class Learner:
     def train_from(self, replay_buffer, cnt=0, return_outputs=False, with_indices=False):
         """One iteration of the learner's loop — `agent.train(replay_buffer.sample_batch(), cnt)` (algos/dqn/train.py:66-76) — with the
         layer-1 forward reading its observation rows straight out of the device ring (ddrl_dqn_step_ring): same index stream, same
-        counters, bit-identical results, a quarter of the batch materialised.  Falls back to sample_batch_device + train where the fused
-        path does not apply (a compact ring, observations narrower than 1024)."""
+        counters, bit-identical results, a quarter of the batch materialised.  Runs sample_batch_device + train itself where the fused
+        call does not apply (observations narrower than 1024, a compact ring whose obs_dim is not a multiple of 16, a ring with one
+        compact and one float32 observation array: DDRL_ERR_UNSUPPORTED) — and on EVERY compact (uint8) ring: ddrl_dqn_step_ring does
+        take a compact ring (the forward stages the rows' bytes and converts them on chip, no float32 batch is written, bit-identical:
+        tests/test_gpu_compact_ring_learner.py), but at config 5's shape it measured 565 us per iteration against the two calls' 559
+        (profiles/compact_ring_learner_before_after.txt: the byte forward is no faster than the float32 one, and the batch forward
+        beats both forwards on scattered ring rows by more than the 32 us gather costs), so this method keeps the faster form there."""
         B = self.cfg.batch
         q = torch.empty(B, self.cfg.n_actions, dtype=torch.float32, device=self.device) if return_outputs else None
         idx = torch.empty(B, dtype=torch.int64, device=self.device) if with_indices else None
-        rc = self._lib.ddrl_dqn_step_ring(self._h, replay_buffer._h, _lib.dptr(self.loss), _lib.dptr(q), _lib.dptr(idx), _lib.stream_ptr())
+        rc = _lib.DDRL_ERR_UNSUPPORTED
+        if not getattr(replay_buffer, "compact_obs", False):
+            rc = self._lib.ddrl_dqn_step_ring(self._h, replay_buffer._h, _lib.dptr(self.loss), _lib.dptr(q), _lib.dptr(idx), _lib.stream_ptr())
         if rc == _lib.DDRL_ERR_UNSUPPORTED:
             b = replay_buffer.sample_batch_device(B, with_indices=with_indices)
             out = self.train(b, cnt, return_outputs=return_outputs)

@@ -586,8 +586,13 @@ int ddrl_dqn_step(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d, const
  * acts / rews / done are gathered (3 x batch floats), the layer-1 FORWARD of every evaluation reads its observation rows straight out of
  * the ring through the index list (the LDS-DMA loads take per-lane source addresses), and only obs1 — which the layer-1 weight gradient
  * contracts over the batch — is gathered (58 MB of config 5's 231 MB).  Results are bit-identical to ddrl_replay_sample + ddrl_dqn_step.
- * Needs the wide layer-1 path (obs_dim >= 1024) and a float32 five-array ring of this observation width on the same device; else
- * DDRL_ERR_UNSUPPORTED (use the two calls; a ring on another device: DDRL_ERR_BAD_ARG).  idx_out_d[batch] (nullable) receives the
+ * Needs the wide layer-1 path (obs_dim >= 1024) and a five-array ring of this observation width on the same device whose two observation
+ * arrays are both float32, or both compact (DDRL_REPLAY_U8_OBS) with obs_dim % 16 == 0: the forward then stages the rows' BYTES (a quarter
+ * of the LDS-DMA traffic) and converts them where it reads its LDS image, the obs1 gather converts on the way — uint8 -> float32 is exact,
+ * so the results are the float32 ring's bit for bit, and the compact ring's sticky DDRL_ERR_NOT_REPRESENTABLE is reported where it always is
+ * (the next call that looks at the ring's counters).  Anything else — narrow observations, a compact ring with obs_dim % 16 != 0, one compact
+ * and one float32 observation array — is DDRL_ERR_UNSUPPORTED with the reason in ddrl_last_error() and nothing drawn (use the two calls; a
+ * ring on another device: DDRL_ERR_BAD_ARG).  idx_out_d[batch] (nullable) receives the
  * indices.  The forward and the weight gradient read the ring at two different points of the call, so the ring rows must stay unchanged
  * until `stream` has passed the call: stores into this ring must be ordered with it on `stream` (or by an event), never concurrent. */
 int ddrl_dqn_step_ring(ddrl_dqn_t *h, ddrl_replay_t *replay, float *loss_d, float *q_d, int64_t *idx_out_d, void *stream);

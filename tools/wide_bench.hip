@@ -69,6 +69,70 @@ static int check(int nev, int M, int N, int K) {
     return ok ? 0 : 1;
 }
 
+// device-side fills of the byte-row arm: pseudo-random pixels, and the float32 image of the same values
+__global__ void k_fill_u8(unsigned char *p, size_t n, unsigned seed) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        unsigned x = (unsigned)i * 2654435761u + seed; x ^= x >> 15; x *= 2246822519u; x ^= x >> 13;
+        p[i] = (unsigned char)(x >> 24);
+    }
+}
+__global__ void k_u8_to_f32(const unsigned char *p, float *f, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) f[i] = (float)p[i];
+}
+// The forward on ring rows through an index list, float32 rows against the BYTES of the same rows (k_wide<true, 4, 32, true>): H1 must be
+// bit-identical; then both timed, alternating, at config 5's shape out of `rows`-row arrays (random rows: far beyond the Infinity Cache).
+static int u8_arm(int nev, int M, int N, int K, int rows, bool timed, const float *w, const float *wt, const float *bz) {
+    const int ldh = (N + 1 + 3) & ~3;
+    const size_t n = (size_t)rows * K;
+    unsigned char *b1, *b2; float *f1, *f2, *hf, *hu, *part; long long *ridx;
+    hipMalloc(&b1, n); hipMalloc(&b2, n); hipMalloc(&f1, n * 4); hipMalloc(&f2, n * 4);
+    hipMalloc(&hf, (size_t)nev * M * ldh * 4); hipMalloc(&hu, (size_t)nev * M * ldh * 4); hipMalloc(&ridx, M * 8);
+    k_fill_u8<<<4096, 256>>>(b1, n, 1u); k_fill_u8<<<4096, 256>>>(b2, n, 77u);
+    k_u8_to_f32<<<4096, 256>>>(b1, f1, n); k_u8_to_f32<<<4096, 256>>>(b2, f2, n);
+    std::vector<long long> ri(M);
+    for (auto &r : ri) r = (long long)(((unsigned long long)rand() * 2654435761ull) % (unsigned long long)rows);
+    ri[0] = rows - 1;
+    hipMemcpy(ridx, ri.data(), M * 8, hipMemcpyHostToDevice);
+    WideArgs a{};
+    wide_plan(a, nev, M, N, K, true, 4, 512, 32, MNU);
+    hipMalloc(&part, wide_part_floats(a) * 4);
+    a.part = part; a.a_rows = M; a.ldo = ldh; a.consts = g_consts;
+    WideArgs u = a;
+    for (int e = 0; e < nev; ++e) {
+        const float *W = e == 2 ? wt : w;
+        a.ev[e] = WideEval{e ? f2 : f1, W, bz, hf + (size_t)e * M * ldh, K, ridx};
+        u.ev[e] = WideEval{reinterpret_cast<const float *>(e ? b2 : b1), W, bz, hu + (size_t)e * M * ldh, K, ridx};
+    }
+    u.a_u8 = 1;
+    hipMemset(hf, 0, (size_t)nev * M * ldh * 4); hipMemset(hu, 0xff, (size_t)nev * M * ldh * 4);
+    launch_wide_fwd(a, 0); launch_wide_fwd(u, 0); hipDeviceSynchronize();
+    std::vector<float> h0((size_t)nev * M * ldh), h1(h0.size());
+    hipMemcpy(h0.data(), hf, h0.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(h1.data(), hu, h1.size() * 4, hipMemcpyDeviceToHost);
+    int diff = 0; double amax = 0;
+    for (int e = 0; e < nev; ++e)
+        for (int i = 0; i < M; ++i) {
+            if (memcmp(&h0[((size_t)e * M + i) * ldh], &h1[((size_t)e * M + i) * ldh], N * 4)) ++diff;
+            for (int j = 0; j < N; ++j) amax = std::max(amax, (double)h0[((size_t)e * M + i) * ldh + j]);
+        }
+    printf("byte rows: nev %d M %4d N %4d K %6d ring %6d rows: %d of %d H1 rows differ from the float32 rows' (max H1 %.3g)  %s (%s)\n", nev, M, N, K, rows,
+           diff, nev * M, amax, diff || !(amax > 0) ? "MISMATCH" : "bit-identical", hipGetErrorString(hipGetLastError()));
+    if (timed && !diff) {
+        hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+        float ms;
+        for (int i = 0; i < 5; ++i) { launch_wide_fwd(a, 0); launch_wide_fwd(u, 0); }
+        for (int rep = 0; rep < 5; ++rep)
+            for (int v = 0; v < 2; ++v) {
+                const WideArgs &x = v ? u : a;
+                hipEventRecord(e0, 0);
+                for (int i = 0; i < 20; ++i) launch_wide_fwd(x, 0);
+                hipEventRecord(e1, 0); hipEventSynchronize(e1); hipEventElapsedTime(&ms, e0, e1);
+                printf("forward on ring rows (%d evaluations, %d workgroups) + reduce, %s A rows: %.1f us\n", nev, x.total, v ? "uint8  " : "float32", ms * 50.f);
+            }
+    }
+    hipFree(b1); hipFree(b2); hipFree(f1); hipFree(f2); hipFree(hf); hipFree(hu); hipFree(part); hipFree(ridx);
+    return diff || !(amax > 0) ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 1) MNU = atoi(argv[1]);
     if (wide_prepare() != hipSuccess) { printf("wide_prepare failed\n"); return 1; }
@@ -113,6 +177,16 @@ int main(int argc, char **argv) {
         for (int i = 0; i < 10; ++i) launch_wide_wgrad(g, 0);
         hipEventRecord(e1, 0); hipEventSynchronize(e1); hipEventElapsedTime(&ms, e0, e1);
         printf("wgrad (%d workgroups): %.1f us  = %.1f TFLOP/s\n", g.total, ms * 100.f, 2.0 * M * N * (double)(K + 1) / (ms * 1e-4) / 1e12);
+    }
+    {   // the forward on the bytes of compact-ring rows: ragged shapes (K % 32 == 16 tails, partial row blocks, narrow tiles), then config 5's
+        std::vector<float> t = rnd((size_t)K * N, 0.0005f);
+        hipMemcpy(w, t.data(), t.size() * 4, hipMemcpyHostToDevice); hipMemcpy(wt, t.data() + 1000, (t.size() - 1000) * 4, hipMemcpyHostToDevice);
+        int ubad = 0;
+        ubad += u8_arm(3, 37, 400, 1040, 300, false, w, wt, bz);
+        ubad += u8_arm(5, 200, 48, 2064, 300, false, w, wt, bz);
+        ubad += u8_arm(3, 96, 400, 1024, 300, false, w, wt, bz);
+        ubad += u8_arm(3, M, N, K, 32768, true, w, wt, bz);
+        if (ubad) return 1;
     }
     {   // race screen: the same launches 100 times, every output bit-identical to the first (LDS-DMA ordering is by vmcnt + barrier only)
         std::vector<float> h0((size_t)3 * M * ldh), h1(h0.size()), g0((size_t)(K + 1) * N), g1(g0.size());
