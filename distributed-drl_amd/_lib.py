@@ -19,6 +19,7 @@ DDRL_ERR_NOMEM = -4
 DDRL_ERR_UNSUPPORTED = -5
 DDRL_ERR_NOT_REPRESENTABLE = -6
 DDRL_ERR_RCCL = -7
+DDRL_ACT_SAMPLE, DDRL_ACT_DETERMINISTIC = 0, 1   # ddrl_dqn_act / ddrl_rollout_step_discrete: mode
 DDRL_REPLAY_ACTS_1D = 1
 DDRL_REPLAY_U8_OBS = 2
 DDRL_ENV_STATE_FIELDS = 32
@@ -137,6 +138,9 @@ SIGNATURES = {
     "ddrl_rollout_begin": (c_int, [_P, _P, _P]),
     "ddrl_rollout_step": (c_int, [_P, _P, _P, c_int32, c_uint32, c_uint64, c_int, _P, _P, _P]),
     "ddrl_env_step_wrapped": (c_int, [_P, _P, c_float, c_float, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "ddrl_env_step_discrete": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "ddrl_rollout_begin_discrete": (c_int, [_P, _P, _P]),
+    "ddrl_rollout_step_discrete": (c_int, [_P, _P, _P, c_int32, c_int, c_float, c_uint32, c_uint64, _P, _P, _P, _P]),
     "ddrl_env_stats": (c_int, [_P, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), _P]),
     "ddrl_env_get_state": (c_int, [_P, _P, _P]),
     "ddrl_env_set_state": (c_int, [_P, _P, _P]),
@@ -164,6 +168,7 @@ SIGNATURES = {
     "ddrl_dqn_step_timed": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P]),
     "ddrl_dqn_step_ring": (c_int, [_P, _P, _P, _P, _P, _P]),
     "ddrl_dqn_q": (c_int, [_P, _P, c_int64, _P, _P]),
+    "ddrl_dqn_act": (c_int, [_P, _P, c_int64, c_int, c_float, c_uint32, c_uint64, _P, _P, _P]),
     "ddrl_winq_create": (c_int, [POINTER(_P), c_int, c_int64, c_int32, c_int32, c_int32, c_int32]),
     "ddrl_winq_destroy": (c_int, [_P]),
     "ddrl_winq_begin": (c_int, [_P, _P, _P, _P]),

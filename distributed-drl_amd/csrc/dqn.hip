@@ -2,6 +2,8 @@
 #include <mutex>
 #include "gemm_core.h"
 #include "wide_l1.h"
+#include "policy_row.h"
+#include "dqn_select.h"
 
 // ==========================================================================================
 // Double-DQN learner (algos/dqn/actor_learner.py:19-107 on algos/dqn/core.py:40-50):
@@ -301,6 +303,87 @@ __global__ void __launch_bounds__(256) k_dqn_stage(const float *o1, const float 
     if (i < B) { acts[i] = ac[i]; rew[i] = r[i]; done[i] = d[i]; }
 }
 
+// ------------------------------------------------------------------------------------------
+// The acting path (ddrl_dqn_act, ddrl_rollout_step_discrete).  The Q network obs -> h1 -> h2 -> n_actions has the shape of the SAC
+// policy network with its head columns renamed, so its forward IS k_actor_fwd (sac1_direct.h, v_mfma_f32_32x32x2_f32): the handle owns
+// an actor handle of shape (obs, ceil(A / 2) "actions", h1, h2) whose mu head holds Q columns [0, half) and whose log_std head holds
+// columns [half, A) (a zero column pads an odd A) — head row c of the partials is action c.  k_q_to_pi writes network 0 of the main
+// parameters (SQN: q1, algos/sqn/actor_learner.py:164) as that actor's flat weight vector, ddrl_actor_set_weights packs it into the
+// operand layout: eagerly at ddrl_dqn_set_weights / ddrl_dqn_import(MAIN), and in front of the next acting forward after a learner step.
+// ------------------------------------------------------------------------------------------
+struct QPiArgs {
+    const float *W1b, *W2b, *W3, *b3;   // [W1 ; b1], [W2 ; b2] (each kernel immediately followed by its bias), W3 [h2][A], b3 [A]
+    float *dst;                        // W1, b1, W2, b2, Wmu [h2][half], bmu, Wls [h2][half], bls
+    long long n01, n12;
+    int h2, A, half;
+};
+__global__ void __launch_bounds__(256) k_q_to_pi(QPiArgs a) {
+    const long long nh = (long long)a.h2 * a.half + a.half, total = a.n01 + a.n12 + 2 * nh;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        float v;
+        if (i < a.n01) v = a.W1b[i];
+        else if (i < a.n01 + a.n12) v = a.W2b[i - a.n01];
+        else {
+            long long e = i - a.n01 - a.n12;
+            const int hi = e >= nh ? 1 : 0;
+            e -= hi * nh;
+            const int c0 = hi * a.half;
+            if (e < (long long)a.h2 * a.half) {
+                const long long j = e / a.half;
+                const int c = c0 + (int)(e - j * a.half);
+                v = c < a.A ? a.W3[j * a.A + c] : 0.f;
+            } else {
+                const int c = c0 + (int)(e - (long long)a.h2 * a.half);
+                v = c < a.A ? a.b3[c] : 0.f;
+            }
+        }
+        a.dst[i] = v;
+    }
+}
+
+// get_action for n rows: one lane per row.  The Q row comes out of the head partials of the acting forward (hp != nullptr; summation order:
+// ddrl_sel::q_row_from_partials) or, for shapes outside that forward's envelope, out of the generic head's Q image (rows of ldq floats,
+// bias included); the selection is ddrl_sel::select_row either way — the device function the fused rollout step runs.
+struct SelArgs {
+    const float *hp, *b_lo, *b_hi;
+    const float *Q;
+    long long n, hp_rows;            // rows of the call, rows of the forward launch (n rounded up to whole 32-row tiles)
+    int ldq, A, half, nt2, sqn, deterministic;
+    float greedy_prob, alpha;
+    uint32_t seed;
+    unsigned long long ctr;
+    float *act_out, *q_out;
+};
+template <int NH>
+__global__ void __launch_bounds__(64) k_dqn_select(SelArgs a) {
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= a.n) return;
+    if (a.hp) {
+        float q[ddrl_sel::MAXQ];
+        ddrl_sel::q_row_from_partials<NH>(a.hp, a.hp_rows, i, a.A, a.half, a.nt2, a.b_lo, a.b_hi, q);
+        const float u0 = ddrl_sel::uniform_at(a.seed, a.ctr + 2ull * (unsigned long long)i);
+        const float u1 = ddrl_sel::uniform_at(a.seed, a.ctr + 2ull * (unsigned long long)i + 1ull);
+        a.act_out[i] = (float)ddrl_sel::select_row(q, a.A, a.sqn, a.deterministic, a.greedy_prob, a.alpha, u0, u1);
+        if (a.q_out) {
+#pragma unroll
+            for (int c = 0; c < ddrl_sel::MAXQ; ++c)
+                if (c < a.A) a.q_out[i * a.A + c] = q[c];
+        }
+        return;
+    }
+    // up to HEAD_MAXA actions, out of the generic head's Q image
+    const float *row = a.Q + i * a.ldq;
+    const float u0 = ddrl_sel::uniform_at(a.seed, a.ctr + 2ull * (unsigned long long)i);
+    const float u1 = ddrl_sel::uniform_at(a.seed, a.ctr + 2ull * (unsigned long long)i + 1ull);
+    float q[HEAD_MAXA];
+#pragma unroll
+    for (int c = 0; c < HEAD_MAXA; ++c) q[c] = row[c < a.A ? c : 0];
+    const int pick = ddrl_sel::select_row(q, a.A, a.sqn, a.deterministic, a.greedy_prob, a.alpha, u0, u1);
+    a.act_out[i] = (float)pick;
+    if (a.q_out)
+        for (int c = 0; c < a.A; ++c) a.q_out[i * a.A + c] = row[c];
+}
+
 }  // namespace
 
 struct ddrl_dqn {
@@ -333,6 +416,13 @@ struct ddrl_dqn {
     int *sk_flag;
     int *sk_err_h;                   // pinned, device-visible: k_wide_sk's sticky "combine timed out" word
     long long steps_launched, poison_after;   // DDRL_SK_POISON_AFTER=n (tests): the host raises the word itself behind the n-th step's launches
+    // acting path (ddrl_dqn_act / ddrl_rollout_step_discrete): nullptr when the shape is outside k_actor_fwd's envelope
+    ddrl_actor_t *act_fwd, *act_sel; // two sets of observation rows / head partials: the fused rollout step's envs, ddrl_dqn_act's rows
+    const char *act_why;             // ... and what keeps it outside
+    float *pi_flat;                  // network 0 of main as the actor's flat weight vector (k_q_to_pi)
+    long long act_rows;              // rows of either set: batch rounded up to whole 32-row tiles
+    int half;                        // ceil(n_actions / 2): Q columns per head of the actor
+    bool pack_stale;                 // a learner step moved main since the last pack
     bool poisoned;                   // that word was seen: the parameters carry at least one step from a wrong layer-1 gradient.  Every step / export
                                      // fails until fresh parameters arrive (set_weights, import of MAIN), so they cannot be pushed or checkpointed
 };
@@ -363,6 +453,8 @@ int ddrl_dqn_destroy(ddrl_dqn_t *h) {
     if (!h) return DDRL_OK;
     ddrl::DeviceGuard g(h->device);
     (void)hipFree(h->slab);
+    if (h->act_fwd) (void)ddrl_actor_destroy(h->act_fwd);
+    if (h->act_sel) (void)ddrl_actor_destroy(h->act_sel);
     (void)hipFree(h->sk_frags_d); (void)hipFree(h->sk_slab); (void)hipFree(h->sk_flag);
     if (h->sk_err_h) (void)hipHostFree(h->sk_err_h);
     delete h;
@@ -416,6 +508,8 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
     ALLOC(H1, (size_t)5 * B * h->ldh1); ALLOC(H2, (size_t)5 * B * h->ldh2); ALLOC(Q, (size_t)5 * B * h->ldq); ALLOC(dQ, (size_t)2 * B * h->ldq);
     ALLOC(dZ2, (size_t)2 * B * h2); ALLOC(dZ1, (size_t)2 * B * h1); ALLOC(loss, 4); ALLOC(qsel, B);
     ALLOC(hpart, (size_t)(B + HEAD_ROWS - 1) / HEAD_ROWS + 64);
+    h->half = (A + 1) / 2;
+    ALLOC(pi_flat, (size_t)o * h1 + h1 + (size_t)h1 * h2 + h2 + 2 * ((size_t)h2 * h->half + h->half) + 64);
     float *ring_idx_f = nullptr;
     items.push_back(Item{&ring_idx_f, reserve((size_t)2 * B + 64)});
     h->wide = wide_applies(o, h1);
@@ -495,6 +589,7 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
         }
     }
     if (h->wide) { h->wf.part = h->wpart; h->wf.consts = h->wconsts; h->wf.a_rows = B; h->wf.ldo = h->ldh1; }
+    h->act_fwd = h->act_sel = nullptr; h->act_why = nullptr; h->pack_stale = true; h->act_rows = ((long long)B + 31) & ~31ll;
     h->sk_on = false; h->sk_frags_d = nullptr; h->sk_slab = nullptr; h->sk_flag = nullptr; h->sk_err_h = nullptr; h->poisoned = false;
     h->steps_launched = 0; h->poison_after = getenv("DDRL_SK_POISON_AFTER") ? atoll(getenv("DDRL_SK_POISON_AFTER")) : -1;
     if (h->wide && !(getenv("DDRL_WIDE_SK") && atoi(getenv("DDRL_WIDE_SK")) == 0)) {
@@ -559,8 +654,42 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
             granted[device] = need;
         }
     }
+    {   // the acting forward, where k_actor_fwd takes the shape (direct_ok of sac1.hip on (obs, half, h1, h2))
+        if (A > ddrl_sel::MAXQ) h->act_why = "n_actions > 8 (the acting forward has 8 head rows)";
+        else if (o + 1 > 13 || o + h->half > 12) h->act_why = "observations too wide for the direct-operand layer 1 (obs_dim + ceil(n_actions / 2) <= 12)";
+        else if (h1 % 4 || h2 % 4 || h1 > 512 || h2 > 512) h->act_why = "hidden sizes outside the direct-operand limits (multiples of 4, <= 512)";
+        else if (h->act_rows > 32 * 4095) h->act_why = "batch too large for the acting forward's row tiles";
+        else {
+            ddrl_sac1_config_t pc{};
+            pc.obs_dim = o; pc.act_dim = h->half; pc.hidden1 = h1; pc.hidden2 = h2; pc.batch = 32; pc.variant = DDRL_SAC1;
+            pc.alpha = 0.1; pc.gamma = cfg->gamma; pc.lr = cfg->lr; pc.polyak = cfg->polyak; pc.beta1 = cfg->beta1; pc.beta2 = cfg->beta2;
+            pc.adam_eps = cfg->adam_eps; pc.act_scale = 1.0;
+            int arc = ddrl_actor_create(&h->act_fwd, device, &pc, h->act_rows);
+            if (arc == DDRL_OK) arc = ddrl_actor_create(&h->act_sel, device, &pc, h->act_rows);
+            if (arc != DDRL_OK) { ddrl_dqn_destroy(h); return arc; }
+            if (!ddrl_actor_internal_view(h->act_fwd).ok) {
+                (void)ddrl_actor_destroy(h->act_fwd); (void)ddrl_actor_destroy(h->act_sel);
+                h->act_fwd = h->act_sel = nullptr;
+                h->act_why = "the direct-operand kernels are switched off (DDRL_SAC1_GENERIC)";
+            }
+        }
+    }
     *out = h;
     return DDRL_OK;
+}
+
+// network 0 of main -> the acting forwards' operand layout (three launches on `s`)
+static int dqn_pack_acting(ddrl_dqn *h, hipStream_t s) {
+    if (!h->act_fwd) return DDRL_OK;
+    const ddrl_dqn_config_t &c = h->cfg;
+    QPiArgs a{h->main_p + h->W1[0], h->main_p + h->W2[0], h->main_p + h->W3[0], h->main_p + h->b3[0], h->pi_flat,
+              (long long)c.obs_dim * c.hidden1 + c.hidden1, (long long)c.hidden1 * c.hidden2 + c.hidden2, c.hidden2, c.n_actions, h->half};
+    k_q_to_pi<<<128, 256, 0, s>>>(a);
+    DDRL_LAUNCH_CHECK();
+    int rc = ddrl_actor_set_weights(h->act_fwd, h->pi_flat, s);
+    if (rc == DDRL_OK) rc = ddrl_actor_set_weights(h->act_sel, h->pi_flat, s);
+    if (rc == DDRL_OK) h->pack_stale = false;
+    return rc;
 }
 
 int ddrl_dqn_set_weights(ddrl_dqn_t *h, const float *flat_main_d, void *stream) {
@@ -570,7 +699,7 @@ int ddrl_dqn_set_weights(ddrl_dqn_t *h, const float *flat_main_d, void *stream) 
     // main AND target: Learner.set_weights runs target_init (algos/dqn/actor_learner.py:99-101)
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_main_d, h->main_p, h->target_p, 1);
     DDRL_LAUNCH_CHECK();
-    return DDRL_OK;
+    return dqn_pack_acting(h, ddrl::as_stream(stream));   // eagerly: a captured acting call never replays a stale pack
 }
 
 int ddrl_dqn_wide_sk(ddrl_dqn_t *h) { return h ? (h->sk_on ? 1 : 0) : DDRL_ERR_BAD_ARG; }
@@ -597,6 +726,7 @@ int ddrl_dqn_import(ddrl_dqn_t *h, int which, const float *flat_d, void *stream)
     if (which == DDRL_SAC1_MAIN) h->poisoned = false;   // fresh main parameters (a resumed learner imports target and moments next)
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_d, buf, nullptr, 1);
     DDRL_LAUNCH_CHECK();
+    if (which == DDRL_SAC1_MAIN) return dqn_pack_acting(h, ddrl::as_stream(stream));
     return DDRL_OK;
 }
 
@@ -681,6 +811,7 @@ static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2
     STAGE_MARK();   // 8 flat Adam + polyak
 #undef STAGE_MARK
     DDRL_LAUNCH_CHECK();
+    h->pack_stale = true;   // main moved: the next acting forward repacks its operand copy first
     if (++h->steps_launched == h->poison_after && h->sk_on && h->sk_err_h) *h->sk_err_h = 1;   // (test hook: what a timed-out combine stores)
     if (q_d) DDRL_HIP_CHECK(hipMemcpy2DAsync(q_d, (size_t)h->cfg.n_actions * sizeof(float), h->Q, (size_t)h->ldq * sizeof(float),
                                              (size_t)h->cfg.n_actions * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s));
@@ -773,4 +904,66 @@ int ddrl_dqn_q(ddrl_dqn_t *h, const float *obs_d, int64_t n, float *q_d, void *s
     return DDRL_OK;
 }
 
+int ddrl_dqn_act(ddrl_dqn_t *h, const float *obs_d, int64_t n, int mode, float greedy_prob, uint32_t seed, uint64_t ctr, float *act_d,
+                 float *q_out_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && obs_d != nullptr && act_d != nullptr, "NULL pointer");
+    DDRL_REQUIRE(n > 0 && n <= h->cfg.batch, "n outside [1, batch]");
+    DDRL_REQUIRE(mode == DDRL_ACT_SAMPLE || mode == DDRL_ACT_DETERMINISTIC, "mode must be DDRL_ACT_SAMPLE or DDRL_ACT_DETERMINISTIC");
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    const ddrl_dqn_config_t &c = h->cfg;
+    SelArgs a{};
+    a.n = n; a.A = c.n_actions; a.half = h->half; a.nt2 = (c.hidden2 + 31) / 32; a.sqn = c.variant == DDRL_SQN; a.deterministic = mode == DDRL_ACT_DETERMINISTIC;
+    a.greedy_prob = greedy_prob; a.alpha = (float)c.alpha; a.seed = seed; a.ctr = ctr; a.act_out = act_d; a.q_out = q_out_d;
+    if (h->act_fwd) {
+        // its own set of observation rows and partials: the rollout's observations and everything a learner step reads stay as they are.
+        // The forward runs whole 32-row tiles: the rows beyond n hold an earlier call's observations (zeros at first) and are never read
+        const ddrl_actor_rollout_view v = ddrl_actor_internal_view(h->act_sel);
+        if (h->pack_stale)
+            if (const int rc = dqn_pack_acting(h, s)) return rc;
+        DDRL_HIP_CHECK(hipMemcpyAsync(v.obs, obs_d, (size_t)n * c.obs_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+        a.hp_rows = (n + 31) & ~31ll;
+        if (const int rc = ddrl_actor_internal_forward(h->act_sel, a.hp_rows, stream, 0)) return rc;
+        a.hp = v.hp; a.b_lo = v.bmu; a.b_hi = v.bls;
+        if (c.n_actions <= 4) k_dqn_select<4><<<(unsigned)((n + 63) / 64), 64, 0, s>>>(a);
+        else k_dqn_select<8><<<(unsigned)((n + 63) / 64), 64, 0, s>>>(a);
+        DDRL_LAUNCH_CHECK();
+        return DDRL_OK;
+    }
+    // outside the acting forward's envelope (wide observations, ...): ddrl_dqn_q's launches + the selection kernel on its Q image.  The staged
+    // rows, H1 / H2 / Q are scratch that every learner step rewrites before it reads them; parameters and optimizer state are not touched.
+    const int o = c.obs_dim;
+    DDRL_HIP_CHECK(hipMemcpy2DAsync(h->x1, (size_t)h->ldx * sizeof(float), obs_d, (size_t)o * sizeof(float), (size_t)o * sizeof(float), (size_t)n,
+                                    hipMemcpyDeviceToDevice, s));
+    if (h->wide) launch_wide_fwd(h->wf, s);
+    else launch_gemm(h->g_f1, s);
+    launch_gemm(h->g_f2, s);
+    launch_gemm(h->g_f3, s);
+    a.Q = h->Q; a.ldq = h->ldq;
+    k_dqn_select<4><<<(unsigned)((n + 63) / 64), 64, 0, s>>>(a);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
 }  // extern "C"
+
+// ---- internal (env.hip: ddrl_rollout_step_discrete) ---------------------------------------------------------------
+ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h) {
+    ddrl_dqn_rollout_view v{};
+    if (!h) return v;
+    v.device = h->device; v.why = h->act_why;
+    v.obs_dim = h->cfg.obs_dim; v.n_actions = h->cfg.n_actions; v.half = h->half; v.nt2 = (h->cfg.hidden2 + 31) / 32; v.batch = h->cfg.batch;
+    v.sqn = h->cfg.variant == DDRL_SQN; v.alpha = (float)h->cfg.alpha;
+    if (!h->act_fwd) return v;
+    const ddrl_actor_rollout_view av = ddrl_actor_internal_view(h->act_fwd);
+    v.ok = 1; v.obs = av.obs; v.hp = av.hp; v.b_lo = av.bmu; v.b_hi = av.bls;
+    return v;
+}
+
+int ddrl_dqn_internal_forward(ddrl_dqn_t *h, long long n, void *stream) {
+    DDRL_REQUIRE(h != nullptr && h->act_fwd != nullptr, "no acting forward");
+    ddrl::DeviceGuard g(h->device);
+    if (h->pack_stale)
+        if (const int rc = dqn_pack_acting(h, ddrl::as_stream(stream))) return rc;
+    return ddrl_actor_internal_forward(h->act_fwd, n, stream, 0);
+}

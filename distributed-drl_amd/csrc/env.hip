@@ -12,6 +12,7 @@
 #include "policy_row.h"
 #include "replay_device.h"
 #include "env_device.h"
+#include "dqn_select.h"
 
 namespace {
 
@@ -35,6 +36,8 @@ __global__ void __launch_bounds__(256) k_env_reset(float *S, long long n, uint32
     }
 }
 
+// DISCRETE: act[n] holds gym's discrete action index as float32 (ddrl_env_step_discrete), mapped through ddrl_sel::lander_action
+template <bool DISCRETE>
 __global__ void __launch_bounds__(256) k_env_step(float *S, long long n, uint32_t seed, float max_ep_len, const float *act,
                                                   float *obs2, float *rew_out, float *done_out, float *next_obs,
                                                   uint8_t *ended_out, EnvStats *stats) {
@@ -47,7 +50,9 @@ __global__ void __launch_bounds__(256) k_env_step(float *S, long long n, uint32_
         e.load(S, n, i);
         float o[8];
         bool done_env;
-        const float2 a = *reinterpret_cast<const float2 *>(act + i * 2);
+        float2 a;
+        if (DISCRETE) ddrl_sel::lander_action(act[i], a.x, a.y);
+        else a = *reinterpret_cast<const float2 *>(act + i * 2);
         const float rew = e.physics(a.x, a.y, done_env, o);
         e.eplen = e.eplen + 1.0f;                       // example/dsac.py:104
         e.epret = e.epret + rew;                        // :103
@@ -413,6 +418,118 @@ __global__ void __launch_bounds__(64) k_env_step_pi(RolloutArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Fused DISCRETE rollout step (RolloutDeviceDQN.step = num_envs iterations of worker_rollout_dqn's policy phase,
+// algos/dqn/train.py:253-274), the sibling of k_env_step_pi for the Double-DQN / SQN actors:
+//   a = agent.get_action(o)      the Q-head partials of the forward launch in front of this kernel summed in column-tile order + bias
+//                                (ddrl_sel::q_row_from_partials), one index selected per env (ddrl_sel::select_row: the device function
+//                                ddrl_dqn_act's selection kernel runs), two uniforms of the counter generator per env
+//   o2, r, d, _ = env.step(a)    the physics above on gym's discrete action table (ddrl_sel::lander_action)
+//   replay_buffer.store(o, a, r, o2, d)   into ring row (ptr + i) % capacity of a (obs1[8], obs2[8], acts, rews, done) ring, env order;
+//                                the last block to finish advances the cursor (ring_commit)
+//   o = o2 (or env.reset())      written into the forward's observation buffer for the next forward launch
+// One thread per env; no exchange between threads except the cursor ticket, and — as in k_env_step_pi, for the reason documented
+// there — no __threadfence() in front of it: nothing but the ticket crosses workgroups inside this launch.
+// ------------------------------------------------------------------------------------------
+struct RolloutQArgs {
+    float *S;
+    long long n;
+    uint32_t seed;
+    float max_ep_len;
+    EnvStats *stats;
+    float *obs;            // [n][8] in / out (the forward's buffer)
+    const float *hp;       // [8][n][16]
+    const float *b_lo, *b_hi;
+    int A, half, nt2, sqn, deterministic;
+    float greedy_prob, alpha;
+    uint32_t noise_seed;
+    unsigned long long noise_ctr;
+    ddrl_replay_dev::RingState *rs;
+    ddrl_replay_dev::RingPtrs ring;
+    float *act_out, *q_out, *next_obs_out;   // optional mirrors: [n], [n][A], [n][8]
+};
+template <int NH>
+__global__ void __launch_bounds__(64) k_env_step_q(RolloutQArgs a) {
+    __shared__ long long s_ptr;
+    if (threadIdx.x == 0) s_ptr = a.rs->ptr;
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, n = a.n;
+    long long n_end = 0, len_end = 0;
+    double ret_end = 0.0;
+    if (i < n) {
+        float q[ddrl_sel::MAXQ];
+        ddrl_sel::q_row_from_partials<NH>(a.hp, n, i, a.A, a.half, a.nt2, a.b_lo, a.b_hi, q);
+        float o1[8];
+        {
+            const float4 *p = reinterpret_cast<const float4 *>(a.obs + i * 8);
+            const float4 u = p[0], v = p[1];
+            o1[0] = u.x; o1[1] = u.y; o1[2] = u.z; o1[3] = u.w; o1[4] = v.x; o1[5] = v.y; o1[6] = v.z; o1[7] = v.w;
+        }
+        Env e;
+        e.seed = a.seed; e.id = (uint32_t)i;
+        e.load(a.S, n, i);
+        const float u0 = ddrl_sel::uniform_at(a.noise_seed, a.noise_ctr + 2ull * (unsigned long long)i);
+        const float u1 = ddrl_sel::uniform_at(a.noise_seed, a.noise_ctr + 2ull * (unsigned long long)i + 1ull);
+        const float act = (float)ddrl_sel::select_row(q, a.A, a.sqn, a.deterministic, a.greedy_prob, a.alpha, u0, u1);
+        float a0, a1;
+        ddrl_sel::lander_action(act, a0, a1);
+        // ---- env.step + the worker's bookkeeping (as k_env_step)
+        float o[8];
+        bool done_env;
+        const float rew = e.physics(a0, a1, done_env, o);
+        e.eplen = e.eplen + 1.0f;
+        e.epret = e.epret + rew;
+        const bool limit = e.eplen >= a.max_ep_len;
+        const float done_store = limit ? 0.0f : (done_env ? 1.0f : 0.0f);
+        const bool ended = done_env || limit;
+        // ---- replay_buffer.store(o, a, r, o2, d)
+        const long long cap = a.ring.capacity;
+        if (i >= n - cap) {  // rows that a later store of the same batch would overwrite are skipped (n > capacity)
+            const long long row = (s_ptr + i) % cap;
+            float4 *p1 = reinterpret_cast<float4 *>(a.ring.a[0] + row * 8), *p2 = reinterpret_cast<float4 *>(a.ring.a[1] + row * 8);
+            p1[0] = make_float4(o1[0], o1[1], o1[2], o1[3]); p1[1] = make_float4(o1[4], o1[5], o1[6], o1[7]);
+            p2[0] = make_float4(o[0], o[1], o[2], o[3]); p2[1] = make_float4(o[4], o[5], o[6], o[7]);
+            a.ring.a[2][row] = act;
+            a.ring.a[3][row] = rew;
+            a.ring.a[4][row] = done_store;
+        }
+        if (a.act_out) a.act_out[i] = act;
+        if (a.q_out) {
+#pragma unroll
+            for (int c = 0; c < ddrl_sel::MAXQ; ++c)
+                if (c < a.A) a.q_out[i * a.A + c] = q[c];
+        }
+        if (ended) {
+            n_end = 1; len_end = (long long)e.eplen; ret_end = (double)e.epret;
+            e.epi = e.epi + 1.0f;
+            e.reset(o);
+        }
+        {
+            float4 *p = reinterpret_cast<float4 *>(a.obs + i * 8);
+            p[0] = make_float4(o[0], o[1], o[2], o[3]);
+            p[1] = make_float4(o[4], o[5], o[6], o[7]);
+            if (a.next_obs_out) {
+                float4 *qn = reinterpret_cast<float4 *>(a.next_obs_out + i * 8);
+                qn[0] = p[0]; qn[1] = p[1];
+            }
+        }
+        e.store(a.S, n, i);
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        n_end += __shfl_xor(n_end, off);
+        len_end += __shfl_xor(len_end, off);
+        ret_end += __shfl_xor(ret_end, off);
+    }
+    if ((threadIdx.x & 63) == 0 && n_end > 0) {
+        atomicAdd((unsigned long long *)&a.stats->episodes, (unsigned long long)n_end);
+        atomicAdd((unsigned long long *)&a.stats->len_sum, (unsigned long long)len_end);
+        atomicAdd(&a.stats->ret_sum, ret_end);
+    }
+    // the last block to finish advances the ring cursor (every block has read rs->ptr before its ticket)
+    __syncthreads();
+    if (threadIdx.x == 0) (void)ddrl_replay_dev::ring_commit(a.rs, a.ring, s_ptr, n);
+}
+
 __global__ void __launch_bounds__(256) k_env_obs(float *S, long long n, uint32_t seed, float *obs_out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -481,8 +598,18 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
                   uint8_t *ended_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && act_d != nullptr, "NULL handle or action pointer");
     ddrl::DeviceGuard g(h->device);
-    k_env_step<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
+    k_env_step<false><<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
         h->S, h->n, h->seed, (float)h->max_ep_len, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d,
+                           uint8_t *ended_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && act_idx_d != nullptr, "NULL handle or action pointer");
+    ddrl::DeviceGuard g(h->device);
+    k_env_step<true><<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
+        h->S, h->n, h->seed, (float)h->max_ep_len, act_idx_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats);
     DDRL_LAUNCH_CHECK();
     return DDRL_OK;
 }
@@ -552,6 +679,62 @@ int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay,
         else k_env_step_pi<8><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
         DDRL_LAUNCH_CHECK();
         if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
+        ddrl_replay_note_store(replay, h->n);
+    }
+    return DDRL_OK;
+}
+
+// the discrete fused step's envelope: 0, or the status with the reason in ddrl_last_error()
+static int rollout_discrete_check(ddrl_env_t *h, const ddrl_dqn_rollout_view &v) {
+    if (!v.ok) {
+        ddrl::set_error("fused discrete rollout step: %s; use ddrl_dqn_act + ddrl_env_step_discrete + ddrl_replay_store", v.why ? v.why : "no acting forward");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (v.obs_dim != 8 || v.n_actions > ddrl_sel::MAXQ || h->n % 32 != 0 || h->n > v.batch) {
+        ddrl::set_error("fused discrete rollout step needs obs_dim 8, n_actions <= 8 and n_envs a multiple of 32 within the handle's batch "
+                        "(obs_dim %d, n_actions %d, n_envs %lld, batch %d); use ddrl_dqn_act + ddrl_env_step_discrete + ddrl_replay_store",
+                        v.obs_dim, v.n_actions, h->n, v.batch);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    DDRL_REQUIRE(v.device == h->device, "the learner / actor handle lives on another device than the envs");
+    return DDRL_OK;
+}
+
+int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream) {
+    DDRL_REQUIRE(h != nullptr && dqn != nullptr, "NULL handle");
+    const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
+    if (const int rc = rollout_discrete_check(h, v)) return rc;
+    ddrl::DeviceGuard g(h->device);
+    k_env_obs<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, v.obs);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
+                               uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && dqn != nullptr && replay != nullptr, "NULL handle");
+    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    DDRL_REQUIRE(mode == DDRL_ACT_SAMPLE || mode == DDRL_ACT_DETERMINISTIC, "mode must be DDRL_ACT_SAMPLE or DDRL_ACT_DETERMINISTIC");
+    const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
+    if (const int rc = rollout_discrete_check(h, v)) return rc;
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    DDRL_REQUIRE(rv.device == h->device, "the replay ring lives on another device than the envs");
+    DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == 8 && rv.ring.w[1] == 8 && rv.ring.w[2] == 1 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
+                 "replay row shape must be (obs1[8], obs2[8], acts, rews, done)");
+    DDRL_REQUIRE(!rv.ring.kind[0] && !rv.ring.kind[1], "the fused rollout step stores into float32 rings only (not a compact uint8 ring)");
+    ddrl::DeviceGuard g(h->device);
+    RolloutQArgs a{};
+    a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
+    a.obs = v.obs; a.hp = v.hp; a.b_lo = v.b_lo; a.b_hi = v.b_hi; a.A = v.n_actions; a.half = v.half; a.nt2 = v.nt2; a.sqn = v.sqn;
+    a.deterministic = mode == DDRL_ACT_DETERMINISTIC; a.greedy_prob = greedy_prob; a.alpha = v.alpha; a.noise_seed = seed;
+    a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.q_out = q_out_d; a.next_obs_out = next_obs_out_d;
+    for (int k = 0; k < n_steps; ++k) {
+        const int rc = ddrl_dqn_internal_forward(dqn, h->n, stream);
+        if (rc != DDRL_OK) return rc;
+        a.noise_ctr = ctr + (uint64_t)k * 2ull * (uint64_t)h->n;
+        if (v.n_actions <= 4) k_env_step_q<4><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
+        else k_env_step_q<8><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
+        DDRL_LAUNCH_CHECK();
         ddrl_replay_note_store(replay, h->n);
     }
     return DDRL_OK;

@@ -1,6 +1,7 @@
 """Double-DQN learner / actor of the multi-node driver (algos/dqn/actor_learner.py:19-107, 175-201;
 network algos/dqn/core.py:40-50) on the MI355X: `Learner(opt, job)` with set_weights / get_weights /
-train(batch, cnt), `Actor(opt, job)` with get_action(o, deterministic) — same names and argument meaning.
+train(batch, cnt), `Actor(opt, job)` with get_action(o, deterministic) — same names and argument meaning — and the batched
+get_actions(obs) of the device rollout (workers.RolloutDeviceDQN).
 `opt` carries obs_dim, act_dim (number of discrete actions), hidden_size, gamma, lr, polyak, batch_size, seed
 (algos/dqn/hyperparams.py:26-60)."""
 import ctypes
@@ -212,13 +213,46 @@ class Learner:
         return q
 
 
+def _get_actions(self, obs, out=None, q_out=None, deterministic=False):
+    """get_action for every row of obs[n, obs_dim] (1 <= n <= max_rows) in one stream-ordered call (ddrl_dqn_act): the main network's Q
+    rows (SQN: q1) from the policy forward's MFMA kernel where the shape fits it, then one action per row — the index as float32, the
+    form the replay ring stores — into `out[n]`; `q_out[n, act_dim]` (optional) receives the Q rows the selection saw.  Row i draws
+    its two uniforms from the object's counter stream (self._noise_seed, self._noise_ctr + 2 i [+ 1]), which advances by 2 n per call.
+    Double-DQN: argmax with probability self.greedy_prob (0.97, actor_learner.py:194-201), a uniform random action otherwise;
+    SQN: one draw from softmax(q1 / alpha) (core.py:30-42); deterministic=True: the first index of the row maximum.  No host
+    synchronisation; nothing a later train() reads or continues from is touched."""
+    obs = self._dev(obs, (-1, self.cfg.obs_dim))
+    n = int(obs.shape[0])
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= n
+    assert q_out is None or (q_out.is_cuda and q_out.is_contiguous() and q_out.dtype == torch.float32 and q_out.numel() >= n * self.cfg.n_actions)
+    mode = _lib.DDRL_ACT_DETERMINISTIC if deterministic else _lib.DDRL_ACT_SAMPLE
+    _lib.check(self._lib.ddrl_dqn_act(self._h, _lib.dptr(obs), n, mode, float(self.greedy_prob), self._noise_seed, self._noise_ctr,
+                                      _lib.dptr(out), _lib.dptr(q_out), _lib.stream_ptr()))
+    self._noise_ctr += 2 * n
+    return out
+
+
+def _noise_stream(opt, job, index=0):
+    """(seed, counter) of an actor's uniform stream — the recipe agent.Actor uses for its normals."""
+    import zlib
+    return (int(getattr(opt, "seed", 0)) * 2654435761 + zlib.crc32(str(job).encode()) + 97 * int(index)) & 0xFFFFFFFF, 0
+
+
 class Actor(Learner):
     """algos/dqn/actor_learner.py:152-201: the q network alone; get_action(o) = argmax q with probability 0.97,
     a uniform random action otherwise (actor_learner.py:193-201; np.random there, a seeded RandomState here)."""
 
-    def __init__(self, opt, job="worker", max_rows=1):
+    greedy_prob = 0.97
+
+    def __init__(self, opt, job="worker", max_rows=1, index=0):
         super().__init__(opt, job, batch=max_rows)
         self._rs = np.random.RandomState(getattr(opt, "seed", 0))
+        self.max_rows = int(max_rows)
+        self._noise_seed, self._noise_ctr = _noise_stream(opt, job, index)
+
+    get_actions = _get_actions
 
     def get_action(self, o):
         if self._rs.uniform() < 0.97:
@@ -269,9 +303,15 @@ class ActorSQN(LearnerSQN):
     """algos/sqn/actor_learner.py:134-201: get_action(o, deterministic) = argmax of / a sample from
     softmax(q1(o) / alpha) (core.py:30-42; tf.random.multinomial there, a seeded RandomState here)."""
 
-    def __init__(self, opt, job="worker", max_rows=1):
+    greedy_prob = 0.97   # (unused by the SQN rules; ddrl_dqn_act takes it for both variants)
+
+    def __init__(self, opt, job="worker", max_rows=1, index=0):
         super().__init__(opt, job, batch=max_rows)
         self._rs = np.random.RandomState(getattr(opt, "seed", 0))
+        self.max_rows = int(max_rows)
+        self._noise_seed, self._noise_ctr = _noise_stream(opt, job, index)
+
+    get_actions = _get_actions
 
     def get_action(self, o, deterministic=False):
         q = self._q_row(o).astype(np.float64)

@@ -89,6 +89,33 @@ class VecLunarLander:
         _lib.check(self._lib.ddrl_env_set_state(self._h, _lib.dptr(s), _lib.stream_ptr()))
 
 
+class VecLunarLanderDiscrete(VecLunarLander):
+    """The same n landers behind gym's discrete LunarLander-v2 action table (ddrl_env_step_discrete): 0 noop, 1 left engine,
+    2 main engine, 3 right engine — under the continuous step's clip rules exactly gym's discrete powers, so no new dynamics.  The env
+    is this project's own one-body lander (see the module header), the table is gym's.  Actions are indices as float32 [n], the
+    form the DQN replay ring stores."""
+
+    act_dim = 4
+
+    def step(self, idx):
+        """env.step(a) for every env on the action table; outputs and bookkeeping of VecLunarLander.step."""
+        idx = idx.to(device=self.device, dtype=torch.float32).contiguous()
+        assert idx.numel() == self.n
+        _lib.check(self._lib.ddrl_env_step_discrete(self._h, _lib.dptr(idx), _lib.dptr(self.obs2), _lib.dptr(self.rew),
+                                                    _lib.dptr(self.done), _lib.dptr(self.obs), _lib.dptr(self.ended), _lib.stream_ptr()))
+        return self.obs2, self.rew, self.done, self.obs, self.ended
+
+    def step_wrapped(self, *a, **kw):
+        raise NotImplementedError("the SAC1 wrapper acts on continuous actions: VecLunarLander.step_wrapped")
+
+    def sample_actions(self, out=None):
+        """env.action_space.sample() for every env: floor of U[0, 4) from the counter generator."""
+        out = out if out is not None else torch.empty(self.n, dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.ddrl_uniform_fill(_lib.dptr(out), self.n, 0.0, 4.0, self.seed ^ 0x5EED5EED, self._sample_ctr, _lib.stream_ptr()))
+        self._sample_ctr += self.n
+        return torch.floor_(out)
+
+
 class _ActionSpace:
     def __init__(self, env):
         self._env = env
@@ -124,6 +151,32 @@ class LunarLander:
     def step(self, a):
         act = torch.as_tensor(np.asarray(a, np.float32).reshape(1, 2))
         o2, r, d, _, ended = self._vec.step(act)
+        ended = bool(ended[0].item())
+        self._fresh = ended
+        return o2[0].cpu().numpy().astype(np.float64), float(r[0].item()), ended, {}
+
+
+class _DiscreteActionSpace:
+    n, shape = 4, ()
+
+    def __init__(self, env):
+        self._env = env
+
+    def sample(self):
+        return int(self._env._vec.sample_actions()[0].item())
+
+
+class LunarLanderDiscrete(LunarLander):
+    """One discrete-action environment with the gym call shape (env.make("LunarLander-v2")): step(a) takes the action index."""
+
+    def __init__(self, seed=0, max_ep_len=1000):
+        self._vec = VecLunarLanderDiscrete(1, seed=seed, max_ep_len=max_ep_len)
+        self.action_space = _DiscreteActionSpace(self)
+        self.observation_space = _ObsSpace()
+        self._fresh = True
+
+    def step(self, a):
+        o2, r, d, _, ended = self._vec.step(torch.full((1,), float(int(a)), dtype=torch.float32))
         ended = bool(ended[0].item())
         self._fresh = ended
         return o2[0].cpu().numpy().astype(np.float64), float(r[0].item()), ended, {}
@@ -201,8 +254,10 @@ class Wrapper(object):
 
 
 def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
-    """gym.make stand-in (example/dsac.py:78).  on_device=True: the test-env marker whose episodes `Actor.test` /
+    """gym.make stand-in (example/dsac.py:78).  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
     `Model.test_agent` run as one launch (DeviceLunarLander)."""
+    if env_name == "LunarLander-v2" and not on_device:   # gym's discrete action table on the same lander (action_space.n == 4)
+        return LunarLanderDiscrete(**kw)
     if "LunarLander" not in env_name:
         raise ValueError("only the LunarLanderContinuous-v2 stand-in is built (SURVEY §8(a) A7): %r" % env_name)
     return DeviceLunarLander(**kw) if on_device else LunarLander(**kw)

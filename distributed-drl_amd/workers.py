@@ -697,6 +697,91 @@ class RolloutDevice:
             self.pull()
 
 
+class RolloutDeviceDQN:
+    """The vectorised rollout worker of the discrete learners (worker_rollout_dqn's loop, algos/dqn/train.py:253-274, for
+    `opt.num_envs` envs in lock step): a VecLunarLanderDiscrete — this project's own one-body lander behind gym's discrete action
+    table — one dqn.Actor / ActorSQN (`opt.variant` "sqn" or `opt.make_actor`; default Double-DQN), a device replay ring
+    (ReplayBufferDQN) and a ParameterServer.  `t` counts this worker's transitions (the reference's gate is on actor_steps,
+    train.py:255).  step(): random actions while t <= start_steps, afterwards ONE Q-forward launch + ONE
+    launch that selects, steps the physics and appends to the ring (ddrl_rollout_step_discrete); shapes outside its envelope run
+    get_actions + env.step + store_batch.  Works with TrainDeviceDQN under ActorLearnerLoop as RolloutDevice does with TrainDevice.
+
+    Weight adoption is at vector-step boundaries only (RolloutDevice's adopt="step"): pull() swaps the weights of every env at
+    once — never staler than the reference's pull at each episode start, not identical to it.  The per-episode version store of
+    RolloutDevice is out of scope here."""
+
+    def __init__(self, ps, replay_buffer, opt, worker_index=0):
+        import torch
+        from . import dqn
+        from .env import VecLunarLanderDiscrete
+        self.ps, self.rb, self.opt = ps, replay_buffer, opt
+        self.env = VecLunarLanderDiscrete(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len)
+        make = getattr(opt, "make_actor", None)
+        if make is None:
+            cls = dqn.ActorSQN if str(getattr(opt, "variant", "ddqn")).lower() == "sqn" else dqn.Actor
+            make = lambda o_, **kw: cls(o_, job="worker", **kw)
+        self.actor = make(opt, max_rows=opt.num_envs, index=worker_index)
+        self.keys = list(self.actor.keys)
+        self.version = -1
+        self.t = 0
+        self.o = torch.empty_like(self.env.obs)
+        self.act = torch.empty(opt.num_envs, dtype=torch.float32, device=self.env.device)
+        self._fused = None if getattr(opt, "fused_rollout", True) else False
+        self._fused_live = False
+        self.auto_pull = True
+        self.pull()
+
+    def pull(self):
+        """ps.pull(keys) + agent.set_weights when the server has something newer."""
+        if self.ps is None or self.ps.version == self.version:
+            return False
+        self.version = self.ps.version
+        self.actor.set_weights(self.keys, self.ps.pull_device(self.keys))
+        return True
+
+    def _fused_ready(self):
+        """Decided once: ddrl_rollout_begin_discrete refuses a shape outside the fused envelope, and the ring must be the DQN layout."""
+        if self._fused is None:
+            from . import _lib
+            from .replay import ReplayBuffer
+            ok = isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
+            if ok:
+                ok = self.actor._lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr()) == 0
+            self._fused, self._fused_live = ok, ok
+        return self._fused
+
+    def step(self, n_steps=1):
+        """One vector step = num_envs iterations of the reference loop; n_steps > 1 issues that many back to back on the weights held."""
+        from . import _lib
+        env, a = self.env, self.actor
+        if self.t > self.opt.start_steps and self._fused_ready():
+            if not self._fused_live:   # the unfused path has stepped the envs since: refresh the forward's observation rows
+                _lib.check(a._lib.ddrl_rollout_begin_discrete(env._h, a._h, _lib.stream_ptr()))
+                self._fused_live = True
+            _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, int(n_steps), _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
+                                                         a._noise_seed, a._noise_ctr, _lib.dptr(self.act), None, _lib.dptr(env.obs), _lib.stream_ptr()))
+            a._noise_ctr += int(n_steps) * 2 * env.n
+            self.t += int(n_steps) * env.n
+            if self.auto_pull:
+                self.pull()
+            return
+        if n_steps > 1:
+            for _ in range(int(n_steps)):
+                self.step()
+            return
+        self._fused_live = False
+        self.o.copy_(env.obs)
+        if self.t > self.opt.start_steps:
+            a.get_actions(self.o, out=self.act)
+        else:
+            env.sample_actions(out=self.act)
+        o2, r, d, _, _ended = env.step(self.act)
+        self.rb.store_batch(self.o, self.act, r, o2, d)
+        self.t += env.n
+        if self.auto_pull:
+            self.pull()
+
+
 class WindowQueue:
     """Per-env o_queue / a_r_d_queue of algos/sac1/sac_ray.py:192-248 on the device (csrc/winq.hip)."""
 

@@ -535,6 +535,14 @@ int ddrl_actor_act_versioned(ddrl_actor_t *h, const float *obs_d, const float *e
 int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream);
 int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed,
                       uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream);
+/* ddrl_env_step on gym's discrete LunarLander-v2 action table — the env the discrete drivers step where the reference's own
+ * (algos/trading_env.py, a proprietary game.so) cannot be had; worker_rollout_dqn's `env.step(a)`, algos/dqn/train.py:262.
+ * act_idx_d[n] holds the index as float32 (the form the DQN ring stores acts in); the index is (int)value clamped to [0, 3]:
+ *   0 noop (0, 0), 1 left engine (0, -1), 2 main engine (1, 0), 3 right engine (0, +1)
+ * which, under the clip rules of the continuous step, are gym's discrete powers exactly (m_power, s_power in {0, 1}, direction =
+ * action - 2).  Outputs and bookkeeping are ddrl_env_step's. */
+int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d, float *rew_d, float *done_d,
+                           float *next_obs_d, uint8_t *ended_d, void *stream);
 /* Episode statistics accumulated on device since the last call: number of finished episodes,
  * sum of their returns and lengths.  Synchronises `stream`; resets the accumulators. Host outs. */
 int ddrl_env_stats(ddrl_env_t *h, int64_t *episodes_h, double *ret_sum_h, int64_t *len_sum_h,
@@ -606,6 +614,38 @@ int ddrl_dqn_step_timed(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d,
                         const float *done_d, int reps, float *stage_ms_h, void *stream);
 /* self.q of the main network (SQN: q1) for n <= batch observations (Actor.get_action, actor_learner.py:193-198). */
 int ddrl_dqn_q(ddrl_dqn_t *h, const float *obs_d, int64_t n, float *q_d, void *stream);
+/* Actor.get_action for n rows in one stream-ordered call (1 <= n <= cfg.batch; no host synchronisation, no allocation): the Q forward of
+ * the main network (SQN: q1 only, algos/sqn/actor_learner.py:164, core.py:63), then one action per row into act_d[n] (the index as
+ * float32); q_out_d[n, n_actions] (nullable) receives the Q rows the selection saw.  Row i owns two uniforms of the counter generator,
+ * u0 = U(seed, ctr + 2i) and u1 = U(seed, ctr + 2i + 1) — the elements ddrl_uniform_fill(lo = 0, hi = 1) yields:
+ *   Double-DQN (algos/dqn/actor_learner.py:194-201)  u0 < greedy_prob (0.97 there): the first index of the row maximum (np.argmax);
+ *                                                    otherwise min((int)floorf(u1 * n_actions), n_actions - 1)
+ *   SQN, DDRL_ACT_DETERMINISTIC                      the first index of the maximum
+ *   SQN, DDRL_ACT_SAMPLE (algos/sqn/core.py:30-42)   inverse CDF in float32: p_k = expf((q_k - max q) / alpha), total and cumulative
+ *                                                    sums in index order, the smallest k with u0 * total < cum_k, else the last index
+ * (DDRL_ACT_DETERMINISTIC on a Double-DQN handle: the maximum, no coin flip.)  u1 is consumed in both variants: a caller advances its
+ * counter by 2n.  Main, target, Adam state and everything a later ddrl_dqn_step reads or continues from are left unchanged.  Shapes the
+ * policy forward's MFMA kernel takes (obs_dim + ceil(n_actions / 2) <= 12, n_actions <= 8, hidden sizes multiples of 4 and <= 512) run it
+ * on a copy of the Q weights in its operand layout — packed at ddrl_dqn_set_weights / ddrl_dqn_import(MAIN), and again in front of the
+ * first acting call after a learner step (re-capture a graph that acts on a stepping handle); every other shape ddrl_dqn_create accepts
+ * runs ddrl_dqn_q's launches plus the selection kernel. */
+#define DDRL_ACT_SAMPLE 0
+#define DDRL_ACT_DETERMINISTIC 1
+int ddrl_dqn_act(ddrl_dqn_t *h, const float *obs_d, int64_t n, int mode, float greedy_prob, uint32_t seed, uint64_t ctr,
+                 float *act_d, float *q_out_d, void *stream);
+/* RolloutDeviceDQN.step fused: ONE vector step of worker_rollout_dqn's policy phase (algos/dqn/train.py:253-274) for all n envs, in two
+ * launches with no host work in between: the Q forward of `dqn`'s main network (SQN: q1) on the observations the handle holds, then
+ * one launch that selects an action per env (the rules and the two uniforms per env of ddrl_dqn_act: step k of n_steps draws from
+ * ctr + k*2n), steps the physics on the discrete table above, stores (o, a, r, o2, d) in env order into `replay` — a
+ * (obs1[8], obs2[8], acts, rews, done) float32 ring — and resets the ended envs.  ddrl_rollout_begin_discrete copies the envs' current
+ * observations into the handle (call it once, and again after any env step / reset issued outside this path).
+ * Envelope: obs_dim 8, n_actions <= 8, hidden sizes multiples of 4 within the direct-operand limits (<= 512), n_envs a multiple of 32
+ * and <= cfg.batch; outside it DDRL_ERR_UNSUPPORTED with the reason in ddrl_last_error() and nothing changed (the unfused sequence is
+ * ddrl_dqn_act + ddrl_env_step_discrete + ddrl_replay_store).  A ring of another layout or device: DDRL_ERR_BAD_ARG.
+ * act_out_d[n], q_out_d[n, n_actions], next_obs_out_d[n, 8]: optional mirrors of the LAST step (may be NULL). */
+int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream);
+int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
+                               uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream);
 
 /* ===================================================================================== */
 /* Rollout-side window queues of the n-step driver: per env, o_queue = deque(maxlen=Ln+1) of  */
