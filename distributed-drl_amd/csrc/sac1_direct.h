@@ -23,10 +23,13 @@
 //   k_dfwd<0>  evaluations 0-2: pi(x), pi(x2), pi_targ(x2) (layer 1 + layer 2 + head partials)                         240 tiles
 //   k_dfwd<1>  evaluations 5-7, action from the policy-head partials, + the stored-action evaluations 3-4 (q1(x,a),
 //              q2(x,a)) beside them (+ the next update's sampler workgroup)                                       240 + 160 + 1
-//   k_dg "bq"  the three Q dgrads, dZ2 generated from H2 on the fly; losses, dq; dQ/da partials; W3 snapshot              312
+//   k_dg "bq"  the Q dgrads (q2(x, a)'s column tiles split with "mid"), dZ2 generated from H2 on the fly; losses, dq;
+//              dQ/da partials; W3 snapshot                                                                                  256
 //   k_dg "mid" the policy dgrad with its A operand generated in the tile, the policy-head backward tiles (images for the
-//              wgrads), the Q layer-2 / head wgrads with Adam + polyak                                                      464
-//   k_dg "pi"  policy layer-2 / head / layer-1 wgrads, Q layer-1 wgrads, Adam + polyak, loss means + optimizer bookkeeping  190
+//              wgrads), the Q layer-2 wgrads with Adam + polyak, the rest of the q2(x, a) dgrad                             500
+//   k_dg "pi"  policy layer-2 / head / layer-1 wgrads, Q layer-1 / head wgrads, Adam + polyak, loss means + optimizer books 210
+// The forward launches also leave what only the backward ones read (H1r4, augmented input rows, generated noise): spread over the
+// column tiles of each row tile (h1_owned, side_aug_tile, side_noise_tile below), not all on column tile 0.
 
 #ifdef DDRL_STAMPS  // diagnostic builds only (tools/upd_bench.hip): per-workgroup cycle stamps of thread 0
 // the stamp buffer travels in the kernel arguments ([kernel id][1024 workgroups][16]): a __device__ pointer variable would
@@ -103,13 +106,13 @@ struct DFJob {
     float *hp;               // head partials [DFH][B][DNT]
     float *H2c4;             // [Np2/4][B][4]   (nullable)  A operand of the dgrads / relu mask of the policy head backward
     float *H2r4;             // [B/4][Lp2][4]   (nullable)  A operand of the head wgrads, relu mask of the generated Q wgrad operand
-    float *H1r4;             // [B/4][Lp1][4]   (nullable, n-tile-0 workgroups)  A operand of the W2 wgrads, relu mask of the dgrads
-    float *aug;              // [B][aug_ld] row-major [in0 | in1] rows (nullable, n-tile-0): layer-1 wgrad partial operand (policy)
-    float *xr4;              // [B/4][32][4] augmented input rows (nullable, n-tile-0): A operand of the Q layer-1 wgrads
+    float *H1r4;             // [B/4][Lp1][4]   (nullable; block b by column tile b % tiles_n: h1_owned)  A operand of the W2 wgrads, relu mask of the dgrads
+    float *aug;              // [B][aug_ld] row-major [in0 | in1] rows (nullable, column tile side_aug_tile): layer-1 wgrad partial operand (policy)
+    float *xr4;              // [B/4][32][4] augmented input rows (nullable, column tile side_aug_tile): A operand of the Q layer-1 wgrads
     int aug_ld;
     // phase 1: the policy evaluation whose sampled action is this job's second input (its parameter copy and noise item: DFArgs::pin_pack)
     const float *php;
-    int side;                // n-tile-0 workgroups: 1 -> act0, logp0, save0   2 -> act2, and logp1 from php1
+    int side;                // column tile 0: 1 -> act0, logp0, save0   2 -> act2, and logp1 from php1
 };
 struct DFArgs {
     int njobs, tiles_n, act, Lp1, Lp2, h2;
@@ -152,6 +155,33 @@ __host__ __device__ __forceinline__ int pi_bmu_off(int K, int Np, int h2, int ac
     return Kp * 16 + Kp * Np + Np + h2 * act;
 }
 __host__ __device__ __forceinline__ int pi_bls_off(int K, int Np, int h2, int act) { return ((pi_bmu_off(K, Np, h2, act) + act + 3) & ~3) + h2 * act; }
+
+// Side outputs of a row tile (what a forward launch leaves for the backward ones beside H2 and the head partials: the H1r4 image, the
+// augmented input rows, the generated noise).  Every column tile of a row tile computes the whole of that row tile's X1 from the same
+// inputs by the same instructions, so any of them can write any part with the same bits — and a launch is as long as its slowest
+// workgroup, not its mean one: with everything on column tile 0, 8 of the 240 workgroups of k_dfwd<0> (24 of 400 in k_dfwd<1>) carried
+// 13 transposes + 52 streaming stores inside their K loops and ended a third after the others.  Block b of the image is written by
+// column tile b % tiles_n (at (400, 300): 13 blocks over 10 tiles, at most two per workgroup and in different waves), the input rows
+// by the LAST column tile and the noise by the one before it where the row tile has them (the low tiles are the ones with a second
+// block when the blocks do not divide: input rows on tile 1 left 8 workgroups with two blocks AND the rows, 6.17 us against 5.7 us for
+// the rest of k_dfwd<0>); the action / log-prob rows of phase 1 stay on tile 0.
+// DDRL_SIDE_SPREAD: bit 0 the image blocks, bit 1 the input rows and the noise (0: everything on column tile 0, as before).
+#ifndef DDRL_SIDE_SPREAD
+#define DDRL_SIDE_SPREAD 3
+#endif
+__host__ __device__ __forceinline__ int side_aug_tile(int tiles_n) { return (DDRL_SIDE_SPREAD & 2) ? tiles_n - 1 : 0; }
+__host__ __device__ __forceinline__ int side_noise_tile(int tiles_n) { return (DDRL_SIDE_SPREAD & 2) ? (tiles_n > 2 ? tiles_n - 2 : tiles_n - 1) : 0; }
+// bit bi: block b0 + bi (bi < nb) of a wave's run of blocks belongs to column tile nt.  One division per wave, none per block.
+__host__ __device__ __forceinline__ int h1_owned(int b0, int nb, int nt, int tiles_n) {
+    if (!(DDRL_SIDE_SPREAD & 1)) return nt == 0 ? 15 : 0;
+    int r = b0 % tiles_n, m = 0;
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi) {
+        if (bi < nb && r == nt) m |= 1 << bi;
+        r = r + 1 == tiles_n ? 0 : r + 1;
+    }
+    return m;
+}
 
 // One 32-unit block of the K loop: layer 1 (NS MFMA steps) -> relu -> 4 * nrq layer-2 MFMA steps.
 template <int NS>
@@ -228,12 +258,13 @@ __device__ __forceinline__ void dops_load_block(DOps &o, const DSrc &s, int bi, 
     for (int rq = 0; rq < 4; ++rq) o.bq[bi][rq] = *reinterpret_cast<const float4 *>(s.W2p + ((long long)(u0 / 4 + 2 * rq + h) * s.Np + s.n0 + l31) * 4);
 }
 
-// K loop of one wave over MT row tiles that share the wave's W2 / W1 registers.  h1r4 != nullptr (n-tile-0 workgroups of
-// a differentiated evaluation): X1 also goes to memory as [row/4][unit][4] through a wave-private LDS tile (registers hold
-// row-in-lane / unit-in-register; the image wants 4 rows per float4).
+// K loop of one wave over MT row tiles that share the wave's W2 / W1 registers.  Bit bi of h1own (h1_owned; 0 unless the
+// evaluation is differentiated): X1 of block bi also goes to memory as [row/4][unit][4] through a wave-private LDS tile
+// (registers hold row-in-lane / unit-in-register; the image wants 4 rows per float4).  The test is wave-uniform and has
+// only the transpose and its stores behind it: every operand load stays in front of the branches.
 template <int NS, int MT, int PRE, class Mid>
 __device__ __forceinline__ void dkloop(DOps &o, const DSrc &src, int K, int lane, const float (&xin)[MT][7], floatx16 (&acc)[MT],
-                                       float *__restrict__ h1r4, int Lp1, int m0, float *__restrict__ tr, Mid &&mid) {
+                                       float *__restrict__ h1r4, int h1own, int Lp1, int m0, float *__restrict__ tr, Mid &&mid) {
     const int l31 = lane & 31, h = lane >> 5, b0 = src.b0, nb = src.nb;
 #pragma unroll
     for (int bi = 0; bi < 4; ++bi) {
@@ -248,7 +279,7 @@ __device__ __forceinline__ void dkloop(DOps &o, const DSrc &src, int K, int lane
             for (int tt = 0; tt < MT; ++tt) {
                 floatx16 x1;
                 dblock<NS>(o.w1[bi], xin[tt], o.bq[bi], nrq, x1, acc[tt]);
-                if (h1r4) {  // block-uniform
+                if ((h1own >> bi) & 1) {  // wave-uniform
 #pragma unroll
                     for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + l31] = x1[r];
                     wave_lds_sync();
@@ -482,18 +513,20 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
         for (int tt = 0; tt < MT; ++tt)
     #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tt][r] = 0.f;
-        float *h1r4 = (jb.H1r4 && first_n) ? jb.H1r4 : nullptr;
+        float *h1r4 = jb.H1r4;
+        const int h1own = h1r4 ? h1_owned(b0, nb, nt, a.tiles_n) : 0;
         {
-            if (ns == 4) dkloop<4, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, a.Lp1, m0, tr[w], epilogue_operands);
-            else if (ns == 5) dkloop<5, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, a.Lp1, m0, tr[w], epilogue_operands);
-            else if (ns == 6) dkloop<6, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, a.Lp1, m0, tr[w], epilogue_operands);
-            else dkloop<7, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, a.Lp1, m0, tr[w], epilogue_operands);
+            if (ns == 4) dkloop<4, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, h1own, a.Lp1, m0, tr[w], epilogue_operands);
+            else if (ns == 5) dkloop<5, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, h1own, a.Lp1, m0, tr[w], epilogue_operands);
+            else if (ns == 6) dkloop<6, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, h1own, a.Lp1, m0, tr[w], epilogue_operands);
+            else dkloop<7, MT, PRE>(ops, src, K, lane, xin, acc, h1r4, h1own, a.Lp1, m0, tr[w], epilogue_operands);
         }
 
         DST(PH, 3);
-        // ---- side outputs of the n-tile-0 workgroups (off the critical path: nothing in this launch reads them)
+        // ---- the other side outputs of the row tile, one column tile each (nothing in this launch reads them, but a workgroup that
+        // writes them ends that much later: side_aug_tile / side_noise_tile keep them apart where the row tile has the tiles)
         s_wh[tid >> 5][tid & 31] = whv;
-        if (first_n && (jb.aug || jb.xr4)) {  // augmented input rows of the layer-1 wgrads (their ones column is set once at create)
+        if (nt == side_aug_tile(a.tiles_n) && (jb.aug || jb.xr4)) {  // augmented input rows of the layer-1 wgrads (their ones column is set once at create)
             for (int idx = tid; idx < 32 * MT * D; idx += 256) {
                 const int r = idx / D, d = idx - r * D;
                 const long long row = m0 + r;
@@ -502,7 +535,7 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
                 if (jb.xr4) jb.xr4[((row >> 2) * 32 + d) * 4 + (row & 3)] = v;
             }
         }
-        if (PH == 0 && a.noise_on && ji == 0 && first_n) {
+        if (PH == 0 && a.noise_on && ji == 0 && nt == side_noise_tile(a.tiles_n)) {
             // eps_x, eps_x2, eps_t of this tile's rows; element index as in one flat [3][B*act] fill
             const unsigned long long nbase = a.opt->noise_ctr;
             const int per_row = 3 * act;

@@ -1,12 +1,74 @@
 // Dev harness: the whole SAC1 update of the direct-operand path inside a hipGraph (config-2 shape), timed, plus — in a
 // -DDDRL_STAMPS build — the per-workgroup anatomy of every launch of the LAST update (cycle stamps of thread 0 and the
-// 100 MHz real-time counter for the launch's dispatch ramp / tail).
+// 100 MHz real-time counter for the launch's dispatch ramp / tail), broken down per job of the k_dg launches and per job and side-output
+// class of the k_dfwd launches (dfwd_classes).
 // hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -mllvm -amdgpu-kernarg-preload-count=16 -mllvm -amdgpu-mfma-vgpr-form
 //       -Wno-unused-function [-DDDRL_STAMPS] tools/upd_bench.hip -o tools/upd_bench.bin
 #include "../distributed-drl_amd/csrc/sac1.hip"
 #include "../distributed-drl_amd/csrc/common.hip"
 #include "../distributed-drl_amd/csrc/replay.hip"
 #include <algorithm>
+#include <cstring>
+
+#ifdef DDRL_STAMPS
+// Per job and class of a k_dfwd launch (k = phase): which workgroups carry the side outputs of their row tile, and when they end.  The tile
+// of a workgroup is recomputed from k_dfwd's own formulas (both orders: XCD panels, and pack bit 30's dependent / stored runs); the class of
+// a tile is the set of extras it carries beside the GEMM every tile does:
+//   H  writes blocks of the H1r4 image (with their count)   X  the augmented input rows (aug / xr4)   N  the generated noise
+//   S  the action / log-prob rows (DFJob::side)             T  the second policy_row of the `two` tile   st  stored-action evaluation
+static void dfwd_classes(const ddrl_sac1_t *h, int k, const std::vector<unsigned long long> &hs, unsigned long long rmin) {
+    const DFHead &H = k == 0 ? h->fh_a[0] : h->fh_b[0];
+    const DFArgs &F = k == 0 ? h->f_a[0] : h->f_b[0];
+    const int tiles_m = H.tiles_m, tpj = H.tpj, njobs = F.njobs, tiles_n = F.tiles_n, nwg = njobs * tpj;   // (the harness runs MT = 1)
+    const int nblk = (H.K + 31) >> 5, bs = nblk >> 2, rem = nblk & 3;
+    struct Cls { char name[24]; int n; double ssum, esum, emax, csum, cmax, p[6]; };
+    for (int ji = 0; ji < njobs; ++ji) {
+        std::vector<Cls> cls;
+        for (int b = 0; b < nwg; ++b) {
+            int t; bool stored = false;
+            if (k == 1 && ((H.pack >> 30) & 1)) {
+                const int nd = 3 * tpj, x = b & 7, slot = b >> 3, qd = nd >> 3, qs = (2 * tpj) >> 3;
+                stored = slot >= qd;
+                t = stored ? nd + x * qs + (slot - qd) : x * qd + slot;
+            } else {
+                const int q = nwg >> 3, r = nwg & 7, x = b & 7;
+                t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
+            }
+            if (t / tpj != ji) continue;
+            const int nt = (t - ji * tpj) / tiles_m;
+            const DFJob &jb = F.job[ji];
+            int nh = 0;
+#ifdef DDRL_SIDE_SPREAD
+            for (int w = 0; w < 4; ++w) {
+                const int nb = bs + (w >= 4 - rem ? 1 : 0), b0 = w * bs + (w > 4 - rem ? w - (4 - rem) : 0);
+                if (jb.H1r4) nh += __builtin_popcount(h1_owned(b0, nb, nt, tiles_n));
+            }
+            const bool X = (jb.aug || jb.xr4) && nt == side_aug_tile(tiles_n), N = k == 0 && F.noise_on && ji == 0 && nt == side_noise_tile(tiles_n);
+#else   // before the side outputs were spread: everything on column tile 0
+            if (jb.H1r4 && nt == 0) nh = nblk;
+            const bool X = (jb.aug || jb.xr4) && nt == 0, N = k == 0 && F.noise_on && ji == 0 && nt == 0;
+#endif
+            const bool S = k == 1 && !stored && nt == 0 && jb.side != 0, T = k == 1 && ji == 1 && nt == 0 && F.php1 != nullptr;
+            char name[24], hb[8] = "";
+            if (nh) snprintf(hb, sizeof hb, "H%d", nh);
+            snprintf(name, sizeof name, "%s%s%s%s%s%s", stored ? "st " : "", hb, X ? "X" : "", N ? "N" : "", S ? "S" : "", T ? "T" : "");
+            if (!name[0] || !strcmp(name, "st ")) strcat(name, "rest");
+            Cls *c = nullptr;
+            for (auto &q : cls) if (!strcmp(q.name, name)) c = &q;
+            if (!c) { cls.push_back(Cls{}); c = &cls.back(); strcpy(c->name, name); }
+            const unsigned long long *p = &hs[((size_t)k * 1024 + b) * 16];
+            if (!p[15]) continue;
+            ++c->n; c->ssum += (p[14] - rmin) / 100.0;
+            const double e = (p[15] - rmin) / 100.0; c->esum += e; c->emax = std::max(c->emax, e);
+            const double cy = (double)(p[5] - p[0]); c->csum += cy; c->cmax = std::max(c->cmax, cy);
+            for (int i = 1; i < 6; ++i) if (p[i] && p[i - 1]) c->p[i] += (double)(p[i] - p[i - 1]);
+        }
+        for (auto &c : cls)
+            if (c.n) printf("      job %d %-10s: %3d wgs  start +%.2f us  end mean +%.2f max +%.2f us | cycles mean %.0f max %.0f | loads %.0f prol %.0f kloop %.0f bar %.0f epi %.0f\n", ji, c.name,
+                            c.n, c.ssum / c.n, c.esum / c.n, c.emax, c.csum / c.n, c.cmax, c.p[1] / c.n, c.p[2] / c.n, c.p[3] / c.n, c.p[4] / c.n, c.p[5] / c.n);
+    }
+}
+#endif
 
 int main(int argc, char **argv) {
     const int per_graph = argc > 1 ? atoi(argv[1]) : 50;
@@ -95,6 +157,7 @@ int main(int argc, char **argv) {
         printf(" | mean total %.0f max %llu\n", tot / nwg, lmax);
         prev_end = rmax;
         // per job of a k_dg launch: when its workgroups start / end relative to the launch's first start (100 MHz real-time counter)
+        if (k < 2) dfwd_classes(h, k, hs, rmin);
         const DGJobs *J = k == 2 ? &h->dg_bq[0] : (k == 3 ? &h->dg_mid : (k == 4 ? &h->dg_pi : nullptr));
         if (J) {
             const int nwgs = J->total_tiles;
