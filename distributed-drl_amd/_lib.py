@@ -169,6 +169,9 @@ SIGNATURES = {
     "ddrl_dqn_step_ring": (c_int, [_P, _P, _P, _P, _P, _P]),
     "ddrl_dqn_q": (c_int, [_P, _P, c_int64, _P, _P]),
     "ddrl_dqn_act": (c_int, [_P, _P, c_int64, c_int, c_float, c_uint32, c_uint64, _P, _P, _P]),
+    "ddrl_dqn_versions_enable": (c_int, [_P, c_int32, _P]),
+    "ddrl_dqn_versions_state": (c_int, [_P, _P, _P, _P]),
+    "ddrl_dqn_versions_adopt": (c_int, [_P, _P, c_int64, _P]),
     "ddrl_winq_create": (c_int, [POINTER(_P), c_int, c_int64, c_int32, c_int32, c_int32, c_int32]),
     "ddrl_winq_destroy": (c_int, [_P]),
     "ddrl_winq_begin": (c_int, [_P, _P, _P, _P]),

@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(64) k_dqn_select(SelArgs a) {
     if (i >= a.n) return;
     if (a.hp) {
         float q[ddrl_sel::MAXQ];
-        ddrl_sel::q_row_from_partials<NH>(a.hp, a.hp_rows, i, a.A, a.half, a.nt2, a.b_lo, a.b_hi, q);
+        ddrl_sel::q_row_from_partials<NH>(a.hp, a.hp_rows, i, a.A, a.half, a.nt2, a.b_lo, a.b_hi, 0ll, q);
         const float u0 = ddrl_sel::uniform_at(a.seed, a.ctr + 2ull * (unsigned long long)i);
         const float u1 = ddrl_sel::uniform_at(a.seed, a.ctr + 2ull * (unsigned long long)i + 1ull);
         a.act_out[i] = (float)ddrl_sel::select_row(q, a.A, a.sqn, a.deterministic, a.greedy_prob, a.alpha, u0, u1);
@@ -945,6 +945,33 @@ int ddrl_dqn_act(ddrl_dqn_t *h, const float *obs_d, int64_t n, int mode, float g
     return DDRL_OK;
 }
 
+// The version store of the acting forward the fused rollout step runs (act_fwd): the inner actor handle owns the slab, the slots and the
+// planning kernels.  act_sel (ddrl_dqn_act's rows) gets none: get_actions keeps acting on the newest weights.
+int ddrl_dqn_versions_enable(ddrl_dqn_t *h, int32_t n_slots, void *stream) {
+    DDRL_REQUIRE(h != nullptr, "handle is NULL");
+    if (!h->act_fwd) {
+        ddrl::set_error("ddrl_dqn_versions_enable: no acting forward to keep versions of: %s", h->act_why ? h->act_why : "shape outside the envelope");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    DDRL_REQUIRE(n_slots >= 2 && n_slots <= VER_MAX_SLOTS, "n_slots outside [2, 2048]");
+    DDRL_REQUIRE(ddrl_actor_internal_view(h->act_fwd).n_slots == 0, "version store already enabled");
+    // slot 0 = the weights held now: a learner step's pending repack comes first
+    if (const int rc = ddrl_dqn_internal_repack(h, stream)) return rc;
+    return ddrl_actor_versions_enable(h->act_fwd, n_slots, stream);
+}
+
+int ddrl_dqn_versions_state(ddrl_dqn_t *h, int32_t *slot_of_env_d, int32_t *state_h, void *stream) {
+    DDRL_REQUIRE(h != nullptr, "handle is NULL");
+    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
+    return ddrl_actor_versions_state(h->act_fwd, slot_of_env_d, state_h, stream);
+}
+
+int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, void *stream) {
+    DDRL_REQUIRE(h != nullptr, "handle is NULL");
+    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
+    return ddrl_actor_versions_adopt(h->act_fwd, ended_d, n, stream);
+}
+
 }  // extern "C"
 
 // ---- internal (env.hip: ddrl_rollout_step_discrete) ---------------------------------------------------------------
@@ -957,13 +984,20 @@ ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h) {
     if (!h->act_fwd) return v;
     const ddrl_actor_rollout_view av = ddrl_actor_internal_view(h->act_fwd);
     v.ok = 1; v.obs = av.obs; v.hp = av.hp; v.b_lo = av.bmu; v.b_hi = av.bls;
+    v.rows = av.max_rows; v.n_slots = av.n_slots; v.slot = av.slot; v.vs = reinterpret_cast<VerState *>(const_cast<void *>(av.vs)); v.vstride = av.vstride;
+    v.vb_lo = av.vbmu; v.vb_hi = av.vbls; v.steps_since_install = av.steps_since_install; v.plan_fresh = av.plan_fresh;
+    v.vcnt = av.vcnt; v.perm = av.perm; v.perm2d_off = av.perm2d_off; v.vtiles = av.vtiles; v.vt_cap = av.vt_cap; v.wg_slots = av.wg_slots;
     return v;
 }
 
-int ddrl_dqn_internal_forward(ddrl_dqn_t *h, long long n, void *stream) {
+int ddrl_dqn_internal_repack(ddrl_dqn_t *h, void *stream) {
     DDRL_REQUIRE(h != nullptr && h->act_fwd != nullptr, "no acting forward");
+    if (!h->pack_stale) return DDRL_OK;
     ddrl::DeviceGuard g(h->device);
-    if (h->pack_stale)
-        if (const int rc = dqn_pack_acting(h, ddrl::as_stream(stream))) return rc;
-    return ddrl_actor_internal_forward(h->act_fwd, n, stream, 0);
+    return dqn_pack_acting(h, ddrl::as_stream(stream));
+}
+
+int ddrl_dqn_internal_forward(ddrl_dqn_t *h, long long n, void *stream, int versioned) {
+    if (const int rc = ddrl_dqn_internal_repack(h, stream)) return rc;
+    return ddrl_actor_internal_forward(h->act_fwd, n, stream, versioned);
 }

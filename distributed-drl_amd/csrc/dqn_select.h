@@ -6,6 +6,7 @@
 // plus what dqn.hip shows of a learner handle to env.hip (internal to libddrl_hip.so).
 #pragma once
 #include "ddrl_common.h"
+#include "policy_row.h"
 
 namespace ddrl_sel {
 
@@ -55,9 +56,11 @@ __device__ __forceinline__ int select_row(const float (&q)[M], int A, int sqn, i
 // path rests: inside a partial as k_actor_fwd states it (layer-2 K blocks in order inside a wave, waves 0..3 in the combine, bias +
 // relu, the tile's columns 0..31 in the head dot), then the partials in column-tile order, then the head bias.
 // NH = head rows fetched: 4 (n_actions <= 4) or 8.  All loads are issued before the first sum.
+// boff: where this row's head biases lie behind b_lo / b_hi — 0, or slot * vstride with a version store (b_lo / b_hi are slot 0's then).
 template <int NH>
 __device__ __forceinline__ void q_row_from_partials(const float *__restrict__ hp, long long n, long long i, int A, int half, int nt2,
-                                                    const float *__restrict__ b_lo, const float *__restrict__ b_hi, float (&q)[MAXQ]) {
+                                                    const float *__restrict__ b_lo, const float *__restrict__ b_hi, long long boff,
+                                                    float (&q)[MAXQ]) {
     const int nq = (nt2 + 3) >> 2;   // float4 groups of a partial row that hold tiles
     float4 v[NH][4];
     float b[NH];
@@ -66,7 +69,7 @@ __device__ __forceinline__ void q_row_from_partials(const float *__restrict__ hp
         const int cm = c < A ? c : 0;
 #pragma unroll
         for (int g = 0; g < 4; ++g) v[c][g] = *reinterpret_cast<const float4 *>(hp + ((long long)cm * n + i) * 16 + 4 * (g < nq ? g : 0));
-        b[c] = cm < half ? b_lo[cm] : b_hi[cm - half];
+        b[c] = cm < half ? b_lo[boff + cm] : b_hi[boff + cm - half];
     }
 #pragma unroll
     for (int c = 0; c < MAXQ; ++c) {
@@ -101,7 +104,26 @@ struct ddrl_dqn_rollout_view {
     const float *b_lo, *b_hi;   // head biases: action c < half at b_lo[c], the others at b_hi[c - half]
     int obs_dim, n_actions, half, nt2, batch, sqn;
     float alpha;
+    // version store of the acting forward (ddrl_dqn_versions_enable; n_slots > 0), the fields of ddrl_actor_rollout_view: the slot every env
+    // acts on, the head biases of slot 0 of the version slab (slot s: + s * vstride), the device state whose first word is the newest slot
+    long long rows;         // rows of the acting forward: a store steps exactly that many envs
+    int n_slots;
+    int *slot;
+    VerState *vs;
+    long long vstride;
+    const float *vb_lo, *vb_hi;
+    long long *steps_since_install;   // host words of the inner actor
+    bool *plan_fresh;
+    // the next forward's plan as the env-step launch writes it (ver_plan_tail)
+    int *vcnt, *perm;
+    long long perm2d_off;
+    VerTile *vtiles;
+    int vt_cap, wg_slots;
 };
 ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h);
-// the acting forward of rows [0, n) of the view's observation buffer (repacks the operand copy first when a learner step moved the parameters)
-int ddrl_dqn_internal_forward(ddrl_dqn_t *h, long long n, void *stream);
+// a learner step moved the parameters: the operand copy is packed again — with a version store that is an install (steps_since_install = 0),
+// so the fused step calls this before it reads that word
+int ddrl_dqn_internal_repack(ddrl_dqn_t *h, void *stream);
+// the acting forward of rows [0, n) of the view's observation buffer (repacks first, like the above); versioned: every env against the
+// version in its slot (ddrl_actor_internal_forward)
+int ddrl_dqn_internal_forward(ddrl_dqn_t *h, long long n, void *stream, int versioned);

@@ -13,6 +13,7 @@
 #include "replay_device.h"
 #include "env_device.h"
 #include "dqn_select.h"
+#include "version_plan.h"
 
 namespace {
 
@@ -178,6 +179,15 @@ __global__ void __launch_bounds__(256) k_env_step_wrapped(float *S, long long n,
 //   o = o2 (or env.reset())      written into the actor's observation buffer for the next forward launch
 // One thread per env: no exchange between threads except the cursor ticket.
 // ------------------------------------------------------------------------------------------
+// The ring ticket of a fused launch in the form ver_plan_tail (version_plan.h) calls it: the cursor state, the ring and the two numbers BY
+// COPY.  (A lambda that captures the kernel's argument struct by reference does the same thing, and changed the scalar address arithmetic
+// the compiler emits for EVERY kernel of this file, the untouched ones included.)
+struct RingTicket {
+    ddrl_replay_dev::RingState *rs;
+    ddrl_replay_dev::RingPtrs ring;
+    long long ptr, n;
+    __device__ bool operator()() const { return ddrl_replay_dev::ring_commit(rs, ring, ptr, n); }
+};
 struct RolloutArgs {
     float *S;
     long long n;
@@ -216,7 +226,6 @@ struct RolloutArgs {
 template <int NH>  // head partial rows fetched per env: 4 (act_dim <= 2) or 8
 __global__ void __launch_bounds__(64) k_env_step_pi(RolloutArgs a) {
     __shared__ long long s_ptr;
-    __shared__ int s_last;
     if (threadIdx.x == 0) s_ptr = a.rs->ptr;
     __syncthreads();
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, n = a.n;
@@ -318,104 +327,10 @@ __global__ void __launch_bounds__(64) k_env_step_pi(RolloutArgs a) {
         atomicAdd((unsigned long long *)&a.stats->len_sum, (unsigned long long)len_end);
         atomicAdd(&a.stats->ret_sum, ret_end);
     }
-    if (a.vcnt) {
-        // this env's place in its group: the lanes of a wave that share a slot go as ONE atomic of their leader (a few thousand envs sit
-        // on a handful of versions; all leaders' atomics leave in one instruction: one round trip whatever the number of groups)
-        const int lane = threadIdx.x & 63;
-        const bool valid = i < n;
-        unsigned long long todo = __ballot(valid);
-        int gsize = 0, rank = 0, leader = lane;
-        while (todo) {
-            const int ld = __ffsll((long long)todo) - 1;
-            const int s0 = __builtin_amdgcn_readlane(my_slot, ld);   // (ld is wave-uniform: no trip through the LDS crossbar per group)
-            const bool mine = valid && my_slot == s0;
-            const unsigned long long m = __ballot(mine);
-            if (mine) { gsize = __popcll(m); rank = __popcll(m & ((1ull << lane) - 1ull)); leader = ld; }
-            todo &= ~m;
-        }
-        int base = 0;
-        if (valid && lane == leader) base = atomicAdd(&a.vcnt[my_slot], gsize);
-        base = __shfl(base, leader);
-        if (valid) a.perm[a.perm2d_off + (long long)my_slot * n + base + rank] = (int)i;
-        // (no fence: the counts are device-scope atomics whose results this wave has waited for — performed before its ticket below —
-        // and nothing else crosses workgroups inside this launch: row lists, records and slots are read by the NEXT launch.  A
-        // __threadfence() here writes back the L2's dirty lines — this launch's ring rows — in every workgroup: +8 us measured.)
-    }
-    // the last block to finish advances the ring cursor (every block has read rs->ptr before its ticket)
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = ddrl_replay_dev::ring_commit(a.rs, a.ring, s_ptr, n) ? 1 : 0;
-    if (!a.vcnt) return;
-    __syncthreads();
-    if (!s_last) return;   // block-uniform
-    // ---- the last workgroup (one wave): the counts -> the next forward's workgroup table (the tables of k_version_plan, sac1.hip; the
-    // row lists are this launch's own: group s at perm2d_off + s * n, so a record's row-list base is known without a scatter pass)
-    __shared__ int t_cnt[VER_MAX_SLOTS], t_start[VER_MAX_SLOTS];
-    __shared__ unsigned short t_slot[VER_MAX_SLOTS + 1024];   // slot of row tile ti (n / 32 + live groups <= 1024 + 2048 tiles)
-    const int lane = threadIdx.x;   // (the counts are read with device-scope atomic loads, behind this workgroup's own ticket)
-    constexpr int PER = VER_MAX_SLOTS / 64;
-    const int per = (a.n_slots + 63) >> 6;   // slots per lane (<= PER): lane l holds slots [per l, per l + per)
-    int c[PER], run = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int j = per * lane + q;
-        c[q] = (q < per && j < a.n_slots) ? __hip_atomic_load(&a.vcnt[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        run += (c[q] + 31) >> 5;
-    }
-    int incl = run;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o);
-        if (lane >= o) incl += u;
-    }
-    const int total = __shfl(incl, 63);
-    // slot of every row tile: each group's first tile gets its slot number, a running maximum over the tiles fills the rest (groups lie
-    // in slot order) — `chunk` tiles per lane, so the one big group of the newest version is not one lane's loop
-    const int chunk = (total + 63) >> 6;
-    for (int k = 0; k < chunk; ++k) t_slot[lane * chunk + k] = 0;
-    __syncthreads();
-    int ts = incl - run;   // first row tile of this lane's first slot
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        if (q < per) {   // wave-uniform
-            const int j = per * lane + q, nt = (c[q] + 31) >> 5;
-            if (j < VER_MAX_SLOTS) { t_cnt[j] = c[q]; t_start[j] = ts; }
-            if (nt > 0) { t_slot[ts] = (unsigned short)j; a.vcnt[j] = 0; }   // (... and zero again for the next launch)
-            ts += nt;
-        }
-    }
-    const VerSplit sp = ver_split(total, a.col_tiles, a.wg_slots, a.vt_cap);
-    if (lane == 0) { a.vs->n_tiles = total; a.vs->n_wgs = sp.n_wgs; }
-    __syncthreads();
-    {
-        int mx = 0;
-        for (int k = 0; k < chunk; ++k) mx = max(mx, (int)t_slot[lane * chunk + k]);
-        int inc = mx;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o);
-            if (lane >= o) inc = max(inc, u);
-        }
-        int runmx = __shfl_up(inc, 1);
-        if (lane == 0) runmx = 0;
-        for (int k = 0; k < chunk; ++k) {
-            runmx = max(runmx, (int)t_slot[lane * chunk + k]);
-            t_slot[lane * chunk + k] = (unsigned short)runmx;
-        }
-    }
-    __syncthreads();
-    // (one wave: every instruction counts — the divisions by the two group counts are done once, the per-record ones by reciprocal)
-    const int n_long_wgs = sp.n_long * sp.g_long;
-    const int gb_l = a.col_tiles / sp.g_long, ge_l = a.col_tiles % sp.g_long, gb_s = a.col_tiles / sp.g_short, ge_s = a.col_tiles % sp.g_short;
-    const float inv_l = 1.0f / (float)sp.g_long, inv_s = 1.0f / (float)sp.g_short;
-    const int base0 = (int)a.perm2d_off, ni = (int)n;
-    for (int b = lane; b < sp.n_wgs; b += 64) {
-        const bool lg = b < n_long_wgs;
-        const int g = lg ? sp.g_long : sp.g_short, bb = lg ? b : b - n_long_wgs;
-        const int q = (int)(((float)bb + 0.5f) * (lg ? inv_l : inv_s));   // bb / g: exact (bb < 2^20, g <= 16: the product is >= 0.03 off a whole number)
-        const int ti = (lg ? 0 : sp.n_long) + q, grp = bb - q * g;
-        const int j = t_slot[ti], k = ti - t_start[j], cj = t_cnt[j];
-        const int gbase = lg ? gb_l : gb_s, gextra = lg ? ge_l : ge_s;
-        const int ntl = gbase + (grp < gextra ? 1 : 0), nt0 = grp * gbase + (grp < gextra ? grp : gextra);
-        a.vtiles[b] = VerTile{j, base0 + j * ni + 32 * k, cj - 32 * k < 32 ? cj - 32 * k : 32, nt0 | (ntl << 8)};
-    }
+    // the next forward's plan (ver_plan_tail, version_plan.h): the grouping, the ring ticket — the last block to finish advances the ring
+    // cursor (every block has read rs->ptr before its ticket) — and, in that last workgroup, the forward's workgroup table
+    const VerPlan vp{a.vcnt, a.perm, a.perm2d_off, a.vtiles, a.vs, a.n_slots, a.col_tiles, a.wg_slots, a.vt_cap};
+    ver_plan_tail(vp, my_slot, i, n, RingTicket{a.rs, a.ring, s_ptr, n});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -447,8 +362,16 @@ struct RolloutQArgs {
     ddrl_replay_dev::RingState *rs;
     ddrl_replay_dev::RingPtrs ring;
     float *act_out, *q_out, *next_obs_out;   // optional mirrors: [n], [n][A], [n][8]
+    // version store of the acting forward (k_env_step_q<.., true> only; behind everything the plain kernel reads): env i acts on slot[i]
+    // (b_lo / b_hi are slot 0's then, slot s is vstride floats further) and adopts the newest version where its episode ends — the
+    // reference worker's pull at the episode boundary (algos/dqn/train.py:249-252) — and the NEXT forward's plan (vp.vcnt nullable)
+    int *slot;
+    const int *newest;
+    long long vstride;
+    VerPlan vp;
 };
-template <int NH>
+// VER: a version store is live.  The plain instantiation is the kernel without one: no slot load, no static LDS for the table build.
+template <int NH, bool VER>
 __global__ void __launch_bounds__(64) k_env_step_q(RolloutQArgs a) {
     __shared__ long long s_ptr;
     if (threadIdx.x == 0) s_ptr = a.rs->ptr;
@@ -456,9 +379,11 @@ __global__ void __launch_bounds__(64) k_env_step_q(RolloutQArgs a) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, n = a.n;
     long long n_end = 0, len_end = 0;
     double ret_end = 0.0;
+    int my_slot = 0;       // the version this env acts on at the NEXT step
     if (i < n) {
         float q[ddrl_sel::MAXQ];
-        ddrl_sel::q_row_from_partials<NH>(a.hp, n, i, a.A, a.half, a.nt2, a.b_lo, a.b_hi, q);
+        if (VER) my_slot = a.slot[i];
+        ddrl_sel::q_row_from_partials<NH>(a.hp, n, i, a.A, a.half, a.nt2, a.b_lo, a.b_hi, VER ? (long long)my_slot * a.vstride : 0ll, q);
         float o1[8];
         {
             const float4 *p = reinterpret_cast<const float4 *>(a.obs + i * 8);
@@ -503,6 +428,7 @@ __global__ void __launch_bounds__(64) k_env_step_q(RolloutQArgs a) {
             n_end = 1; len_end = (long long)e.eplen; ret_end = (double)e.epret;
             e.epi = e.epi + 1.0f;
             e.reset(o);
+            if (VER) { my_slot = *a.newest; a.slot[i] = my_slot; }   // train.py:251-252  weights = ps.pull(keys); agent.set_weights(keys, weights)
         }
         {
             float4 *p = reinterpret_cast<float4 *>(a.obs + i * 8);
@@ -524,6 +450,10 @@ __global__ void __launch_bounds__(64) k_env_step_q(RolloutQArgs a) {
         atomicAdd((unsigned long long *)&a.stats->episodes, (unsigned long long)n_end);
         atomicAdd((unsigned long long *)&a.stats->len_sum, (unsigned long long)len_end);
         atomicAdd(&a.stats->ret_sum, ret_end);
+    }
+    if constexpr (VER) {   // the grouping, the ring ticket and the next forward's workgroup table: the function k_env_step_pi calls
+        ver_plan_tail(a.vp, my_slot, i, n, RingTicket{a.rs, a.ring, s_ptr, n});
+        return;
     }
     // the last block to finish advances the ring cursor (every block has read rs->ptr before its ticket)
     __syncthreads();
@@ -728,13 +658,38 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
     a.obs = v.obs; a.hp = v.hp; a.b_lo = v.b_lo; a.b_hi = v.b_hi; a.A = v.n_actions; a.half = v.half; a.nt2 = v.nt2; a.sqn = v.sqn;
     a.deterministic = mode == DDRL_ACT_DETERMINISTIC; a.greedy_prob = greedy_prob; a.alpha = v.alpha; a.noise_seed = seed;
     a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.q_out = q_out_d; a.next_obs_out = next_obs_out_d;
-    for (int k = 0; k < n_steps; ++k) {
-        const int rc = ddrl_dqn_internal_forward(dqn, h->n, stream);
+    const bool store = v.n_slots > 0;
+    if (store && h->n != v.rows) {
+        ddrl::set_error("fused discrete rollout step: a handle with a version store steps exactly the acting forward's %lld rows (n_envs %lld)", v.rows, h->n);
+        return DDRL_ERR_BAD_ARG;
+    }
+    const unsigned grid = (unsigned)((h->n + 63) / 64);
+    hipStream_t s = ddrl::as_stream(stream);
+    for (int k = 0; k < n_steps; ++k) {   // ddrl_rollout_step's loop body
+        // a learner step's pending repack is an install: before steps_since_install is read
+        if (const int rc = ddrl_dqn_internal_repack(dqn, stream)) return rc;
+        // version store: once no install has happened for max_ep_len steps every env has been through an episode end and acts on
+        // the newest version — the plain launch pair on the handle's current weights is then the same computation
+        const bool versioned = store && *v.steps_since_install < (long long)h->max_ep_len;
+        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
+        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
+        if (store) *v.steps_since_install += 1;
+        const int rc = ddrl_dqn_internal_forward(dqn, h->n, stream, versioned ? 1 : 0);
         if (rc != DDRL_OK) return rc;
         a.noise_ctr = ctr + (uint64_t)k * 2ull * (uint64_t)h->n;
-        if (v.n_actions <= 4) k_env_step_q<4><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
-        else k_env_step_q<8><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
+        if (versioned) {
+            a.b_lo = v.vb_lo; a.b_hi = v.vb_hi; a.slot = v.slot; a.newest = reinterpret_cast<const int *>(v.vs);   // VerState::newest is its first word
+            a.vstride = v.vstride;
+            a.vp = VerPlan{fused_plan ? v.vcnt : nullptr, v.perm, v.perm2d_off, v.vtiles, v.vs, v.n_slots, v.nt2, v.wg_slots, v.vt_cap};
+            if (v.n_actions <= 4) k_env_step_q<4, true><<<grid, 64, 0, s>>>(a);
+            else k_env_step_q<8, true><<<grid, 64, 0, s>>>(a);
+        } else {
+            a.b_lo = v.b_lo; a.b_hi = v.b_hi;
+            if (v.n_actions <= 4) k_env_step_q<4, false><<<grid, 64, 0, s>>>(a);
+            else k_env_step_q<8, false><<<grid, 64, 0, s>>>(a);
+        }
         DDRL_LAUNCH_CHECK();
+        if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
         ddrl_replay_note_store(replay, h->n);
     }
     return DDRL_OK;

@@ -234,6 +234,30 @@ def _get_actions(self, obs, out=None, q_out=None, deterministic=False):
     return out
 
 
+# -- version store: exact per-env weight adoption of the vectorised discrete rollout worker (algos/dqn/train.py:249-252) -------------------
+def _enable_versions(self, n_slots):
+    """Keep `n_slots` resident copies of the acting Q network (ddrl_dqn_versions_enable): set_weights / import_ of MAIN / the repack after
+    a learner step then store a NEW version (instead of replacing the one every env acts on) and the fused rollout step moves an env to
+    the newest version at that env's own episode end.  get_actions keeps acting on the newest weights."""
+    _lib.check(self._lib.ddrl_dqn_versions_enable(self._h, int(n_slots), _lib.stream_ptr()))
+    self.n_slots = int(n_slots)
+
+
+def _version_state(self, with_slots=True):
+    """-> (slot of every env [max_rows] int32 device tensor or None, dict(newest, live, tiles, out_of_slots))."""
+    rows = (self.max_rows + 31) & ~31      # the acting forward's rows: whole 32-row tiles
+    slots = torch.empty(rows, dtype=torch.int32, device=self.device) if with_slots else None
+    st = (ctypes.c_int32 * 4)()
+    _lib.check(self._lib.ddrl_dqn_versions_state(self._h, _lib.dptr(slots), st, _lib.stream_ptr()))
+    return (slots[:self.max_rows] if with_slots else None), {"newest": int(st[0]), "live": int(st[1]), "tiles": int(st[2]), "out_of_slots": bool(st[3])}
+
+
+def _adopt_where_ended(self, ended):
+    """Episode ends of steps taken outside the fused rollout step (uint8 mask of env.step): those envs pull."""
+    ended = ended.to(device=self.device, dtype=torch.uint8).contiguous()
+    _lib.check(self._lib.ddrl_dqn_versions_adopt(self._h, _lib.dptr(ended), int(ended.numel()), _lib.stream_ptr()))
+
+
 def _noise_stream(opt, job, index=0):
     """(seed, counter) of an actor's uniform stream — the recipe agent.Actor uses for its normals."""
     import zlib
@@ -253,6 +277,7 @@ class Actor(Learner):
         self._noise_seed, self._noise_ctr = _noise_stream(opt, job, index)
 
     get_actions = _get_actions
+    enable_versions, version_state, adopt_where_ended = _enable_versions, _version_state, _adopt_where_ended
 
     def get_action(self, o):
         if self._rs.uniform() < 0.97:
@@ -312,6 +337,7 @@ class ActorSQN(LearnerSQN):
         self._noise_seed, self._noise_ctr = _noise_stream(opt, job, index)
 
     get_actions = _get_actions
+    enable_versions, version_state, adopt_where_ended = _enable_versions, _version_state, _adopt_where_ended
 
     def get_action(self, o, deterministic=False):
         q = self._q_row(o).astype(np.float64)

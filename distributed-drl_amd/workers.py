@@ -706,9 +706,15 @@ class RolloutDeviceDQN:
     launch that selects, steps the physics and appends to the ring (ddrl_rollout_step_discrete); shapes outside its envelope run
     get_actions + env.step + store_batch.  Works with TrainDeviceDQN under ActorLearnerLoop as RolloutDevice does with TrainDevice.
 
-    Weight adoption is at vector-step boundaries only (RolloutDevice's adopt="step"): pull() swaps the weights of every env at
-    once — never staler than the reference's pull at each episode start, not identical to it.  The per-episode version store of
-    RolloutDevice is out of scope here."""
+    Weight adoption (`opt.adopt`, default "step"): the reference's worker pulls the server's weights once per episode, for its own env
+    only (algos/dqn/train.py:249-252: env.reset(), ps.pull, agent.set_weights), so its envs act on different versions at any moment.
+    "episode" reproduces that exactly, as RolloutDevice does on the continuous side: the actor's acting forward keeps
+    min(num_envs, max_ep_len) + 2 resident versions of the Q network (dqn.Actor.enable_versions), pull() — at the START of step():
+    what the server holds now is what an env ending in this step pulls — stores the server's weights as the newest one, and the fused
+    step's kernel (the random-action phase: adopt_where_ended) moves an env to it where that env's episode ends: the vector of envs is
+    then indistinguishable from num_envs reference workers stepped in lock step.  "episode" needs the fused envelope and num_envs equal
+    to the acting forward's rows (a multiple of 32); a shape or ring outside it falls back to "step", as does the default: pull() after
+    the step swaps the weights of every env at once — never staler than the reference's pull at each episode start, not identical."""
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
@@ -726,10 +732,16 @@ class RolloutDeviceDQN:
         self.t = 0
         self.o = torch.empty_like(self.env.obs)
         self.act = torch.empty(opt.num_envs, dtype=torch.float32, device=self.env.device)
+        self.q_out = None         # optional [num_envs, act_dim] float32 device tensor: the fused step's Q rows of its LAST step (tests, probes)
         self._fused = None if getattr(opt, "fused_rollout", True) else False
         self._fused_live = False
+        self.adopt = getattr(opt, "adopt", "step")
+        assert self.adopt in ("episode", "step"), self.adopt
+        self._versions = False
         self.auto_pull = True
         self.pull()
+        if self.adopt == "episode" and self._fused is None:
+            self._fused_ready()   # the version store starts from the initial pull, before any step
 
     def pull(self):
         """ps.pull(keys) + agent.set_weights when the server has something newer."""
@@ -748,21 +760,28 @@ class RolloutDeviceDQN:
             if ok:
                 ok = self.actor._lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr()) == 0
             self._fused, self._fused_live = ok, ok
+            if ok and self.adopt == "episode" and self.actor.max_rows == self.env.n:
+                # every env on the weights of the initial pull; later pulls become versions adopted at episode ends
+                self.actor.enable_versions(min(2048, min(self.env.n, int(self.opt.max_ep_len)) + 2))
+                self._versions = True
         return self._fused
 
     def step(self, n_steps=1):
         """One vector step = num_envs iterations of the reference loop; n_steps > 1 issues that many back to back on the weights held."""
         from . import _lib
         env, a = self.env, self.actor
+        if self._versions and self.auto_pull:
+            self.pull()   # what the server holds NOW is what an env ending its episode in this step pulls (train.py:249-252)
         if self.t > self.opt.start_steps and self._fused_ready():
             if not self._fused_live:   # the unfused path has stepped the envs since: refresh the forward's observation rows
                 _lib.check(a._lib.ddrl_rollout_begin_discrete(env._h, a._h, _lib.stream_ptr()))
                 self._fused_live = True
             _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, int(n_steps), _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
-                                                         a._noise_seed, a._noise_ctr, _lib.dptr(self.act), None, _lib.dptr(env.obs), _lib.stream_ptr()))
+                                                         a._noise_seed, a._noise_ctr, _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs),
+                                                         _lib.stream_ptr()))
             a._noise_ctr += int(n_steps) * 2 * env.n
             self.t += int(n_steps) * env.n
-            if self.auto_pull:
+            if not self._versions and self.auto_pull:
                 self.pull()
             return
         if n_steps > 1:
@@ -775,10 +794,12 @@ class RolloutDeviceDQN:
             a.get_actions(self.o, out=self.act)
         else:
             env.sample_actions(out=self.act)
-        o2, r, d, _, _ended = env.step(self.act)
+        o2, r, d, _, ended = env.step(self.act)
+        if self._versions:
+            a.adopt_where_ended(ended)   # (clears the forward's plan_fresh: the next versioned forward plans for the moved envs)
         self.rb.store_batch(self.o, self.act, r, o2, d)
         self.t += env.n
-        if self.auto_pull:
+        if not self._versions and self.auto_pull:
             self.pull()
 
 

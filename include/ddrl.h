@@ -643,6 +643,24 @@ int ddrl_dqn_act(ddrl_dqn_t *h, const float *obs_d, int64_t n, int mode, float g
  * and <= cfg.batch; outside it DDRL_ERR_UNSUPPORTED with the reason in ddrl_last_error() and nothing changed (the unfused sequence is
  * ddrl_dqn_act + ddrl_env_step_discrete + ddrl_replay_store).  A ring of another layout or device: DDRL_ERR_BAD_ARG.
  * act_out_d[n], q_out_d[n, n_actions], next_obs_out_d[n, 8]: optional mirrors of the LAST step (may be NULL). */
+/* Exact per-env weight adoption for the vectorised discrete rollout worker.  worker_rollout_dqn pulls the server's weights once per episode,
+ * for its own env only (algos/dqn/train.py:249-252: env.reset(), ps.pull, agent.set_weights), so n workers hold up to min(n, max_ep_len) + 1
+ * versions at a time.  ddrl_dqn_versions_enable gives the handle's acting forward — the one ddrl_rollout_step_discrete runs — `n_slots`
+ * resident copies of the Q network in its operand layout ([2, 2048]; n_slots >= min(n_envs, max_ep_len) + 2 never runs out; once per handle)
+ * and a slot word per env, all on slot 0 = the weights held now.  A handle without that forward (wide observations, n_actions > 8, ...):
+ * DDRL_ERR_UNSUPPORTED with the reason in ddrl_last_error().  From then on
+ *   every weight install (ddrl_dqn_set_weights, ddrl_dqn_import of MAIN, the repack in front of the first acting call after a learner step)
+ *                               stores the NEWEST version in a slot no env acts on (the newest slot itself while no env has adopted it);
+ *   ddrl_rollout_step_discrete  evaluates every env against the version in its slot and moves an env to the newest version where its episode
+ *                               ends; it then steps exactly the acting forward's rows (cfg.batch rounded up to 32): DDRL_ERR_BAD_ARG otherwise.
+ *                               max_ep_len steps after the last install every env holds the newest version and the plain launch pair runs;
+ *   ddrl_dqn_versions_adopt     does that move for steps taken outside the fused path (ended_d[n]: uint8 mask of ddrl_env_step_discrete).
+ * ddrl_dqn_act keeps evaluating the newest weights on rows of its own and leaves store, slots and plan alone.  ddrl_dqn_versions_state:
+ * slot_of_env_d[cfg.batch rounded up to 32] (device, nullable) and state_h[4] = {newest slot, slots in use at the last install, row tiles of
+ * the last versioned launch's plan, sticky out-of-slots flag} (host, nullable; synchronises `stream`) — ddrl_actor_versions_state's. */
+int ddrl_dqn_versions_enable(ddrl_dqn_t *h, int32_t n_slots, void *stream);
+int ddrl_dqn_versions_state(ddrl_dqn_t *h, int32_t *slot_of_env_d, int32_t *state_h, void *stream);
+int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, void *stream);
 int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream);
 int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
                                uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream);
