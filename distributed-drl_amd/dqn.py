@@ -234,6 +234,42 @@ def _get_actions(self, obs, out=None, q_out=None, deterministic=False):
     return out
 
 
+EVAL_ROW = 20   # floats per step of an evaluation trace (csrc/eval_q.hip)
+
+
+def _evaluate(self, n=10, seed=0, first_episode=0, max_ep_len=None, deterministic=None, greedy_prob=None, trace=False):
+    """n evaluation episodes on the device as ONE launch (ddrl_dqn_eval, csrc/eval_q.hip): episode e is the (first_episode + e)-th
+    episode a host `LunarLanderDiscrete(seed, max_ep_len)` plays, acted on with this actor's current main weights (SQN: q1) under
+    get_actions' selection rules.  Defaults are what the class's _test_action does: Double-DQN samples with greedy_prob 0.97, SQN is
+    deterministic.  Step t of episode e draws its two uniforms at self._noise_ctr + 2 (e max_ep_len + t) [+ 1] of the object's counter
+    stream, which advances by 2 n max_ep_len per call, whatever the mode.
+    -> dict(ret float64 [n], len int32 [n]) NumPy, and with trace=True `trace` float32 [n, max_ep_len, 20]: per step obs[8] acted on,
+    the q row [8:16] (zeros beyond act_dim), the action index, rew, ended, 0; zero rows past an episode's end.
+    One weight snapshot, one launch, one synchronisation; weights, Adam state and the acting forward's packed copy are untouched."""
+    n = int(n)
+    if max_ep_len is None:
+        max_ep_len = getattr(self.opt, "max_ep_len", None)
+        if max_ep_len is None:
+            raise ValueError("evaluate: max_ep_len is neither given nor an attribute of the actor's options")
+    max_ep_len = int(max_ep_len)
+    deterministic = self._eval_deterministic if deterministic is None else bool(deterministic)
+    greedy_prob = float(self.greedy_prob if greedy_prob is None else greedy_prob)
+    flat = self.export(_lib.SAC1_MAIN)
+    ret = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+    ln = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+    tr = torch.empty(max(n, 1), max(max_ep_len, 1), EVAL_ROW, dtype=torch.float32, device=self.device) if trace else None
+    mode = _lib.DDRL_ACT_DETERMINISTIC if deterministic else _lib.DDRL_ACT_SAMPLE
+    _lib.check(self._lib.ddrl_dqn_eval(ctypes.byref(self.cfg), _lib.dptr(flat), n, int(seed) & 0xFFFFFFFF, int(first_episode), max_ep_len,
+                                       mode, greedy_prob, self._noise_seed, self._noise_ctr, _lib.dptr(ret), _lib.dptr(ln), _lib.dptr(tr),
+                                       _lib.stream_ptr()))
+    self._noise_ctr += 2 * n * max_ep_len
+    torch.cuda.current_stream().synchronize()
+    out = {"ret": ret.cpu().numpy(), "len": ln.cpu().numpy()}
+    if trace:
+        out["trace"] = tr.cpu().numpy()
+    return out
+
+
 # -- version store: exact per-env weight adoption of the vectorised discrete rollout worker (algos/dqn/train.py:249-252) -------------------
 def _enable_versions(self, n_slots):
     """Keep `n_slots` resident copies of the acting Q network (ddrl_dqn_versions_enable): set_weights / import_ of MAIN / the repack after
@@ -287,9 +323,28 @@ class Actor(Learner):
     def _test_action(self, o):
         return self.get_action(o)
 
+    _eval_deterministic = False   # evaluate's default mode: what _test_action does
+    evaluate = _evaluate
+
     def test(self, test_env, n=10):
         """actor_learner.py:230-251: n episodes to their terminal with the actor's own get_action; (mean return, mean of
-        test_env.rewards[0] at each episode's end — the trading env's score)."""
+        test_env.rewards[0] at each episode's end — the trading env's score).
+        On a test env with `on_device` (env.DeviceLunarLanderDiscrete) the n episodes run as ONE launch (evaluate) from
+        test_env.episodes_played on, which then advances by n; the lander's score is its return, so (mean return, mean return).
+        The env's max_ep_len must equal opt.max_ep_len where the options carry one (the device plays whole episodes).  Outside the
+        kernel's envelope (DdrlUnsupported) the host loop below runs on test_env.host_env(): the same episode indices."""
+        if getattr(test_env, "on_device", False):
+            want = int(getattr(self.opt, "max_ep_len", test_env.max_ep_len))
+            if int(test_env.max_ep_len) != want:
+                raise ValueError("the test env's max_ep_len (%d) must equal the agent's (%d): the device plays whole episodes"
+                                 % (test_env.max_ep_len, want))
+            try:
+                ret = float(np.mean(self.evaluate(n, test_env.seed, test_env.episodes_played, want)["ret"]))
+                out = (ret, ret)
+            except _lib.DdrlUnsupported:
+                out = self.test(test_env.host_env(), n)
+            test_env.episodes_played += n
+            return out
         test_rets, scores = [], []
         for _ in range(n):
             o, r, d, ep_ret, ep_len = test_env.reset(), 0, False, 0, 0
@@ -350,4 +405,6 @@ class ActorSQN(LearnerSQN):
     def _test_action(self, o):
         return self.get_action(o, deterministic=True)     # algos/sqn/actor_learner.py:238
 
+    _eval_deterministic = True
+    evaluate = _evaluate
     test, write_tb = Actor.test, Actor.write_tb

@@ -167,19 +167,28 @@ class _DiscreteActionSpace:
 
 
 class LunarLanderDiscrete(LunarLander):
-    """One discrete-action environment with the gym call shape (env.make("LunarLander-v2")): step(a) takes the action index."""
+    """One discrete-action environment with the gym call shape (env.make("LunarLander-v2")): step(a) takes the action index.
+    `rewards[0]` is the Python-float sum of the step rewards since the last reset() (0.0 after one): the score dqn.Actor.test reads
+    at every episode's end (algos/dqn/actor_learner.py:246; the trading env's bookkeeping) — on the lander, the episode's return."""
 
     def __init__(self, seed=0, max_ep_len=1000):
         self._vec = VecLunarLanderDiscrete(1, seed=seed, max_ep_len=max_ep_len)
         self.action_space = _DiscreteActionSpace(self)
         self.observation_space = _ObsSpace()
         self._fresh = True
+        self.rewards = [0.0]
+
+    def reset(self):
+        self.rewards = [0.0]
+        return super().reset()
 
     def step(self, a):
         o2, r, d, _, ended = self._vec.step(torch.full((1,), float(int(a)), dtype=torch.float32))
         ended = bool(ended[0].item())
         self._fresh = ended
-        return o2[0].cpu().numpy().astype(np.float64), float(r[0].item()), ended, {}
+        r = float(r[0].item())
+        self.rewards[0] += r
+        return o2[0].cpu().numpy().astype(np.float64), r, ended, {}
 
 
 class DeviceLunarLander:
@@ -206,13 +215,30 @@ class DeviceLunarLander:
     def host_env(self):
         """A host `LunarLander` of the same seed positioned at the next episode this env would play (the fallback of a policy
         outside ddrl_policy_eval's envelope)."""
-        host = LunarLander(self.seed, self.max_ep_len)
+        host = self._host_class(self.seed, self.max_ep_len)
         if self.episodes_played:
             s = host._vec.get_state()
             s[13] = float(self.episodes_played)   # EPI (csrc/env_device.h): the episode index names the env's random stream
             host._vec.set_state(s)
             host._vec.reset()
         return host
+
+    _host_class = LunarLander
+
+
+class DeviceLunarLanderDiscrete(DeviceLunarLander):
+    """The same marker for the discrete lander (action_space.n == 4): `dqn.Actor.test` / `ActorSQN.test` given one run their episodes
+    as one launch (`evaluate`, csrc/eval_q.hip); host_env() is a `LunarLanderDiscrete` positioned at `episodes_played`."""
+
+    _host_class = LunarLanderDiscrete
+
+    def __init__(self, seed=0, max_ep_len=1000):
+        super().__init__(seed, max_ep_len)
+        self.action_space = _DiscreteActionSpace(self)
+
+    def step(self, a):
+        raise RuntimeError("DeviceLunarLanderDiscrete is not steppable: its episodes run on the device (dqn.Actor.evaluate / "
+                           "dqn.Actor.test); use env.make(\"LunarLander-v2\") for an env to step from the host")
 
 
 class Wrapper(object):
@@ -255,9 +281,9 @@ class Wrapper(object):
 
 def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     """gym.make stand-in (example/dsac.py:78).  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
-    `Model.test_agent` run as one launch (DeviceLunarLander)."""
-    if env_name == "LunarLander-v2" and not on_device:   # gym's discrete action table on the same lander (action_space.n == 4)
-        return LunarLanderDiscrete(**kw)
+    `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)."""
+    if env_name == "LunarLander-v2":   # gym's discrete action table on the same lander (action_space.n == 4)
+        return DeviceLunarLanderDiscrete(**kw) if on_device else LunarLanderDiscrete(**kw)
     if "LunarLander" not in env_name:
         raise ValueError("only the LunarLanderContinuous-v2 stand-in is built (SURVEY §8(a) A7): %r" % env_name)
     return DeviceLunarLander(**kw) if on_device else LunarLander(**kw)

@@ -441,7 +441,9 @@ def worker_test_dqn(ps, node_buffer, opt, node_ps=None, make_env=None, make_agen
                     max_rounds=None):
     """algos/dqn/train.py:289-355: pull everything, 10 test episodes, actor / learner counters before and after (a_l_ratio and the
     learner's update frequency over the test's duration), TensorBoard scalars, the whole weight dict pickled every save_interval
-    learner steps, every server and every buffer checkpointed every checkpoint_freq seconds."""
+    learner steps, every server and every buffer checkpointed every checkpoint_freq seconds.
+    make_env=lambda: env.make(opt.env_name, on_device=True, seed=opt.seed, max_ep_len=opt.max_ep_len) hands agent.test the device
+    marker (env.DeviceLunarLanderDiscrete): the ten episodes of a round then run as one launch (dqn.Actor.evaluate)."""
     import pickle
     import numpy as np
     if make_agent is None:

@@ -664,6 +664,25 @@ int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, vo
 int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream);
 int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
                                uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream);
+/* The DQN / SQN test worker's evaluation episodes as ONE launch: Actor.test (algos/dqn/actor_learner.py:230-251,
+ * algos/sqn/actor_learner.py:229-250) — n episodes of get_action(o) + env.step(a) on the discrete lander — with one workgroup per
+ * episode and no host round trip per step: the discrete counterpart of ddrl_policy_eval.  q_flat_d is the flat main vector in variable
+ * order, as ddrl_dqn_export(MAIN) writes it (q1: W1[obs][h1], b1, W2[h1][h2], b2, W3[h2][n_actions], b3; SQN: q2 follows and is
+ * ignored); no learner handle is involved.  cfg->variant / cfg->alpha select Double-DQN or SQN, `mode` and `greedy_prob` are
+ * ddrl_dqn_act's.  Episode e of the call plays the lander's stream (env_seed, env id 0, episode first_episode + e) on
+ * ddrl_env_step_discrete's action table; step t (0-based) of episode e (0-based, call-relative) owns the uniforms
+ * u0 = U(noise_seed, noise_ctr + 2 (e * max_ep_len + t)) and u1 = U(.., .. + 1) of ddrl_uniform_fill's generator: a caller advances its
+ * counter by 2 * n_episodes * max_ep_len per call, whatever the mode.  ret_d[n] = the float64 sum of the float32 step rewards in step
+ * order, len_d[n] = steps played, trace_d (NULL, or [n][max_ep_len][20] 16-byte aligned) = per step the observation acted on [0:8], the
+ * q row [8:16] (zeros beyond n_actions), the action index [16], the reward [17], ended (0 / 1) [18], 0 [19]; rows past an episode's end
+ * are written as zeros.  The q row's float32 summation order is stated in csrc/eval_q.hip's header.  Stream-ordered on the CURRENT
+ * device: no host synchronisation, no allocation.
+ * DDRL_ERR_BAD_ARG unless obs_dim == 8, n_actions >= 1, n_episodes >= 1, max_ep_len >= 1, hidden sizes >= 1, max_ep_len and
+ * first_episode + n_episodes exact in float32 (<= 2^24), trace_d 16-byte aligned and a valid mode; DDRL_ERR_UNSUPPORTED with the
+ * reason in ddrl_last_error() for a hidden width > 512 or n_actions > 8. */
+int ddrl_dqn_eval(const ddrl_dqn_config_t *cfg, const float *q_flat_d, int32_t n_episodes, uint32_t env_seed, uint32_t first_episode,
+                  int32_t max_ep_len, int mode, float greedy_prob, uint32_t noise_seed, uint64_t noise_ctr, double *ret_d, int32_t *len_d,
+                  float *trace_d, void *stream);
 
 /* ===================================================================================== */
 /* Rollout-side window queues of the n-step driver: per env, o_queue = deque(maxlen=Ln+1) of  */

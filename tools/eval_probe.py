@@ -10,7 +10,15 @@ small enough that most episodes run into the limit (--short-len, default 60: eve
 Prints both times, the env steps played, microseconds per env step for each path, and the kernel's register / LDS / scratch use as
 the code object inside libddrl_hip.so records it.
 
-    python tools/eval_probe.py [--out profiles/eval_on_device.txt]"""
+    python tools/eval_probe.py [--out profiles/eval_on_device.txt]
+
+--discrete: the DQN / SQN counterpart (dqn.Actor.evaluate, csrc/eval_q.hip).  Host loop = dqn.Actor.test on env.LunarLanderDiscrete,
+one launch = ddrl_dqn_eval; both between HIP events in the same process, one warm-up and five repetitions each, every repetition
+listed with its env steps and microseconds per env step.  10 episodes at hidden (400, 300), max_ep_len 1000 and --short-len.  The two
+paths draw their coin flips from different generators (a host RandomState against the device's counter stream), so they play
+different steps of the same episodes: the comparison is per env step.
+
+    python tools/eval_probe.py --discrete [--out profiles/eval_on_device_discrete.txt]"""
 import argparse
 import ctypes
 import os
@@ -26,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def kernel_resources(lib_path, pattern="k_eval_episodes"):
+def kernel_resources(lib_path, pattern="k_eval_episodesI"):
     """[(kernel name, vgprs, sgprs, LDS bytes, scratch bytes, vgpr spills)] from the gfx950 code objects bundled in the library."""
     llvm = "/opt/rocm/llvm/bin"
     out = []
@@ -46,13 +54,89 @@ def kernel_resources(lib_path, pattern="k_eval_episodes"):
     return out
 
 
+def discrete(a, say):
+    """The --discrete arm (module docstring)."""
+    import numpy as np
+    import torch
+    from distributed_drl_amd import _lib, dqn, env
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+
+    arch = _lib.require_gpu()
+    lib = _lib.load()
+    n = a.episodes if a.episodes != 25 else 10
+    say("eval_probe --discrete: Double-DQN, %d episodes, env seed %d, glorot weights (seed 0), hidden (400, 300), greedy_prob 0.97, %s" % (n, a.seed, arch))
+    ok = True
+    for max_ep_len in (1000, a.short_len):
+        class Opt:
+            obs_dim, act_dim, hidden_size, gamma, lr, polyak, batch_size, seed, alpha = 8, 4, [400, 300], 0.99, 1e-3, 0.995, 1, 0, 0.1
+        Opt.max_ep_len = max_ep_len
+        actor = dqn.Actor(Opt, "test", max_rows=1)
+        host = []      # (ms, env steps) of the warm-up and the five repetitions
+
+        class Counting(env.LunarLanderDiscrete):
+            steps = 0
+
+            def step(self, act):
+                Counting.steps += 1
+                return super().step(act)
+        for _ in range(6):
+            actor._rs = np.random.RandomState(0)
+            e, Counting.steps = Counting(a.seed, max_ep_len), 0
+            torch.cuda.synchronize()
+            ms, _ = timed(lambda: actor.test(e, n))
+            host.append((ms, Counting.steps))
+        flat = actor.export()
+        ret = torch.empty(n, dtype=torch.float64, device="cuda")
+        ln = torch.empty(n, dtype=torch.int32, device="cuda")
+        dev = []
+        for _ in range(6):
+            ms, _ = timed(lambda: _lib.check(lib.ddrl_dqn_eval(ctypes.byref(actor.cfg), _lib.dptr(flat), n, a.seed, 0, max_ep_len, _lib.DDRL_ACT_SAMPLE,
+                                                               0.97, actor._noise_seed, 0, _lib.dptr(ret), _lib.dptr(ln), None, _lib.stream_ptr())))
+            dev.append((ms, int(ln.sum().item())))
+        longest, at_limit = int(ln.max().item()), int((ln == max_ep_len).sum().item())
+        say("max_ep_len %d: %d episodes" % (max_ep_len, n))
+        per = {}
+        for name, runs in (("host loop ", host), ("one launch", dev)):
+            per[name] = [ms * 1e3 / st for ms, st in runs[1:]]
+            say("  %s  warm-up %.3f ms (%d env steps); five repetitions: %s" % (name, runs[0][0], runs[0][1], "; ".join("%.3f ms / %d steps = %.2f us / env step" % (ms, st, ms * 1e3 / st) for ms, st in runs[1:])))
+        say("  one launch: longest episode %d steps, %d of %d at the limit, %.2f us / step of the longest episode (median run)"
+            % (longest, at_limit, n, statistics.median(ms for ms, _ in dev[1:]) * 1e3 / longest))
+        slowest_dev, fastest_host = max(per["one launch"]), min(per["host loop "])
+        ok = ok and slowest_dev < fastest_host
+        say("  per env step: host / device = %.1f x (medians); slowest device repetition %.2f us, fastest host repetition %.2f us: %s"
+            % (statistics.median(per["host loop "]) / statistics.median(per["one launch"]), slowest_dev, fastest_host,
+               "every device repetition is faster than every host repetition" if slowest_dev < fastest_host else "CRITERION MISSED"))
+    for name, vg, sg, lds, scratch, spill in kernel_resources(_lib.LIB_PATH, "k_eval_episodes_qI"):
+        say("code object: %s  vgprs %d  sgprs %d  LDS %d B  scratch %d B  vgpr spills %d" % (name, vg, sg, lds, scratch, spill))
+    return ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--episodes", type=int, default=25)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--short-len", type=int, default=60)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--discrete", action="store_true")
     a = ap.parse_args()
+    if a.discrete:
+        lines = []
+
+        def say(s):
+            print(s, flush=True)
+            lines.append(s)
+        ok = discrete(a, say)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        sys.exit(0 if ok else 1)
     import torch
     from distributed_drl_amd import _lib, env
     from distributed_drl_amd.agent import Actor, HyperParameters
