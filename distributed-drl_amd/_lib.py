@@ -167,6 +167,10 @@ SIGNATURES = {
     "ddrl_dqn_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ddrl_dqn_step_timed": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P]),
     "ddrl_dqn_step_ring": (c_int, [_P, _P, _P, _P, _P, _P]),
+    "ddrl_dqn_loop_create": (c_int, [POINTER(_P), _P, _P, c_int32, _P]),
+    "ddrl_dqn_loop_destroy": (c_int, [_P]),
+    "ddrl_dqn_loop_run": (c_int, [_P, c_int64, _P]),
+    "ddrl_dqn_loop_info": (c_int, [_P, POINTER(c_int32)]),
     "ddrl_dqn_q": (c_int, [_P, _P, c_int64, _P, _P]),
     "ddrl_dqn_act": (c_int, [_P, _P, c_int64, c_int, c_float, c_uint32, c_uint64, _P, _P, _P]),
     "ddrl_dqn_eval": (c_int, [POINTER(DqnConfig), _P, c_int32, c_uint32, c_uint32, c_int32, c_int, c_float, c_uint32, c_uint64, _P, _P, _P, _P]),

@@ -12,6 +12,8 @@
 // one Adam over main/q1, polyak over all.  Layers 1 and 2 (obs_dim is arbitrary here) are jobs of the generic MFMA GEMM kernel,
 // the head (its forward for every evaluation, the reference's row logic, its dgrad) is ONE launch (k_dqn_head), Adam + polyak one
 // flat launch that also finishes the loss mean: 6 launches per update (+ a staging launch when the rows cannot be read in place).
+// The learner loop (dqn_loop.hip, ddrl_dqn_loop_*) runs the narrow update out of one of two input sets that its own sampler fills in
+// place — those 6 launches and nothing else, the next update's draw riding in the head launch (k_dqn_head_sample).
 // Wide observations (obs_dim >= 1024, config 5's 28 224) take layer 1 through the tiled kernels of wide_l1.h instead (forward split
 // over K + reduce; the weight gradient as equal shares of the stage sequence, k_wide_sk), reading the caller's observation rows in place.
 // variant DDRL_SQN = the soft-Q learner of algos/sqn/actor_learner.py:19-78 on algos/sqn/core.py:30-79:
@@ -83,7 +85,7 @@ __device__ __forceinline__ void head_q4(const HeadArgs &a, const float *sH, cons
         }
     }
 }
-__global__ void __launch_bounds__(256) k_dqn_head(HeadArgs a) {
+__device__ __forceinline__ void head_body(const HeadArgs &a) {
     // the workgroup's H2 rows and every evaluation's [W3 ; b3] are staged into LDS with ALL loads in flight at once (the first cut
     // read them inside the dot-product loops: 30 dependent round trips per wave, 30 us for 3.7 MFLOP)
     extern __shared__ __attribute__((aligned(16))) float hsm[];
@@ -248,6 +250,67 @@ __global__ void __launch_bounds__(256) k_dqn_head(HeadArgs a) {
         a.part[blockIdx.x] = p;
     }
 }
+__global__ void __launch_bounds__(256) k_dqn_head(HeadArgs a) { head_body(a); }
+
+// ------------------------------------------------------------------------------------------
+// The learner loop's sampler (ddrl_dqn_loop_*): `idxs = np.random.randint(0, size, B)` of the ring's own MT19937 stream
+// (ddrl_replay_dev::sample_block, the draw every other path runs) and the five gathers, written where the update reads them — rows of
+// ldx floats in the padded images x1 / x2 of one of the learner's two input sets (their ones column is physical and untouched), acts /
+// rew / done beside them — so that an update of the loop has no staging launch.  One workgroup of 256 lanes.  The draw leaves the
+// indices in `idx` (B words of the learner's slab); the gather behind the barrier reads them back: the workgroup's own stores through
+// the CU's vector cache, one round trip, off every update's dependent chain (the sampler rides beside an update, see below).
+// sample_block and its dense gather (replay_device.h) are used as they are: the SAC1 launches that embed them compile from unchanged
+// sources.  A feed plan is not followed here (fuse_gather = 0 skips it): ddrl_dqn_loop_run refuses a fed ring.
+// ------------------------------------------------------------------------------------------
+struct SetSampler {
+    ddrl_replay_dev::RingState *st;
+    ddrl_replay_dev::RingPtrs ring;   // (obs1[obs], obs2[obs], acts, rews, done), float32
+    long long *idx;
+    float *x1, *x2, *acts, *rew, *done;
+    int B, obs, ldx;
+};
+__device__ __forceinline__ void sample_into_set(const SetSampler &m) {
+    const bool rows = m.st->size > 0;   // (nothing in this launch stores into the ring) an empty ring: the draw raises the sticky error
+    ddrl_replay_dev::sample_block(m.st, m.ring, ddrl_replay_dev::BatchPtrs{}, m.B, m.idx, 0);
+    if (!rows) return;
+    __syncthreads();
+    const int tid = threadIdx.x;
+    const float *r1 = m.ring.a[0], *r2 = m.ring.a[1];
+    if ((m.obs & 3) == 0 && ddrl_replay_dev::aligned16(r1, r2) && ddrl_replay_dev::aligned16(m.x1, m.x2)) {   // (ldx is a multiple of 4)
+        const int w4 = m.obs >> 2, l4 = m.ldx >> 2;
+        const float4 *s1 = reinterpret_cast<const float4 *>(r1), *s2 = reinterpret_cast<const float4 *>(r2);
+        float4 *d1 = reinterpret_cast<float4 *>(m.x1), *d2 = reinterpret_cast<float4 *>(m.x2);
+        for (int e = tid; e < m.B * w4; e += 256) {
+            const int b = e / w4, c = e - b * w4;
+            const long long r = m.idx[b] * w4 + c;
+            const float4 u = s1[r], v = s2[r];
+            d1[b * l4 + c] = u; d2[b * l4 + c] = v;
+        }
+    } else {
+        for (int e = tid; e < m.B * m.obs; e += 256) {
+            const int b = e / m.obs, c = e - b * m.obs;
+            const long long r = m.idx[b] * m.obs + c;
+            const float u = r1[r], v = r2[r];
+            m.x1[b * m.ldx + c] = u; m.x2[b * m.ldx + c] = v;
+        }
+    }
+    for (int b = tid; b < m.B; b += 256) {
+        const long long r = m.idx[b];
+        m.acts[b] = m.ring.a[2][r]; m.rew[b] = m.ring.a[3][r]; m.done[b] = m.ring.a[4][r];
+    }
+}
+// a call's first draw: a launch of its own
+__global__ void __launch_bounds__(256) k_dqn_sample(SetSampler m) { sample_into_set(m); }
+// The sampler of update u + 1 rides in update u's HEAD launch, as the workgroup behind the head's own: it writes the other input set and
+// the ring's sampler state, the head reads H2 and its own set's acts / rew / done — independent.  Why the head and not the Adam launch
+// (where SAC1's generic path carries its sampler): k_adam_polyak and sample_block's gather live in the headers the SAC1 update compiles
+// from; a strided gather and a second extra workgroup there would change those kernels' sources for a DQN feature.  The head launch is
+// this file's own, sits in the middle of the update (the draw is done long before the next update's layer 1 asks for it), and its
+// grid at the lander's batch (32 workgroups) leaves the 256 CUs mostly idle anyway.
+__global__ void __launch_bounds__(256) k_dqn_head_sample(HeadArgs a, SetSampler m, int head_blocks) {
+    if ((int)blockIdx.x == head_blocks) { sample_into_set(m); return; }
+    head_body(a);
+}
 
 // acts / rews / done of the sampled rows (ddrl_dqn_step_ring: the observation rows stay in the ring)
 __global__ void __launch_bounds__(256) k_dqn_gather3(const float *__restrict__ ra, const float *__restrict__ rr, const float *__restrict__ rd,
@@ -395,10 +458,13 @@ struct ddrl_dqn {
     float *slab;
     float *main_p, *target_p, *m, *v, *grad;
     float *x1, *x2, *acts, *rew, *done, *H1, *H2, *Q, *dQ, *dZ2, *dZ1, *loss, *qsel;
+    float *set1[5];       // the second input set (x1, x2, acts, rew, done) of the learner loop, narrow path only: update u reads one set while
+                          // the sampler of update u + 1 fills the other (ddrl_dqn_loop_*); every other entry point lives on set 0 above
     int ldx, ldh1, ldh2, ldq;
     OptState *opt;
     int opt_cur;
     Seg *segs_d;
+    GemmJobs g_f1_s1, g_b1_s1;               // the two launches that read the observation images, built on set 1
     GemmJobs g_f1, g_f2, g_f3, g_b2, g_b1;   // g_f3: the head forward as GEMM jobs, ddrl_dqn_q only (the update's head lives in k_dqn_head)
     HeadArgs head;
     float *hpart;
@@ -445,6 +511,24 @@ static int dqn_poison_check(ddrl_dqn *h, hipStream_t s, bool drain) {
                     "refuses to step or export until it is given fresh parameters (set_weights / import of the main parameters, e.g. from a "
                     "checkpoint); it then runs the tile-per-workgroup kernel (DDRL_WIDE_SK=0 selects that from the start).");
     return DDRL_ERR_HIP;
+}
+
+// Dynamic LDS of a head launch: the attribute belongs to the function (which: 0 k_dqn_head, 1 k_dqn_head_sample) on this device, not to
+// the handle: it only ever grows
+static int head_grant_lds(int device, int which, size_t need) {
+    static size_t granted[2][64] = {{0}};
+    static std::mutex granted_mu;
+    std::lock_guard<std::mutex> lk(granted_mu);
+    if (device >= 0 && device < 64 && need > granted[which][device]) {
+        const void *fn = which ? reinterpret_cast<const void *>(k_dqn_head_sample) : reinterpret_cast<const void *>(k_dqn_head);
+        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
+        if (ea != hipSuccess) {
+            ddrl::set_error("hipFuncSetAttribute(%s, %zu bytes of LDS): %s", which ? "k_dqn_head_sample" : "k_dqn_head", need, hipGetErrorString(ea));
+            return DDRL_ERR_HIP;
+        }
+        granted[which][device] = need;
+    }
+    return DDRL_OK;
 }
 
 extern "C" {
@@ -517,6 +601,8 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
     if (h->wide) {
         wide_plan(h->wf, nev_all, B, h1, o, true, 4, 512);
         ALLOC(wpart, wide_part_floats(h->wf)); ALLOC(wconsts, 8);
+    } else {
+        ALLOC(set1[0], (size_t)B * h->ldx); ALLOC(set1[1], (size_t)B * h->ldx); ALLOC(set1[2], B); ALLOC(set1[3], B); ALLOC(set1[4], B);
     }
 #undef ALLOC
     const size_t opt_off = reserve((2 * sizeof(OptState) + 3) / 4);
@@ -548,6 +634,10 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
     }
     k_fill_col<<<(B + 255) / 256, 256>>>(h->x1, B, h->ldx, o, 1.0f);
     k_fill_col<<<(B + 255) / 256, 256>>>(h->x2, B, h->ldx, o, 1.0f);
+    if (!h->wide) {
+        k_fill_col<<<(B + 255) / 256, 256>>>(h->set1[0], B, h->ldx, o, 1.0f);
+        k_fill_col<<<(B + 255) / 256, 256>>>(h->set1[1], B, h->ldx, o, 1.0f);
+    }
     k_fill_col<<<(5 * B + 255) / 256, 256>>>(h->H1, 5ll * B, h->ldh1, h1, 1.0f);
     k_fill_col<<<(5 * B + 255) / 256, 256>>>(h->H2, 5ll * B, h->ldh2, h2, 1.0f);
     DDRL_LAUNCH_CHECK();
@@ -567,6 +657,7 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
             h->wf_x2[ev] = xin[ev] == h->x2;
         }
         gemm_add(h->g_f1, gemm_fwd(xin[ev], h->ldx, par[ev] + h->W1[n], par[ev] + h->b1[n], h->H1 + ev * BH1, h->ldh1, B, o, h1));
+        if (!h->wide) gemm_add(h->g_f1_s1, gemm_fwd(h->set1[xin[ev] == h->x2 ? 1 : 0], h->ldx, par[ev] + h->W1[n], par[ev] + h->b1[n], h->H1 + ev * BH1, h->ldh1, B, o, h1));
         gemm_add(h->g_f2, gemm_fwd(h->H1 + ev * BH1, h->ldh1, par[ev] + h->W2[n], par[ev] + h->b2[n], h->H2 + ev * BH2, h->ldh2, B, h1, h2));
         GemmJob j = gemm_fwd(h->H2 + ev * BH2, h->ldh2, par[ev] + h->W3[n], par[ev] + h->b3[n], h->Q + ev * BQ, h->ldq, B, h2, A);
         j.relu = 0;
@@ -582,6 +673,7 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
         gemm_add(h->g_b2, gemm_dgrad(dZ2, Pm + h->W2[n], h->H1 + ev * BH1, h->ldh1, dZ1, B, h1, h2));
         gemm_add(h->g_b2, gemm_wgrad(h->H1 + ev * BH1, h->ldh1, h1, dZ2, h2, h2, G + h->W2[n], h2, B));
         gemm_add(h->g_b1, gemm_wgrad(h->x1, h->ldx, o, dZ1, h1, h1, G + h->W1[n], h1, B));
+        if (!h->wide) gemm_add(h->g_b1_s1, gemm_wgrad(h->set1[0], h->ldx, o, dZ1, h1, h1, G + h->W1[n], h1, B));
         if (h->wide) {   // [dW1 ; db1] = [x | 1]^T dZ1: the bias row follows the kernel in the flat gradient
             wide_plan(h->ww[n], 1, o + 1, h1, B, false, 4, 0);
             h->ww[n].ev[0] = WideEval{h->x1, dZ1, nullptr, G + h->W1[n], h->ldx};
@@ -639,20 +731,9 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
         ddrl_dqn_destroy(h);
         return DDRL_ERR_BAD_ARG;
     }
-    {   // the attribute belongs to the function on this device, not to the handle: it only ever grows
-        static size_t granted[64] = {0};
-        static std::mutex granted_mu;
-        std::lock_guard<std::mutex> lk(granted_mu);
-        const size_t need = head_lds_bytes(h->head);
-        if (device >= 0 && device < 64 && need > granted[device]) {
-            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head), hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-            if (ea != hipSuccess) {
-                ddrl::set_error("hipFuncSetAttribute(k_dqn_head, %zu bytes of LDS): %s", need, hipGetErrorString(ea));
-                ddrl_dqn_destroy(h);
-                return DDRL_ERR_HIP;
-            }
-            granted[device] = need;
-        }
+    if (const int lrc = head_grant_lds(device, 0, head_lds_bytes(h->head))) {
+        ddrl_dqn_destroy(h);
+        return lrc;
     }
     {   // the acting forward, where k_actor_fwd takes the shape (direct_ok of sac1.hip on (obs, half, h1, h2))
         if (A > ddrl_sel::MAXQ) h->act_why = "n_actions > 8 (the acting forward has 8 head rows)";
@@ -732,6 +813,18 @@ int ddrl_dqn_import(ddrl_dqn_t *h, int which, const float *flat_d, void *stream)
 
 }  // extern "C"
 
+// The update's last launch: flat Adam + polyak out of the current copy of the optimizer state into the other one, + one workgroup: the
+// loss mean from k_dqn_head's partials
+static void dqn_launch_adam(ddrl_dqn_t *h, float *loss_d, hipStream_t s) {
+    const int B = h->cfg.batch;
+    const long long blocks = (h->total_int / 4 + 255) / 256;
+    h->ad.adam_blocks = (int)blocks;
+    h->ad.opt = h->opt + h->opt_cur; h->ad.opt_next = h->opt + (h->opt_cur ^ 1);
+    h->opt_cur ^= 1;
+    h->ad.loss_part = h->hpart; h->ad.loss_out = h->loss; h->ad.loss_out2 = loss_d; h->ad.loss_n = (B + HEAD_ROWS - 1) / HEAD_ROWS; h->ad.loss_scale = 0.5f / (float)B;
+    k_adam_polyak<<<(unsigned)blocks + 1, 256, 0, s>>>(h->ad);
+}
+
 // The launches of one update.  ev != nullptr: an event after every stage (DDRL_DQN_STAGES + 1 events, ev[0] first) for
 // ddrl_dqn_step_timed; the update itself is the same either way.
 // ridx != nullptr: obs1_d / obs2_d are the replay ring's observation arrays and batch row r is their row ridx[r] (ddrl_dqn_step_ring).
@@ -800,14 +893,7 @@ static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2
         launch_gemm(h->g_b1, s);
     }
     STAGE_MARK();   // 7 layer-1 wgrad
-    {
-        const long long blocks = (h->total_int / 4 + 255) / 256;
-        h->ad.adam_blocks = (int)blocks;
-        h->ad.opt = h->opt + h->opt_cur; h->ad.opt_next = h->opt + (h->opt_cur ^ 1);
-        h->opt_cur ^= 1;
-        h->ad.loss_part = h->hpart; h->ad.loss_out = h->loss; h->ad.loss_out2 = loss_d; h->ad.loss_n = (B + HEAD_ROWS - 1) / HEAD_ROWS; h->ad.loss_scale = 0.5f / (float)B;
-        k_adam_polyak<<<(unsigned)blocks + 1, 256, 0, s>>>(h->ad);   // + one workgroup: the loss mean from k_dqn_head's partials
-    }
+    dqn_launch_adam(h, loss_d, s);
     STAGE_MARK();   // 8 flat Adam + polyak
 #undef STAGE_MARK
     DDRL_LAUNCH_CHECK();
@@ -1000,4 +1086,105 @@ int ddrl_dqn_internal_repack(ddrl_dqn_t *h, void *stream) {
 int ddrl_dqn_internal_forward(ddrl_dqn_t *h, long long n, void *stream, int versioned) {
     if (const int rc = ddrl_dqn_internal_repack(h, stream)) return rc;
     return ddrl_actor_internal_forward(h->act_fwd, n, stream, versioned);
+}
+
+// ---- internal (dqn_loop.hip: ddrl_dqn_loop_*) ---------------------------------------------------------------------
+// internal (replay.hip): the host side of a draw that one of this file's kernels performs
+bool ddrl_replay_internal_has_feed(ddrl_replay_t *h);
+int ddrl_replay_internal_require_rows(ddrl_replay_t *h, void *stream);
+
+// The envelope of the learner loop: the narrow path on a five-array float32 ring of this learner's widths that the one-workgroup sampler
+// can draw and gather at cfg.batch.  Changes nothing but the head kernel's LDS attribute.
+int ddrl_dqn_internal_loop_check(ddrl_dqn_t *h, ddrl_replay_t *replay) {
+    DDRL_REQUIRE(h != nullptr && replay != nullptr, "NULL handle");
+    const int B = h->cfg.batch, o = h->cfg.obs_dim;
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    DDRL_REQUIRE(rv.device == h->device, "the replay ring lives on another device than the learner");
+    if (h->wide) {
+        ddrl::set_error("ddrl_dqn_loop: the wide layer-1 path (obs_dim >= 1024, its stream-K weight gradient spins on flags and can poison the learner) "
+                        "is kept out of graphs: use ddrl_dqn_step_ring per update");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (ddrl_replay_is_window_ring(replay, 0, 0)) {
+        ddrl::set_error("ddrl_dqn_loop: an n-step window ring is not supported by the DQN / SQN learners");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == o && rv.ring.w[1] == o && rv.ring.w[2] == 1 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
+                 "the ring must be (obs1[obs_dim], obs2[obs_dim], acts, rews, done) of this learner's observation width");
+    for (int j = 0; j < 5; ++j)
+        if (rv.ring.kind[j]) {
+            ddrl::set_error("ddrl_dqn_loop: a compact (uint8) ring is not supported: the loop's sampler gathers float32 rows");
+            return DDRL_ERR_UNSUPPORTED;
+        }
+    const long long bytes = (long long)B * (2ll * o + 3) * (long long)sizeof(float);   // what ddrl_replay_can_fuse caps (an empty ring is a run-time error)
+    if (B > ddrl_replay_dev::MAX_FUSED_BATCH || bytes > ddrl_replay_dev::MAX_FUSED_BYTES) {
+        ddrl::set_error("ddrl_dqn_loop: batch %d x %lld bytes per row is over the one-workgroup sampler's caps (%d rows, %lld bytes)", B,
+                        (2ll * o + 3) * (long long)sizeof(float), ddrl_replay_dev::MAX_FUSED_BATCH, ddrl_replay_dev::MAX_FUSED_BYTES);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    // k_dqn_head_sample's static LDS is the head's 1.8 KB + the sampler's two MT19937 states (5 KB; with the gather out of the draw its index
+    // array is gone): beside the 150 KB ddrl_dqn_create allows the head's staging it stays inside the CU's 160 KB
+    return head_grant_lds(h->device, 1, head_lds_bytes(h->head));
+}
+
+static SetSampler dqn_set_sampler(ddrl_dqn_t *h, ddrl_replay_t *replay, int set) {
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    SetSampler m{};
+    m.st = rv.state; m.ring = rv.ring; m.idx = h->ring_idx;
+    m.x1 = set ? h->set1[0] : h->x1; m.x2 = set ? h->set1[1] : h->x2;
+    m.acts = set ? h->set1[2] : h->acts; m.rew = set ? h->set1[3] : h->rew; m.done = set ? h->set1[4] : h->done;
+    m.B = h->cfg.batch; m.obs = h->cfg.obs_dim; m.ldx = h->ldx;
+    return m;
+}
+
+// sample_batch into input set `set` as a launch of its own.  rows: ask the ring first whether it has any (never inside a capture: the
+// mirror may have to be read back)
+int ddrl_dqn_internal_sample_into(ddrl_dqn_t *h, ddrl_replay_t *replay, int set, bool rows, void *stream) {
+    if (rows)
+        if (const int rc = ddrl_replay_internal_require_rows(replay, stream)) return rc;
+    ddrl::DeviceGuard g(h->device);
+    k_dqn_sample<<<1, 256, 0, ddrl::as_stream(stream)>>>(dqn_set_sampler(h, replay, set));
+    DDRL_LAUNCH_CHECK();
+    ddrl_replay_note_sample(replay);
+    return DDRL_OK;
+}
+
+// agent.train on input set `set`: ddrl_dqn_step's launches without the staging one.  ride != nullptr: the next update's sample_batch out of
+// that ring goes into the other set as one more workgroup of the head launch.
+int ddrl_dqn_internal_update(ddrl_dqn_t *h, int set, ddrl_replay_t *ride, float *loss_d, void *stream) {
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    const int B = h->cfg.batch;
+    launch_gemm(set ? h->g_f1_s1 : h->g_f1, s);
+    launch_gemm(h->g_f2, s);
+    HeadArgs H = h->head;
+    if (set) { H.acts = h->set1[2]; H.rew = h->set1[3]; H.done = h->set1[4]; }
+    const int head_blocks = (B + HEAD_ROWS - 1) / HEAD_ROWS;
+    if (ride) k_dqn_head_sample<<<(unsigned)head_blocks + 1, 256, head_lds_bytes(H), s>>>(H, dqn_set_sampler(h, ride, set ^ 1), head_blocks);
+    else k_dqn_head<<<(unsigned)head_blocks, 256, head_lds_bytes(H), s>>>(H);
+    launch_gemm(h->g_b2, s);
+    launch_gemm(set ? h->g_b1_s1 : h->g_b1, s);
+    dqn_launch_adam(h, loss_d, s);
+    DDRL_LAUNCH_CHECK();
+    h->pack_stale = true;   // main moved: the next acting forward repacks its operand copy first
+    ++h->steps_launched;
+    if (ride) ddrl_replay_note_sample(ride);
+    return DDRL_OK;
+}
+
+// Make copy 0 of the double-buffered optimizer state the current one, so that a captured graph starts and ends on the same copy whatever
+// the number of updates it holds (a copy node of sizeof(OptState) bytes in a graph of odd length)
+int ddrl_dqn_internal_opt_sync(ddrl_dqn_t *h, void *stream) {
+    if (h->opt_cur == 0) return DDRL_OK;
+    ddrl::DeviceGuard g(h->device);
+    DDRL_HIP_CHECK(hipMemcpyAsync(h->opt, h->opt + 1, sizeof(OptState), hipMemcpyDeviceToDevice, ddrl::as_stream(stream)));
+    h->opt_cur = 0;
+    return DDRL_OK;
+}
+
+// `n` updates ran out of captured graphs: what their launches do to the host-side state when they are issued eagerly
+void ddrl_dqn_internal_note_updates(ddrl_dqn_t *h, long long n) {
+    if (n <= 0) return;
+    h->pack_stale = true;
+    h->steps_launched += n;
 }

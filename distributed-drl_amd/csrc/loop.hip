@@ -18,6 +18,7 @@
 // the previous update — the job of the reference's `Cache` prefetch process
 // (algos/sac1/sac1.py:103-130).
 #include "ddrl_common.h"
+#include "loop_family.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -36,16 +37,8 @@ struct ddrl_loop {
     uint32_t seed;
     float *buf[2][8];
     int batch;
-    // One captured length.  exec[pre][start][tail]:
-    //   pre   0: head-sampled — opens with a stand-alone sampler launch;  1: pre-sampled — the replay before it drew its first batch
-    //   start the input set of its first update
-    //   tail  1: the last update draws the first batch of the replay that follows (into the set its own last update does not read)
-    // INPUT-SET PARITY: both starting sets are captured where a replay can meet them, nothing is tracked across calls.  A
-    // head-sampled graph starts on set 0 whatever ran before it (its sampler is stream-ordered behind every earlier reader of set 0,
-    // as the single graph's always was); a pre-sampled graph starts where the replay before it left its draw, which is set 1 only
-    // behind an odd number of odd-length replays — an odd `per_graph`, the length-1 graph being the last of any call.  Variants
-    // that no call can reach stay nullptr (variant_needed).  Eager updates keep alternating on `parity` among themselves.
-    struct Graph { int len; hipGraphExec_t exec[2][2][2]; };
+    using Graph = ddrl_family::Graph;   // one captured length and its variants exec[pre][start][tail] (loop_family.h); eager updates keep
+                                        // alternating on `parity` among themselves
     std::vector<Graph> family;  // per_graph, then the powers of two below it, descending
     bool chain;                 // the sampler chain runs across replays (off under DDRL_LOOP_FORK: every replay head-sampled, no tail draw)
     bool captured;
@@ -85,17 +78,11 @@ static int fork_mode() {
 }
 
 static bool variant_needed(const ddrl_loop *h, int len, int pre, int start, int tail) {
-    if (!h->chain) return !pre && !start && !tail;
-    if (start && (!pre || (h->per_graph & 1) == 0)) return false;
-    if (tail && len == 1 && h->per_graph != 1) return false;   // the length-1 remainder ends its call
-    return true;
+    return ddrl_family::variant_needed(h->chain, h->per_graph, len, pre, start, tail);
 }
 
 static void destroy_family(ddrl_loop *h) {
-    for (auto &g : h->family)
-        for (int v = 0; v < 8; ++v)
-            if (g.exec[v >> 2][(v >> 1) & 1][v & 1]) (void)hipGraphExecDestroy(g.exec[v >> 2][(v >> 1) & 1][v & 1]);
-    h->family.clear();
+    ddrl_family::destroy(h->family);
     h->captured = false;
 }
 
@@ -202,11 +189,7 @@ static int capture(ddrl_loop *h, hipStream_t main_s, int n, int mode, int pre, i
 static int capture_family(ddrl_loop *h, hipStream_t main_s) {
     const int mode = fork_mode();
     h->chain = mode == 0;
-    h->family.clear();
-    h->family.push_back(ddrl_loop::Graph{h->per_graph, {}});
-    int p = 1;
-    while (p * 2 < h->per_graph) p *= 2;
-    for (; p >= 1 && p < h->per_graph; p >>= 1) h->family.push_back(ddrl_loop::Graph{p, {}});
+    h->family = ddrl_family::lengths(h->per_graph);
     for (auto &g : h->family)
         for (int v = 0; v < 8; ++v) {
             const int pre = v >> 2, start = (v >> 1) & 1, tail = v & 1;
@@ -266,21 +249,8 @@ int ddrl_loop_run(ddrl_loop_t *h, int64_t n_updates, void *stream) {
             const int rc2 = ddrl_sac1_internal_opt_sync(h->learner, stream);
             if (rc2 != DDRL_OK) return rc2;
         }
-        // Greedy: per_graph-sized replays, then each power of two at most once (left < per_graph <= 2 x the largest of them).
-        // The first replay of the call is head-sampled; each replay that another one follows draws that one's first batch.
-        bool first = true;
-        int set = 0;
-        for (const auto &g : h->family)
-            while (left >= g.len) {
-                const int pre = (!first && h->chain) ? 1 : 0, tail = (h->chain && left > g.len) ? 1 : 0;
-                if (!pre) set = 0;
-                hipGraphExec_t exec = g.exec[pre][set][tail];
-                DDRL_REQUIRE(exec != nullptr, "no captured graph for this replay (internal)");
-                DDRL_HIP_CHECK(hipGraphLaunch(exec, s));
-                set ^= g.len & 1;
-                left -= g.len;
-                first = false;
-            }
+        const int rc3 = ddrl_family::replay(h->family, h->chain, left, s);   // greedy, head-sampled first, tail-sampling all but the last
+        if (rc3 != DDRL_OK) return rc3;
     }
     for (; left > 0; --left) {
         int rc = one_update(h, stream);

@@ -375,6 +375,15 @@ void ddrl_replay_note_store(ddrl_replay_t *h, long long n) {  // host mirror boo
     h->h_steps += n * h->ring.steps_inc;
 }
 
+static int require_rows(ddrl_replay *h, hipStream_t s);
+// Internal (dqn.hip: the DQN / SQN loop's sampler draws AND gathers in a launch of its own kernels): the host side of such a draw.
+// Is a feed plan attached (that sampler does not follow one); are there rows to draw from (DDRL_ERR_EMPTY_BUFFER as every draw reports it)
+bool ddrl_replay_internal_has_feed(ddrl_replay_t *h) { return h->feed_on; }
+int ddrl_replay_internal_require_rows(ddrl_replay_t *h, void *stream) {
+    ddrl::DeviceGuard g(h->device);
+    return require_rows(h, ddrl::as_stream(stream));
+}
+
 // A draw needs rows: the mirror may lag behind graph replays / masked stores, so ask the device before reporting empty
 static int require_rows(ddrl_replay *h, hipStream_t s) {
     if (h->h_size <= 0 || h->h_dirty) {

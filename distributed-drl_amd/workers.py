@@ -980,14 +980,33 @@ class TrainDevice:
         self.run(1)
 
 
+def cut_updates(choices, cnt, push_freq):
+    """The pieces TrainDeviceDQN runs as one ddrl_dqn_loop_run call each: `choices[i]` is the (node, buffer) drawn for update number
+    cnt + i; a piece is a maximal run of one (node, buffer) that no push falls inside — the weights go out after every update whose
+    number is a multiple of push_freq, so a piece ends there.  Returns [((node, buffer), length, push_after)]."""
+    pieces = []
+    for i, key in enumerate(choices):
+        if pieces and pieces[-1][0] == key and not pieces[-1][2]:
+            pieces[-1][1] += 1
+        else:
+            pieces.append([key, 1, False])
+        pieces[-1][2] = (cnt + i) % push_freq == 0
+    return [tuple(p) for p in pieces]
+
+
 class TrainDeviceDQN:
     """Device-resident form of algos/dqn/train.py:213-231 + its Cache (177-210): every update draws from a random buffer of a random
     node (`np.random.choice`, the Cache's draw) — `agent.train_from(buffer)`: the indices come from that buffer's own sampler, the
     layer-1 forward reads the rows where they lie (ddrl_dqn_step_ring) — and the weights go to EVERY node's parameter server after each
     push_freq-th update.  No helper thread: with the buffers in the learner's HBM there is no sample latency left to hide.
-    `node_buffer[node][buffer]` and `node_ps[node]` are plain (same-process) objects."""
+    `node_buffer[node][buffer]` and `node_ps[node]` are plain (same-process) objects.
+    updates_per_graph > 0 (opt-in): the same updates in the same order — the same two `rng.choice` draws per update, the same pushes on
+    the same weights, bit-identical results — but every maximal run of updates on one buffer between two pushes (cut_updates) is ONE
+    ddrl_dqn_loop_run call: sampler and update on the device, replayed from captured graphs of `updates_per_graph` updates and the
+    powers of two below.  A buffer or learner outside that call's envelope (wide observations, a compact ring: DDRL_ERR_UNSUPPORTED at
+    ddrl_dqn_loop_create, decided once per buffer) keeps running `train_from`."""
 
-    def __init__(self, node_ps, node_buffer, opt, learner_index=0, make_agent=None, rng=None):
+    def __init__(self, node_ps, node_buffer, opt, learner_index=0, make_agent=None, rng=None, updates_per_graph=0):
         import numpy as np
         if make_agent is None:
             from .dqn import Learner
@@ -998,18 +1017,69 @@ class TrainDeviceDQN:
         self.agent.set_weights(self.keys, node_ps[0].pull(self.keys))
         self.rng = np.random if rng is None else rng
         self.cnt = 1
+        self.updates_per_graph = int(updates_per_graph)
+        self._loops = {}   # id(ring) -> (ring, loop handle; None: outside ddrl_dqn_loop_create's envelope, runs train_from)
+
+    def __del__(self):
+        loops, self._loops = getattr(self, "_loops", {}), {}
+        for _, h in loops.values():
+            if h:
+                self.agent._lib.ddrl_dqn_loop_destroy(h)
+
+    def _loop_of(self, rb):
+        import ctypes
+        from . import _lib
+        if id(rb) not in self._loops:
+            h = ctypes.c_void_p()
+            rc = self.agent._lib.ddrl_dqn_loop_create(ctypes.byref(h), self.agent._h, rb._h, self.updates_per_graph, _lib.dptr(self.agent.loss))
+            if rc != _lib.DDRL_ERR_UNSUPPORTED:
+                _lib.check(rc)
+            self._loops[id(rb)] = (rb, h if rc == _lib.DDRL_OK else None)
+        return self._loops[id(rb)][1]
+
+    def loop_info(self, rb):
+        """(updates_per_graph, captured, kernel nodes, other nodes) of the buffer's loop handle (ddrl_dqn_loop_info); None without one."""
+        import ctypes
+        from . import _lib
+        h = self._loops.get(id(rb), (None, None))[1]
+        if not h:
+            return None
+        info = (ctypes.c_int32 * 4)()
+        _lib.check(self.agent._lib.ddrl_dqn_loop_info(h, info))
+        return tuple(int(v) for v in info)
+
+    def _push(self):
+        keys, values = self.agent.get_weights()
+        for ps in self.node_ps:
+            ps.push(keys, values)
 
     def run(self, n_updates):
         opt = self.opt
+        if self.updates_per_graph <= 0:
+            for _ in range(int(n_updates)):
+                node_idx = self.rng.choice(opt.num_nodes, 1)[0]
+                buffer_idx = self.rng.choice(opt.num_buffers, 1)[0]
+                self.agent.train_from(self.node_buffer[node_idx][buffer_idx], self.cnt)
+                if self.cnt % opt.push_freq == 0:
+                    self._push()
+                self.cnt += 1
+            return self.cnt - 1
+        from . import _lib
+        choices = []
         for _ in range(int(n_updates)):
             node_idx = self.rng.choice(opt.num_nodes, 1)[0]
-            buffer_idx = self.rng.choice(opt.num_buffers, 1)[0]
-            self.agent.train_from(self.node_buffer[node_idx][buffer_idx], self.cnt)
-            if self.cnt % opt.push_freq == 0:
-                keys, values = self.agent.get_weights()
-                for ps in self.node_ps:
-                    ps.push(keys, values)
-            self.cnt += 1
+            choices.append((node_idx, self.rng.choice(opt.num_buffers, 1)[0]))
+        for (node_idx, buffer_idx), k, push in cut_updates(choices, self.cnt, opt.push_freq):
+            rb = self.node_buffer[node_idx][buffer_idx]
+            h = self._loop_of(rb)
+            if h:
+                _lib.check(self.agent._lib.ddrl_dqn_loop_run(h, k, _lib.stream_ptr()))
+            else:
+                for i in range(k):
+                    self.agent.train_from(rb, self.cnt + i)
+            self.cnt += k
+            if push:
+                self._push()
         return self.cnt - 1
 
 

@@ -604,6 +604,32 @@ int ddrl_dqn_step(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d, const
  * indices.  The forward and the weight gradient read the ring at two different points of the call, so the ring rows must stay unchanged
  * until `stream` has passed the call: stores into this ring must be ordered with it on `stream` (or by an event), never concurrent. */
 int ddrl_dqn_step_ring(ddrl_dqn_t *h, ddrl_replay_t *replay, float *loss_d, float *q_d, int64_t *idx_out_d, void *stream);
+/* The learner's hot loop on the device — n iterations of `batch = replay_buffer.sample_batch(B); agent.train(batch, cnt)`
+ * (algos/dqn/train.py:66-76 + actor_learner.py:110-119; algos/sqn likewise) per call with no host work per update: the discrete
+ * counterpart of ddrl_loop_*, with its contract.  The result equals the sequential sample -> update order, bit for bit what
+ * ddrl_replay_sample + ddrl_dqn_step give (no store can fall inside a call): a call's first update is head-sampled (a stand-alone
+ * sampler launch), each later update's batch is drawn by one more workgroup of the head launch of the update before it — into the
+ * other of the learner's two input sets, as padded rows: no staging launch — and the call's last update draws nothing, so the caller
+ * may store into the ring before the next call.  The first call of at least `updates_per_graph` updates runs one update eagerly
+ * (an empty ring: DDRL_ERR_EMPTY_BUFFER from there, nothing captured), then captures a family of single-branch hipGraphs —
+ * `updates_per_graph` and every power of two below it, the variants a call can reach — and from then on no update of any call runs
+ * eagerly.  updates_per_graph = 0: always eager, through the same two input sets.  loss_d (nullable) receives every update's q_loss
+ * (after a call: the last one's); it is baked into the graphs and must stay valid for the handle's life.  After a call the acting
+ * forward repacks before its next use, as after ddrl_dqn_step.
+ * Envelope (ddrl_dqn_loop_create; anything else is DDRL_ERR_UNSUPPORTED with the reason in ddrl_last_error(), nothing changed): the
+ * narrow layer-1 path (obs_dim < 1024: the wide path's stream-K weight gradient stays out of graphs) on a five-array float32 ring
+ * (obs1[obs_dim], obs2[obs_dim], acts, rews, done) whose batch fits the one-workgroup sampler (<= 4096 rows, <= 256 KiB) — no compact
+ * (uint8) ring, no n-step window ring.  A ring on another device or of another width: DDRL_ERR_BAD_ARG.  ddrl_dqn_loop_run refuses a
+ * ring with a feed plan attached (ddrl_replay_set_feed) with DDRL_ERR_UNSUPPORTED.
+ * ddrl_dqn_loop_info: info_h[4] = {updates_per_graph, captured (0 / 1), kernel nodes, other nodes} — the node counts of the full-length,
+ * head-sampled, non-tail graph, read at capture time: 6 updates_per_graph + 1 kernels, plus one copy node of the optimizer state
+ * where updates_per_graph is odd. */
+typedef struct ddrl_dqn_loop ddrl_dqn_loop_t;
+int ddrl_dqn_loop_create(ddrl_dqn_loop_t **out, ddrl_dqn_t *learner, ddrl_replay_t *replay, int32_t updates_per_graph,
+                         float *loss_d);
+int ddrl_dqn_loop_destroy(ddrl_dqn_loop_t *h);
+int ddrl_dqn_loop_run(ddrl_dqn_loop_t *h, int64_t n_updates, void *stream);
+int ddrl_dqn_loop_info(ddrl_dqn_loop_t *h, int32_t *info_h);
 /* `reps` updates (each exactly ddrl_dqn_step) with a HIP event between the launch groups on `stream`; stage_ms_h[DDRL_DQN_STAGES] receives
  * the mean milliseconds of: 0 input staging (nothing when the rows are read in place), 1 layer-1 forward of all evaluations (+ split-K
  * reduce), 2 layer-2 forward, 3 the head launch (Q of every evaluation, backup / loss / dQ, head dgrad), 4 and 5 unused (0),

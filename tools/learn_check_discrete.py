@@ -3,7 +3,8 @@
 ActorLearnerLoop — on the project's own one-body lander behind gym's discrete action table, with the reference's hyper-parameters
 (algos/sqn/hyperparams.py via dqn.HyperParameters: alpha 0.1, gamma 0.99, lr 1e-3, polyak 0.995, batch 128, hidden [400, 300],
 start_steps 1e4, push_freq 100, a_l_ratio 10).  No tuning, no threshold: the curve is appended to the output file as it comes out.
-python tools/learn_check_discrete.py [seconds=280] [sqn|ddqn] [envs=256] [out=profiles/discrete_learning_curve.txt]"""
+python tools/learn_check_discrete.py [seconds=280] [sqn|ddqn] [envs=256] [out=profiles/discrete_learning_curve.txt] [updates_per_graph=0]
+(updates_per_graph > 0: the learner's loop through ddrl_dqn_loop_run, replayed graphs; 0, the default: the eager path)"""
 import os
 import sys
 import time
@@ -20,6 +21,7 @@ seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 280.0
 variant = sys.argv[2] if len(sys.argv) > 2 else "sqn"
 n = int(sys.argv[3]) if len(sys.argv) > 3 else 256
 out_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "discrete_learning_curve.txt")
+per_graph = int(sys.argv[5]) if len(sys.argv) > 5 else 0
 
 opt = dqn.HyperParameters(obs_dim=8, act_dim=4, env_name="LunarLander-v2", exp_name=variant + "-lander", num_workers=1, a_l_ratio=10)
 opt.num_envs, opt.max_ep_len, opt.variant = n, 1000, variant
@@ -27,7 +29,7 @@ L = dqn.LearnerSQN if variant == "sqn" else dqn.Learner
 ps = d.ParameterServer(*L(opt).get_weights())
 rb = d.ReplayBufferDQN(opt, 0, seed=0)
 rollout = RolloutDeviceDQN(ps, rb, opt)
-trainer = TrainDeviceDQN([ps], [[rb]], opt, make_agent=lambda o_: L(o_, job="learner"), rng=np.random.RandomState(0))
+trainer = TrainDeviceDQN([ps], [[rb]], opt, make_agent=lambda o_: L(o_, job="learner"), rng=np.random.RandomState(0), updates_per_graph=per_graph)
 loop = ActorLearnerLoop(rollout, trainer, opt)
 
 
