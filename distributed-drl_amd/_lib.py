@@ -23,6 +23,8 @@ DDRL_ACT_SAMPLE, DDRL_ACT_DETERMINISTIC = 0, 1   # ddrl_dqn_act / ddrl_rollout_s
 DDRL_REPLAY_ACTS_1D = 1
 DDRL_REPLAY_U8_OBS = 2
 DDRL_ENV_STATE_FIELDS = 32
+DDRL_ENV3_STATE_FIELDS = 66   # the articulated model's block (ddrl_env_state_fields tells which a handle holds)
+DDRL_ENV_ONE_BODY, DDRL_ENV_ARTICULATED = 0, 1   # ddrl_env_model_t.kind
 SAC1_STAGES = 12
 DQN_STAGES = 9   # include/ddrl.h: DDRL_DQN_STAGES
 SAC1_MAIN, SAC1_TARGET, SAC1_ADAM_M, SAC1_ADAM_V, SAC1_GRAD = range(5)
@@ -51,6 +53,14 @@ class DqnConfig(ctypes.Structure):
     def __init__(self, obs_dim, n_actions, hidden1=400, hidden2=300, batch=128, gamma=0.99, lr=1e-3, polyak=0.995, beta1=0.9,
                  beta2=0.999, adam_eps=1e-8, variant=0, alpha=0.1):
         super().__init__(obs_dim, n_actions, hidden1, hidden2, batch, variant, gamma, lr, polyak, beta1, beta2, adam_eps, alpha)
+
+
+class EnvModel(ctypes.Structure):
+    """ddrl_env_model_t; the iteration counts are Box2D's world.Step arguments as gym calls it (6 * 30, 2 * 30)."""
+    _fields_ = [("kind", c_int32), ("velocity_iterations", c_int32), ("position_iterations", c_int32)]
+
+    def __init__(self, kind=DDRL_ENV_ONE_BODY, velocity_iterations=180, position_iterations=60):
+        super().__init__(kind, velocity_iterations, position_iterations)
 
 
 _P = c_void_p  # device pointers and opaque handles cross as void*
@@ -132,6 +142,8 @@ SIGNATURES = {
     "ddrl_actor_act_one": (c_int, [_P, _P, c_uint32, c_uint64, c_int, _P, _P]),
     "ddrl_policy_eval": (c_int, [POINTER(Sac1Config), _P, c_int32, c_uint32, c_uint32, c_int32, _P, _P, _P, _P]),
     "ddrl_env_create": (c_int, [POINTER(_P), c_int, c_int64, c_uint32, c_int32]),
+    "ddrl_env_create_ex": (c_int, [POINTER(_P), c_int, c_int64, c_uint32, c_int32, POINTER(EnvModel)]),
+    "ddrl_env_state_fields": (c_int, [_P]),
     "ddrl_env_destroy": (c_int, [_P]),
     "ddrl_env_reset": (c_int, [_P, _P, _P, _P]),
     "ddrl_env_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),

@@ -482,17 +482,46 @@ struct ddrl_env {
     int max_ep_len;
     float *S;
     EnvStats *stats;
+    int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's only
+    int fields;           // rows of S: DDRL_ENV_STATE_FIELDS or DDRL_ENV3_STATE_FIELDS
 };
+
+// the articulated model's launches (env3.hip)
+int ddrl_env3_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
+int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d,
+                          float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+
+// the entry points whose kernels hold the one-body model refuse an articulated handle before they touch anything
+#define DDRL_ONE_BODY_ONLY(h, what)                                                                                                   \
+    do {                                                                                                                              \
+        if ((h)->kind != DDRL_ENV_ONE_BODY) {                                                                                         \
+            ::ddrl::set_error("%s: not built for the articulated lander (DDRL_ENV_ARTICULATED); its kernel holds the one-body model — " \
+                              "use ddrl_env_step / ddrl_env_step_discrete with the unfused act and store calls", what);                \
+            return DDRL_ERR_UNSUPPORTED;                                                                                              \
+        }                                                                                                                             \
+    } while (0)
 
 extern "C" {
 
 int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len) {
+    return ddrl_env_create_ex(out, device, n_envs, seed, max_ep_len, nullptr);
+}
+
+int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len, const ddrl_env_model_t *model) {
     DDRL_REQUIRE(out != nullptr && n_envs > 0 && max_ep_len > 0, "bad out/n_envs/max_ep_len");
     DDRL_REQUIRE(max_ep_len < (1 << 24), "max_ep_len must stay exact in float32");
+    const int kind = model ? model->kind : DDRL_ENV_ONE_BODY;
+    DDRL_REQUIRE(kind == DDRL_ENV_ONE_BODY || kind == DDRL_ENV_ARTICULATED, "model kind must be DDRL_ENV_ONE_BODY or DDRL_ENV_ARTICULATED");
+    DDRL_REQUIRE(kind == DDRL_ENV_ONE_BODY || (model->velocity_iterations >= 1 && model->position_iterations >= 1),
+                 "the articulated model needs velocity_iterations >= 1 and position_iterations >= 1");
+    const int NF = kind == DDRL_ENV_ARTICULATED ? DDRL_ENV3_STATE_FIELDS : DDRL_ENV_STATE_FIELDS;
     ddrl::DeviceGuard g(device);
     if (!g.ok) { ddrl::set_error("cannot select device %d", device); return DDRL_ERR_HIP; }
     ddrl_env *h = new ddrl_env();
     h->device = device; h->n = n_envs; h->seed = seed; h->max_ep_len = max_ep_len; h->S = nullptr; h->stats = nullptr;
+    h->kind = kind; h->fields = NF;
+    h->vit = kind == DDRL_ENV_ARTICULATED ? model->velocity_iterations : 0;
+    h->pit = kind == DDRL_ENV_ARTICULATED ? model->position_iterations : 0;
     if (hipMalloc((void **)&h->S, (size_t)NF * n_envs * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&h->stats, sizeof(EnvStats)) != hipSuccess) {
         ddrl::set_error("hipMalloc failed for %lld envs", (long long)n_envs);
@@ -501,8 +530,12 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
     }
     DDRL_HIP_CHECK(hipMemset(h->S, 0, (size_t)NF * n_envs * sizeof(float)));
     DDRL_HIP_CHECK(hipMemset(h->stats, 0, sizeof(EnvStats)));
-    k_env_reset<<<(unsigned)((n_envs + 255) / 256), 256, 0, nullptr>>>(h->S, h->n, h->seed, nullptr, nullptr);
-    DDRL_LAUNCH_CHECK();
+    if (kind == DDRL_ENV_ARTICULATED) {
+        if (const int rc = ddrl_env3_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, nullptr, nullptr, nullptr)) return rc;
+    } else {
+        k_env_reset<<<(unsigned)((n_envs + 255) / 256), 256, 0, nullptr>>>(h->S, h->n, h->seed, nullptr, nullptr);
+        DDRL_LAUNCH_CHECK();
+    }
     DDRL_HIP_CHECK(hipStreamSynchronize(nullptr));
     *out = h;
     return DDRL_OK;
@@ -519,6 +552,7 @@ int ddrl_env_destroy(ddrl_env_t *h) {
 int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     ddrl::DeviceGuard g(h->device);
+    if (h->kind == DDRL_ENV_ARTICULATED) return ddrl_env3_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, mask_d, obs_d, stream);
     k_env_reset<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, mask_d, obs_d);
     DDRL_LAUNCH_CHECK();
     return DDRL_OK;
@@ -528,6 +562,9 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
                   uint8_t *ended_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && act_d != nullptr, "NULL handle or action pointer");
     ddrl::DeviceGuard g(h->device);
+    if (h->kind == DDRL_ENV_ARTICULATED)
+        return ddrl_env3_launch_step(0, h->S, h->n, h->seed, h->max_ep_len, h->vit, h->pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d,
+                                     h->stats, stream);
     k_env_step<false><<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
         h->S, h->n, h->seed, (float)h->max_ep_len, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats);
     DDRL_LAUNCH_CHECK();
@@ -538,6 +575,9 @@ int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d,
                            uint8_t *ended_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && act_idx_d != nullptr, "NULL handle or action pointer");
     ddrl::DeviceGuard g(h->device);
+    if (h->kind == DDRL_ENV_ARTICULATED)
+        return ddrl_env3_launch_step(1, h->S, h->n, h->seed, h->max_ep_len, h->vit, h->pit, act_idx_d, obs2_d, rew_d, done_d, next_obs_d,
+                                     ended_d, h->stats, stream);
     k_env_step<true><<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
         h->S, h->n, h->seed, (float)h->max_ep_len, act_idx_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats);
     DDRL_LAUNCH_CHECK();
@@ -548,6 +588,7 @@ int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float ob
                           int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d,
                           void *stream) {
     DDRL_REQUIRE(h != nullptr && act_d != nullptr, "NULL pointer");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_env_step_wrapped");
     DDRL_REQUIRE(action_repeat >= 1 && limit_steps >= 1, "action_repeat and limit_steps must be >= 1");
     ddrl::DeviceGuard g(h->device);
     k_env_step_wrapped<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
@@ -559,6 +600,7 @@ int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float ob
 
 int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream) {
     DDRL_REQUIRE(h != nullptr && actor != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin");
     const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
     DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
     DDRL_REQUIRE(v.obs_dim == 8 && h->n <= v.max_rows && v.device == h->device, "actor / env mismatch (obs_dim 8, max_rows >= n_envs, same device)");
@@ -571,6 +613,7 @@ int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream) {
 int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed, uint64_t noise_ctr,
                       int deterministic, float *act_out_d, float *next_obs_out_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && actor != nullptr && replay != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step");
     const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
     DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
     DDRL_REQUIRE(v.obs_dim == 8 && v.act <= 2 && h->n <= v.max_rows && h->n % 32 == 0 && v.device == h->device,
@@ -632,6 +675,7 @@ static int rollout_discrete_check(ddrl_env_t *h, const ddrl_dqn_rollout_view &v)
 
 int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream) {
     DDRL_REQUIRE(h != nullptr && dqn != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin_discrete");
     const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
     if (const int rc = rollout_discrete_check(h, v)) return rc;
     ddrl::DeviceGuard g(h->device);
@@ -643,6 +687,7 @@ int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream) {
 int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
                                uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && dqn != nullptr && replay != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step_discrete");
     DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     DDRL_REQUIRE(mode == DDRL_ACT_SAMPLE || mode == DDRL_ACT_DETERMINISTIC, "mode must be DDRL_ACT_SAMPLE or DDRL_ACT_DETERMINISTIC");
     const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
@@ -709,17 +754,22 @@ int ddrl_env_stats(ddrl_env_t *h, int64_t *episodes_h, double *ret_sum_h, int64_
     return DDRL_OK;
 }
 
+int ddrl_env_state_fields(ddrl_env_t *h) {
+    DDRL_REQUIRE(h != nullptr, "handle is NULL");
+    return h->fields;
+}
+
 int ddrl_env_get_state(ddrl_env_t *h, float *state_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && state_d != nullptr, "NULL pointer");
     ddrl::DeviceGuard g(h->device);
-    DDRL_HIP_CHECK(hipMemcpyAsync(state_d, h->S, (size_t)NF * h->n * sizeof(float), hipMemcpyDeviceToDevice, ddrl::as_stream(stream)));
+    DDRL_HIP_CHECK(hipMemcpyAsync(state_d, h->S, (size_t)h->fields * h->n * sizeof(float), hipMemcpyDeviceToDevice, ddrl::as_stream(stream)));
     return DDRL_OK;
 }
 
 int ddrl_env_set_state(ddrl_env_t *h, const float *state_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && state_d != nullptr, "NULL pointer");
     ddrl::DeviceGuard g(h->device);
-    DDRL_HIP_CHECK(hipMemcpyAsync(h->S, state_d, (size_t)NF * h->n * sizeof(float), hipMemcpyDeviceToDevice, ddrl::as_stream(stream)));
+    DDRL_HIP_CHECK(hipMemcpyAsync(h->S, state_d, (size_t)h->fields * h->n * sizeof(float), hipMemcpyDeviceToDevice, ddrl::as_stream(stream)));
     return DDRL_OK;
 }
 

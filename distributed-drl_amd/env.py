@@ -13,19 +13,34 @@ import torch
 from . import _lib
 
 
+def _check_model(model):
+    if model not in ("simple", "articulated"):
+        raise ValueError("env model must be \"simple\" or \"articulated\": %r" % (model,))
+    return model
+
+
 class VecLunarLander:
     """n environments stepped by one kernel launch; all tensors stay on the device."""
 
     obs_dim, act_dim, act_high = 8, 2, 1.0
 
-    def __init__(self, n_envs, seed=0, max_ep_len=1000, device=None):
+    def __init__(self, n_envs, seed=0, max_ep_len=1000, device=None, model="simple", velocity_iterations=180, position_iterations=60):
+        """model: "simple" — the one-body lander (ddrl_env_create) — or "articulated" — hull and two jointed legs on Box2D's island
+        solve with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default; ddrl_env_create_ex).
+        The articulated env has reset / step / stats / get_state / set_state; step_wrapped and the fused rollout launches refuse it."""
         _lib.require_gpu()
         self._lib = _lib.load()
         self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.model = _check_model(model)
         h = ctypes.c_void_p()
-        _lib.check(self._lib.ddrl_env_create(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len))
+        if self.model == "simple":
+            _lib.check(self._lib.ddrl_env_create(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len))
+        else:
+            m = _lib.EnvModel(_lib.DDRL_ENV_ARTICULATED, int(velocity_iterations), int(position_iterations))
+            _lib.check(self._lib.ddrl_env_create_ex(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len, ctypes.byref(m)))
         self._h = h
+        self.state_fields = int(self._lib.ddrl_env_state_fields(h))
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
         self.obs = e(self.n, 8)        # observation to act on next
         self.obs2 = e(self.n, 8)       # o2 of the last transition
@@ -80,12 +95,14 @@ class VecLunarLander:
         return int(ep.value), float(rs.value), int(ln.value)
 
     def get_state(self):
-        s = torch.empty(_lib.DDRL_ENV_STATE_FIELDS, self.n, dtype=torch.float32, device=self.device)
+        s = torch.empty(self.state_fields, self.n, dtype=torch.float32, device=self.device)
         _lib.check(self._lib.ddrl_env_get_state(self._h, _lib.dptr(s), _lib.stream_ptr()))
         return s
 
     def set_state(self, s):
         s = s.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(s.shape) != (self.state_fields, self.n):
+            raise ValueError("state block must be [%d, %d] for this env's model, got %s" % (self.state_fields, self.n, tuple(s.shape)))
         _lib.check(self._lib.ddrl_env_set_state(self._h, _lib.dptr(s), _lib.stream_ptr()))
 
 
@@ -136,8 +153,9 @@ class LunarLander:
     reference-style loops (worker_rollout with num_envs == 1, worker_test).  `d` is True at the
     time limit too, as gym's TimeLimit wrapper reports it."""
 
-    def __init__(self, seed=0, max_ep_len=1000):
-        self._vec = VecLunarLander(1, seed=seed, max_ep_len=max_ep_len)
+    def __init__(self, seed=0, max_ep_len=1000, model="simple", velocity_iterations=180, position_iterations=60):
+        self._vec = VecLunarLander(1, seed=seed, max_ep_len=max_ep_len, model=model, velocity_iterations=velocity_iterations,
+                                   position_iterations=position_iterations)
         self.action_space = _ActionSpace(self)
         self.observation_space = _ObsSpace()
         self._fresh = True  # the kernel resets finished envs itself
@@ -171,8 +189,9 @@ class LunarLanderDiscrete(LunarLander):
     `rewards[0]` is the Python-float sum of the step rewards since the last reset() (0.0 after one): the score dqn.Actor.test reads
     at every episode's end (algos/dqn/actor_learner.py:246; the trading env's bookkeeping) — on the lander, the episode's return."""
 
-    def __init__(self, seed=0, max_ep_len=1000):
-        self._vec = VecLunarLanderDiscrete(1, seed=seed, max_ep_len=max_ep_len)
+    def __init__(self, seed=0, max_ep_len=1000, model="simple", velocity_iterations=180, position_iterations=60):
+        self._vec = VecLunarLanderDiscrete(1, seed=seed, max_ep_len=max_ep_len, model=model, velocity_iterations=velocity_iterations,
+                                           position_iterations=position_iterations)
         self.action_space = _DiscreteActionSpace(self)
         self.observation_space = _ObsSpace()
         self._fresh = True
@@ -280,8 +299,14 @@ class Wrapper(object):
 
 
 def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
-    """gym.make stand-in (example/dsac.py:78).  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
+    """gym.make stand-in (example/dsac.py:78).  model="simple" | "articulated" (+ velocity_iterations, position_iterations) is passed on to the env.  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
     `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)."""
+    if on_device and _check_model(kw.get("model", "simple")) != "simple":
+        raise ValueError("env.make(on_device=True, model=%r): the on-device evaluation kernels (ddrl_policy_eval, csrc/eval.hip; ddrl_dqn_eval, "
+                         "csrc/eval_q.hip) hold the one-body lander only — no evaluation kernel for the articulated model is built yet; "
+                         "use on_device=False for a host-stepped env of that model" % (kw.get("model"),))
+    if on_device:
+        kw = {k: v for k, v in kw.items() if k not in ("model", "velocity_iterations", "position_iterations")}
     if env_name == "LunarLander-v2":   # gym's discrete action table on the same lander (action_space.n == 4)
         return DeviceLunarLanderDiscrete(**kw) if on_device else LunarLanderDiscrete(**kw)
     if "LunarLander" not in env_name:

@@ -589,6 +589,17 @@ def worker_train_nstep(ps, replay_buffer, opt, learner_index, make_agent=None, m
 # ------------------------------------------------------------------------------------------
 # device style: everything stays in HBM (plain objects, not actor handles)
 # ------------------------------------------------------------------------------------------
+def _env_model_kw(opt):
+    """The env-model arguments of a rollout worker's envs: `opt.env_model` ("simple", the default, or "articulated") and, for the
+    articulated lander, `opt.env_velocity_iterations` / `opt.env_position_iterations` (gym's 180 / 60 unless set).  On the articulated
+    model the workers run their unfused sequence (act, env.step, store): the fused launches hold the one-body lander."""
+    model = getattr(opt, "env_model", "simple")
+    if model == "simple":
+        return {}
+    return dict(model=model, velocity_iterations=int(getattr(opt, "env_velocity_iterations", 180)),
+                position_iterations=int(getattr(opt, "env_position_iterations", 60)))
+
+
 class RolloutDevice:
     """State of one vectorised rollout worker: `opt.num_envs` envs, one Actor, a local replay
     shard and a ParameterServer (or a comm.ParamBroadcast on multi-GPU runs).
@@ -606,7 +617,7 @@ class RolloutDevice:
         from .env import VecLunarLander
         self.ps, self.rb, self.opt = ps, replay_buffer, opt
         self.env = VecLunarLander(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index),
-                                  max_ep_len=opt.max_ep_len)
+                                  max_ep_len=opt.max_ep_len, **_env_model_kw(opt))
         self.actor = Actor(opt, job="worker", max_rows=opt.num_envs, index=worker_index)
         self.span = ps.span(self.actor.keys) if ps is not None else None
         self._layout = getattr(ps, "layout", 0)
@@ -650,6 +661,7 @@ class RolloutDevice:
             from . import _lib
             from .replay import ReplayBuffer
             ok = isinstance(self.rb, ReplayBuffer) and not getattr(self.rb, "_acts_1d", False) and self.env.n % 32 == 0
+            ok = ok and self.env.model == "simple"   # the fused launch holds the one-body lander (ddrl_rollout_begin refuses the other)
             if ok:
                 ok = self.actor._lib.ddrl_rollout_begin(self.env._h, self.actor._h, _lib.stream_ptr()) == 0
             self._fused, self._fused_live = ok, ok
@@ -723,7 +735,8 @@ class RolloutDeviceDQN:
         from . import dqn
         from .env import VecLunarLanderDiscrete
         self.ps, self.rb, self.opt = ps, replay_buffer, opt
-        self.env = VecLunarLanderDiscrete(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len)
+        self.env = VecLunarLanderDiscrete(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len,
+                                          **_env_model_kw(opt))
         make = getattr(opt, "make_actor", None)
         if make is None:
             cls = dqn.ActorSQN if str(getattr(opt, "variant", "ddqn")).lower() == "sqn" else dqn.Actor
@@ -759,6 +772,7 @@ class RolloutDeviceDQN:
             from . import _lib
             from .replay import ReplayBuffer
             ok = isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
+            ok = ok and self.env.model == "simple"   # the fused launch holds the one-body lander (ddrl_rollout_begin_discrete refuses the other)
             if ok:
                 ok = self.actor._lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr()) == 0
             self._fused, self._fused_live = ok, ok

@@ -459,19 +459,41 @@ int ddrl_actor_act_one(ddrl_actor_t *h, const float *obs_d, uint32_t noise_seed,
  * [n][max_ep_len][12] 16-byte aligned) = per step the observation acted on [8], the action [2], the reward, ended (0 / 1); rows past
  * an episode's end are written as zeros.  Stream-ordered on the CURRENT device: no host synchronisation, no allocation.
  * DDRL_ERR_BAD_ARG unless obs_dim == 8, act_dim == 2, n_episodes >= 1, max_ep_len >= 1 (and max_ep_len, first_episode + n_episodes
- * exact in float32: <= 2^24); DDRL_ERR_UNSUPPORTED outside ddrl_actor_act_one's envelope (a hidden width > 512). */
+ * exact in float32: <= 2^24); DDRL_ERR_UNSUPPORTED outside ddrl_actor_act_one's envelope (a hidden width > 512).
+ * Takes no env handle: the episodes are the ONE-BODY lander's (DDRL_ENV_ONE_BODY); the articulated model has no evaluation kernel yet. */
 int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int32_t n_episodes, uint32_t env_seed, uint32_t first_episode,
                      int32_t max_ep_len, double *ret_d, int32_t *len_d, float *trace_d, void *stream);
 
 /* ===================================================================================== */
 /* Batched lander environment — stands where gym's LunarLanderContinuous-v2 env.step /     */
 /* env.reset are called (example/dsac.py:78-79,102,127).  gym/Box2D are third-party and    */
-/* absent; the dynamics are this build's own Box2D-style rigid-body model, */
-/* validated against oracle/env_oracle.py, not against Box2D ("parity unpinned").          */
+/* absent; the dynamics are this build's own Box2D-style models, validated  */
+/* against their NumPy oracles, not against Box2D ("parity unpinned").  Two models:        */
+/*   DDRL_ENV_ONE_BODY     one rigid body, two rigid leg contact points, 4 contact sweeps   */
+/*                         (oracle/env_oracle.py) — ddrl_env_create, every fused rollout    */
+/*                         launch, the wrapped step, ddrl_policy_eval and ddrl_dqn_eval;     */
+/*   DDRL_ENV_ARTICULATED  hull + two legs on revolute joints (limits, spring-like motor),  */
+/*                         leg-corner contacts against the terrain segments, Box2D's island */
+/*                         solve with create-time iteration counts (tests/lander3_oracle.py)*/
+/*                         — ddrl_env_create_ex; reset / step / step_discrete / stats /     */
+/*                         get_state / set_state only.                                      */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
 
 int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len);
+/* ddrl_env_create with a model.  model == NULL or kind == DDRL_ENV_ONE_BODY: the env of ddrl_env_create bit for bit (the iteration
+ * fields are ignored).  kind == DDRL_ENV_ARTICULATED: the three-body lander; velocity_iterations / position_iterations are the
+ * arguments of Box2D's world.Step (gym: 6*30 and 2*30), each >= 1.  An unknown kind or an iteration count < 1: DDRL_ERR_BAD_ARG.
+ * Given an articulated handle, ddrl_env_step_wrapped, ddrl_rollout_begin / ddrl_rollout_step and ddrl_rollout_begin_discrete /
+ * ddrl_rollout_step_discrete return DDRL_ERR_UNSUPPORTED (reason in ddrl_last_error()) and change nothing: their kernels hold the
+ * one-body model.  The unfused sequence (act + ddrl_env_step[_discrete] + store) works on both. */
+#define DDRL_ENV_ONE_BODY 0
+#define DDRL_ENV_ARTICULATED 1
+typedef struct { int32_t kind, velocity_iterations, position_iterations; } ddrl_env_model_t;
+int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len,
+                       const ddrl_env_model_t *model);
+/* Rows of the handle's state block: DDRL_ENV_STATE_FIELDS (one-body) or DDRL_ENV3_STATE_FIELDS (articulated). */
+int ddrl_env_state_fields(ddrl_env_t *h);
 int ddrl_env_destroy(ddrl_env_t *h);
 /* env.reset() for every env (mask_d == NULL) or for envs with mask_d[i] != 0 (device uint8[n]).
  * obs_d[n,8] receives the current observation of every env. */
@@ -547,9 +569,10 @@ int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d,
  * sum of their returns and lengths.  Synchronises `stream`; resets the accumulators. Host outs. */
 int ddrl_env_stats(ddrl_env_t *h, int64_t *episodes_h, double *ret_sum_h, int64_t *len_sum_h,
                    void *stream);
-/* Raw state access for parity tests: copies the [DDRL_ENV_STATE_FIELDS, n] float32 state block
+/* Raw state access for parity tests: copies the [ddrl_env_state_fields(h), n] float32 state block
  * to / from a device buffer. */
 #define DDRL_ENV_STATE_FIELDS 32
+#define DDRL_ENV3_STATE_FIELDS 66
 int ddrl_env_get_state(ddrl_env_t *h, float *state_d, void *stream);
 int ddrl_env_set_state(ddrl_env_t *h, const float *state_d, void *stream);
 
@@ -705,7 +728,8 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
  * device: no host synchronisation, no allocation.
  * DDRL_ERR_BAD_ARG unless obs_dim == 8, n_actions >= 1, n_episodes >= 1, max_ep_len >= 1, hidden sizes >= 1, max_ep_len and
  * first_episode + n_episodes exact in float32 (<= 2^24), trace_d 16-byte aligned and a valid mode; DDRL_ERR_UNSUPPORTED with the
- * reason in ddrl_last_error() for a hidden width > 512 or n_actions > 8. */
+ * reason in ddrl_last_error() for a hidden width > 512 or n_actions > 8.
+ * Takes no env handle: the episodes are the ONE-BODY lander's (DDRL_ENV_ONE_BODY); the articulated model has no evaluation kernel yet. */
 int ddrl_dqn_eval(const ddrl_dqn_config_t *cfg, const float *q_flat_d, int32_t n_episodes, uint32_t env_seed, uint32_t first_episode,
                   int32_t max_ep_len, int mode, float greedy_prob, uint32_t noise_seed, uint64_t noise_ctr, double *ret_d, int32_t *len_d,
                   float *trace_d, void *stream);
