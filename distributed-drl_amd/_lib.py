@@ -23,6 +23,7 @@ DDRL_ACT_SAMPLE, DDRL_ACT_DETERMINISTIC = 0, 1   # ddrl_dqn_act / ddrl_rollout_s
 DDRL_REPLAY_ACTS_1D = 1
 DDRL_REPLAY_U8_OBS = 2
 DDRL_ENV_STATE_FIELDS = 32
+DDRL_NSTEP_FUSED_MAX_LN = 16   # include/ddrl.h: the fused n-step rollout step stages a workgroup's windows in LDS
 DDRL_ENV3_STATE_FIELDS = 66   # the articulated model's block (ddrl_env_state_fields tells which a handle holds)
 DDRL_ENV_ONE_BODY, DDRL_ENV_ARTICULATED = 0, 1   # ddrl_env_model_t.kind
 SAC1_STAGES = 12
@@ -64,6 +65,12 @@ class EnvModel(ctypes.Structure):
 
 
 _P = c_void_p  # device pointers and opaque handles cross as void*
+
+
+class RolloutNStepOut(ctypes.Structure):
+    """ddrl_rollout_nstep_out_t: device mirrors of ddrl_rollout_step_nstep, each nullable."""
+    _fields_ = [("act", _P), ("obs2", _P), ("rew", _P), ("done", _P), ("next_obs", _P), ("ended", _P)]
+
 
 # name -> (restype, argtypes).  Must list every symbol include/ddrl.h declares
 # (tests/test_workers_cpu.py checks header <-> table <-> library).
@@ -194,6 +201,9 @@ SIGNATURES = {
     "ddrl_winq_begin": (c_int, [_P, _P, _P, _P]),
     "ddrl_winq_push": (c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "ddrl_winq_buffers": (c_int, [_P, POINTER(_P), POINTER(_P)]),
+    "ddrl_rollout_begin_nstep": (c_int, [_P, _P, _P, _P]),
+    "ddrl_rollout_step_nstep": (c_int, [_P, _P, _P, _P, c_int32, c_float, c_float, c_float, c_int32, c_int32, c_int32, c_uint32, c_uint64,
+                                        _P, _P]),
     "ddrl_normal_fill": (c_int, [_P, c_int64, c_uint32, c_uint64, _P]),
     "ddrl_uniform_fill": (c_int, [_P, c_int64, c_float, c_float, c_uint32, c_uint64, _P]),
 }

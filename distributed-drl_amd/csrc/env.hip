@@ -14,6 +14,7 @@
 #include "env_device.h"
 #include "dqn_select.h"
 #include "version_plan.h"
+#include "rollout_nstep.h"
 
 namespace {
 
@@ -736,6 +737,124 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
         DDRL_LAUNCH_CHECK();
         if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
         ddrl_replay_note_store(replay, h->n);
+    }
+    return DDRL_OK;
+}
+
+// the fused n-step step's envelope (kernel: rollout_nstep.hip): 0, or the status with the reason in ddrl_last_error().  Nothing is
+// launched or written before it has passed.
+static int rollout_nstep_check(ddrl_env_t *h, const ddrl_actor_rollout_view &v, const ddrl_winq_view &q) {
+    if (h->n % 32 != 0) {   // (first: an actor for such a row count has no direct-operand policy either, which says less)
+        ddrl::set_error("fused n-step rollout step needs n_envs a multiple of 32 (n_envs %lld); use the unfused calls", h->n);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (!v.ok) {
+        ddrl::set_error("fused n-step rollout step: the actor has no direct-operand policy (shape outside the envelope); use "
+                        "ddrl_actor_act + ddrl_env_step_wrapped + ddrl_winq_push + ddrl_replay_store_masked_ex");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (v.obs_dim != 8 || v.act != 2 || h->n % 32 != 0 || h->n > v.max_rows || (v.n_slots > 0 && h->n != v.max_rows)) {
+        ddrl::set_error("fused n-step rollout step needs obs_dim 8, act_dim 2 and n_envs a multiple of 32 within the actor's max_rows (all of "
+                        "them with a version store): obs_dim %d, act_dim %d, n_envs %lld, max_rows %lld", v.obs_dim, v.act, h->n, v.max_rows);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (q.n != h->n || q.obs != 8 || q.act != 2) {
+        ddrl::set_error("fused n-step rollout step: the window queues hold %lld envs of obs_dim %d, act_dim %d; the envs are %lld of 8 and 2",
+                        q.n, q.obs, q.act, h->n);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (q.Ln > DDRL_NSTEP_FUSED_MAX_LN) {
+        ddrl::set_error("fused n-step rollout step: Ln %d is above DDRL_NSTEP_FUSED_MAX_LN (%d: the workgroup's windows are staged in LDS); use "
+                        "the unfused calls", q.Ln, DDRL_NSTEP_FUSED_MAX_LN);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    DDRL_REQUIRE(v.device == h->device && q.device == h->device, "actor, window queues and envs must live on one device");
+    return DDRL_OK;
+}
+static int rollout_nstep_ring_check(ddrl_env_t *h, const ddrl_winq_view &q, const ddrl_replay_dev::SamplerView &rv) {
+    const ddrl_replay_dev::RingPtrs &r = rv.ring;
+    if (r.n_arr != 4) {
+        ddrl::set_error("fused n-step rollout step stores into a four-array window ring {o, a, r, d}; this ring has %d arrays", r.n_arr);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (r.kind[0] || r.kind[1] || r.kind[2] || r.kind[3]) {
+        ddrl::set_error("fused n-step rollout step stores into float32 rings only (not a compact uint8 ring)");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (r.w[0] != (q.Ln + 1) * 8 || r.w[1] != q.Ln * 2 || r.w[2] != q.Ln || r.w[3] != q.Ln) {
+        ddrl::set_error("fused n-step rollout step: the ring's rows {%d, %d, %d, %d} are not the queues' windows {(Ln+1)*8, Ln*2, Ln, Ln} at Ln %d",
+                        r.w[0], r.w[1], r.w[2], r.w[3], q.Ln);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    const unsigned long long al_o = reinterpret_cast<unsigned long long>(r.a[0]) | reinterpret_cast<unsigned long long>(q.o);
+    const unsigned long long al_a = reinterpret_cast<unsigned long long>(r.a[1]) | reinterpret_cast<unsigned long long>(q.a);
+    if (r.capacity >= (1ll << 31) || (al_o & 15ull) || (al_a & 7ull)) {
+        ddrl::set_error("fused n-step rollout step: ring capacity must be below 2^31 and the window arrays vector-aligned");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    DDRL_REQUIRE(rv.device == h->device, "the window ring lives on another device than the envs");
+    return DDRL_OK;
+}
+
+int ddrl_rollout_begin_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin_nstep");
+    const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
+    const ddrl_winq_view q = ddrl_winq_internal_view(winq);
+    if (const int rc = rollout_nstep_check(h, v, q)) return rc;
+    ddrl::DeviceGuard g(h->device);
+    return ddrl_nstep_launch_begin(q.o, h->n, q.Ln, v.obs, q.t, q.save_freq, q.rdy[*q.parity], stream);
+}
+
+int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
+                            float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
+                            int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr, const ddrl_rollout_nstep_out_t *out,
+                            void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr && window_ring != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step_nstep");
+    DDRL_REQUIRE(n_steps >= 1 && action_repeat >= 1 && limit_steps >= 1, "n_steps, action_repeat and limit_steps must be >= 1");
+    const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
+    const ddrl_winq_view q = ddrl_winq_internal_view(winq);
+    if (const int rc = rollout_nstep_check(h, v, q)) return rc;
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(window_ring);
+    if (const int rc = rollout_nstep_ring_check(h, q, rv)) return rc;
+    ddrl::DeviceGuard g(h->device);
+    NStepLaunch a{};
+    a.S = h->S; a.n = h->n; a.seed = h->seed; a.stats = h->stats;
+    a.limit_steps = (float)limit_steps; a.act_noise = act_noise; a.obs_noise = obs_noise; a.reward_scale = reward_scale;
+    a.repeat = action_repeat; a.adopt = adopt_at_episode_end ? 1 : 0;
+    a.obs = v.obs; a.hp = v.hp; a.nt2 = v.nt2; a.scale = v.scale; a.noise_seed = noise_seed;
+    const bool store = v.n_slots > 0;
+    a.slot = store ? v.slot : nullptr;
+    a.newest = store ? reinterpret_cast<const int *>(v.vs) : nullptr;   // VerState::newest is its first word
+    a.vstride = v.vstride;
+    a.perm = v.perm; a.perm2d_off = v.perm2d_off; a.vtiles = v.vtiles; a.vs = reinterpret_cast<VerState *>(const_cast<void *>(v.vs));
+    a.n_slots = v.n_slots; a.col_tiles = v.nt2; a.wg_slots = v.wg_slots; a.vt_cap = v.vt_cap;
+    a.qo = q.o; a.qa = q.a; a.qr = q.r; a.qd = q.d; a.qt = q.t; a.Ln = q.Ln; a.save_freq = q.save_freq;
+    a.rs = rv.state; a.ring = rv.ring;
+    if (out) {
+        a.act_out = out->act; a.obs2_out = out->obs2; a.rew_out = out->rew; a.done_out = out->done; a.next_obs_out = out->next_obs;
+        a.ended_out = out->ended;
+    }
+    for (int k = 0; k < n_steps; ++k) {   // the loop body of worker_rollout, n_steps times with the weights the actor holds
+        // version store: `limit_steps` after the last install every env has been through an episode end — the plain launch on the
+        // actor's current weights (ddrl_rollout_step's test, with the wrapped-step limit; ddrl_actor_act_versioned makes the same one)
+        const bool versioned = store && *v.steps_since_install < (long long)limit_steps;
+        a.versioned = versioned ? 1 : 0;
+        a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
+        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
+        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
+        a.vcnt = fused_plan ? v.vcnt : nullptr;
+        if (store) *v.steps_since_install += 1;
+        if (const int rc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0)) return rc;
+        a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * 2ull;
+        a.rdy_in = q.rdy[*q.parity]; a.rdy_out = q.rdy[1 - *q.parity];
+        if (const int rc = ddrl_nstep_launch_step(a, stream)) return rc;
+        *q.parity = 1 - *q.parity;
+        // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
+        if (versioned) *v.plan_fresh = fused_plan;
+        else if (store && a.adopt) *v.plan_fresh = false;
+        ddrl_replay_note_masked_store(window_ring);   // the row count is known on the device only
     }
     return DDRL_OK;
 }

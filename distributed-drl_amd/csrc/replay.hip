@@ -374,6 +374,7 @@ void ddrl_replay_note_store(ddrl_replay_t *h, long long n) {  // host mirror boo
     h->h_size = (h->h_size + n > h->ring.capacity) ? h->ring.capacity : h->h_size + n;
     h->h_steps += n * h->ring.steps_inc;
 }
+void ddrl_replay_note_masked_store(ddrl_replay_t *h) { h->h_dirty = true; }   // as ddrl_replay_store_masked_ex leaves it (ddrl_rollout_step_nstep)
 
 static int require_rows(ddrl_replay *h, hipStream_t s);
 // Internal (dqn.hip: the DQN / SQN loop's sampler draws AND gathers in a launch of its own kernels): the host side of such a draw.

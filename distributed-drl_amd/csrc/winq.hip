@@ -6,6 +6,7 @@
 // `replay_buffer.store(o_queue, a_r_d_queue)` for every env whose queues are full is one masked row
 // store (ddrl_replay_store_masked_ex) straight from these arrays.
 #include "ddrl_common.h"
+#include "rollout_nstep.h"
 
 namespace {
 
@@ -54,7 +55,14 @@ __global__ void __launch_bounds__(256) k_winq_push(WinQ q, const float *__restri
 struct ddrl_winq {
     int device;
     WinQ q;
+    uint8_t *rdy[2];   // readiness bytes of the fused n-step rollout step (rollout_nstep.h), zero-padded to a multiple of 1024 envs
+    int parity;
 };
+
+ddrl_winq_view ddrl_winq_internal_view(ddrl_winq_t *h) {
+    return ddrl_winq_view{h->q.o, h->q.a, h->q.r, h->q.d, h->q.t, h->q.n, h->q.Ln, h->q.obs, h->q.act, h->q.save_freq, h->device,
+                          {h->rdy[0], h->rdy[1]}, &h->parity};
+}
 
 extern "C" {
 
@@ -62,6 +70,7 @@ int ddrl_winq_destroy(ddrl_winq_t *h) {
     if (!h) return DDRL_OK;
     ddrl::DeviceGuard g(h->device);
     (void)hipFree(h->q.o); (void)hipFree(h->q.a); (void)hipFree(h->q.r); (void)hipFree(h->q.d); (void)hipFree(h->q.t);
+    (void)hipFree(h->rdy[0]); (void)hipFree(h->rdy[1]);
     delete h;
     return DDRL_OK;
 }
@@ -74,10 +83,11 @@ int ddrl_winq_create(ddrl_winq_t **out, int device, int64_t n_envs, int32_t Ln, 
     ddrl_winq *h = new ddrl_winq();
     h->device = device;
     h->q = WinQ{nullptr, nullptr, nullptr, nullptr, nullptr, n_envs, Ln, obs_dim, act_dim, save_freq};
-    const size_t n = (size_t)n_envs;
-    const size_t bytes[5] = {n * (Ln + 1) * obs_dim * 4, n * Ln * act_dim * 4, n * Ln * 4, n * Ln * 4, n * sizeof(int)};
-    void **ptr[5] = {(void **)&h->q.o, (void **)&h->q.a, (void **)&h->q.r, (void **)&h->q.d, (void **)&h->q.t};
-    for (int i = 0; i < 5; ++i) {
+    h->rdy[0] = h->rdy[1] = nullptr; h->parity = 0;
+    const size_t n = (size_t)n_envs, nr = (n + 1023) / 1024 * 1024;
+    const size_t bytes[7] = {n * (Ln + 1) * obs_dim * 4, n * Ln * act_dim * 4, n * Ln * 4, n * Ln * 4, n * sizeof(int), nr, nr};
+    void **ptr[7] = {(void **)&h->q.o, (void **)&h->q.a, (void **)&h->q.r, (void **)&h->q.d, (void **)&h->q.t, (void **)&h->rdy[0], (void **)&h->rdy[1]};
+    for (int i = 0; i < 7; ++i) {
         hipError_t e = hipMalloc(ptr[i], bytes[i]);
         if (e == hipSuccess) e = hipMemset(*ptr[i], 0, bytes[i]);
         if (e != hipSuccess) {

@@ -902,6 +902,13 @@ class RolloutDeviceNStep:
                 self._versions = True
             except ValueError:       # a policy outside the direct-operand envelope: whole-vector swap
                 self._versions = False
+        # The policy phase as two launches (ddrl_rollout_step_nstep): `opt.fused_nstep_rollout`, default True — the measurement behind the
+        # default is profiles/nstep_rollout.txt.  None: not decided yet (_fused_ready); _fused_live: the actor's observation rows and
+        # the queues' readiness bytes are those of the last fused step (no unfused step since; a caller that rewrites the queues or
+        # t_queue by hand between two fused steps clears it, so that ddrl_rollout_begin_nstep runs again).
+        self._fused = None if getattr(opt, "fused_nstep_rollout", True) else False
+        self._fused_live = False
+        self._out = None
 
     pull = RolloutDevice.pull
 
@@ -910,11 +917,52 @@ class RolloutDeviceNStep:
         for _ in range(int(n_steps)):
             self._step_once()
 
+    def _fused_ready(self):
+        """Can this worker take the fused launch pair (ddrl_rollout_step_nstep)?  Decided once.  The fused step evaluates the
+        direct-operand forward, which is what the unfused sequence runs only with the version store on (get_actions_versioned; without
+        it get_actions runs the row-major kernels, whose float32 sums are ordered differently): the store is part of the envelope, so
+        that the two paths stay bit-identical.  The C entry point checks the rest (shapes of env, actor, queues and rings)."""
+        if self._fused is None:
+            from . import _lib
+            from .replay import ReplayBufferNStep
+            ok = self._versions and self.env.model == "simple" and all(isinstance(rb, ReplayBufferNStep) for rb in self.rbs)
+            ok = ok and self.env.n % 32 == 0 and self.winq.Ln <= _lib.DDRL_NSTEP_FUSED_MAX_LN
+            ok = ok and all(rb.max_size < (1 << 31) and rb.Ln == self.winq.Ln and (rb.obs_dim, rb.act_dim) == (8, 2) for rb in self.rbs)
+            if ok:
+                ok = self.actor._lib.ddrl_rollout_begin_nstep(self.env._h, self.actor._h, self.winq._h, _lib.stream_ptr()) == 0
+            if ok:
+                env = self.env
+                self._out = _lib.RolloutNStepOut(act=_lib.dptr(self.act), next_obs=_lib.dptr(env.obs), ended=_lib.dptr(env.ended))
+            self._fused, self._fused_live = ok, ok
+        return self._fused
+
+    def _step_fused(self):
+        """The policy phase of _step_once as the forward + ONE launch (csrc/rollout_nstep.hip); same bits as the sequence below."""
+        import ctypes
+        from . import _lib
+        env, opt, a = self.env, self.opt, self.actor
+        rb = self.rbs[int(self.pick.choice(len(self.rbs), 1)[0])]   # replay_buffer[np.random.choice(opt.num_buffers, 1)[0]]
+        if not self._fused_live:     # the unfused path has touched the env or the queues since: observation rows and readiness bytes anew
+            _lib.check(a._lib.ddrl_rollout_begin_nstep(env._h, a._h, self.winq._h, _lib.stream_ptr()))
+            self._fused_live = True
+        _lib.check(a._lib.ddrl_rollout_step_nstep(env._h, a._h, self.winq._h, rb._h, 1, float(getattr(opt, "act_noise", 0.0)),
+                                                  float(getattr(opt, "obs_noise", 0.0)), float(getattr(opt, "reward_scale", 1.0)),
+                                                  self.WRAPPER_REPEAT, self.limit_steps, 1 if self._learning else 0, a._noise_seed,
+                                                  a._noise_ctr, ctypes.byref(self._out), _lib.stream_ptr()))
+        a._noise_ctr += env.n * a.cfg.act_dim
+        if not self._learning:       # sac_ray.py:255-259, as below: the counters after this step's store decide about THIS step's episode ends
+            self._learning = self.rbs[0].get_counts()[1] > opt.start_steps
+            if self._learning:
+                a.adopt_where_ended(env.ended)
+
     def _step_once(self):
         """One vector step = num_envs iterations of sac_ray.py:208-262."""
         env, opt = self.env, self.opt
         if self._versions:
             self.pull()              # what the server holds now is what an env ending its episode in this step would pull
+        if (self.filling_steps > opt.start_steps or getattr(opt, "weights_file", "")) and self._fused_ready():
+            return self._step_fused()
+        self._fused_live = False
         self.o.copy_(env.obs)
         if self.filling_steps > opt.start_steps or getattr(opt, "weights_file", ""):
             if self._versions:

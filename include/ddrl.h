@@ -754,6 +754,50 @@ int ddrl_winq_push(ddrl_winq_t *h, const float *obs2_d, const float *act_d, cons
 /* Device pointers of the window arrays (o, a, r, d; row = env) and of t_queue (int32[n]). */
 int ddrl_winq_buffers(ddrl_winq_t *h, float **arrays_h, int32_t **t_queue_h);
 
+/* ---- Fused n-step rollout step: one vector step of worker_rollout of the n-step driver (algos/sac1/sac_ray.py:208-262, with the
+ * Wrapper of algos/sac1/hyperparams.py:107-134 around env.step) as TWO launches — the actor's policy forward (plain or versioned, the
+ * test of ddrl_rollout_step with limit_steps in place of max_ep_len) and ONE kernel that, per env and in this order, does what
+ * ddrl_actor_act_versioned's head, ddrl_env_step_wrapped, ddrl_winq_push, ddrl_replay_store_masked_ex, ddrl_actor_versions_adopt and
+ * ddrl_winq_begin(ended) do as launches of their own, bit for bit:
+ *   a = get_action(o) with noise word ddrl_normal_fill(noise_seed, noise_ctr)[i * act_dim + c]   (sac_ray.py:224-227)
+ *   o2, r, d = Wrapper.step(a): action noise, the repeat loop, observation noise, reward scale     (hyperparams.py:122-134)
+ *   ep_len / ep_ret; ended = d or ep_len >= limit_steps; the queued done is the raw d             (sac_ray.py:212-221, 252)
+ *   the env's windows slide by one and take (o2, the NOISY a, r, d); ready = t_queue >= Ln and t_queue % save_freq == 0; t_queue += 1
+ *                                                                                                 (sac_ray.py:229-248)
+ *   ready: the window becomes ring row (ptr + rank) % capacity, rank = number of ready envs with a smaller index (the row order and the
+ *   skip rule of ddrl_replay_store_masked_ex); the cursor advances by the number of ready envs     (sac_ray.py:243-246, 55-69)
+ *   ended: episode statistics, env.reset() with the Wrapper's reset noise, o_queue = [o], t_queue = 1, and — only if
+ *   adopt_at_episode_end — the env moves to the newest policy version of the actor's version store (sac_ray.py:199-207, 252-262)
+ *   the next observation goes into the actor's forward buffer, and the next versioned forward's plan is written by the same launch.
+ * n_steps > 1 repeats the pair with the weights the actor holds; step k draws noise words from noise_ctr + k * n_envs * act_dim.
+ * `out` (nullable, every member nullable) names device mirrors written per step: act[n][2] the NOISY action as Wrapper.step's
+ * `action +=` leaves it, obs2[n][8], rew[n], done[n], next_obs[n][8] (after a reset where the episode ended), ended[n].
+ * The launch reads one of two readiness arrays of the queue handle and writes the other; which is which alternates per launch and is
+ * HOST state of the handle, so a stream capture of this call must hold an even number of steps to be replayable.
+ * ddrl_rollout_begin_nstep writes the envs' current observations — the newest entry of every env's o_queue, i.e. the `o` its worker
+ * holds, Wrapper noise included (sac_ray.py:199-207, 248) — into the actor's forward buffer and rebuilds the queue handle's readiness
+ * bytes from t_queue: call it before the first fused step (behind ddrl_winq_begin) and whenever ddrl_env_*, ddrl_winq_begin or
+ * ddrl_winq_push have touched the env or the queues since the last fused step.
+ * Envelope: one-body lander, obs_dim 8, act_dim 2, n_envs % 32 == 0 within the actor's max_rows (== max_rows with a version store), a
+ * direct-operand actor, a float32 four-array window ring {(Ln+1)*8, Ln*2, Ln, Ln} with capacity < 2^31, a queue handle of the same
+ * n_envs, Ln and dims, Ln <= DDRL_NSTEP_FUSED_MAX_LN, everything on one device.  Outside it: DDRL_ERR_UNSUPPORTED (an articulated env
+ * handle, a ring or queue of another shape, n_envs, Ln) or DDRL_ERR_BAD_ARG (NULL handles, n_steps / action_repeat / limit_steps < 1)
+ * with the reason in ddrl_last_error(), and nothing is changed. */
+#define DDRL_NSTEP_FUSED_MAX_LN 16
+typedef struct {
+    float *act;        /* [n][2] */
+    float *obs2;       /* [n][8] */
+    float *rew;        /* [n] */
+    float *done;       /* [n] */
+    float *next_obs;   /* [n][8] */
+    uint8_t *ended;    /* [n] */
+} ddrl_rollout_nstep_out_t;
+int ddrl_rollout_begin_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream);
+int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
+                            float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
+                            int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr, const ddrl_rollout_nstep_out_t *out,
+                            void *stream);
+
 /* ===================================================================================== */
 /* Counter-based noise (stands in for tf.random_normal, core.py:77, and                    */
 /* env.action_space.sample(), example/dsac.py:99) — same generator as oracle/noise_oracle  */
