@@ -156,6 +156,8 @@ SIGNATURES = {
     "ddrl_env_step": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ddrl_rollout_begin": (c_int, [_P, _P, _P]),
     "ddrl_rollout_step": (c_int, [_P, _P, _P, c_int32, c_uint32, c_uint64, c_int, _P, _P, _P]),
+    "ddrl_rollout_begin_articulated": (c_int, [_P, _P, _P]),
+    "ddrl_rollout_step_articulated": (c_int, [_P, _P, _P, c_int32, c_uint32, c_uint64, c_int, _P, _P, _P]),
     "ddrl_env_step_wrapped": (c_int, [_P, _P, c_float, c_float, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "ddrl_env_step_discrete": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ddrl_rollout_begin_discrete": (c_int, [_P, _P, _P]),

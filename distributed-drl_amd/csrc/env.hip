@@ -15,6 +15,7 @@
 #include "dqn_select.h"
 #include "version_plan.h"
 #include "rollout_nstep.h"
+#include "rollout_args.h"
 
 namespace {
 
@@ -180,50 +181,6 @@ __global__ void __launch_bounds__(256) k_env_step_wrapped(float *S, long long n,
 //   o = o2 (or env.reset())      written into the actor's observation buffer for the next forward launch
 // One thread per env: no exchange between threads except the cursor ticket.
 // ------------------------------------------------------------------------------------------
-// The ring ticket of a fused launch in the form ver_plan_tail (version_plan.h) calls it: the cursor state, the ring and the two numbers BY
-// COPY.  (A lambda that captures the kernel's argument struct by reference does the same thing, and changed the scalar address arithmetic
-// the compiler emits for EVERY kernel of this file, the untouched ones included.)
-struct RingTicket {
-    ddrl_replay_dev::RingState *rs;
-    ddrl_replay_dev::RingPtrs ring;
-    long long ptr, n;
-    __device__ bool operator()() const { return ddrl_replay_dev::ring_commit(rs, ring, ptr, n); }
-};
-struct RolloutArgs {
-    float *S;
-    long long n;
-    uint32_t seed;
-    float max_ep_len;
-    EnvStats *stats;
-    // policy
-    float *obs;            // [n][obs_dim] in / out (actor's buffer)
-    const float *hp;       // [8][n][16]
-    const float *bmu, *bls;
-    int act, nt2;
-    float scale;
-    int deterministic;
-    uint32_t noise_seed;
-    unsigned long long noise_ctr;
-    // version store of the actor (nullable): env i acts on slot[i] (bmu / bls are slot 0's then, slot s is vstride floats further)
-    // and adopts the newest version where its episode ends — the reference worker's pull at episode end (example/dsac.py:127-130)
-    int *slot;
-    const int *newest;
-    long long vstride;
-    // ... and the NEXT forward's plan, written by this launch (nullable: vcnt): every env counts itself into its slot's group and files
-    // itself in that group's row list; the last workgroup to finish turns the counts into the forward's workgroup table (what
-    // k_version_plan does as a launch of its own, 7-11 us between this launch and the forward that waits for it)
-    int *vcnt;             // [VER_MAX_SLOTS], zero on entry, zero again on exit
-    int *perm;             // row lists: group s at perm[perm2d_off + s * n ..)
-    long long perm2d_off;
-    VerTile *vtiles;
-    VerState *vs;
-    int n_slots, col_tiles, wg_slots, vt_cap;
-    // replay ring
-    ddrl_replay_dev::RingState *rs;
-    ddrl_replay_dev::RingPtrs ring;
-    // optional mirrors for the host-side objects
-    float *act_out, *next_obs_out;
-};
 template <int NH>  // head partial rows fetched per env: 4 (act_dim <= 2) or 8
 __global__ void __launch_bounds__(64) k_env_step_pi(RolloutArgs a) {
     __shared__ long long s_ptr;
@@ -502,6 +459,81 @@ int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, in
         }                                                                                                                             \
     } while (0)
 
+// the articulated pair (ddrl_rollout_begin_articulated / _step_articulated) refuses a one-body handle before it touches anything
+#define DDRL_ARTICULATED_ONLY(h, what, instead)                                                                                       \
+    do {                                                                                                                              \
+        if ((h)->kind != DDRL_ENV_ARTICULATED) {                                                                                      \
+            ::ddrl::set_error("%s: built for the articulated lander (DDRL_ENV_ARTICULATED); this handle holds the one-body model — " \
+                              "use %s", what, instead);                                                                               \
+            return DDRL_ERR_UNSUPPORTED;                                                                                              \
+        }                                                                                                                             \
+    } while (0)
+// the articulated pair's envelope, checked before anything is launched or written: DDRL_ERR_UNSUPPORTED with the function's name
+static int rollout3_check(const char *what, ddrl_env_t *h, const ddrl_actor_rollout_view &v, const ddrl_replay_dev::SamplerView *rv) {
+    const char *why = nullptr;
+    if (!v.ok) why = "the actor has no direct-operand policy (shape outside the envelope)";
+    else if (v.obs_dim != 8 || v.act > 2) why = "the actor must have obs_dim 8 and act_dim <= 2";
+    else if (h->n % 32 != 0 || h->n > v.max_rows) why = "n_envs must be a multiple of 32 within the actor's max_rows";
+    else if (v.n_slots > 0 && h->n != v.max_rows) why = "an actor with a version store steps exactly max_rows envs";
+    else if (v.device != h->device) why = "actor and envs must live on one device";
+    else if (rv) {
+        const ddrl_replay_dev::RingPtrs &r = rv->ring;
+        if (r.n_arr != 5 || r.w[0] != 8 || r.w[1] != 8 || r.w[2] != 2 || r.w[3] != 1 || r.w[4] != 1)
+            why = "the replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)";
+        else if (r.kind[0] || r.kind[1]) why = "the fused rollout step stores into float32 rings only (not a compact uint8 ring)";
+        else if (rv->device != h->device) why = "the replay ring lives on another device than the envs";
+    }
+    if (!why) return DDRL_OK;
+    ddrl::set_error("%s: %s; use ddrl_actor_act + ddrl_env_step + ddrl_replay_store", what, why);
+    return DDRL_ERR_UNSUPPORTED;
+}
+
+// The continuous fused step behind ddrl_rollout_step (one-body lander: k_env_step_pi) and ddrl_rollout_step_articulated (rollout3.hip:
+// k_env3_step_pi): the envelope, then n_steps times the loop body of worker_rollout — the forward, `launch(a)`, the host's bookkeeping.
+// `launch` is the two entry points' only difference: it issues the env-step kernel of the handle's model on a filled RolloutArgs.
+template <class Launch>
+static int rollout_step_loop(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed,
+                             uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream, Launch launch) {
+    const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
+    DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
+    DDRL_REQUIRE(v.obs_dim == 8 && v.act <= 2 && h->n <= v.max_rows && h->n % 32 == 0 && v.device == h->device,
+                 "actor / env mismatch (obs_dim 8, act_dim <= 2, n_envs a multiple of 32 within max_rows, same device)");
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == 8 && rv.ring.w[1] == 8 && rv.ring.w[2] == 2 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
+                 "replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)");
+    DDRL_REQUIRE(!rv.ring.kind[0] && !rv.ring.kind[1], "the fused rollout step stores into float32 rings only (not a compact uint8 ring)");
+    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    ddrl::DeviceGuard g(h->device);
+    RolloutArgs a{};
+    a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
+    a.obs = v.obs; a.hp = v.hp; a.bmu = v.bmu; a.bls = v.bls; a.act = v.act; a.nt2 = v.nt2; a.scale = v.scale;
+    a.deterministic = deterministic; a.noise_seed = noise_seed;
+    a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.next_obs_out = next_obs_out_d;
+    const bool store = v.n_slots > 0;
+    DDRL_REQUIRE(!store || h->n == v.max_rows, "an actor with a version store steps exactly max_rows envs");
+    for (int k = 0; k < n_steps; ++k) {  // the loop body of worker_rollout, n_steps times with the weights the actor holds
+        // version store: once no install has happened for max_ep_len steps every env has been through an episode end and
+        // acts on the newest version — the plain launch on the actor's current weights is then the same computation
+        const bool versioned = store && *v.steps_since_install < (long long)h->max_ep_len;
+        a.slot = versioned ? v.slot : nullptr;
+        a.newest = versioned ? reinterpret_cast<const int *>(v.vs) : nullptr;   // VerState::newest is its first word
+        a.vstride = v.vstride;
+        a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
+        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
+        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
+        a.vcnt = fused_plan ? v.vcnt : nullptr; a.perm = v.perm; a.perm2d_off = v.perm2d_off; a.vtiles = v.vtiles;
+        a.vs = reinterpret_cast<VerState *>(const_cast<void *>(v.vs)); a.n_slots = v.n_slots; a.col_tiles = v.nt2; a.wg_slots = v.wg_slots; a.vt_cap = v.vt_cap;
+        if (store) *v.steps_since_install += 1;
+        const int rc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0);
+        if (rc != DDRL_OK) return rc;
+        a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * (uint64_t)v.act;
+        if (const int lrc = launch(a)) return lrc;
+        if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
+        ddrl_replay_note_store(replay, h->n);
+    }
+    return DDRL_OK;
+}
+
 extern "C" {
 
 int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len) {
@@ -615,47 +647,34 @@ int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay,
                       int deterministic, float *act_out_d, float *next_obs_out_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && actor != nullptr && replay != nullptr, "NULL handle");
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step");
+    return rollout_step_loop(h, actor, replay, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
+                             [&](const RolloutArgs &a) -> int {
+                                 // one wave per workgroup: 4096 envs spread over 64 CUs instead of 16 (the kernel is a chain of dependent latencies)
+                                 if (a.act <= 2) k_env_step_pi<4><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
+                                 else k_env_step_pi<8><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
+                                 DDRL_LAUNCH_CHECK();
+                                 return DDRL_OK;
+                             });
+}
+
+// ---- the same pair on the articulated lander (kernels: rollout3.hip)
+int ddrl_rollout_begin_articulated(ddrl_env_t *h, ddrl_actor_t *actor, void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr, "NULL handle");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_begin_articulated", "ddrl_rollout_begin");
     const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
-    DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
-    DDRL_REQUIRE(v.obs_dim == 8 && v.act <= 2 && h->n <= v.max_rows && h->n % 32 == 0 && v.device == h->device,
-                 "actor / env mismatch (obs_dim 8, act_dim <= 2, n_envs a multiple of 32 within max_rows, same device)");
-    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
-    DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == 8 && rv.ring.w[1] == 8 && rv.ring.w[2] == 2 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
-                 "replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)");
-    DDRL_REQUIRE(!rv.ring.kind[0] && !rv.ring.kind[1], "the fused rollout step stores into float32 rings only (not a compact uint8 ring)");
-    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (const int rc = rollout3_check("ddrl_rollout_begin_articulated", h, v, nullptr)) return rc;
     ddrl::DeviceGuard g(h->device);
-    RolloutArgs a{};
-    a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
-    a.obs = v.obs; a.hp = v.hp; a.bmu = v.bmu; a.bls = v.bls; a.act = v.act; a.nt2 = v.nt2; a.scale = v.scale;
-    a.deterministic = deterministic; a.noise_seed = noise_seed;
-    a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.next_obs_out = next_obs_out_d;
-    const bool store = v.n_slots > 0;
-    DDRL_REQUIRE(!store || h->n == v.max_rows, "an actor with a version store steps exactly max_rows envs");
-    for (int k = 0; k < n_steps; ++k) {  // the loop body of worker_rollout, n_steps times with the weights the actor holds
-        // version store: once no install has happened for max_ep_len steps every env has been through an episode end and
-        // acts on the newest version — the plain launch on the actor's current weights is then the same computation
-        const bool versioned = store && *v.steps_since_install < (long long)h->max_ep_len;
-        a.slot = versioned ? v.slot : nullptr;
-        a.newest = versioned ? reinterpret_cast<const int *>(v.vs) : nullptr;   // VerState::newest is its first word
-        a.vstride = v.vstride;
-        a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
-        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
-        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
-        a.vcnt = fused_plan ? v.vcnt : nullptr; a.perm = v.perm; a.perm2d_off = v.perm2d_off; a.vtiles = v.vtiles;
-        a.vs = reinterpret_cast<VerState *>(const_cast<void *>(v.vs)); a.n_slots = v.n_slots; a.col_tiles = v.nt2; a.wg_slots = v.wg_slots; a.vt_cap = v.vt_cap;
-        if (store) *v.steps_since_install += 1;
-        const int rc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0);
-        if (rc != DDRL_OK) return rc;
-        a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * (uint64_t)v.act;
-        // one wave per workgroup: 4096 envs spread over 64 CUs instead of 16 (the kernel is a chain of dependent latencies)
-        if (v.act <= 2) k_env_step_pi<4><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
-        else k_env_step_pi<8><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
-        DDRL_LAUNCH_CHECK();
-        if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
-        ddrl_replay_note_store(replay, h->n);
-    }
-    return DDRL_OK;
+    return ddrl_rollout3_launch_obs(h->S, h->n, v.obs, stream);
+}
+
+int ddrl_rollout_step_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed,
+                                  uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && replay != nullptr, "NULL handle");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_step_articulated", "ddrl_rollout_step");
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    if (const int rc = rollout3_check("ddrl_rollout_step_articulated", h, ddrl_actor_internal_view(actor), &rv)) return rc;
+    return rollout_step_loop(h, actor, replay, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
+                             [&](const RolloutArgs &a) -> int { return ddrl_rollout3_launch_step(&a, h->vit, h->pit, stream); });
 }
 
 // the discrete fused step's envelope: 0, or the status with the reason in ddrl_last_error()

@@ -27,7 +27,9 @@ class VecLunarLander:
     def __init__(self, n_envs, seed=0, max_ep_len=1000, device=None, model="simple", velocity_iterations=180, position_iterations=60):
         """model: "simple" — the one-body lander (ddrl_env_create) — or "articulated" — hull and two jointed legs on Box2D's island
         solve with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default; ddrl_env_create_ex).
-        The articulated env has reset / step / stats / get_state / set_state; step_wrapped and the fused rollout launches refuse it."""
+        The articulated env has reset / step / stats / get_state / set_state; step_wrapped and the fused rollout launches refuse it.
+        (Those are ddrl_rollout_step and its discrete and n-step siblings; the continuous worker's pair for this model,
+        ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated, is reached through workers.RolloutDevice.)"""
         _lib.require_gpu()
         self._lib = _lib.load()
         self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)

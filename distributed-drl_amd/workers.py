@@ -592,7 +592,9 @@ def worker_train_nstep(ps, replay_buffer, opt, learner_index, make_agent=None, m
 def _env_model_kw(opt):
     """The env-model arguments of a rollout worker's envs: `opt.env_model` ("simple", the default, or "articulated") and, for the
     articulated lander, `opt.env_velocity_iterations` / `opt.env_position_iterations` (gym's 180 / 60 unless set).  On the articulated
-    model the workers run their unfused sequence (act, env.step, store): the fused launches hold the one-body lander."""
+    model the workers run their unfused sequence (act, env.step, store): the fused launches of ddrl_rollout_step and its discrete
+    and n-step siblings hold the one-body lander.  The continuous worker alone (RolloutDevice) has a fused step on that model, behind
+    `opt.fused_rollout_articulated` (default False): that flag is RolloutDevice's, and changes nothing here."""
     model = getattr(opt, "env_model", "simple")
     if model == "simple":
         return {}
@@ -609,7 +611,12 @@ class RolloutDevice:
     exactly on the fused path: the actor keeps min(num_envs, max_ep_len) + 2 resident policy versions, pull() stores what the
     server holds as the newest one, and the env-step kernel moves an env to it where that env's episode ends — the vector of envs
     is then indistinguishable from num_envs reference workers stepped in lock step.  "step" (and shapes outside the fused
-    envelope) swaps the weights of every env at the next vector step: never staler than the reference, not identical to it."""
+    envelope) swaps the weights of every env at the next vector step: never staler than the reference, not identical to it.
+
+    The articulated lander (`opt.env_model = "articulated"`) runs the unfused sequence — and so adopts per step — unless
+    `opt.fused_rollout_articulated` is set (default False): then the worker takes ddrl_rollout_begin_articulated /
+    ddrl_rollout_step_articulated, the same launch pair with the three-body solver in the env-step kernel, and "episode" adoption
+    holds on that model too.  The one-body worker ignores the flag."""
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
@@ -654,16 +661,26 @@ class RolloutDevice:
             self.actor.set_weights(self.actor.keys, self.ps.pull_device(self.actor.keys))
         return True
 
+    def _rollout_calls(self):
+        """The fused pair of the envs' model: (begin, step) of the C library."""
+        lib = self.actor._lib
+        if self.env.model == "articulated":
+            return lib.ddrl_rollout_begin_articulated, lib.ddrl_rollout_step_articulated
+        return lib.ddrl_rollout_begin, lib.ddrl_rollout_step
+
     def _fused_ready(self):
-        """Can this worker take the fused launch pair (ddrl_rollout_step)?  Decided once: the actor's shape must be inside
-        the direct-operand envelope and the ring must be the plain five-array SAC layout."""
+        """Can this worker take the fused launch pair (ddrl_rollout_step; on the articulated lander ddrl_rollout_step_articulated,
+        and only with opt.fused_rollout_articulated set)?  Decided once: the actor's shape must be inside the direct-operand
+        envelope and the ring must be the plain five-array SAC layout."""
         if self._fused is None:
             from . import _lib
             from .replay import ReplayBuffer
             ok = isinstance(self.rb, ReplayBuffer) and not getattr(self.rb, "_acts_1d", False) and self.env.n % 32 == 0
-            ok = ok and self.env.model == "simple"   # the fused launch holds the one-body lander (ddrl_rollout_begin refuses the other)
+            # ddrl_rollout_begin holds the one-body lander and refuses the other; the articulated pair is opt-in
+            ok = ok and (self.env.model == "simple" or
+                         (self.env.model == "articulated" and bool(getattr(self.opt, "fused_rollout_articulated", False))))
             if ok:
-                ok = self.actor._lib.ddrl_rollout_begin(self.env._h, self.actor._h, _lib.stream_ptr()) == 0
+                ok = self._rollout_calls()[0](self.env._h, self.actor._h, _lib.stream_ptr()) == 0
             self._fused, self._fused_live = ok, ok
             if ok and self.adopt == "episode" and self.actor.max_rows == self.env.n:
                 # every env on the weights of the initial pull; later pulls become versions adopted at episode ends
@@ -682,10 +699,10 @@ class RolloutDevice:
             self.pull()   # what the server holds NOW is what an env ending its episode in this step pulls (dsac.py:127-130)
         if self.t > self.opt.start_steps and self._fused_ready():
             if not self._fused_live:   # the unfused path has stepped the envs since: refresh the actor's observation rows
-                _lib.check(self.actor._lib.ddrl_rollout_begin(env._h, self.actor._h, _lib.stream_ptr()))
+                _lib.check(self._rollout_calls()[0](env._h, self.actor._h, _lib.stream_ptr()))
                 self._fused_live = True
             a = self.actor
-            _lib.check(a._lib.ddrl_rollout_step(env._h, a._h, self.rb._h, int(n_steps), a._noise_seed, a._noise_ctr, 0, _lib.dptr(self.act),
+            _lib.check(self._rollout_calls()[1](env._h, a._h, self.rb._h, int(n_steps), a._noise_seed, a._noise_ctr, 0, _lib.dptr(self.act),
                                                 _lib.dptr(env.obs), _lib.stream_ptr()))
             a._noise_ctr += int(n_steps) * env.n * a.cfg.act_dim
             self.t += int(n_steps)

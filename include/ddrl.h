@@ -476,7 +476,8 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /*                         leg-corner contacts against the terrain segments, Box2D's island */
 /*                         solve with create-time iteration counts (tests/lander3_oracle.py)*/
 /*                         — ddrl_env_create_ex; reset / step / step_discrete / stats /     */
-/*                         get_state / set_state only.                                      */
+/*                         get_state / set_state, and the continuous fused rollout step     */
+/*                         behind ddrl_rollout_begin_articulated / _step_articulated.       */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
 
@@ -486,7 +487,8 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
  * arguments of Box2D's world.Step (gym: 6*30 and 2*30), each >= 1.  An unknown kind or an iteration count < 1: DDRL_ERR_BAD_ARG.
  * Given an articulated handle, ddrl_env_step_wrapped, ddrl_rollout_begin / ddrl_rollout_step and ddrl_rollout_begin_discrete /
  * ddrl_rollout_step_discrete return DDRL_ERR_UNSUPPORTED (reason in ddrl_last_error()) and change nothing: their kernels hold the
- * one-body model.  The unfused sequence (act + ddrl_env_step[_discrete] + store) works on both. */
+ * one-body model.  The unfused sequence (act + ddrl_env_step[_discrete] + store) works on both; the continuous fused step on an
+ * articulated handle is ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated. */
 #define DDRL_ENV_ONE_BODY 0
 #define DDRL_ENV_ARTICULATED 1
 typedef struct { int32_t kind, velocity_iterations, position_iterations; } ddrl_env_model_t;
@@ -557,6 +559,21 @@ int ddrl_actor_act_versioned(ddrl_actor_t *h, const float *obs_d, const float *e
 int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream);
 int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed,
                       uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream);
+/* The same pair on the ARTICULATED lander (an env handle of ddrl_env_create_ex, kind = DDRL_ENV_ARTICULATED): one vector step of
+ * worker_rollout's policy phase (example/dsac.py:96-130) as the policy-forward launch and ONE launch that finishes get_action, runs the
+ * three-body solver with the handle's iteration counts, appends (o, a, r, o2, d) to the ring, resets the ended envs and — with a
+ * version store — moves an env to the newest version where its episode ends (dsac.py:127-130).  Arguments, noise stream, mirrors,
+ * n_steps and the version store mean what they mean in ddrl_rollout_begin / ddrl_rollout_step; given the same head partials the
+ * action is the one ddrl_rollout_step computes, and the transition is bit for bit ddrl_env_step's on that action.
+ * ddrl_rollout_begin_articulated writes the envs' current observations into the actor's rows (no reset, no step): call it once, and
+ * again after any ddrl_env_step / ddrl_env_reset / ddrl_env_set_state issued outside this path.
+ * Envelope: a direct-operand actor with obs_dim 8 and act_dim <= 2, n_envs a multiple of 32 within max_rows (exactly max_rows with a
+ * version store), a five-array float32 ring (obs1[8], obs2[8], acts[2], rews, done), everything on one device.  Outside it, and on a
+ * one-body handle (use ddrl_rollout_begin / ddrl_rollout_step there): DDRL_ERR_UNSUPPORTED, the function's name and the reason in
+ * ddrl_last_error(), nothing launched or written.  ddrl_rollout_begin / ddrl_rollout_step keep refusing an articulated handle. */
+int ddrl_rollout_begin_articulated(ddrl_env_t *h, ddrl_actor_t *actor, void *stream);
+int ddrl_rollout_step_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed,
+                                  uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream);
 /* ddrl_env_step on gym's discrete LunarLander-v2 action table — the env the discrete drivers step where the reference's own
  * (algos/trading_env.py, a proprietary game.so) cannot be had; worker_rollout_dqn's `env.step(a)`, algos/dqn/train.py:262.
  * act_idx_d[n] holds the index as float32 (the form the DQN ring stores acts in); the index is (int)value clamped to [0, 3]:
