@@ -280,6 +280,13 @@ def stream_ptr():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def aligned(t, nbytes):
+    """`t` (contiguous) itself when its first byte lies on the nbytes grid include/ddrl.h's memory contract asks of a pointer, else a
+    copy in a fresh allocation (torch's allocator hands out 512-byte aligned blocks).  For INPUTS only: a copy cannot stand in for
+    a buffer the library writes — there the library's own refusal (DDRL_ERR_BAD_ARG -> ValueError) is the right answer."""
+    return t if t.data_ptr() % nbytes == 0 else t.clone()
+
+
 def dptr(t):
     """Device pointer of a contiguous float32/int64/uint8 CUDA tensor (or None -> NULL)."""
     if t is None:

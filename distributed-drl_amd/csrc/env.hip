@@ -449,6 +449,12 @@ int ddrl_env3_launch_reset(float *S, long long n, uint32_t seed, int vit, int pi
 int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d,
                           float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
 
+// Memory contract (include/ddrl.h): the env family's kernels move an observation row as two float4 and a continuous action row as one
+// float2, so caller pointers to [n,8] observations must be 16-byte aligned and to [n,2] actions 8-byte aligned.  Checked here, before
+// any launch: a pointer off that grid is refused with its name in ddrl_last_error() and nothing is touched.  (NULL passes: optional.)
+#define DDRL_REQUIRE_ALIGNED(p, bytes) \
+    DDRL_REQUIRE((reinterpret_cast<uintptr_t>(p) & (uintptr_t)((bytes) - 1)) == 0, #p " must be " #bytes "-byte aligned")
+
 // the entry points whose kernels hold the one-body model refuse an articulated handle before they touch anything
 #define DDRL_ONE_BODY_ONLY(h, what)                                                                                                   \
     do {                                                                                                                              \
@@ -584,6 +590,7 @@ int ddrl_env_destroy(ddrl_env_t *h) {
 
 int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
+    DDRL_REQUIRE_ALIGNED(obs_d, 16);
     ddrl::DeviceGuard g(h->device);
     if (h->kind == DDRL_ENV_ARTICULATED) return ddrl_env3_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, mask_d, obs_d, stream);
     k_env_reset<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, mask_d, obs_d);
@@ -594,6 +601,9 @@ int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *str
 int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d,
                   uint8_t *ended_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && act_d != nullptr, "NULL handle or action pointer");
+    DDRL_REQUIRE_ALIGNED(act_d, 8);
+    DDRL_REQUIRE_ALIGNED(obs2_d, 16);
+    DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
     ddrl::DeviceGuard g(h->device);
     if (h->kind == DDRL_ENV_ARTICULATED)
         return ddrl_env3_launch_step(0, h->S, h->n, h->seed, h->max_ep_len, h->vit, h->pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d,
@@ -607,6 +617,8 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
 int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d,
                            uint8_t *ended_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && act_idx_d != nullptr, "NULL handle or action pointer");
+    DDRL_REQUIRE_ALIGNED(obs2_d, 16);
+    DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
     ddrl::DeviceGuard g(h->device);
     if (h->kind == DDRL_ENV_ARTICULATED)
         return ddrl_env3_launch_step(1, h->S, h->n, h->seed, h->max_ep_len, h->vit, h->pit, act_idx_d, obs2_d, rew_d, done_d, next_obs_d,
@@ -622,6 +634,9 @@ int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float ob
                           void *stream) {
     DDRL_REQUIRE(h != nullptr && act_d != nullptr, "NULL pointer");
     DDRL_ONE_BODY_ONLY(h, "ddrl_env_step_wrapped");
+    DDRL_REQUIRE_ALIGNED(act_d, 8);
+    DDRL_REQUIRE_ALIGNED(obs2_d, 16);
+    DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
     DDRL_REQUIRE(action_repeat >= 1 && limit_steps >= 1, "action_repeat and limit_steps must be >= 1");
     ddrl::DeviceGuard g(h->device);
     k_env_step_wrapped<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(
@@ -647,6 +662,8 @@ int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay,
                       int deterministic, float *act_out_d, float *next_obs_out_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && actor != nullptr && replay != nullptr, "NULL handle");
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step");
+    DDRL_REQUIRE_ALIGNED(act_out_d, 8);
+    DDRL_REQUIRE_ALIGNED(next_obs_out_d, 16);
     return rollout_step_loop(h, actor, replay, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
                              [&](const RolloutArgs &a) -> int {
                                  // one wave per workgroup: 4096 envs spread over 64 CUs instead of 16 (the kernel is a chain of dependent latencies)
@@ -671,6 +688,8 @@ int ddrl_rollout_step_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_repla
                                   uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && actor != nullptr && replay != nullptr, "NULL handle");
     DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_step_articulated", "ddrl_rollout_step");
+    DDRL_REQUIRE_ALIGNED(act_out_d, 8);
+    DDRL_REQUIRE_ALIGNED(next_obs_out_d, 16);
     const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
     if (const int rc = rollout3_check("ddrl_rollout_step_articulated", h, ddrl_actor_internal_view(actor), &rv)) return rc;
     return rollout_step_loop(h, actor, replay, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
@@ -708,6 +727,7 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
                                uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && dqn != nullptr && replay != nullptr, "NULL handle");
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step_discrete");
+    DDRL_REQUIRE_ALIGNED(next_obs_out_d, 16);
     DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     DDRL_REQUIRE(mode == DDRL_ACT_SAMPLE || mode == DDRL_ACT_DETERMINISTIC, "mode must be DDRL_ACT_SAMPLE or DDRL_ACT_DETERMINISTIC");
     const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
@@ -832,6 +852,11 @@ int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *win
     DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr && window_ring != nullptr, "NULL handle");
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step_nstep");
     DDRL_REQUIRE(n_steps >= 1 && action_repeat >= 1 && limit_steps >= 1, "n_steps, action_repeat and limit_steps must be >= 1");
+    if (out) {
+        DDRL_REQUIRE_ALIGNED(out->act, 8);
+        DDRL_REQUIRE_ALIGNED(out->obs2, 16);
+        DDRL_REQUIRE_ALIGNED(out->next_obs, 16);
+    }
     const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
     const ddrl_winq_view q = ddrl_winq_internal_view(winq);
     if (const int rc = rollout_nstep_check(h, v, q)) return rc;

@@ -65,7 +65,7 @@ class VecLunarLander:
     def step(self, act):
         """env.step(a) for every env + episode bookkeeping of example/dsac.py:102-127.
         Returns (obs2, rew, done_as_stored, next_obs, ended) — device tensors owned by the env."""
-        act = act.to(device=self.device, dtype=torch.float32).contiguous()
+        act = _lib.aligned(act.to(device=self.device, dtype=torch.float32).contiguous(), 8)   # ddrl.h: act_d is read as float2 rows
         _lib.check(self._lib.ddrl_env_step(self._h, _lib.dptr(act), _lib.dptr(self.obs2), _lib.dptr(self.rew),
                                            _lib.dptr(self.done), _lib.dptr(self.obs), _lib.dptr(self.ended),
                                            _lib.stream_ptr()))
@@ -73,7 +73,9 @@ class VecLunarLander:
 
     def step_wrapped(self, act, act_noise=0.0, obs_noise=0.0, reward_scale=1.0, action_repeat=3, limit_steps=None):
         """env.step through `Wrapper` (algos/sac1/hyperparams.py:107-134) + the n-step rollout's episode
-        bookkeeping (algos/sac1/sac_ray.py:212-258).  Same outputs as step(); done is the raw d."""
+        bookkeeping (algos/sac1/sac_ray.py:212-258).  Same outputs as step(); done is the raw d.  `act` (a contiguous float32 device
+        tensor) receives the noisy action in place, so a view that starts off the 8-byte grid is not copied: the library refuses it
+        (ValueError naming act_d)."""
         act = act.to(device=self.device, dtype=torch.float32).contiguous()
         limit = int(limit_steps if limit_steps is not None else self.max_ep_len)
         _lib.check(self._lib.ddrl_env_step_wrapped(self._h, _lib.dptr(act), float(act_noise), float(obs_noise), float(reward_scale),

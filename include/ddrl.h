@@ -21,6 +21,17 @@
  *     outputs are caller-allocated; handles own all persistent device memory.
  *   - handles are not thread-safe (the reference's actors execute methods serially,
  *     algos/sac1/sac_ray.py:316-317); the Python actor shim serialises calls per handle.
+ *
+ * Memory contract (tests/test_gpu_abi_memory.py holds every entry point to it, between guard bands)
+ *   - an output is written exactly in its documented extent [rows, width]: every element of it, and no byte before or behind it;
+ *     where a comment says an output is left untouched (a refused call, a fed plan entry's idx_d) not one byte of it changes.
+ *   - an input is never written, unless its comment says so (today: act_d of ddrl_env_step_wrapped), and a result depends on the
+ *     documented extent of the inputs alone — never on what lies next to them.
+ *   - a *_d pointer needs the alignment of its element type (4 bytes for float32 / int32, 8 for int64 / double) and no more, unless
+ *     its comment states a stricter one.  Stricter today: the [n,8] observation and [n,2] action pointers of the ddrl_env_* steps and
+ *     of the fused rollout steps' mirrors (16 / 8 bytes: their kernels move whole rows as vectors) and trace_d of the two evaluation
+ *     entries (16 bytes).  A pointer off its stated grid is refused with DDRL_ERR_BAD_ARG before anything is launched or written,
+ *     and ddrl_last_error() names it.
  */
 #ifndef DDRL_H
 #define DDRL_H
@@ -297,7 +308,8 @@ int ddrl_sac1_opt_state_set(ddrl_sac1_t *h, int64_t t_pi, int64_t t_q, uint64_t 
  * polyak target update with the post-update main.  tf.random_normal (core.py:77) is replaced by
  * explicit noise inputs eps_x_d (main policy at x), eps_x2_d (main policy at x2), eps_t_d
  * (target policy at x2), each device float32[B,act].  losses_d: device float32[3]
- * = (pi_loss, q1_loss, q2_loss) (step_ops[0:3], actor_learner.py:97).  Optional per-row outputs
+ * = (pi_loss, q1_loss, q2_loss) (step_ops[0:3], actor_learner.py:97) — float32[4] with v_loss last on a DDRL_SAC_V handle
+ * (example/model.py:66).  Optional per-row outputs
  * (may be NULL): q1_d[B], q2_d[B], logp_pi_d[B]  (step_ops[3:6]). */
 int ddrl_sac1_step(ddrl_sac1_t *h, const float *obs1_d, const float *obs2_d, const float *acts_d,
                    const float *rews_d, const float *done_d, const float *eps_x_d,
@@ -498,7 +510,7 @@ int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t se
 int ddrl_env_state_fields(ddrl_env_t *h);
 int ddrl_env_destroy(ddrl_env_t *h);
 /* env.reset() for every env (mask_d == NULL) or for envs with mask_d[i] != 0 (device uint8[n]).
- * obs_d[n,8] receives the current observation of every env. */
+ * obs_d[n,8] receives the current observation of every env (may be NULL; 16-byte aligned, else DDRL_ERR_BAD_ARG). */
 int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *stream);
 /* One env.step(a) per env followed by the reference's episode bookkeeping
  * (example/dsac.py:102-127): outputs the transition as it is stored —
@@ -508,7 +520,9 @@ int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *str
  * then resets every env whose episode ended (d or ep_len == max_ep_len) and writes
  *   next_obs_d[n,8]  the observation to act on next (o2, or the reset observation),
  *   ended_d[n]       (uint8, may be NULL) 1 where an episode ended this step.
- * act_d[n,2] device float32. */
+ * act_d[n,2] device float32.  Every output may be NULL (that one is then not written).
+ * Alignment: act_d 8 bytes, obs2_d and next_obs_d 16 bytes (rows move as float2 / float4); rew_d, done_d, ended_d that of their
+ * element.  A pointer off that grid: DDRL_ERR_BAD_ARG naming it, before any launch — state, statistics and outputs unchanged. */
 int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d, float *done_d,
                   float *next_obs_d, uint8_t *ended_d, void *stream);
 /* env.step through `Wrapper(env, obs_noise, act_noise, reward_scale, action_repeat)`
@@ -518,7 +532,8 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
  * bookkeeping (algos/sac1/sac_ray.py:212-258): an episode ends on d or after `limit_steps` wrapped
  * steps (= ceil(max_ep_len / opt.action_repeat)), done_d is the raw d.  Same outputs as ddrl_env_step.
  * act_d is updated IN PLACE with the action noise, as the reference's `action += ...` mutates the caller's
- * array (hyperparams.py:124): what the rollout appends to its a_r_d_queue afterwards is the noisy action. */
+ * array (hyperparams.py:124): what the rollout appends to its a_r_d_queue afterwards is the noisy action.
+ * Alignment as for ddrl_env_step: act_d 8 bytes, obs2_d and next_obs_d 16 bytes, else DDRL_ERR_BAD_ARG before any launch. */
 int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale,
                           int32_t action_repeat, int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d,
                           float *next_obs_d, uint8_t *ended_d, void *stream);
@@ -533,7 +548,8 @@ int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float ob
  * shape the direct-operand policy supports (LunarLander: obs 8, act 2, hidden % 4 == 0, n % 32 == 0) — else
  * DDRL_ERR_BAD_ARG; the unfused sequence is ddrl_actor_act + ddrl_env_step + ddrl_replay_store.
  * n_steps >= 1 vector steps are issued back to back (step k draws noise elements noise_ctr + k*n*act ...).
- * act_out_d[n,2], next_obs_out_d[n,8]: optional mirrors of the LAST step (may be NULL). */
+ * act_out_d[n,2], next_obs_out_d[n,8]: optional mirrors of the LAST step (may be NULL); act_out_d 8-byte, next_obs_out_d 16-byte aligned
+ * — here and in ddrl_rollout_step_articulated — else DDRL_ERR_BAD_ARG naming the pointer: nothing launched, env, actor and ring unchanged. */
 /* Exact per-env weight adoption for a vectorised rollout worker.  A reference worker pulls the server's weights at ITS OWN episode end
  * (example/dsac.py:127-130; algos/sac1/sac1.py:209-213) and acts on them until its next one, so n workers hold up to
  * min(n, max_ep_len) + 1 different versions at a time.  ddrl_actor_versions_enable gives the actor `n_slots` resident copies of the
@@ -579,7 +595,8 @@ int ddrl_rollout_step_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_repla
  * act_idx_d[n] holds the index as float32 (the form the DQN ring stores acts in); the index is (int)value clamped to [0, 3]:
  *   0 noop (0, 0), 1 left engine (0, -1), 2 main engine (1, 0), 3 right engine (0, +1)
  * which, under the clip rules of the continuous step, are gym's discrete powers exactly (m_power, s_power in {0, 1}, direction =
- * action - 2).  Outputs and bookkeeping are ddrl_env_step's. */
+ * action - 2).  Outputs and bookkeeping are ddrl_env_step's, and so is the alignment of obs2_d and next_obs_d (16 bytes, else
+ * DDRL_ERR_BAD_ARG before any launch); act_idx_d[n] is read element by element (4 bytes). */
 int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d, float *rew_d, float *done_d,
                            float *next_obs_d, uint8_t *ended_d, void *stream);
 /* Episode statistics accumulated on device since the last call: number of finished episodes,
@@ -708,7 +725,8 @@ int ddrl_dqn_act(ddrl_dqn_t *h, const float *obs_d, int64_t n, int mode, float g
  * Envelope: obs_dim 8, n_actions <= 8, hidden sizes multiples of 4 within the direct-operand limits (<= 512), n_envs a multiple of 32
  * and <= cfg.batch; outside it DDRL_ERR_UNSUPPORTED with the reason in ddrl_last_error() and nothing changed (the unfused sequence is
  * ddrl_dqn_act + ddrl_env_step_discrete + ddrl_replay_store).  A ring of another layout or device: DDRL_ERR_BAD_ARG.
- * act_out_d[n], q_out_d[n, n_actions], next_obs_out_d[n, 8]: optional mirrors of the LAST step (may be NULL). */
+ * act_out_d[n], q_out_d[n, n_actions], next_obs_out_d[n, 8]: optional mirrors of the LAST step (may be NULL).  next_obs_out_d must be
+ * 16-byte aligned (DDRL_ERR_BAD_ARG naming it, nothing launched or changed); act_out_d and q_out_d are written element by element. */
 /* Exact per-env weight adoption for the vectorised discrete rollout worker.  worker_rollout_dqn pulls the server's weights once per episode,
  * for its own env only (algos/dqn/train.py:249-252: env.reset(), ps.pull, agent.set_weights), so n workers hold up to min(n, max_ep_len) + 1
  * versions at a time.  ddrl_dqn_versions_enable gives the handle's acting forward — the one ddrl_rollout_step_discrete runs — `n_slots`
@@ -789,6 +807,7 @@ int ddrl_winq_buffers(ddrl_winq_t *h, float **arrays_h, int32_t **t_queue_h);
  * n_steps > 1 repeats the pair with the weights the actor holds; step k draws noise words from noise_ctr + k * n_envs * act_dim.
  * `out` (nullable, every member nullable) names device mirrors written per step: act[n][2] the NOISY action as Wrapper.step's
  * `action +=` leaves it, obs2[n][8], rew[n], done[n], next_obs[n][8] (after a reset where the episode ended), ended[n].
+ * out->act must be 8-byte, out->obs2 and out->next_obs 16-byte aligned: DDRL_ERR_BAD_ARG naming the member, nothing launched or changed.
  * The launch reads one of two readiness arrays of the queue handle and writes the other; which is which alternates per launch and is
  * HOST state of the handle, so a stream capture of this call must hold an even number of steps to be replayable.
  * ddrl_rollout_begin_nstep writes the envs' current observations — the newest entry of every env's o_queue, i.e. the `o` its worker
