@@ -1040,7 +1040,7 @@ int ddrl_dqn_versions_enable(ddrl_dqn_t *h, int32_t n_slots, void *stream) {
         return DDRL_ERR_UNSUPPORTED;
     }
     DDRL_REQUIRE(n_slots >= 2 && n_slots <= VER_MAX_SLOTS, "n_slots outside [2, 2048]");
-    DDRL_REQUIRE(ddrl_actor_internal_view(h->act_fwd).n_slots == 0, "version store already enabled");
+    DDRL_REQUIRE(ddrl_actor_internal_view(h->act_fwd).ver.n_slots == 0, "version store already enabled");
     // slot 0 = the weights held now: a learner step's pending repack comes first
     if (const int rc = ddrl_dqn_internal_repack(h, stream)) return rc;
     return ddrl_actor_versions_enable(h->act_fwd, n_slots, stream);
@@ -1048,13 +1048,13 @@ int ddrl_dqn_versions_enable(ddrl_dqn_t *h, int32_t n_slots, void *stream) {
 
 int ddrl_dqn_versions_state(ddrl_dqn_t *h, int32_t *slot_of_env_d, int32_t *state_h, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
-    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
+    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).ver.n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
     return ddrl_actor_versions_state(h->act_fwd, slot_of_env_d, state_h, stream);
 }
 
 int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
-    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
+    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).ver.n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
     return ddrl_actor_versions_adopt(h->act_fwd, ended_d, n, stream);
 }
 
@@ -1070,9 +1070,7 @@ ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h) {
     if (!h->act_fwd) return v;
     const ddrl_actor_rollout_view av = ddrl_actor_internal_view(h->act_fwd);
     v.ok = 1; v.obs = av.obs; v.hp = av.hp; v.b_lo = av.bmu; v.b_hi = av.bls;
-    v.rows = av.max_rows; v.n_slots = av.n_slots; v.slot = av.slot; v.vs = reinterpret_cast<VerState *>(const_cast<void *>(av.vs)); v.vstride = av.vstride;
-    v.vb_lo = av.vbmu; v.vb_hi = av.vbls; v.steps_since_install = av.steps_since_install; v.plan_fresh = av.plan_fresh;
-    v.vcnt = av.vcnt; v.perm = av.perm; v.perm2d_off = av.perm2d_off; v.vtiles = av.vtiles; v.vt_cap = av.vt_cap; v.wg_slots = av.wg_slots;
+    v.rows = av.max_rows; v.ver = av.ver; v.vb_lo = av.vbmu; v.vb_hi = av.vbls;
     return v;
 }
 

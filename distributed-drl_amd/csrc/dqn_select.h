@@ -104,21 +104,10 @@ struct ddrl_dqn_rollout_view {
     const float *b_lo, *b_hi;   // head biases: action c < half at b_lo[c], the others at b_hi[c - half]
     int obs_dim, n_actions, half, nt2, batch, sqn;
     float alpha;
-    // version store of the acting forward (ddrl_dqn_versions_enable; n_slots > 0), the fields of ddrl_actor_rollout_view: the slot every env
-    // acts on, the head biases of slot 0 of the version slab (slot s: + s * vstride), the device state whose first word is the newest slot
+    // version store of the acting forward (ddrl_dqn_versions_enable): the inner actor's, and the head biases of slot 0 of its slab
     long long rows;         // rows of the acting forward: a store steps exactly that many envs
-    int n_slots;
-    int *slot;
-    VerState *vs;
-    long long vstride;
+    ddrl_version_view ver;
     const float *vb_lo, *vb_hi;
-    long long *steps_since_install;   // host words of the inner actor
-    bool *plan_fresh;
-    // the next forward's plan as the env-step launch writes it (ver_plan_tail)
-    int *vcnt, *perm;
-    long long perm2d_off;
-    VerTile *vtiles;
-    int vt_cap, wg_slots;
 };
 ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h);
 // a learner step moved the parameters: the operand copy is packed again — with a version store that is an install (steps_since_install = 0),

@@ -474,19 +474,74 @@ int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, in
             return DDRL_ERR_UNSUPPORTED;                                                                                              \
         }                                                                                                                             \
     } while (0)
-// the articulated pair's envelope, checked before anything is launched or written: DDRL_ERR_UNSUPPORTED with the function's name
+// ---- what the fused rollout entry points below share on the host.  (The kernels are kept apart on purpose.)
+// "A five-array float32 transition ring (obs1[8], obs2[8], acts[w], rews, done)": what a ring is not, for the caller to report in its own
+// status and words.
+enum RingFault { RING_FITS = 0, RING_ROW_SHAPE, RING_COMPACT };
+static RingFault transition_ring_fault(const ddrl_replay_dev::RingPtrs &r, int w) {
+    if (r.n_arr != 5 || r.w[0] != 8 || r.w[1] != 8 || r.w[2] != w || r.w[3] != 1 || r.w[4] != 1) return RING_ROW_SHAPE;
+    return (r.kind[0] || r.kind[1]) ? RING_COMPACT : RING_FITS;
+}
+static const char *const RING_COMPACT_MSG = "the fused rollout step stores into float32 rings only (not a compact uint8 ring)";
+
+// the observations of the envs' present state into the forward's rows (ddrl_rollout_begin, ddrl_rollout_begin_discrete)
+static int launch_env_obs(ddrl_env_t *h, float *obs, void *stream) {
+    ddrl::DeviceGuard g(h->device);
+    k_env_obs<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, obs);
+    DDRL_LAUNCH_CHECK();
+    return DDRL_OK;
+}
+
+// The version store's side of ONE vector step of every fused loop, around `step(versioned, fused_plan)` — the entry point's own forward,
+// argument patch and launch.  versioned: once no install has happened for `horizon` steps (max_ep_len, or the wrapped step's
+// limit_steps) every env has been through an episode end and acts on the newest version — the plain launch on the handle's current
+// weights is then the same computation.  fused_plan: the next forward's plan rides in this launch (base offsets of the row lists must
+// fit the records' int).  Behind the launch plan_fresh says whether the launch's own tail has planned for the envs its episode ends
+// moved to the newest version, or the next forward has to.
+template <class Step>
+static int rollout_versioned_step(const ddrl_version_view &ver, long long n, long long horizon, Step step) {
+    const bool store = ver.n_slots > 0;
+    const bool versioned = store && *ver.steps_since_install < horizon;
+    const bool fused_plan = versioned && ver.vcnt != nullptr && ver.perm2d_off + (long long)ver.n_slots * n < (1ll << 31) && n / 32 <= 1024;
+    if (store) *ver.steps_since_install += 1;
+    if (const int rc = step(versioned, fused_plan)) return rc;
+    if (versioned) *ver.plan_fresh = fused_plan;
+    return DDRL_OK;
+}
+// ... and the plan's tables as the launch takes them: k_env_step_q as they stand, the other argument structs field by field
+static VerPlan ver_plan_of(const ddrl_version_view &ver, bool fused_plan, int col_tiles) {
+    return VerPlan{fused_plan ? ver.vcnt : nullptr, ver.perm, ver.perm2d_off, ver.vtiles, ver.vs, ver.n_slots, col_tiles, ver.wg_slots, ver.vt_cap};
+}
+template <class Args>
+static void set_ver_plan(Args &a, const VerPlan &p) {
+    a.vcnt = p.vcnt; a.perm = p.perm; a.perm2d_off = p.perm2d_off; a.vtiles = p.vtiles; a.vs = p.vs;
+    a.n_slots = p.n_slots; a.col_tiles = p.col_tiles; a.wg_slots = p.wg_slots; a.vt_cap = p.vt_cap;
+}
+
+// the one-body continuous step's envelope: DDRL_ERR_BAD_ARG
+static int rollout_check(ddrl_env_t *h, const ddrl_actor_rollout_view &v, const ddrl_replay_dev::SamplerView &rv, int32_t n_steps) {
+    DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
+    DDRL_REQUIRE(v.obs_dim == 8 && v.act <= 2 && h->n <= v.max_rows && h->n % 32 == 0 && v.device == h->device,
+                 "actor / env mismatch (obs_dim 8, act_dim <= 2, n_envs a multiple of 32 within max_rows, same device)");
+    const RingFault rf = transition_ring_fault(rv.ring, 2);
+    DDRL_REQUIRE(rf != RING_ROW_SHAPE, "replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)");
+    DDRL_REQUIRE(rf != RING_COMPACT, RING_COMPACT_MSG);
+    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    DDRL_REQUIRE(v.ver.n_slots == 0 || h->n == v.max_rows, "an actor with a version store steps exactly max_rows envs");
+    return DDRL_OK;
+}
+// the articulated pair's envelope (rv: the step's ring): DDRL_ERR_UNSUPPORTED with the function's name
 static int rollout3_check(const char *what, ddrl_env_t *h, const ddrl_actor_rollout_view &v, const ddrl_replay_dev::SamplerView *rv) {
     const char *why = nullptr;
     if (!v.ok) why = "the actor has no direct-operand policy (shape outside the envelope)";
     else if (v.obs_dim != 8 || v.act > 2) why = "the actor must have obs_dim 8 and act_dim <= 2";
     else if (h->n % 32 != 0 || h->n > v.max_rows) why = "n_envs must be a multiple of 32 within the actor's max_rows";
-    else if (v.n_slots > 0 && h->n != v.max_rows) why = "an actor with a version store steps exactly max_rows envs";
+    else if (v.ver.n_slots > 0 && h->n != v.max_rows) why = "an actor with a version store steps exactly max_rows envs";
     else if (v.device != h->device) why = "actor and envs must live on one device";
     else if (rv) {
-        const ddrl_replay_dev::RingPtrs &r = rv->ring;
-        if (r.n_arr != 5 || r.w[0] != 8 || r.w[1] != 8 || r.w[2] != 2 || r.w[3] != 1 || r.w[4] != 1)
-            why = "the replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)";
-        else if (r.kind[0] || r.kind[1]) why = "the fused rollout step stores into float32 rings only (not a compact uint8 ring)";
+        const RingFault rf = transition_ring_fault(rv->ring, 2);
+        if (rf == RING_ROW_SHAPE) why = "the replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)";
+        else if (rf == RING_COMPACT) why = RING_COMPACT_MSG;
         else if (rv->device != h->device) why = "the replay ring lives on another device than the envs";
     }
     if (!why) return DDRL_OK;
@@ -495,46 +550,29 @@ static int rollout3_check(const char *what, ddrl_env_t *h, const ddrl_actor_roll
 }
 
 // The continuous fused step behind ddrl_rollout_step (one-body lander: k_env_step_pi) and ddrl_rollout_step_articulated (rollout3.hip:
-// k_env3_step_pi): the envelope, then n_steps times the loop body of worker_rollout — the forward, `launch(a)`, the host's bookkeeping.
-// `launch` is the two entry points' only difference: it issues the env-step kernel of the handle's model on a filled RolloutArgs.
+// k_env3_step_pi), behind the entry point's own envelope: n_steps times the loop body of worker_rollout — the forward, `launch(a)`, the
+// host's bookkeeping.  `launch` issues the env-step kernel of the handle's model on a filled RolloutArgs.
 template <class Launch>
-static int rollout_step_loop(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed,
-                             uint64_t noise_ctr, int deterministic, float *act_out_d, float *next_obs_out_d, void *stream, Launch launch) {
-    const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
-    DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
-    DDRL_REQUIRE(v.obs_dim == 8 && v.act <= 2 && h->n <= v.max_rows && h->n % 32 == 0 && v.device == h->device,
-                 "actor / env mismatch (obs_dim 8, act_dim <= 2, n_envs a multiple of 32 within max_rows, same device)");
-    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
-    DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == 8 && rv.ring.w[1] == 8 && rv.ring.w[2] == 2 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
-                 "replay row shape must be (obs1[8], obs2[8], acts[2], rews, done)");
-    DDRL_REQUIRE(!rv.ring.kind[0] && !rv.ring.kind[1], "the fused rollout step stores into float32 rings only (not a compact uint8 ring)");
-    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+static int rollout_step_loop(ddrl_env_t *h, ddrl_actor_t *actor, const ddrl_actor_rollout_view &v, ddrl_replay_t *replay,
+                             const ddrl_replay_dev::SamplerView &rv, int32_t n_steps, uint32_t noise_seed, uint64_t noise_ctr,
+                             int deterministic, float *act_out_d, float *next_obs_out_d, void *stream, Launch launch) {
     ddrl::DeviceGuard g(h->device);
     RolloutArgs a{};
     a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
-    a.obs = v.obs; a.hp = v.hp; a.bmu = v.bmu; a.bls = v.bls; a.act = v.act; a.nt2 = v.nt2; a.scale = v.scale;
-    a.deterministic = deterministic; a.noise_seed = noise_seed;
+    a.obs = v.obs; a.hp = v.hp; a.act = v.act; a.nt2 = v.nt2; a.scale = v.scale;
+    a.deterministic = deterministic; a.noise_seed = noise_seed; a.vstride = v.ver.vstride;
     a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.next_obs_out = next_obs_out_d;
-    const bool store = v.n_slots > 0;
-    DDRL_REQUIRE(!store || h->n == v.max_rows, "an actor with a version store steps exactly max_rows envs");
     for (int k = 0; k < n_steps; ++k) {  // the loop body of worker_rollout, n_steps times with the weights the actor holds
-        // version store: once no install has happened for max_ep_len steps every env has been through an episode end and
-        // acts on the newest version — the plain launch on the actor's current weights is then the same computation
-        const bool versioned = store && *v.steps_since_install < (long long)h->max_ep_len;
-        a.slot = versioned ? v.slot : nullptr;
-        a.newest = versioned ? reinterpret_cast<const int *>(v.vs) : nullptr;   // VerState::newest is its first word
-        a.vstride = v.vstride;
-        a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
-        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
-        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
-        a.vcnt = fused_plan ? v.vcnt : nullptr; a.perm = v.perm; a.perm2d_off = v.perm2d_off; a.vtiles = v.vtiles;
-        a.vs = reinterpret_cast<VerState *>(const_cast<void *>(v.vs)); a.n_slots = v.n_slots; a.col_tiles = v.nt2; a.wg_slots = v.wg_slots; a.vt_cap = v.vt_cap;
-        if (store) *v.steps_since_install += 1;
-        const int rc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0);
+        const int rc = rollout_versioned_step(v.ver, h->n, h->max_ep_len, [&](bool versioned, bool fused_plan) -> int {
+            a.slot = versioned ? v.ver.slot : nullptr;
+            a.newest = versioned ? &v.ver.vs->newest : nullptr;
+            a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
+            set_ver_plan(a, ver_plan_of(v.ver, fused_plan, v.nt2));
+            if (const int frc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0)) return frc;
+            a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * (uint64_t)v.act;
+            return launch(a);
+        });
         if (rc != DDRL_OK) return rc;
-        a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * (uint64_t)v.act;
-        if (const int lrc = launch(a)) return lrc;
-        if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
         ddrl_replay_note_store(replay, h->n);
     }
     return DDRL_OK;
@@ -652,10 +690,7 @@ int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream) {
     const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
     DDRL_REQUIRE(v.ok, "actor has no direct-operand policy (shape outside the envelope): use ddrl_actor_act + ddrl_env_step + ddrl_replay_store");
     DDRL_REQUIRE(v.obs_dim == 8 && h->n <= v.max_rows && v.device == h->device, "actor / env mismatch (obs_dim 8, max_rows >= n_envs, same device)");
-    ddrl::DeviceGuard g(h->device);
-    k_env_obs<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, v.obs);
-    DDRL_LAUNCH_CHECK();
-    return DDRL_OK;
+    return launch_env_obs(h, v.obs, stream);
 }
 
 int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay, int32_t n_steps, uint32_t noise_seed, uint64_t noise_ctr,
@@ -664,7 +699,10 @@ int ddrl_rollout_step(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_replay_t *replay,
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step");
     DDRL_REQUIRE_ALIGNED(act_out_d, 8);
     DDRL_REQUIRE_ALIGNED(next_obs_out_d, 16);
-    return rollout_step_loop(h, actor, replay, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
+    const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    if (const int rc = rollout_check(h, v, rv, n_steps)) return rc;
+    return rollout_step_loop(h, actor, v, replay, rv, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
                              [&](const RolloutArgs &a) -> int {
                                  // one wave per workgroup: 4096 envs spread over 64 CUs instead of 16 (the kernel is a chain of dependent latencies)
                                  if (a.act <= 2) k_env_step_pi<4><<<(unsigned)((h->n + 63) / 64), 64, 0, ddrl::as_stream(stream)>>>(a);
@@ -690,9 +728,11 @@ int ddrl_rollout_step_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_repla
     DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_step_articulated", "ddrl_rollout_step");
     DDRL_REQUIRE_ALIGNED(act_out_d, 8);
     DDRL_REQUIRE_ALIGNED(next_obs_out_d, 16);
+    const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
     const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
-    if (const int rc = rollout3_check("ddrl_rollout_step_articulated", h, ddrl_actor_internal_view(actor), &rv)) return rc;
-    return rollout_step_loop(h, actor, replay, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
+    if (const int rc = rollout3_check("ddrl_rollout_step_articulated", h, v, &rv)) return rc;
+    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    return rollout_step_loop(h, actor, v, replay, rv, n_steps, noise_seed, noise_ctr, deterministic, act_out_d, next_obs_out_d, stream,
                              [&](const RolloutArgs &a) -> int { return ddrl_rollout3_launch_step(&a, h->vit, h->pit, stream); });
 }
 
@@ -717,10 +757,7 @@ int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream) {
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin_discrete");
     const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
     if (const int rc = rollout_discrete_check(h, v)) return rc;
-    ddrl::DeviceGuard g(h->device);
-    k_env_obs<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, v.obs);
-    DDRL_LAUNCH_CHECK();
-    return DDRL_OK;
+    return launch_env_obs(h, v.obs, stream);
 }
 
 int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
@@ -734,17 +771,16 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
     if (const int rc = rollout_discrete_check(h, v)) return rc;
     const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
     DDRL_REQUIRE(rv.device == h->device, "the replay ring lives on another device than the envs");
-    DDRL_REQUIRE(rv.ring.n_arr == 5 && rv.ring.w[0] == 8 && rv.ring.w[1] == 8 && rv.ring.w[2] == 1 && rv.ring.w[3] == 1 && rv.ring.w[4] == 1,
-                 "replay row shape must be (obs1[8], obs2[8], acts, rews, done)");
-    DDRL_REQUIRE(!rv.ring.kind[0] && !rv.ring.kind[1], "the fused rollout step stores into float32 rings only (not a compact uint8 ring)");
+    const RingFault rf = transition_ring_fault(rv.ring, 1);
+    DDRL_REQUIRE(rf != RING_ROW_SHAPE, "replay row shape must be (obs1[8], obs2[8], acts, rews, done)");
+    DDRL_REQUIRE(rf != RING_COMPACT, RING_COMPACT_MSG);
     ddrl::DeviceGuard g(h->device);
     RolloutQArgs a{};
     a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
     a.obs = v.obs; a.hp = v.hp; a.b_lo = v.b_lo; a.b_hi = v.b_hi; a.A = v.n_actions; a.half = v.half; a.nt2 = v.nt2; a.sqn = v.sqn;
     a.deterministic = mode == DDRL_ACT_DETERMINISTIC; a.greedy_prob = greedy_prob; a.alpha = v.alpha; a.noise_seed = seed;
     a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.q_out = q_out_d; a.next_obs_out = next_obs_out_d;
-    const bool store = v.n_slots > 0;
-    if (store && h->n != v.rows) {
+    if (v.ver.n_slots > 0 && h->n != v.rows) {
         ddrl::set_error("fused discrete rollout step: a handle with a version store steps exactly the acting forward's %lld rows (n_envs %lld)", v.rows, h->n);
         return DDRL_ERR_BAD_ARG;
     }
@@ -753,28 +789,23 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
     for (int k = 0; k < n_steps; ++k) {   // ddrl_rollout_step's loop body
         // a learner step's pending repack is an install: before steps_since_install is read
         if (const int rc = ddrl_dqn_internal_repack(dqn, stream)) return rc;
-        // version store: once no install has happened for max_ep_len steps every env has been through an episode end and acts on
-        // the newest version — the plain launch pair on the handle's current weights is then the same computation
-        const bool versioned = store && *v.steps_since_install < (long long)h->max_ep_len;
-        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
-        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
-        if (store) *v.steps_since_install += 1;
-        const int rc = ddrl_dqn_internal_forward(dqn, h->n, stream, versioned ? 1 : 0);
+        const int rc = rollout_versioned_step(v.ver, h->n, h->max_ep_len, [&](bool versioned, bool fused_plan) -> int {
+            if (const int frc = ddrl_dqn_internal_forward(dqn, h->n, stream, versioned ? 1 : 0)) return frc;
+            a.noise_ctr = ctr + (uint64_t)k * 2ull * (uint64_t)h->n;
+            if (versioned) {
+                a.b_lo = v.vb_lo; a.b_hi = v.vb_hi; a.slot = v.ver.slot; a.newest = &v.ver.vs->newest; a.vstride = v.ver.vstride;
+                a.vp = ver_plan_of(v.ver, fused_plan, v.nt2);
+                if (v.n_actions <= 4) k_env_step_q<4, true><<<grid, 64, 0, s>>>(a);
+                else k_env_step_q<8, true><<<grid, 64, 0, s>>>(a);
+            } else {
+                a.b_lo = v.b_lo; a.b_hi = v.b_hi;
+                if (v.n_actions <= 4) k_env_step_q<4, false><<<grid, 64, 0, s>>>(a);
+                else k_env_step_q<8, false><<<grid, 64, 0, s>>>(a);
+            }
+            DDRL_LAUNCH_CHECK();
+            return DDRL_OK;
+        });
         if (rc != DDRL_OK) return rc;
-        a.noise_ctr = ctr + (uint64_t)k * 2ull * (uint64_t)h->n;
-        if (versioned) {
-            a.b_lo = v.vb_lo; a.b_hi = v.vb_hi; a.slot = v.slot; a.newest = reinterpret_cast<const int *>(v.vs);   // VerState::newest is its first word
-            a.vstride = v.vstride;
-            a.vp = VerPlan{fused_plan ? v.vcnt : nullptr, v.perm, v.perm2d_off, v.vtiles, v.vs, v.n_slots, v.nt2, v.wg_slots, v.vt_cap};
-            if (v.n_actions <= 4) k_env_step_q<4, true><<<grid, 64, 0, s>>>(a);
-            else k_env_step_q<8, true><<<grid, 64, 0, s>>>(a);
-        } else {
-            a.b_lo = v.b_lo; a.b_hi = v.b_hi;
-            if (v.n_actions <= 4) k_env_step_q<4, false><<<grid, 64, 0, s>>>(a);
-            else k_env_step_q<8, false><<<grid, 64, 0, s>>>(a);
-        }
-        DDRL_LAUNCH_CHECK();
-        if (versioned) *v.plan_fresh = fused_plan;   // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
         ddrl_replay_note_store(replay, h->n);
     }
     return DDRL_OK;
@@ -792,7 +823,7 @@ static int rollout_nstep_check(ddrl_env_t *h, const ddrl_actor_rollout_view &v, 
                         "ddrl_actor_act + ddrl_env_step_wrapped + ddrl_winq_push + ddrl_replay_store_masked_ex");
         return DDRL_ERR_UNSUPPORTED;
     }
-    if (v.obs_dim != 8 || v.act != 2 || h->n % 32 != 0 || h->n > v.max_rows || (v.n_slots > 0 && h->n != v.max_rows)) {
+    if (v.obs_dim != 8 || v.act != 2 || h->n % 32 != 0 || h->n > v.max_rows || (v.ver.n_slots > 0 && h->n != v.max_rows)) {
         ddrl::set_error("fused n-step rollout step needs obs_dim 8, act_dim 2 and n_envs a multiple of 32 within the actor's max_rows (all of "
                         "them with a version store): obs_dim %d, act_dim %d, n_envs %lld, max_rows %lld", v.obs_dim, v.act, h->n, v.max_rows);
         return DDRL_ERR_UNSUPPORTED;
@@ -868,12 +899,10 @@ int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *win
     a.limit_steps = (float)limit_steps; a.act_noise = act_noise; a.obs_noise = obs_noise; a.reward_scale = reward_scale;
     a.repeat = action_repeat; a.adopt = adopt_at_episode_end ? 1 : 0;
     a.obs = v.obs; a.hp = v.hp; a.nt2 = v.nt2; a.scale = v.scale; a.noise_seed = noise_seed;
-    const bool store = v.n_slots > 0;
-    a.slot = store ? v.slot : nullptr;
-    a.newest = store ? reinterpret_cast<const int *>(v.vs) : nullptr;   // VerState::newest is its first word
-    a.vstride = v.vstride;
-    a.perm = v.perm; a.perm2d_off = v.perm2d_off; a.vtiles = v.vtiles; a.vs = reinterpret_cast<VerState *>(const_cast<void *>(v.vs));
-    a.n_slots = v.n_slots; a.col_tiles = v.nt2; a.wg_slots = v.wg_slots; a.vt_cap = v.vt_cap;
+    const bool store = v.ver.n_slots > 0;
+    a.slot = store ? v.ver.slot : nullptr;
+    a.newest = store ? &v.ver.vs->newest : nullptr;
+    a.vstride = v.ver.vstride;
     a.qo = q.o; a.qa = q.a; a.qr = q.r; a.qd = q.d; a.qt = q.t; a.Ln = q.Ln; a.save_freq = q.save_freq;
     a.rs = rv.state; a.ring = rv.ring;
     if (out) {
@@ -881,23 +910,20 @@ int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *win
         a.ended_out = out->ended;
     }
     for (int k = 0; k < n_steps; ++k) {   // the loop body of worker_rollout, n_steps times with the weights the actor holds
-        // version store: `limit_steps` after the last install every env has been through an episode end — the plain launch on the
-        // actor's current weights (ddrl_rollout_step's test, with the wrapped-step limit; ddrl_actor_act_versioned makes the same one)
-        const bool versioned = store && *v.steps_since_install < (long long)limit_steps;
-        a.versioned = versioned ? 1 : 0;
-        a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
-        // the next forward's plan rides in this launch (base offsets of the row lists must fit the records' int)
-        const bool fused_plan = versioned && v.vcnt != nullptr && v.perm2d_off + (long long)v.n_slots * h->n < (1ll << 31) && h->n / 32 <= 1024;
-        a.vcnt = fused_plan ? v.vcnt : nullptr;
-        if (store) *v.steps_since_install += 1;
-        if (const int rc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0)) return rc;
-        a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * 2ull;
-        a.rdy_in = q.rdy[*q.parity]; a.rdy_out = q.rdy[1 - *q.parity];
-        if (const int rc = ddrl_nstep_launch_step(a, stream)) return rc;
-        *q.parity = 1 - *q.parity;
-        // episode ends of this step moved envs to the newest version: the launch's own tail has planned for that, or the next forward plans
-        if (versioned) *v.plan_fresh = fused_plan;
-        else if (store && a.adopt) *v.plan_fresh = false;
+        // the horizon is the wrapped step's limit (ddrl_actor_act_versioned makes the same test)
+        const int rc = rollout_versioned_step(v.ver, h->n, limit_steps, [&](bool versioned, bool fused_plan) -> int {
+            a.versioned = versioned ? 1 : 0;
+            a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
+            set_ver_plan(a, ver_plan_of(v.ver, fused_plan, v.nt2));
+            if (const int frc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0)) return frc;
+            a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * 2ull;
+            a.rdy_in = q.rdy[*q.parity]; a.rdy_out = q.rdy[1 - *q.parity];
+            if (const int lrc = ddrl_nstep_launch_step(a, stream)) return lrc;
+            *q.parity = 1 - *q.parity;
+            if (!versioned && store && a.adopt) *v.ver.plan_fresh = false;   // an unplanned launch moved envs: the next forward plans
+            return DDRL_OK;
+        });
+        if (rc != DDRL_OK) return rc;
         ddrl_replay_note_masked_store(window_ring);   // the row count is known on the device only
     }
     return DDRL_OK;

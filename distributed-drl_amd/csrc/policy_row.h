@@ -98,21 +98,13 @@ __host__ __device__ inline VerSplit ver_split(int n_tiles, int col_tiles, int sl
     return v;
 }
 
-// What the fused rollout step (env.hip) needs from an actor handle (sac1.hip): internal to libddrl_hip.so.
-struct ddrl_actor_rollout_view {
-    int ok, device;
-    float *obs;         // [max_rows][obs_dim]: the observations the next forward launch acts on
-    const float *hp;    // head partials of the last forward launch [DFH = 8][n][DNT = 16]
-    const float *bmu, *bls;
-    int obs_dim, act, nt2;
-    long long max_rows;
-    float scale;
-    // version store (n_slots > 0): the slot every env acts on, the head biases of slot 0 (slot s: + s * vstride), device state
+// An actor's version store (n_slots > 0) as the fused rollout steps (env.hip) see it: filled by ddrl_actor_internal_view, handed on whole by
+// ddrl_dqn_internal_view.  Host side only: never a kernel argument.
+struct ddrl_version_view {
     int n_slots;
-    int *slot;
-    const void *vs;     // VerState (sac1_direct.h): .newest is what an env adopts at its episode end
+    int *slot;          // the slot every env acts on (the head biases of slot s lie s * vstride floats behind slot 0's)
+    VerState *vs;       // device state: .newest, its first word, is what an env adopts at its episode end
     long long vstride;
-    const float *vbmu, *vbls;
     long long *steps_since_install;
     bool *plan_fresh;   // host flag of the actor: the forward's tile table matches the slots (cleared behind every launch that moves an env)
     // the forward's plan as the env-step launch writes it (fused: no planning launch between a vector step and the next forward)
@@ -121,6 +113,18 @@ struct ddrl_actor_rollout_view {
     long long perm2d_off;
     VerTile *vtiles;
     int vt_cap, wg_slots;
+};
+// What the fused rollout step (env.hip) needs from an actor handle (sac1.hip): internal to libddrl_hip.so.
+struct ddrl_actor_rollout_view {
+    int ok, device;
+    float *obs;         // [max_rows][obs_dim]: the observations the next forward launch acts on
+    const float *hp;    // head partials of the last forward launch [DFH = 8][n][DNT = 16]
+    const float *bmu, *bls;
+    int obs_dim, act, nt2;
+    long long max_rows; // ... and the rows a version store steps: all of them
+    float scale;
+    ddrl_version_view ver;
+    const float *vbmu, *vbls;   // the head biases of slot 0
 };
 int ddrl_actor_internal_forward(ddrl_actor_t *h, long long n, void *stream, int versioned);
 ddrl_actor_rollout_view ddrl_actor_internal_view(ddrl_actor_t *h);

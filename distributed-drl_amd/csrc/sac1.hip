@@ -2640,11 +2640,9 @@ ddrl_actor_rollout_view ddrl_actor_internal_view(ddrl_actor *h) {
     ddrl_actor_rollout_view v{};
     if (!h || !h->direct) return v;
     v.ok = 1; v.obs = h->obs_d; v.hp = h->hp_d; v.bmu = h->pi_d + h->Ld.pi_bmu; v.bls = h->pi_d + h->Ld.pi_bls;
-    v.n_slots = h->n_slots; v.slot = h->slot_d; v.vs = h->vs_d; v.vstride = h->vstride;
+    v.ver = ddrl_version_view{h->n_slots, h->slot_d, h->vs_d, h->vstride, &h->steps_since_install, &h->plan_fresh,
+                              h->vcnt_d, h->perm_d, h->perm2d_off, h->vtiles_d, h->vt_cap, h->wg_slots};
     v.vbmu = h->n_slots ? h->vslab + h->Ld.pi_bmu : nullptr; v.vbls = h->n_slots ? h->vslab + h->Ld.pi_bls : nullptr;
-    v.steps_since_install = &h->steps_since_install;
-    v.plan_fresh = &h->plan_fresh;
-    v.vcnt = h->vcnt_d; v.perm = h->perm_d; v.perm2d_off = h->perm2d_off; v.vtiles = h->vtiles_d; v.vt_cap = h->vt_cap; v.wg_slots = h->wg_slots;
     v.obs_dim = h->cfg.obs_dim; v.act = h->cfg.act_dim; v.nt2 = (h->cfg.hidden2 + 31) / 32; v.max_rows = h->max_rows;
     v.scale = (float)h->cfg.act_scale; v.device = h->device;
     return v;

@@ -602,45 +602,43 @@ def _env_model_kw(opt):
                 position_iterations=int(getattr(opt, "env_position_iterations", 60)))
 
 
-class RolloutDevice:
-    """State of one vectorised rollout worker: `opt.num_envs` envs, one Actor, a local replay
-    shard and a ParameterServer (or a comm.ParamBroadcast on multi-GPU runs).
+class _RolloutWorker:
+    """What the three device rollout workers share: `opt.num_envs` envs stepped in lock step by one actor, the pull from a
+    ParameterServer (or a comm.ParamBroadcast on multi-GPU runs), the decision for the fused launch pair and weight adoption.  A
+    subclass builds `env` and `actor`, calls _start(), and supplies _fused_eligible(), _fused_begin() and its fused launch.
 
-    Weight adoption (`opt.adopt`, default "episode"): the reference runs one worker per env and each pulls the server's weights at
-    ITS OWN episode end (example/dsac.py:127-130), so at any time the envs act on different versions.  "episode" reproduces that
-    exactly on the fused path: the actor keeps min(num_envs, max_ep_len) + 2 resident policy versions, pull() stores what the
-    server holds as the newest one, and the env-step kernel moves an env to it where that env's episode ends — the vector of envs
-    is then indistinguishable from num_envs reference workers stepped in lock step.  "step" (and shapes outside the fused
-    envelope) swaps the weights of every env at the next vector step: never staler than the reference, not identical to it.
+    The fused pair (`_fused`: None until _fused_ready() has decided, once; then True or False for good): a begin call that puts the
+    envs' observations into the actor's rows, and a step call that is ONE forward launch + ONE launch that finishes the action, steps
+    the physics and stores.  The begin call doubles as the envelope test: the C entry point refuses a shape it has no kernel for, and
+    the worker then stays on its unfused sequence (act, env.step, store) — as it does in its random-action phase.  `_fused_live`: the
+    actor's rows are those the last fused step left (no unfused step since); a fused step that finds it False runs the begin call first.
 
-    The articulated lander (`opt.env_model = "articulated"`) runs the unfused sequence — and so adopts per step — unless
-    `opt.fused_rollout_articulated` is set (default False): then the worker takes ddrl_rollout_begin_articulated /
-    ddrl_rollout_step_articulated, the same launch pair with the three-body solver in the env-step kernel, and "episode" adoption
-    holds on that model too.  The one-body worker ignores the flag."""
+    Weight adoption (`opt.adopt`): the reference runs one worker per env and each pulls the server's weights at ITS OWN episode end
+    (example/dsac.py:127-130, algos/dqn/train.py:249-252, algos/sac1/sac_ray.py:252-262), so at any time the envs act on different
+    versions.  "episode" reproduces that exactly: the actor keeps min(num_envs, horizon) + 2 resident versions (`_versions`; horizon =
+    the steps after which every env has been through an episode end), pull() — at the START of a step: what the server holds now is
+    what an env ending its episode in this step pulls — stores the server's weights as the newest one, and the fused step's kernel (on
+    the unfused sequence actor.adopt_where_ended) moves an env to it where that env's episode ends: the vector of envs is then
+    indistinguishable from num_envs reference workers stepped in lock step.  "step", and a shape outside the fused envelope, pulls
+    AFTER the step and swaps the weights of every env at once: never staler than the reference, not identical to it.
+    `auto_pull`: step() looks at the server itself; FreeRunningLoop turns it off and pulls at segment boundaries."""
 
-    def __init__(self, ps, replay_buffer, opt, worker_index=0):
-        import torch
-        from .agent import Actor
-        from .env import VecLunarLander
-        self.ps, self.rb, self.opt = ps, replay_buffer, opt
-        self.env = VecLunarLander(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index),
-                                  max_ep_len=opt.max_ep_len, **_env_model_kw(opt))
-        self.actor = Actor(opt, job="worker", max_rows=opt.num_envs, index=worker_index)
-        self.span = ps.span(self.actor.keys) if ps is not None else None
+    _flat_pull = True     # pull() takes the actor's keys as one span of the server's flat table where it has one
+    _t_per_step = 1       # what one vector step adds to `t`
+
+    def _start(self, ps, fused, adopt):
+        """The shared state, then the initial pull (dsac.py:88-90).  fused: the worker's opt-out flag; adopt: its default."""
+        self.ps, self.keys = ps, list(self.actor.keys)
+        self.span = ps.span(self.keys) if ps is not None and self._flat_pull else None
         self._layout = getattr(ps, "layout", 0)
         self.version = -1
-        self.t = 0
-        self.o = torch.empty_like(self.env.obs)
-        self.act = torch.empty(opt.num_envs, 2, dtype=torch.float32, device=self.env.device)
-        self._fused = None if getattr(opt, "fused_rollout", True) else False
+        self._fused = None if fused else False
         self._fused_live = False
-        self.adopt = getattr(opt, "adopt", "episode")
+        self.adopt = getattr(self.opt, "adopt", adopt)
         assert self.adopt in ("episode", "step"), self.adopt
         self._versions = False
-        self.auto_pull = True     # step() looks at the server itself; FreeRunningLoop turns it off and pulls at segment boundaries
+        self.auto_pull = True
         self.pull()
-        if self.adopt == "episode" and self._fused is None:
-            self._fused_ready()   # the version store starts from the initial pull (dsac.py:88-90), before any step
 
     def pull(self):
         """ps.pull(keys) + agent.set_weights when the server has something newer."""
@@ -648,8 +646,8 @@ class RolloutDevice:
             return False
         self.version = self.ps.version
         layout = getattr(self.ps, "layout", 0)
-        if layout != self._layout:          # a key entered or left the server's flat table since the span was looked up
-            self.span, self._layout = self.ps.span(self.actor.keys), layout
+        if self._flat_pull and layout != self._layout:   # a key entered or left the server's flat table since the span was looked up
+            self.span, self._layout = self.ps.span(self.keys), layout
         if self.span is not None:
             import torch
             flat = getattr(self.ps, "flat", None)
@@ -658,54 +656,46 @@ class RolloutDevice:
             else:
                 self.actor.set_weights_flat(self.ps.pull_flat(*self.span))
         else:
-            self.actor.set_weights(self.actor.keys, self.ps.pull_device(self.actor.keys))
+            self.actor.set_weights(self.keys, self.ps.pull_device(self.keys))
         return True
 
-    def _rollout_calls(self):
-        """The fused pair of the envs' model: (begin, step) of the C library."""
-        lib = self.actor._lib
-        if self.env.model == "articulated":
-            return lib.ddrl_rollout_begin_articulated, lib.ddrl_rollout_step_articulated
-        return lib.ddrl_rollout_begin, lib.ddrl_rollout_step
+    def _enable_versions(self, horizon):
+        """Every env on the weights held now; later pulls become versions adopted at episode ends."""
+        self.actor.enable_versions(min(2048, min(self.env.n, int(horizon)) + 2))
+        self._versions = True
 
     def _fused_ready(self):
-        """Can this worker take the fused launch pair (ddrl_rollout_step; on the articulated lander ddrl_rollout_step_articulated,
-        and only with opt.fused_rollout_articulated set)?  Decided once: the actor's shape must be inside the direct-operand
-        envelope and the ring must be the plain five-array SAC layout."""
+        """Can this worker take its fused launch pair?  Decided once: _fused_eligible() (rings, flags), then the begin call itself."""
         if self._fused is None:
-            from . import _lib
-            from .replay import ReplayBuffer
-            ok = isinstance(self.rb, ReplayBuffer) and not getattr(self.rb, "_acts_1d", False) and self.env.n % 32 == 0
-            # ddrl_rollout_begin holds the one-body lander and refuses the other; the articulated pair is opt-in
-            ok = ok and (self.env.model == "simple" or
-                         (self.env.model == "articulated" and bool(getattr(self.opt, "fused_rollout_articulated", False))))
+            ok = bool(self._fused_eligible())
             if ok:
-                ok = self._rollout_calls()[0](self.env._h, self.actor._h, _lib.stream_ptr()) == 0
+                ok = self._fused_begin() == 0
             self._fused, self._fused_live = ok, ok
-            if ok and self.adopt == "episode" and self.actor.max_rows == self.env.n:
-                # every env on the weights of the initial pull; later pulls become versions adopted at episode ends
-                self.actor.enable_versions(min(2048, min(self.env.n, int(self.opt.max_ep_len)) + 2))
-                self._versions = True
+            self._fused_decided(ok)
         return self._fused
 
+    def _fused_decided(self, ok):
+        if ok and self.adopt == "episode" and self.actor.max_rows == self.env.n:
+            self._enable_versions(self.opt.max_ep_len)
+
+    def _fused_refresh(self):
+        """In front of a fused step: the begin call again where the unfused sequence has stepped the envs since the last one."""
+        if not self._fused_live:
+            from . import _lib
+            _lib.check(self._fused_begin())
+            self._fused_live = True
+
     def step(self, n_steps=1):
-        """One vector step = num_envs reference iterations (dsac.py:96-130); n_steps > 1 issues that many back to back with the
-        weights the actor holds (the reference pulls at episode ends only).  Policy phase: ONE policy-forward launch + ONE
-        launch that finishes get_action, steps the physics and appends the transitions to the ring (ddrl_rollout_step);
-        random-action phase (t <= start_steps) and shapes outside the envelope: get_action / env.step / store launches."""
-        from . import _lib
+        """One vector step = num_envs iterations of the reference loop; n_steps > 1 issues that many back to back with the weights the
+        actor holds (the reference pulls at episode ends only).  Policy phase: the fused pair; random-action phase (t <= start_steps)
+        and shapes outside the envelope: get_actions / env.step / store_batch launches.  (RolloutDevice, RolloutDeviceDQN.)"""
         env = self.env
         if self._versions and self.auto_pull:
-            self.pull()   # what the server holds NOW is what an env ending its episode in this step pulls (dsac.py:127-130)
+            self.pull()
         if self.t > self.opt.start_steps and self._fused_ready():
-            if not self._fused_live:   # the unfused path has stepped the envs since: refresh the actor's observation rows
-                _lib.check(self._rollout_calls()[0](env._h, self.actor._h, _lib.stream_ptr()))
-                self._fused_live = True
-            a = self.actor
-            _lib.check(self._rollout_calls()[1](env._h, a._h, self.rb._h, int(n_steps), a._noise_seed, a._noise_ctr, 0, _lib.dptr(self.act),
-                                                _lib.dptr(env.obs), _lib.stream_ptr()))
-            a._noise_ctr += int(n_steps) * env.n * a.cfg.act_dim
-            self.t += int(n_steps)
+            self._fused_refresh()
+            self._fused_step(int(n_steps))
+            self.t += int(n_steps) * self._t_per_step
             if not self._versions and self.auto_pull:
                 self.pull()
             return
@@ -721,37 +711,78 @@ class RolloutDevice:
             env.sample_actions(out=self.act)
         o2, r, d, _, ended = env.step(self.act)
         if self._versions:
-            self.actor.adopt_where_ended(ended)
+            self.actor.adopt_where_ended(ended)   # (clears the forward's plan_fresh: the next versioned forward plans for the moved envs)
         self.rb.store_batch(self.o, self.act, r, o2, d)
-        self.t += 1
+        self.t += self._t_per_step
         if not self._versions and self.auto_pull:
             self.pull()
 
 
-class RolloutDeviceDQN:
-    """The vectorised rollout worker of the discrete learners (worker_rollout_dqn's loop, algos/dqn/train.py:253-274, for
-    `opt.num_envs` envs in lock step): a VecLunarLanderDiscrete — this project's own one-body lander behind gym's discrete action
-    table — one dqn.Actor / ActorSQN (`opt.variant` "sqn" or `opt.make_actor`; default Double-DQN), a device replay ring
-    (ReplayBufferDQN) and a ParameterServer.  `t` counts this worker's transitions (the reference's gate is on actor_steps,
-    train.py:255).  step(): random actions while t <= start_steps, afterwards ONE Q-forward launch + ONE
-    launch that selects, steps the physics and appends to the ring (ddrl_rollout_step_discrete); shapes outside its envelope run
-    get_actions + env.step + store_batch.  Works with TrainDeviceDQN under ActorLearnerLoop as RolloutDevice does with TrainDevice.
+class RolloutDevice(_RolloutWorker):
+    """The vectorised rollout worker of example/dsac.py:96-130: VecLunarLander envs, one Actor, a local replay shard (the plain
+    five-array SAC ring).  Fused pair: ddrl_rollout_begin / ddrl_rollout_step; adoption defaults to "episode", horizon max_ep_len.
 
-    Weight adoption (`opt.adopt`, default "step"): the reference's worker pulls the server's weights once per episode, for its own env
-    only (algos/dqn/train.py:249-252: env.reset(), ps.pull, agent.set_weights), so its envs act on different versions at any moment.
-    "episode" reproduces that exactly, as RolloutDevice does on the continuous side: the actor's acting forward keeps
-    min(num_envs, max_ep_len) + 2 resident versions of the Q network (dqn.Actor.enable_versions), pull() — at the START of step():
-    what the server holds now is what an env ending in this step pulls — stores the server's weights as the newest one, and the fused
-    step's kernel (the random-action phase: adopt_where_ended) moves an env to it where that env's episode ends: the vector of envs is
-    then indistinguishable from num_envs reference workers stepped in lock step.  "episode" needs the fused envelope and num_envs equal
-    to the acting forward's rows (a multiple of 32); a shape or ring outside it falls back to "step", as does the default: pull() after
-    the step swaps the weights of every env at once — never staler than the reference's pull at each episode start, not identical."""
+    The articulated lander (`opt.env_model = "articulated"`) runs the unfused sequence — and so adopts per step — unless
+    `opt.fused_rollout_articulated` is set (default False): then the worker takes ddrl_rollout_begin_articulated /
+    ddrl_rollout_step_articulated, the same launch pair with the three-body solver in the env-step kernel, and "episode" adoption
+    holds on that model too.  The one-body worker ignores the flag."""
+
+    def __init__(self, ps, replay_buffer, opt, worker_index=0):
+        import torch
+        from .agent import Actor
+        from .env import VecLunarLander
+        self.rb, self.opt = replay_buffer, opt
+        self.env = VecLunarLander(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index),
+                                  max_ep_len=opt.max_ep_len, **_env_model_kw(opt))
+        self.actor = Actor(opt, job="worker", max_rows=opt.num_envs, index=worker_index)
+        self.t = 0
+        self.o = torch.empty_like(self.env.obs)
+        self.act = torch.empty(opt.num_envs, 2, dtype=torch.float32, device=self.env.device)
+        self._start(ps, getattr(opt, "fused_rollout", True), "episode")
+        if self.adopt == "episode":
+            self._fused_ready()   # the version store starts from the initial pull, before any step
+
+    def _rollout_calls(self):
+        """The fused pair of the envs' model: (begin, step) of the C library."""
+        lib = self.actor._lib
+        if self.env.model == "articulated":
+            return lib.ddrl_rollout_begin_articulated, lib.ddrl_rollout_step_articulated
+        return lib.ddrl_rollout_begin, lib.ddrl_rollout_step
+
+    def _fused_eligible(self):
+        from .replay import ReplayBuffer
+        ok = isinstance(self.rb, ReplayBuffer) and not getattr(self.rb, "_acts_1d", False) and self.env.n % 32 == 0
+        # ddrl_rollout_begin holds the one-body lander and refuses the other; the articulated pair is opt-in
+        return ok and (self.env.model == "simple" or
+                       (self.env.model == "articulated" and bool(getattr(self.opt, "fused_rollout_articulated", False))))
+
+    def _fused_begin(self):
+        from . import _lib
+        return self._rollout_calls()[0](self.env._h, self.actor._h, _lib.stream_ptr())
+
+    def _fused_step(self, n_steps):
+        from . import _lib
+        env, a = self.env, self.actor
+        _lib.check(self._rollout_calls()[1](env._h, a._h, self.rb._h, n_steps, a._noise_seed, a._noise_ctr, 0, _lib.dptr(self.act),
+                                            _lib.dptr(env.obs), _lib.stream_ptr()))
+        a._noise_ctr += n_steps * env.n * a.cfg.act_dim
+
+
+class RolloutDeviceDQN(_RolloutWorker):
+    """The vectorised rollout worker of the discrete learners (worker_rollout_dqn's loop, algos/dqn/train.py:253-274): a
+    VecLunarLanderDiscrete — this project's own one-body lander behind gym's discrete action table — one dqn.Actor / ActorSQN
+    (`opt.variant` "sqn" or `opt.make_actor`; default Double-DQN), a device replay ring (ReplayBufferDQN, not compact) and a
+    ParameterServer, pulled key by key.  `t` counts this worker's transitions (the reference's gate is on actor_steps, train.py:255).
+    Fused pair: ddrl_rollout_begin_discrete / ddrl_rollout_step_discrete (the one-body lander only); adoption defaults to "step",
+    "episode" has horizon max_ep_len.  Works with TrainDeviceDQN under ActorLearnerLoop as RolloutDevice does with TrainDevice."""
+
+    _flat_pull = False
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
         from . import dqn
         from .env import VecLunarLanderDiscrete
-        self.ps, self.rb, self.opt = ps, replay_buffer, opt
+        self.rb, self.opt = replay_buffer, opt
         self.env = VecLunarLanderDiscrete(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len,
                                           **_env_model_kw(opt))
         make = getattr(opt, "make_actor", None)
@@ -759,81 +790,30 @@ class RolloutDeviceDQN:
             cls = dqn.ActorSQN if str(getattr(opt, "variant", "ddqn")).lower() == "sqn" else dqn.Actor
             make = lambda o_, **kw: cls(o_, job="worker", **kw)
         self.actor = make(opt, max_rows=opt.num_envs, index=worker_index)
-        self.keys = list(self.actor.keys)
-        self.version = -1
-        self.t = 0
+        self.t, self._t_per_step = 0, self.env.n
         self.o = torch.empty_like(self.env.obs)
         self.act = torch.empty(opt.num_envs, dtype=torch.float32, device=self.env.device)
         self.q_out = None         # optional [num_envs, act_dim] float32 device tensor: the fused step's Q rows of its LAST step (tests, probes)
-        self._fused = None if getattr(opt, "fused_rollout", True) else False
-        self._fused_live = False
-        self.adopt = getattr(opt, "adopt", "step")
-        assert self.adopt in ("episode", "step"), self.adopt
-        self._versions = False
-        self.auto_pull = True
-        self.pull()
-        if self.adopt == "episode" and self._fused is None:
+        self._start(ps, getattr(opt, "fused_rollout", True), "step")
+        if self.adopt == "episode":
             self._fused_ready()   # the version store starts from the initial pull, before any step
 
-    def pull(self):
-        """ps.pull(keys) + agent.set_weights when the server has something newer."""
-        if self.ps is None or self.ps.version == self.version:
-            return False
-        self.version = self.ps.version
-        self.actor.set_weights(self.keys, self.ps.pull_device(self.keys))
-        return True
+    def _fused_eligible(self):
+        from .replay import ReplayBuffer
+        return (isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
+                and self.env.model == "simple")
 
-    def _fused_ready(self):
-        """Decided once: ddrl_rollout_begin_discrete refuses a shape outside the fused envelope, and the ring must be the DQN layout."""
-        if self._fused is None:
-            from . import _lib
-            from .replay import ReplayBuffer
-            ok = isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
-            ok = ok and self.env.model == "simple"   # the fused launch holds the one-body lander (ddrl_rollout_begin_discrete refuses the other)
-            if ok:
-                ok = self.actor._lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr()) == 0
-            self._fused, self._fused_live = ok, ok
-            if ok and self.adopt == "episode" and self.actor.max_rows == self.env.n:
-                # every env on the weights of the initial pull; later pulls become versions adopted at episode ends
-                self.actor.enable_versions(min(2048, min(self.env.n, int(self.opt.max_ep_len)) + 2))
-                self._versions = True
-        return self._fused
+    def _fused_begin(self):
+        from . import _lib
+        return self.actor._lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr())
 
-    def step(self, n_steps=1):
-        """One vector step = num_envs iterations of the reference loop; n_steps > 1 issues that many back to back on the weights held."""
+    def _fused_step(self, n_steps):
         from . import _lib
         env, a = self.env, self.actor
-        if self._versions and self.auto_pull:
-            self.pull()   # what the server holds NOW is what an env ending its episode in this step pulls (train.py:249-252)
-        if self.t > self.opt.start_steps and self._fused_ready():
-            if not self._fused_live:   # the unfused path has stepped the envs since: refresh the forward's observation rows
-                _lib.check(a._lib.ddrl_rollout_begin_discrete(env._h, a._h, _lib.stream_ptr()))
-                self._fused_live = True
-            _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, int(n_steps), _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
-                                                         a._noise_seed, a._noise_ctr, _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs),
-                                                         _lib.stream_ptr()))
-            a._noise_ctr += int(n_steps) * 2 * env.n
-            self.t += int(n_steps) * env.n
-            if not self._versions and self.auto_pull:
-                self.pull()
-            return
-        if n_steps > 1:
-            for _ in range(int(n_steps)):
-                self.step()
-            return
-        self._fused_live = False
-        self.o.copy_(env.obs)
-        if self.t > self.opt.start_steps:
-            a.get_actions(self.o, out=self.act)
-        else:
-            env.sample_actions(out=self.act)
-        o2, r, d, _, ended = env.step(self.act)
-        if self._versions:
-            a.adopt_where_ended(ended)   # (clears the forward's plan_fresh: the next versioned forward plans for the moved envs)
-        self.rb.store_batch(self.o, self.act, r, o2, d)
-        self.t += env.n
-        if not self._versions and self.auto_pull:
-            self.pull()
+        _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
+                                                     a._noise_seed, a._noise_ctr, _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs),
+                                                     _lib.stream_ptr()))
+        a._noise_ctr += n_steps * 2 * env.n
 
 
 class WindowQueue:
@@ -874,7 +854,7 @@ class WindowQueue:
         return self.ready
 
 
-class RolloutDeviceNStep:
+class RolloutDeviceNStep(_RolloutWorker):
     """worker_rollout of the n-step driver (algos/sac1/sac_ray.py:179-262) for `opt.num_envs` envs per launch:
     Wrapper'd env.step (action noise, action repeat 3, observation noise, reward scale), the per-env window
     queues, and `replay_buffer[random shard].store(o_queue, a_r_d_queue)` for every env whose queues are full —
@@ -882,7 +862,11 @@ class RolloutDeviceNStep:
     ps=None (a rollout rank of partition.py): nothing is pulled — the worker still owns an Actor, which takes the learner's
     broadcasts through actor.set_weights_flat, as RolloutDevice's does, and acts with it once filling_steps > opt.start_steps
     (until then, and for ever with the default start_steps inside a short run, on random actions as before; earlier versions
-    had no Actor without a server and stayed on random actions throughout)."""
+    had no Actor without a server and stayed on random actions throughout).
+    Fused pair: ddrl_rollout_begin_nstep / ddrl_rollout_step_nstep, for the policy phase with the version store on.  Adoption defaults
+    to "episode" with horizon limit_steps, the store is enabled in the constructor, and an env adopts at `d or ep_len * action_repeat >=
+    max_ep_len` only once the buffer's steps exceed start_steps (`_learning`, sac_ray.py:252-262).  Its step() is its own: the
+    filling phase counts filling_steps, not t, and every step pushes the window queues."""
 
     WRAPPER_REPEAT = 3  # the literal in sac_ray.py:189 (opt.action_repeat only scales the episode limit)
 
@@ -891,67 +875,53 @@ class RolloutDeviceNStep:
         import torch
         from .agent import Actor
         from .env import VecLunarLander
-        self.ps, self.opt = ps, opt
+        self.opt = opt
         self.rbs = list(replay_buffers) if isinstance(replay_buffers, (list, tuple)) else [replay_buffers]
         n = int(opt.num_envs)
         self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23)
         self.limit_steps = -(-int(opt.max_ep_len) // int(opt.action_repeat))   # ep_len * action_repeat >= max_ep_len (sac_ray.py:252)
         self.actor = Actor(opt, job="worker", max_rows=n, index=worker_index)
-        self.span = ps.span(self.actor.keys) if ps is not None else None
-        self._layout = getattr(ps, "layout", 0)
-        self.version = -1
         self.filling_steps = 0
         self.winq = WindowQueue(n, opt.Ln, opt.obs_dim, opt.act_dim, getattr(opt, "save_freq", 1), device=self.env.device.index)
         self.winq.begin(self.env.obs)
         self.o = torch.empty_like(self.env.obs)
         self.act = torch.empty(n, 2, dtype=torch.float32, device=self.env.device)
         self.pick = np.random.RandomState(int(opt.seed) + 7919 * int(worker_index))
-        self.pull()
-        # Weight adoption as in RolloutDevice: "episode" (default) = every env acts on what ITS OWN episode end pulled
-        # (sac_ray.py:252-262: at `d or ep_len * action_repeat >= max_ep_len`, and only once the buffer's steps exceed start_steps),
-        # through the actor's version store; "step" = every env on the newest weights from the next vector step on.
-        self.adopt = getattr(opt, "adopt", "episode")
-        self._versions = False
+        # `opt.fused_nstep_rollout`, default True: the measurement behind the default is profiles/nstep_rollout.txt.  _fused_live covers
+        # the queues' readiness bytes too: a caller that rewrites the queues or t_queue by hand between two fused steps clears it
+        self._start(ps, getattr(opt, "fused_nstep_rollout", True), "episode")
         self._learning = bool(getattr(opt, "weights_file", ""))   # steps > start_steps seen (sticky): pulls happen from then on
         if self.adopt == "episode" and n % 32 == 0:
             try:
-                self.actor.enable_versions(min(2048, min(n, self.limit_steps) + 2))
-                self._versions = True
+                self._enable_versions(self.limit_steps)
             except ValueError:       # a policy outside the direct-operand envelope: whole-vector swap
-                self._versions = False
-        # The policy phase as two launches (ddrl_rollout_step_nstep): `opt.fused_nstep_rollout`, default True — the measurement behind the
-        # default is profiles/nstep_rollout.txt.  None: not decided yet (_fused_ready); _fused_live: the actor's observation rows and
-        # the queues' readiness bytes are those of the last fused step (no unfused step since; a caller that rewrites the queues or
-        # t_queue by hand between two fused steps clears it, so that ddrl_rollout_begin_nstep runs again).
-        self._fused = None if getattr(opt, "fused_nstep_rollout", True) else False
-        self._fused_live = False
+                pass
         self._out = None
-
-    pull = RolloutDevice.pull
 
     def step(self, n_steps=1):
         """n_steps vector steps, back to back."""
         for _ in range(int(n_steps)):
             self._step_once()
 
-    def _fused_ready(self):
-        """Can this worker take the fused launch pair (ddrl_rollout_step_nstep)?  Decided once.  The fused step evaluates the
-        direct-operand forward, which is what the unfused sequence runs only with the version store on (get_actions_versioned; without
-        it get_actions runs the row-major kernels, whose float32 sums are ordered differently): the store is part of the envelope, so
-        that the two paths stay bit-identical.  The C entry point checks the rest (shapes of env, actor, queues and rings)."""
-        if self._fused is None:
+    def _fused_eligible(self):
+        """The fused step evaluates the direct-operand forward, which is what the unfused sequence runs only with the version store on
+        (get_actions_versioned; without it get_actions runs the row-major kernels, whose float32 sums are ordered differently): the
+        store is part of the envelope, so that the two paths stay bit-identical.  The C entry point checks the rest."""
+        from . import _lib
+        from .replay import ReplayBufferNStep
+        ok = self._versions and self.env.model == "simple" and all(isinstance(rb, ReplayBufferNStep) for rb in self.rbs)
+        ok = ok and self.env.n % 32 == 0 and self.winq.Ln <= _lib.DDRL_NSTEP_FUSED_MAX_LN
+        return ok and all(rb.max_size < (1 << 31) and rb.Ln == self.winq.Ln and (rb.obs_dim, rb.act_dim) == (8, 2) for rb in self.rbs)
+
+    def _fused_begin(self):
+        from . import _lib
+        return self.actor._lib.ddrl_rollout_begin_nstep(self.env._h, self.actor._h, self.winq._h, _lib.stream_ptr())
+
+    def _fused_decided(self, ok):
+        if ok:
             from . import _lib
-            from .replay import ReplayBufferNStep
-            ok = self._versions and self.env.model == "simple" and all(isinstance(rb, ReplayBufferNStep) for rb in self.rbs)
-            ok = ok and self.env.n % 32 == 0 and self.winq.Ln <= _lib.DDRL_NSTEP_FUSED_MAX_LN
-            ok = ok and all(rb.max_size < (1 << 31) and rb.Ln == self.winq.Ln and (rb.obs_dim, rb.act_dim) == (8, 2) for rb in self.rbs)
-            if ok:
-                ok = self.actor._lib.ddrl_rollout_begin_nstep(self.env._h, self.actor._h, self.winq._h, _lib.stream_ptr()) == 0
-            if ok:
-                env = self.env
-                self._out = _lib.RolloutNStepOut(act=_lib.dptr(self.act), next_obs=_lib.dptr(env.obs), ended=_lib.dptr(env.ended))
-            self._fused, self._fused_live = ok, ok
-        return self._fused
+            env = self.env
+            self._out = _lib.RolloutNStepOut(act=_lib.dptr(self.act), next_obs=_lib.dptr(env.obs), ended=_lib.dptr(env.ended))
 
     def _step_fused(self):
         """The policy phase of _step_once as the forward + ONE launch (csrc/rollout_nstep.hip); same bits as the sequence below."""
@@ -959,9 +929,7 @@ class RolloutDeviceNStep:
         from . import _lib
         env, opt, a = self.env, self.opt, self.actor
         rb = self.rbs[int(self.pick.choice(len(self.rbs), 1)[0])]   # replay_buffer[np.random.choice(opt.num_buffers, 1)[0]]
-        if not self._fused_live:     # the unfused path has touched the env or the queues since: observation rows and readiness bytes anew
-            _lib.check(a._lib.ddrl_rollout_begin_nstep(env._h, a._h, self.winq._h, _lib.stream_ptr()))
-            self._fused_live = True
+        self._fused_refresh()        # (observation rows and readiness bytes anew, where the unfused path has touched the env or the queues)
         _lib.check(a._lib.ddrl_rollout_step_nstep(env._h, a._h, self.winq._h, rb._h, 1, float(getattr(opt, "act_noise", 0.0)),
                                                   float(getattr(opt, "obs_noise", 0.0)), float(getattr(opt, "reward_scale", 1.0)),
                                                   self.WRAPPER_REPEAT, self.limit_steps, 1 if self._learning else 0, a._noise_seed,
