@@ -195,6 +195,9 @@ SIGNATURES = {
     "ddrl_dqn_q": (c_int, [_P, _P, c_int64, _P, _P]),
     "ddrl_dqn_act": (c_int, [_P, _P, c_int64, c_int, c_float, c_uint32, c_uint64, _P, _P, _P]),
     "ddrl_dqn_eval": (c_int, [POINTER(DqnConfig), _P, c_int32, c_uint32, c_uint32, c_int32, c_int, c_float, c_uint32, c_uint64, _P, _P, _P, _P]),
+    "ddrl_env_eval_policy": (c_int, [_P, _P, c_int32, c_uint32, c_int32, _P]),
+    "ddrl_env_eval_q": (c_int, [_P, _P, c_int32, c_uint32, c_int, c_float, c_uint32, c_uint64, c_int32, _P]),
+    "ddrl_env_eval_results": (c_int, [_P, POINTER(_P), POINTER(_P), POINTER(_P), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "ddrl_dqn_versions_enable": (c_int, [_P, c_int32, _P]),
     "ddrl_dqn_versions_state": (c_int, [_P, _P, _P, _P]),
     "ddrl_dqn_versions_adopt": (c_int, [_P, _P, c_int64, _P]),

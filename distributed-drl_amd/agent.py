@@ -550,14 +550,18 @@ class Model(Learner):
 
 def _device_episodes(actor, test_env, n, max_ep_len):
     """The episodes of Actor.test / Model.test_agent on an env.DeviceLunarLander: `actor.evaluate` from the env's episode count
-    on, which then advances by n.  -> the n returns as Python floats, in episode order (what the host loop's `ep_ret`s are).
+    on, which then advances by n (a marker of the articulated model: `actor.evaluate_env`, the handle-fed launch of that model).
+    -> the n returns as Python floats, in episode order (what the host loop's `ep_ret`s are).
     Outside the kernel's envelope (DDRL_ERR_UNSUPPORTED: a hidden width > 512) a host LunarLander of the same seed, positioned
     at the same episode, is stepped instead."""
     if int(test_env.max_ep_len) != int(max_ep_len):
         raise ValueError("the test env's max_ep_len (%d) must equal the agent's (%d): the device plays whole episodes"
                          % (test_env.max_ep_len, max_ep_len))
     try:
-        rets = [float(x) for x in actor.evaluate(n, test_env.seed, test_env.episodes_played, max_ep_len)["ret"]]
+        if getattr(test_env, "model", "simple") != "simple":   # the articulated lander: the handle-fed launch (ddrl_env_eval_policy)
+            rets = [float(x) for x in actor.evaluate_env(test_env, n)["ret"]]
+        else:
+            rets = [float(x) for x in actor.evaluate(n, test_env.seed, test_env.episodes_played, max_ep_len)["ret"]]
     except _lib.DdrlUnsupported:
         host, rets = test_env.host_env(), []
         for _ in range(n):
@@ -695,6 +699,20 @@ class Actor(_Net):
         if trace:
             out["trace"] = tr.cpu().numpy()
         return out
+
+    def evaluate_env(self, dev_env, n=25, first_episode=None, trace=False):
+        """n deterministic evaluation episodes of `dev_env`'s model — an env.DeviceLunarLander of either model — as one launch fed from
+        handles (ddrl_env_eval_policy, csrc/eval3.hip): episode e is the (first_episode + e)-th episode a host
+        `LunarLander(dev_env.seed, dev_env.max_ep_len, model=...)` plays (default: from dev_env.episodes_played on; the count is NOT
+        advanced here), acted on with this actor's current weights — the library reads them out of the actor handle — by
+        get_action(o, deterministic=True)'s arithmetic.  -> the dict `evaluate` returns, read from the results block the marker's
+        handle owns.  The actor's weights and noise counter and the lending handle's env state are untouched."""
+        n = int(n)
+        first = int(dev_env.episodes_played if first_episode is None else first_episode)
+        vec = dev_env.handle()
+        _lib.check(self._lib.ddrl_env_eval_policy(vec._h, self._h, n, first, 1 if trace else 0, _lib.stream_ptr()))
+        from .env import eval_results
+        return eval_results(vec, 12)
 
     def test(self, test_env, replay_buffer=None, n=25):
         """Deterministic evaluation episodes (actor_learner.py:199-218); returns the mean return.  With opt.summary_dir set the

@@ -1061,6 +1061,13 @@ int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, vo
 }  // extern "C"
 
 // ---- internal (env.hip: ddrl_rollout_step_discrete) ---------------------------------------------------------------
+// the configuration and the device, for the handle-fed evaluation entry points (eval3.hip; declared in eval_episodes.h)
+int ddrl_dqn_internal_config(ddrl_dqn_t *h, ddrl_dqn_config_t *cfg_out, int *device_out) {
+    if (!h) return DDRL_ERR_BAD_ARG;
+    *cfg_out = h->cfg; *device_out = h->device;
+    return DDRL_OK;
+}
+
 ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h) {
     ddrl_dqn_rollout_view v{};
     if (!h) return v;

@@ -12,6 +12,7 @@
 #include "policy_row.h"
 #include "replay_device.h"
 #include "env_device.h"
+#include "env_handle.h"
 #include "dqn_select.h"
 #include "version_plan.h"
 #include "rollout_nstep.h"
@@ -433,16 +434,7 @@ __global__ void __launch_bounds__(256) k_env_obs(float *S, long long n, uint32_t
 
 }  // namespace
 
-struct ddrl_env {
-    int device;
-    long long n;
-    uint32_t seed;
-    int max_ep_len;
-    float *S;
-    EnvStats *stats;
-    int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's only
-    int fields;           // rows of S: DDRL_ENV_STATE_FIELDS or DDRL_ENV3_STATE_FIELDS
-};
+// struct ddrl_env: env_handle.h (shared with eval3.hip, whose evaluation entry points own the handle's results block)
 
 // the articulated model's launches (env3.hip)
 int ddrl_env3_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
@@ -622,6 +614,7 @@ int ddrl_env_destroy(ddrl_env_t *h) {
     if (!h) return DDRL_OK;
     ddrl::DeviceGuard g(h->device);
     (void)hipFree(h->S); (void)hipFree(h->stats);
+    (void)hipFree(h->ev_block); (void)hipFree(h->ev_w);   // the evaluation results block and weight staging (eval3.hip)
     delete h;
     return DDRL_OK;
 }

@@ -1,0 +1,26 @@
+// The env handle behind ddrl_env_* as the translation units that reach into it see it: env.hip (create / destroy, the step and the
+// fused rollout entry points) and eval3.hip (the evaluation episodes, which borrow the handle's model and own its results block).
+// Host side only: never a kernel argument.
+#pragma once
+#include "ddrl_common.h"
+#include "env_device.h"
+
+struct ddrl_env {
+    int device;
+    long long n;
+    uint32_t seed;
+    int max_ep_len;
+    float *S;
+    EnvStats *stats;
+    int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's only
+    int fields;           // rows of S: DDRL_ENV_STATE_FIELDS or DDRL_ENV3_STATE_FIELDS
+    // ---- evaluation episodes (ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_results, eval3.hip).  Everything below is
+    // allocated at the first evaluation, grows when a call needs more, and is freed by ddrl_env_destroy; S and stats above are
+    // neither read nor written by an evaluation.
+    unsigned char *ev_block;   // ret float64 [n] | len int32 [n] | trace float32 [n][max_ep_len][row], each part 256-byte aligned
+    size_t ev_bytes;           // its capacity
+    float *ev_w;               // the agent's weights in the flat external order, as the launch reads them
+    size_t ev_w_floats;        // its capacity
+    size_t ev_len_off, ev_trace_off;   // the last call's layout ...
+    int ev_n, ev_row;                  // ... its episode count and trace row (0: no trace); ev_n == 0: no evaluation yet
+};

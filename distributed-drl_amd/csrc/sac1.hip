@@ -2636,6 +2636,13 @@ int ddrl_actor_internal_forward(ddrl_actor *h, long long n, void *stream, int ve
     return DDRL_OK;
 }
 
+// the configuration and the device, for the handle-fed evaluation entry points (eval3.hip; declared in eval_episodes.h)
+int ddrl_actor_internal_config(ddrl_actor *h, ddrl_sac1_config_t *cfg_out, int *device_out) {
+    if (!h) return DDRL_ERR_BAD_ARG;
+    *cfg_out = h->cfg; *device_out = h->device;
+    return DDRL_OK;
+}
+
 ddrl_actor_rollout_view ddrl_actor_internal_view(ddrl_actor *h) {
     ddrl_actor_rollout_view v{};
     if (!h || !h->direct) return v;

@@ -270,6 +270,26 @@ def _evaluate(self, n=10, seed=0, first_episode=0, max_ep_len=None, deterministi
     return out
 
 
+def _evaluate_env(self, dev_env, n=10, first_episode=None, deterministic=None, greedy_prob=None, trace=False):
+    """n evaluation episodes of `dev_env`'s model — an env.DeviceLunarLanderDiscrete of either model — as one launch fed from handles
+    (ddrl_env_eval_q, csrc/eval3.hip): episode e is the (first_episode + e)-th episode a host
+    `LunarLanderDiscrete(dev_env.seed, dev_env.max_ep_len, model=...)` plays (default: from dev_env.episodes_played on; the count is NOT
+    advanced here), acted on with this handle's current main weights (SQN: q1), which the library reads out of the handle.  Modes,
+    defaults and the noise-counter rule are `evaluate`'s: the counter advances by 2 n max_ep_len per call, whatever the mode.
+    -> the dict `evaluate` returns, read from the results block the marker's handle owns."""
+    n = int(n)
+    first = int(dev_env.episodes_played if first_episode is None else first_episode)
+    deterministic = self._eval_deterministic if deterministic is None else bool(deterministic)
+    greedy_prob = float(self.greedy_prob if greedy_prob is None else greedy_prob)
+    mode = _lib.DDRL_ACT_DETERMINISTIC if deterministic else _lib.DDRL_ACT_SAMPLE
+    vec = dev_env.handle()
+    _lib.check(self._lib.ddrl_env_eval_q(vec._h, self._h, n, first, mode, greedy_prob, self._noise_seed, self._noise_ctr,
+                                         1 if trace else 0, _lib.stream_ptr()))
+    self._noise_ctr += 2 * n * int(dev_env.max_ep_len)
+    from .env import eval_results
+    return eval_results(vec, EVAL_ROW)
+
+
 # -- version store: exact per-env weight adoption of the vectorised discrete rollout worker (algos/dqn/train.py:249-252) -------------------
 def _enable_versions(self, n_slots):
     """Keep `n_slots` resident copies of the acting Q network (ddrl_dqn_versions_enable): set_weights / import_ of MAIN / the repack after
@@ -324,13 +344,14 @@ class Actor(Learner):
         return self.get_action(o)
 
     _eval_deterministic = False   # evaluate's default mode: what _test_action does
-    evaluate = _evaluate
+    evaluate, evaluate_env = _evaluate, _evaluate_env
 
     def test(self, test_env, n=10):
         """actor_learner.py:230-251: n episodes to their terminal with the actor's own get_action; (mean return, mean of
         test_env.rewards[0] at each episode's end — the trading env's score).
         On a test env with `on_device` (env.DeviceLunarLanderDiscrete) the n episodes run as ONE launch (evaluate) from
         test_env.episodes_played on, which then advances by n; the lander's score is its return, so (mean return, mean return).
+        A marker of the articulated model runs evaluate_env (ddrl_env_eval_q, csrc/eval3.hip) instead.
         The env's max_ep_len must equal opt.max_ep_len where the options carry one (the device plays whole episodes).  Outside the
         kernel's envelope (DdrlUnsupported) the host loop below runs on test_env.host_env(): the same episode indices."""
         if getattr(test_env, "on_device", False):
@@ -339,7 +360,10 @@ class Actor(Learner):
                 raise ValueError("the test env's max_ep_len (%d) must equal the agent's (%d): the device plays whole episodes"
                                  % (test_env.max_ep_len, want))
             try:
-                ret = float(np.mean(self.evaluate(n, test_env.seed, test_env.episodes_played, want)["ret"]))
+                if getattr(test_env, "model", "simple") != "simple":   # the articulated lander: the handle-fed launch (ddrl_env_eval_q)
+                    ret = float(np.mean(self.evaluate_env(test_env, n)["ret"]))
+                else:
+                    ret = float(np.mean(self.evaluate(n, test_env.seed, test_env.episodes_played, want)["ret"]))
                 out = (ret, ret)
             except _lib.DdrlUnsupported:
                 out = self.test(test_env.host_env(), n)
@@ -406,5 +430,5 @@ class ActorSQN(LearnerSQN):
         return self.get_action(o, deterministic=True)     # algos/sqn/actor_learner.py:238
 
     _eval_deterministic = True
-    evaluate = _evaluate
+    evaluate, evaluate_env = _evaluate, _evaluate_env
     test, write_tb = Actor.test, Actor.write_tb

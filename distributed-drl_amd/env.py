@@ -216,17 +216,28 @@ class LunarLanderDiscrete(LunarLander):
 
 class DeviceLunarLander:
     """The test env of an on-device evaluation: a MARKER, not a steppable env.  It holds what names the episodes a host
-    `LunarLander(seed, max_ep_len)` would play one after another — the seed and how many episodes have been played — and
-    `Actor.test` / `Model.test_agent` given one run their episodes as one launch (`Actor.evaluate`, csrc/eval.hip) and advance
-    the count.  reset / action_space exist so that nothing breaks on attribute access at construction; step raises."""
+    `LunarLander(seed, max_ep_len, model=...)` would play one after another — the seed, the model and how many episodes have been
+    played — and `Actor.test` / `Model.test_agent` given one run their episodes as one launch and advance the count: on the one-body
+    lander (model="simple") `Actor.evaluate` (ddrl_policy_eval, csrc/eval.hip), on the articulated lander `Actor.evaluate_env`
+    (ddrl_env_eval_policy, csrc/eval3.hip), which borrows `handle()`: a one-env handle of the marker's model, created at the first
+    use, that names the model to the library and owns the results block.  Its env state is never stepped.
+    reset / action_space exist so that nothing breaks on attribute access at construction; step raises."""
 
     on_device = True
 
-    def __init__(self, seed=0, max_ep_len=1000):
+    def __init__(self, seed=0, max_ep_len=1000, *, model="simple", velocity_iterations=180, position_iterations=60):
         self.seed, self.max_ep_len = int(seed) & 0xFFFFFFFF, int(max_ep_len)
+        self.model = _check_model(model)
+        self.velocity_iterations, self.position_iterations = int(velocity_iterations), int(position_iterations)
         self.episodes_played = 0
         self.action_space = _ActionSpace(self)
         self.observation_space = _ObsSpace()
+        self._lend = None
+
+    def _model_kw(self):
+        if self.model == "simple":
+            return {}
+        return dict(model=self.model, velocity_iterations=self.velocity_iterations, position_iterations=self.position_iterations)
 
     def reset(self):
         return np.zeros(8, np.float64)
@@ -235,13 +246,22 @@ class DeviceLunarLander:
         raise RuntimeError("DeviceLunarLander is not steppable: its episodes run on the device (Actor.evaluate / Actor.test / "
                            "Model.test_agent); use env.make(name) for an env to step from the host")
 
+    def handle(self):
+        """The one-env handle (a VecLunarLander of this marker's seed, max_ep_len and model) lent to ddrl_env_eval_policy /
+        ddrl_env_eval_q; created on first use."""
+        if self._lend is None:
+            self._lend = VecLunarLander(1, seed=self.seed, max_ep_len=self.max_ep_len, **self._model_kw())
+        return self._lend
+
     def host_env(self):
-        """A host `LunarLander` of the same seed positioned at the next episode this env would play (the fallback of a policy
-        outside ddrl_policy_eval's envelope)."""
-        host = self._host_class(self.seed, self.max_ep_len)
+        """A host env of the same seed and model positioned at the next episode this env would play (the fallback of a policy
+        outside the evaluation kernels' envelope)."""
+        host = self._host_class(self.seed, self.max_ep_len, **self._model_kw())
         if self.episodes_played:
             s = host._vec.get_state()
-            s[13] = float(self.episodes_played)   # EPI (csrc/env_device.h): the episode index names the env's random stream
+            # EPI: the episode index names the env's random stream.  Field 13 in BOTH layouts (csrc/env_device.h's enum, which
+            # env3_device.h's load / store index with too; tests/lander3_oracle.py keeps it there for this line)
+            s[13] = float(self.episodes_played)
             host._vec.set_state(s)
             host._vec.reset()
         return host
@@ -251,17 +271,41 @@ class DeviceLunarLander:
 
 class DeviceLunarLanderDiscrete(DeviceLunarLander):
     """The same marker for the discrete lander (action_space.n == 4): `dqn.Actor.test` / `ActorSQN.test` given one run their episodes
-    as one launch (`evaluate`, csrc/eval_q.hip); host_env() is a `LunarLanderDiscrete` positioned at `episodes_played`."""
+    as one launch (`evaluate`, csrc/eval_q.hip; on the articulated model `evaluate_env`, csrc/eval3.hip); host_env() is a
+    `LunarLanderDiscrete` positioned at `episodes_played`."""
 
     _host_class = LunarLanderDiscrete
 
-    def __init__(self, seed=0, max_ep_len=1000):
-        super().__init__(seed, max_ep_len)
+    def __init__(self, seed=0, max_ep_len=1000, **model_kw):
+        super().__init__(seed, max_ep_len, **model_kw)
         self.action_space = _DiscreteActionSpace(self)
 
     def step(self, a):
         raise RuntimeError("DeviceLunarLanderDiscrete is not steppable: its episodes run on the device (dqn.Actor.evaluate / "
                            "dqn.Actor.test); use env.make(\"LunarLander-v2\") for an env to step from the host")
+
+
+def eval_results(vec, want_row):
+    """The results of the last ddrl_env_eval_policy / ddrl_env_eval_q on `vec` (a VecLunarLander) as NumPy: dict(ret float64 [n],
+    len int32 [n]) and, where that call kept a trace, `trace` float32 [n, max_ep_len, want_row].  Read from the block the env handle
+    owns (ddrl_env_eval_results) through __cuda_array_interface__ views, as replay.py reads its rings; synchronises the stream."""
+    ret, ln, tr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    n, L, row = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _lib.check(vec._lib.ddrl_env_eval_results(vec._h, ctypes.byref(ret), ctypes.byref(ln), ctypes.byref(tr), ctypes.byref(n),
+                                              ctypes.byref(L), ctypes.byref(row)))
+    n, L, row = int(n.value), int(L.value), int(row.value)
+
+    def view(ptr, count, typestr):
+        class _Holder:
+            __cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(_Holder(), device=vec.device)
+    torch.cuda.current_stream().synchronize()
+    out = {"ret": view(ret.value, n, "<f8").cpu().numpy(), "len": view(ln.value, n, "<i4").cpu().numpy()}
+    if row:
+        if row != want_row:
+            raise _lib.DdrlError("the env handle's last evaluation kept a trace of %d floats per step, not %d" % (row, want_row))
+        out["trace"] = view(tr.value, n * L * row, "<f4").cpu().numpy().reshape(n, L, row)
+    return out
 
 
 class Wrapper(object):
@@ -304,11 +348,13 @@ class Wrapper(object):
 
 def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     """gym.make stand-in (example/dsac.py:78).  model="simple" | "articulated" (+ velocity_iterations, position_iterations) is passed on to the env.  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
-    `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)."""
+    `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)
+    on the one-body lander; the articulated model's marker is built by make_device."""
     if on_device and _check_model(kw.get("model", "simple")) != "simple":
-        raise ValueError("env.make(on_device=True, model=%r): the on-device evaluation kernels (ddrl_policy_eval, csrc/eval.hip; ddrl_dqn_eval, "
-                         "csrc/eval_q.hip) hold the one-body lander only — no evaluation kernel for the articulated model is built yet; "
-                         "use on_device=False for a host-stepped env of that model" % (kw.get("model"),))
+        raise ValueError("env.make(on_device=True, model=%r): this door builds the one-body lander's marker only (ddrl_policy_eval, csrc/eval.hip; "
+                         "ddrl_dqn_eval, csrc/eval_q.hip) — the evaluation kernel for the articulated model (ddrl_env_eval_policy / "
+                         "ddrl_env_eval_q, csrc/eval3.hip) is reached through env.make_device(env_name, model=%r, ...); "
+                         "use on_device=False for a host-stepped env of that model" % (kw.get("model"), kw.get("model")))
     if on_device:
         kw = {k: v for k, v in kw.items() if k not in ("model", "velocity_iterations", "position_iterations")}
     if env_name == "LunarLander-v2":   # gym's discrete action table on the same lander (action_space.n == 4)
@@ -316,3 +362,15 @@ def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     if "LunarLander" not in env_name:
         raise ValueError("only the LunarLanderContinuous-v2 stand-in is built (SURVEY §8(a) A7): %r" % env_name)
     return DeviceLunarLander(**kw) if on_device else LunarLander(**kw)
+
+
+def make_device(env_name="LunarLanderContinuous-v2", **kw):
+    """The test-env marker of an on-device evaluation for EITHER model: seed, max_ep_len and model="simple" | "articulated"
+    (+ velocity_iterations, position_iterations) as env.make takes them.  "LunarLander-v2": DeviceLunarLanderDiscrete (dqn.Actor.test /
+    ActorSQN.test), else DeviceLunarLander (Actor.test / Model.test_agent).  The one-body marker is what make(on_device=True) returns."""
+    _check_model(kw.get("model", "simple"))
+    if env_name == "LunarLander-v2":
+        return DeviceLunarLanderDiscrete(**kw)
+    if "LunarLander" not in env_name:
+        raise ValueError("only the LunarLanderContinuous-v2 stand-in is built (SURVEY §8(a) A7): %r" % env_name)
+    return DeviceLunarLander(**kw)

@@ -41,6 +41,16 @@ def _default_env(name, args):
     return _env.make(name, seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len))
 
 
+def _default_test_env(name, args):
+    """The test workers' env when the caller passes no make_env: the host env of _default_env — or, with `args.test_on_device` set
+    (default False), the device marker of `args.env_model` (env.make_device with _env_model_kw): a round's evaluation episodes then
+    run as one launch, on the one-body and on the articulated lander."""
+    if not getattr(args, "test_on_device", False):
+        return _default_env(name, args)
+    from . import env as _env
+    return _env.make_device(name, seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len), **_env_model_kw(args))
+
+
 def _stop(args):
     ev = getattr(args, "stop_event", None)
     return ev is not None and ev.is_set()
@@ -121,14 +131,15 @@ def worker_train(ps, replay_buffer, args, make_agent=None):
 
 def worker_test(ps, args, start_time=None, n=10, make_env=None, make_agent=None, log=print, max_rounds=None):
     """example/dsac.py:153-177: pull, run n deterministic episodes, log, repeat.  With `args.logger_kwargs`
-    (dsac.py:205) the rounds also go to an EpochLogger: config.json + progress.txt (AverageTestEpRet, Time)."""
+    (dsac.py:205) the rounds also go to an EpochLogger: config.json + progress.txt (AverageTestEpRet, Time).
+    make_env None and `args.test_on_device` set: the test env is the device marker of `args.env_model` (_default_test_env)."""
     logger = None
     if getattr(args, "logger_kwargs", None):
         from .logx import EpochLogger
         logger = EpochLogger(**args.logger_kwargs)
         logger.save_config({k: v for k, v in vars(args).items()} if hasattr(args, "__dict__") else {})
     if make_env is None:
-        make_env = lambda name: _default_env(name, args)
+        make_env = lambda name: _default_test_env(name, args)
     if make_agent is None:
         from .agent import Actor
         make_agent = lambda a: Actor(a, job="test")   # example/dsac.py's test worker logs through EpochLogger only (no tf.summary writer)
@@ -239,9 +250,10 @@ def worker_train_sac1(ps, replay_buffer, opt, learner_index, make_agent=None, ma
 
 def worker_test_sac1(ps, replay_buffer, opt, make_env=None, make_agent=None, log=print, sleep=time.sleep, max_rounds=None, n=25):
     """algos/sac1/sac1.py:214-252: pull, 25 deterministic episodes, print test_reward / counters / update frequency,
-    `ps.save_weights()` whenever the return beats the best so far, sleep 5 s, repeat."""
+    `ps.save_weights()` whenever the return beats the best so far, sleep 5 s, repeat.
+    make_env None and `opt.test_on_device` set: the test env is the device marker of `opt.env_model` (_default_test_env)."""
     if make_env is None:
-        make_env = lambda name: _default_env(name, opt)
+        make_env = lambda name: _default_test_env(name, opt)
     if make_agent is None:
         from .agent import Actor
         make_agent = lambda o: Actor(o, job="main")
@@ -443,14 +455,16 @@ def worker_test_dqn(ps, node_buffer, opt, node_ps=None, make_env=None, make_agen
     learner's update frequency over the test's duration), TensorBoard scalars, the whole weight dict pickled every save_interval
     learner steps, every server and every buffer checkpointed every checkpoint_freq seconds.
     make_env=lambda: env.make(opt.env_name, on_device=True, seed=opt.seed, max_ep_len=opt.max_ep_len) hands agent.test the device
-    marker (env.DeviceLunarLanderDiscrete): the ten episodes of a round then run as one launch (dqn.Actor.evaluate)."""
+    marker (env.DeviceLunarLanderDiscrete): the ten episodes of a round then run as one launch (dqn.Actor.evaluate).  With make_env
+    None and `opt.test_on_device` set the marker of `opt.env_model` is built here (_default_test_env): on the articulated lander the
+    launch is dqn.Actor.evaluate_env."""
     import pickle
     import numpy as np
     if make_agent is None:
         from .dqn import Actor
         make_agent = lambda o_: Actor(o_, job="test")
     if make_env is None:
-        make_env = lambda: _default_env(opt.env_name, opt)
+        make_env = lambda: _default_test_env(opt.env_name, opt)
     if node_ps is None:
         node_ps = [ps]
     if wait is None:

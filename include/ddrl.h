@@ -472,7 +472,8 @@ int ddrl_actor_act_one(ddrl_actor_t *h, const float *obs_d, uint32_t noise_seed,
  * an episode's end are written as zeros.  Stream-ordered on the CURRENT device: no host synchronisation, no allocation.
  * DDRL_ERR_BAD_ARG unless obs_dim == 8, act_dim == 2, n_episodes >= 1, max_ep_len >= 1 (and max_ep_len, first_episode + n_episodes
  * exact in float32: <= 2^24); DDRL_ERR_UNSUPPORTED outside ddrl_actor_act_one's envelope (a hidden width > 512).
- * Takes no env handle: the episodes are the ONE-BODY lander's (DDRL_ENV_ONE_BODY); the articulated model has no evaluation kernel yet. */
+ * Takes no env handle: the episodes are the ONE-BODY lander's (DDRL_ENV_ONE_BODY).  The articulated model's evaluation episodes — and
+ * the same launch fed from an actor handle instead of caller memory — are ddrl_env_eval_policy (below, with the env entry points). */
 int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int32_t n_episodes, uint32_t env_seed, uint32_t first_episode,
                      int32_t max_ep_len, double *ret_d, int32_t *len_d, float *trace_d, void *stream);
 
@@ -488,8 +489,9 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /*                         leg-corner contacts against the terrain segments, Box2D's island */
 /*                         solve with create-time iteration counts (tests/lander3_oracle.py)*/
 /*                         — ddrl_env_create_ex; reset / step / step_discrete / stats /     */
-/*                         get_state / set_state, and the continuous fused rollout step     */
-/*                         behind ddrl_rollout_begin_articulated / _step_articulated.       */
+/*                         get_state / set_state, the continuous fused rollout step behind  */
+/*                         ddrl_rollout_begin_articulated / _step_articulated, and the      */
+/*                         evaluation episodes of ddrl_env_eval_policy / ddrl_env_eval_q.   */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
 
@@ -764,10 +766,49 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
  * DDRL_ERR_BAD_ARG unless obs_dim == 8, n_actions >= 1, n_episodes >= 1, max_ep_len >= 1, hidden sizes >= 1, max_ep_len and
  * first_episode + n_episodes exact in float32 (<= 2^24), trace_d 16-byte aligned and a valid mode; DDRL_ERR_UNSUPPORTED with the
  * reason in ddrl_last_error() for a hidden width > 512 or n_actions > 8.
- * Takes no env handle: the episodes are the ONE-BODY lander's (DDRL_ENV_ONE_BODY); the articulated model has no evaluation kernel yet. */
+ * Takes no env handle: the episodes are the ONE-BODY lander's (DDRL_ENV_ONE_BODY).  The articulated model's evaluation episodes — and
+ * the same launch fed from a ddrl_dqn_t instead of caller memory — are ddrl_env_eval_q (below). */
 int ddrl_dqn_eval(const ddrl_dqn_config_t *cfg, const float *q_flat_d, int32_t n_episodes, uint32_t env_seed, uint32_t first_episode,
                   int32_t max_ep_len, int mode, float greedy_prob, uint32_t noise_seed, uint64_t noise_ctr, double *ret_d, int32_t *len_d,
                   float *trace_d, void *stream);
+/* The evaluation episodes of EITHER lander model, fed from handles: ddrl_policy_eval's / ddrl_dqn_eval's launch with every argument
+ * taken from where it already lives.  No caller device memory is involved.
+ *   h       NAMES the model: kind, velocity / position iterations, env seed, max_ep_len and device of an env handle of ddrl_env_create
+ *           or ddrl_env_create_ex.  The handle's own env state block, statistics and observations are neither read nor written, and
+ *           n_envs does not matter: episode e of the call is the (first_episode + e)-th episode a ONE-env handle of that seed and
+ *           model plays (env id 0, episode index first_episode + e), exactly as ddrl_policy_eval defines it for the one-body lander.
+ *           DDRL_ENV_ARTICULATED: one workgroup per episode runs the policy / Q row in ddrl_policy_eval's / ddrl_dqn_eval's summation
+ *           order and one lane of it steps the three-body solver with the handle's iteration counts — observations, rewards, ended
+ *           and lengths are bit for bit ddrl_env_step's / ddrl_env_step_discrete's on the recorded actions.  DDRL_ENV_ONE_BODY: the
+ *           very kernel ddrl_policy_eval / ddrl_dqn_eval launch.
+ *   actor   the weights: the actor's CURRENT policy, as ddrl_actor_get_weights returns it — with a version store enabled that is the
+ *           NEWEST installed version (the last ddrl_actor_set_weights), whatever versions the rollout's envs still act on.  Actor
+ *           weights, version store, observation rows and noise are untouched.  Deterministic actions (tanh(mu) * act_scale).
+ *   dqn     the weights: q1 of the handle's MAIN network, as ddrl_dqn_eval reads it from the flat vector ddrl_dqn_export(MAIN)
+ *           writes.  mode, greedy_prob, noise_seed, noise_ctr and the variant / alpha of the handle's configuration mean what they
+ *           mean in ddrl_dqn_eval: step t of episode e owns the uniforms at noise_ctr + 2 (e * max_ep_len + t) [+ 1], a caller advances
+ *           its counter by 2 * n_episodes * max_ep_len per call.  Main, target and optimizer state are untouched.
+ * RESULTS go to a block the env handle owns: ret float64 [n], len int32 [n] and, when want_trace != 0, trace float32
+ * [n][max_ep_len][12] (ddrl_env_eval_policy) or [n][max_ep_len][20] (ddrl_env_eval_q) in the formats of ddrl_policy_eval /
+ * ddrl_dqn_eval, rows past an episode's end zeroed.  The block — and a staging vector for the weights, filled by one pack launch in
+ * front of the episodes' launch — is allocated at the first call and GROWS when a call needs more: such a call allocates and frees
+ * device memory (it synchronises the device and cannot be captured into a graph); a call that fits issues its two launches
+ * stream-ordered with no host synchronisation.  The results are stream-ordered on `stream` and valid until the next evaluation on
+ * that handle or its destruction.  One host thread and one stream at a time per env handle, as for every handle here.
+ * ddrl_env_eval_results hands out the addresses and sizes of the LAST evaluation's results (as ddrl_replay_buffers does: host outs,
+ * each nullable; it writes no device memory and does not synchronise): *trace == NULL and *trace_row == 0 after a call without trace,
+ * else *trace_row == 12 or 20.  Before any evaluation on the handle: DDRL_ERR_BAD_ARG.
+ * REFUSALS, each with the function's name and the reason in ddrl_last_error() and nothing launched, allocated or changed (the previous
+ * results stay valid): DDRL_ERR_BAD_ARG for a NULL handle, n_episodes < 1, first_episode + n_episodes > 2^24 (the episode index must
+ * stay exact in float32), handles on different devices, an actor that is not 8 -> 2, a Q network that does not take 8 observations,
+ * an unknown mode; DDRL_ERR_UNSUPPORTED outside the row kernels' envelope — a hidden width > 512, more than 8 actions — where a
+ * caller steps a host env instead. */
+int ddrl_env_eval_policy(ddrl_env_t *h, ddrl_actor_t *actor, int32_t n_episodes, uint32_t first_episode, int32_t want_trace,
+                         void *stream);
+int ddrl_env_eval_q(ddrl_env_t *h, ddrl_dqn_t *dqn, int32_t n_episodes, uint32_t first_episode, int mode, float greedy_prob,
+                    uint32_t noise_seed, uint64_t noise_ctr, int32_t want_trace, void *stream);
+int ddrl_env_eval_results(ddrl_env_t *h, void **ret, void **len, void **trace, int32_t *n_episodes, int32_t *max_ep_len,
+                          int32_t *trace_row);
 
 /* ===================================================================================== */
 /* Rollout-side window queues of the n-step driver: per env, o_queue = deque(maxlen=Ln+1) of  */

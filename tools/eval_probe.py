@@ -34,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def kernel_resources(lib_path, pattern="k_eval_episodesI"):
+def kernel_resources(lib_path, pattern="k_eval_episodesINS_3EnvE"):   # the one-body instantiations (Env3: tools/eval3_probe.py)
     """[(kernel name, vgprs, sgprs, LDS bytes, scratch bytes, vgpr spills)] from the gfx950 code objects bundled in the library."""
     llvm = "/opt/rocm/llvm/bin"
     out = []
@@ -113,7 +113,7 @@ def discrete(a, say):
         say("  per env step: host / device = %.1f x (medians); slowest device repetition %.2f us, fastest host repetition %.2f us: %s"
             % (statistics.median(per["host loop "]) / statistics.median(per["one launch"]), slowest_dev, fastest_host,
                "every device repetition is faster than every host repetition" if slowest_dev < fastest_host else "CRITERION MISSED"))
-    for name, vg, sg, lds, scratch, spill in kernel_resources(_lib.LIB_PATH, "k_eval_episodes_qI"):
+    for name, vg, sg, lds, scratch, spill in kernel_resources(_lib.LIB_PATH, "k_eval_episodes_qINS_3EnvE"):
         say("code object: %s  vgprs %d  sgprs %d  LDS %d B  scratch %d B  vgpr spills %d" % (name, vg, sg, lds, scratch, spill))
     return ok
 
