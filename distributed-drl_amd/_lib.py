@@ -162,6 +162,9 @@ SIGNATURES = {
     "ddrl_env_step_discrete": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ddrl_rollout_begin_discrete": (c_int, [_P, _P, _P]),
     "ddrl_rollout_step_discrete": (c_int, [_P, _P, _P, c_int32, c_int, c_float, c_uint32, c_uint64, _P, _P, _P, _P]),
+    "ddrl_rollout_begin_discrete_articulated": (c_int, [_P, _P, _P]),
+    "ddrl_rollout_step_discrete_articulated": (c_int, [_P, _P, _P, c_int32, c_int, c_float, c_uint32, c_uint64, _P]),
+    "ddrl_env_rollout_mirrors": (c_int, [_P, POINTER(_P), POINTER(_P), POINTER(_P), POINTER(c_int32), POINTER(c_int32)]),
     "ddrl_env_stats": (c_int, [_P, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), _P]),
     "ddrl_env_get_state": (c_int, [_P, _P, _P]),
     "ddrl_env_set_state": (c_int, [_P, _P, _P]),

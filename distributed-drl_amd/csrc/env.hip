@@ -305,30 +305,7 @@ __global__ void __launch_bounds__(64) k_env_step_pi(RolloutArgs a) {
 // One thread per env; no exchange between threads except the cursor ticket, and — as in k_env_step_pi, for the reason documented
 // there — no __threadfence() in front of it: nothing but the ticket crosses workgroups inside this launch.
 // ------------------------------------------------------------------------------------------
-struct RolloutQArgs {
-    float *S;
-    long long n;
-    uint32_t seed;
-    float max_ep_len;
-    EnvStats *stats;
-    float *obs;            // [n][8] in / out (the forward's buffer)
-    const float *hp;       // [8][n][16]
-    const float *b_lo, *b_hi;
-    int A, half, nt2, sqn, deterministic;
-    float greedy_prob, alpha;
-    uint32_t noise_seed;
-    unsigned long long noise_ctr;
-    ddrl_replay_dev::RingState *rs;
-    ddrl_replay_dev::RingPtrs ring;
-    float *act_out, *q_out, *next_obs_out;   // optional mirrors: [n], [n][A], [n][8]
-    // version store of the acting forward (k_env_step_q<.., true> only; behind everything the plain kernel reads): env i acts on slot[i]
-    // (b_lo / b_hi are slot 0's then, slot s is vstride floats further) and adopts the newest version where its episode ends — the
-    // reference worker's pull at the episode boundary (algos/dqn/train.py:249-252) — and the NEXT forward's plan (vp.vcnt nullable)
-    int *slot;
-    const int *newest;
-    long long vstride;
-    VerPlan vp;
-};
+// (RolloutQArgs: rollout_args.h, shared with the articulated lander's k_env3_step_q, rollout3_q.hip.)
 // VER: a version store is live.  The plain instantiation is the kernel without one: no slot load, no static LDS for the table build.
 template <int NH, bool VER>
 __global__ void __launch_bounds__(64) k_env_step_q(RolloutQArgs a) {
@@ -570,6 +547,40 @@ static int rollout_step_loop(ddrl_env_t *h, ddrl_actor_t *actor, const ddrl_acto
     return DDRL_OK;
 }
 
+// The discrete fused step behind ddrl_rollout_step_discrete (one-body lander: k_env_step_q) and ddrl_rollout_step_discrete_articulated
+// (rollout3_q.hip: k_env3_step_q), behind the entry point's own envelope: n_steps times the loop body of worker_rollout_dqn — the
+// pending repack, the forward, `launch(a, versioned)`, the host's bookkeeping.  `launch` issues the env-step kernel of the handle's model
+// on a filled RolloutQArgs.
+template <class Launch>
+static int rollout_discrete_step_loop(ddrl_env_t *h, ddrl_dqn_t *dqn, const ddrl_dqn_rollout_view &v, ddrl_replay_t *replay,
+                                      const ddrl_replay_dev::SamplerView &rv, int32_t n_steps, int mode, float greedy_prob, uint32_t seed,
+                                      uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream, Launch launch) {
+    ddrl::DeviceGuard g(h->device);
+    RolloutQArgs a{};
+    a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
+    a.obs = v.obs; a.hp = v.hp; a.b_lo = v.b_lo; a.b_hi = v.b_hi; a.A = v.n_actions; a.half = v.half; a.nt2 = v.nt2; a.sqn = v.sqn;
+    a.deterministic = mode == DDRL_ACT_DETERMINISTIC; a.greedy_prob = greedy_prob; a.alpha = v.alpha; a.noise_seed = seed;
+    a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.q_out = q_out_d; a.next_obs_out = next_obs_out_d;
+    for (int k = 0; k < n_steps; ++k) {   // ddrl_rollout_step's loop body
+        // a learner step's pending repack is an install: before steps_since_install is read
+        if (const int rc = ddrl_dqn_internal_repack(dqn, stream)) return rc;
+        const int rc = rollout_versioned_step(v.ver, h->n, h->max_ep_len, [&](bool versioned, bool fused_plan) -> int {
+            if (const int frc = ddrl_dqn_internal_forward(dqn, h->n, stream, versioned ? 1 : 0)) return frc;
+            a.noise_ctr = ctr + (uint64_t)k * 2ull * (uint64_t)h->n;
+            if (versioned) {
+                a.b_lo = v.vb_lo; a.b_hi = v.vb_hi; a.slot = v.ver.slot; a.newest = &v.ver.vs->newest; a.vstride = v.ver.vstride;
+                a.vp = ver_plan_of(v.ver, fused_plan, v.nt2);
+            } else {
+                a.b_lo = v.b_lo; a.b_hi = v.b_hi;
+            }
+            return launch(a, versioned);
+        });
+        if (rc != DDRL_OK) return rc;
+        ddrl_replay_note_store(replay, h->n);
+    }
+    return DDRL_OK;
+}
+
 extern "C" {
 
 int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len) {
@@ -615,6 +626,7 @@ int ddrl_env_destroy(ddrl_env_t *h) {
     ddrl::DeviceGuard g(h->device);
     (void)hipFree(h->S); (void)hipFree(h->stats);
     (void)hipFree(h->ev_block); (void)hipFree(h->ev_w);   // the evaluation results block and weight staging (eval3.hip)
+    (void)hipFree(h->ro_block);                           // the articulated discrete rollout step's mirrors
     delete h;
     return DDRL_OK;
 }
@@ -767,40 +779,99 @@ int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *re
     const RingFault rf = transition_ring_fault(rv.ring, 1);
     DDRL_REQUIRE(rf != RING_ROW_SHAPE, "replay row shape must be (obs1[8], obs2[8], acts, rews, done)");
     DDRL_REQUIRE(rf != RING_COMPACT, RING_COMPACT_MSG);
-    ddrl::DeviceGuard g(h->device);
-    RolloutQArgs a{};
-    a.S = h->S; a.n = h->n; a.seed = h->seed; a.max_ep_len = (float)h->max_ep_len; a.stats = h->stats;
-    a.obs = v.obs; a.hp = v.hp; a.b_lo = v.b_lo; a.b_hi = v.b_hi; a.A = v.n_actions; a.half = v.half; a.nt2 = v.nt2; a.sqn = v.sqn;
-    a.deterministic = mode == DDRL_ACT_DETERMINISTIC; a.greedy_prob = greedy_prob; a.alpha = v.alpha; a.noise_seed = seed;
-    a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.q_out = q_out_d; a.next_obs_out = next_obs_out_d;
     if (v.ver.n_slots > 0 && h->n != v.rows) {
         ddrl::set_error("fused discrete rollout step: a handle with a version store steps exactly the acting forward's %lld rows (n_envs %lld)", v.rows, h->n);
         return DDRL_ERR_BAD_ARG;
     }
     const unsigned grid = (unsigned)((h->n + 63) / 64);
     hipStream_t s = ddrl::as_stream(stream);
-    for (int k = 0; k < n_steps; ++k) {   // ddrl_rollout_step's loop body
-        // a learner step's pending repack is an install: before steps_since_install is read
-        if (const int rc = ddrl_dqn_internal_repack(dqn, stream)) return rc;
-        const int rc = rollout_versioned_step(v.ver, h->n, h->max_ep_len, [&](bool versioned, bool fused_plan) -> int {
-            if (const int frc = ddrl_dqn_internal_forward(dqn, h->n, stream, versioned ? 1 : 0)) return frc;
-            a.noise_ctr = ctr + (uint64_t)k * 2ull * (uint64_t)h->n;
-            if (versioned) {
-                a.b_lo = v.vb_lo; a.b_hi = v.vb_hi; a.slot = v.ver.slot; a.newest = &v.ver.vs->newest; a.vstride = v.ver.vstride;
-                a.vp = ver_plan_of(v.ver, fused_plan, v.nt2);
-                if (v.n_actions <= 4) k_env_step_q<4, true><<<grid, 64, 0, s>>>(a);
-                else k_env_step_q<8, true><<<grid, 64, 0, s>>>(a);
-            } else {
-                a.b_lo = v.b_lo; a.b_hi = v.b_hi;
-                if (v.n_actions <= 4) k_env_step_q<4, false><<<grid, 64, 0, s>>>(a);
-                else k_env_step_q<8, false><<<grid, 64, 0, s>>>(a);
-            }
-            DDRL_LAUNCH_CHECK();
-            return DDRL_OK;
-        });
-        if (rc != DDRL_OK) return rc;
-        ddrl_replay_note_store(replay, h->n);
+    return rollout_discrete_step_loop(h, dqn, v, replay, rv, n_steps, mode, greedy_prob, seed, ctr, act_out_d, q_out_d, next_obs_out_d, stream,
+                                      [&](const RolloutQArgs &a, bool versioned) -> int {
+                                          if (versioned) {
+                                              if (v.n_actions <= 4) k_env_step_q<4, true><<<grid, 64, 0, s>>>(a);
+                                              else k_env_step_q<8, true><<<grid, 64, 0, s>>>(a);
+                                          } else {
+                                              if (v.n_actions <= 4) k_env_step_q<4, false><<<grid, 64, 0, s>>>(a);
+                                              else k_env_step_q<8, false><<<grid, 64, 0, s>>>(a);
+                                          }
+                                          DDRL_LAUNCH_CHECK();
+                                          return DDRL_OK;
+                                      });
+}
+
+// ---- the same pair on the articulated lander (kernel: rollout3_q.hip).  Handles only: the step's mirrors are a block the env handle
+// owns (env_handle.h), allocated by the first begin call that passes the envelope and handed out by ddrl_env_rollout_mirrors.
+// The envelope (rv: the step's ring): DDRL_ERR_UNSUPPORTED with the function's name
+static int rollout3_discrete_check(const char *what, ddrl_env_t *h, const ddrl_dqn_rollout_view &v, const ddrl_replay_dev::SamplerView *rv) {
+    const char *why = nullptr;
+    if (!v.ok) why = v.why ? v.why : "no acting forward";
+    else if (v.obs_dim != 8 || v.n_actions > ddrl_sel::MAXQ) why = "the handle must have obs_dim 8 and n_actions <= 8";
+    else if (h->n % 32 != 0 || h->n > v.batch) why = "n_envs must be a multiple of 32 within the handle's batch";
+    else if (v.ver.n_slots > 0 && h->n != v.rows) why = "a handle with a version store steps exactly the acting forward's rows";
+    else if (v.device != h->device) why = "the learner / actor handle lives on another device than the envs";
+    else if (rv) {
+        const RingFault rf = transition_ring_fault(rv->ring, 1);
+        if (rf == RING_ROW_SHAPE) why = "the replay row shape must be (obs1[8], obs2[8], acts, rews, done)";
+        else if (rf == RING_COMPACT) why = RING_COMPACT_MSG;
+        else if (rv->device != h->device) why = "the replay ring lives on another device than the envs";
     }
+    if (!why) return DDRL_OK;
+    ddrl::set_error("%s: %s; use ddrl_dqn_act + ddrl_env_step_discrete + ddrl_replay_store", what, why);
+    return DDRL_ERR_UNSUPPORTED;
+}
+
+int ddrl_rollout_begin_discrete_articulated(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream) {
+    DDRL_REQUIRE(h != nullptr && dqn != nullptr, "NULL handle");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_begin_discrete_articulated", "ddrl_rollout_begin_discrete");
+    const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
+    if (const int rc = rollout3_discrete_check("ddrl_rollout_begin_discrete_articulated", h, v, nullptr)) return rc;
+    ddrl::DeviceGuard g(h->device);
+    hipStream_t s = ddrl::as_stream(stream);
+    const size_t n = (size_t)h->n;
+    if (!h->ro_block) {   // the first begin call inside the envelope: the mirror block, zeroed
+        float *p = nullptr;
+        if (hipMalloc((void **)&p, n * (8 + DDRL_ROLLOUT_MIRROR_Q + 1) * sizeof(float)) != hipSuccess) {
+            ddrl::set_error("ddrl_rollout_begin_discrete_articulated: hipMalloc failed for the mirrors of %lld envs", h->n);
+            return DDRL_ERR_NOMEM;
+        }
+        DDRL_HIP_CHECK(hipMemsetAsync(p, 0, n * (8 + DDRL_ROLLOUT_MIRROR_Q + 1) * sizeof(float), s));
+        h->ro_block = p;
+    }
+    h->ro_actions = v.n_actions;
+    // the envs' current observations into the forward's rows and into the next-observation mirror: what the next step acts on
+    if (const int rc = ddrl_rollout3_launch_obs(h->S, h->n, v.obs, stream)) return rc;
+    DDRL_HIP_CHECK(hipMemcpyAsync(h->ro_block, v.obs, n * 8 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return DDRL_OK;
+}
+
+int ddrl_rollout_step_discrete_articulated(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode,
+                                           float greedy_prob, uint32_t seed, uint64_t ctr, void *stream) {
+    DDRL_REQUIRE(h != nullptr && dqn != nullptr && replay != nullptr, "NULL handle");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_step_discrete_articulated", "ddrl_rollout_step_discrete");
+    DDRL_REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    DDRL_REQUIRE(mode == DDRL_ACT_SAMPLE || mode == DDRL_ACT_DETERMINISTIC, "mode must be DDRL_ACT_SAMPLE or DDRL_ACT_DETERMINISTIC");
+    const ddrl_dqn_rollout_view v = ddrl_dqn_internal_view(dqn);
+    const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
+    if (const int rc = rollout3_discrete_check("ddrl_rollout_step_discrete_articulated", h, v, &rv)) return rc;
+    DDRL_REQUIRE(h->ro_block != nullptr, "ddrl_rollout_step_discrete_articulated: no ddrl_rollout_begin_discrete_articulated on this env handle yet");
+    h->ro_actions = v.n_actions;
+    const long long n = h->n;
+    float *next_obs = h->ro_block, *q = next_obs + n * 8, *act = q + n * DDRL_ROLLOUT_MIRROR_Q;
+    return rollout_discrete_step_loop(h, dqn, v, replay, rv, n_steps, mode, greedy_prob, seed, ctr, act, q, next_obs, stream,
+                                      [&](const RolloutQArgs &a, bool versioned) -> int {
+                                          return ddrl_rollout3_launch_step_q(&a, versioned ? 1 : 0, h->vit, h->pit, stream);
+                                      });
+}
+
+int ddrl_env_rollout_mirrors(ddrl_env_t *h, const float **act, const float **q, const float **next_obs, int32_t *n_envs, int32_t *n_actions) {
+    DDRL_REQUIRE(h != nullptr, "ddrl_env_rollout_mirrors: handle is NULL");
+    DDRL_REQUIRE(h->ro_block != nullptr, "ddrl_env_rollout_mirrors: no ddrl_rollout_begin_discrete_articulated on this env handle yet");
+    const float *b = h->ro_block;
+    if (next_obs) *next_obs = b;
+    if (q) *q = b + h->n * 8;
+    if (act) *act = b + h->n * (8 + DDRL_ROLLOUT_MIRROR_Q);
+    if (n_envs) *n_envs = (int32_t)h->n;
+    if (n_actions) *n_actions = h->ro_actions;
     return DDRL_OK;
 }
 

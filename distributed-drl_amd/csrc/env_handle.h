@@ -23,4 +23,12 @@ struct ddrl_env {
     size_t ev_w_floats;        // its capacity
     size_t ev_len_off, ev_trace_off;   // the last call's layout ...
     int ev_n, ev_row;                  // ... its episode count and trace row (0: no trace); ev_n == 0: no evaluation yet
+    // ---- mirrors of the articulated discrete fused rollout step (ddrl_rollout_begin_discrete_articulated / _step_discrete_articulated /
+    // ddrl_env_rollout_mirrors, env.hip; written by k_env3_step_q, rollout3_q.hip).  One allocation of n * (8 + DDRL_ROLLOUT_MIRROR_Q + 1)
+    // floats made by the first begin call that passes its envelope, never resized, freed by ddrl_env_destroy:
+    // next observations [n][8] (16-byte aligned: the block's start) | Q rows [n][ro_actions], n * DDRL_ROLLOUT_MIRROR_Q floats set
+    // aside | action indices [n].  S and stats above are never reallocated.
+    float *ro_block;           // nullptr: no begin call yet
+    int ro_actions;            // n_actions of the handle the last begin / step call took: the row width of the Q mirror
 };
+constexpr int DDRL_ROLLOUT_MIRROR_Q = 8;   // ddrl_sel::MAXQ: the widest Q row the fused discrete step takes

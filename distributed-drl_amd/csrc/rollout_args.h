@@ -1,6 +1,7 @@
 // What the continuous fused rollout step's two kernels share: k_env_step_pi (env.hip, the one-body lander) and k_env3_step_pi
 // (rollout3.hip, the articulated lander) take the same arguments, finish get_action from the forward's head partials by the same
-// statements and pass the same ring ticket to ver_plan_tail (version_plan.h).  Internal linkage throughout, as env_device.h: each
+// statements and pass the same ring ticket to ver_plan_tail (version_plan.h) — and what the DISCRETE step's two kernels share likewise:
+// k_env_step_q (env.hip) and k_env3_step_q (rollout3_q.hip) take one RolloutQArgs and the same ticket.  Internal linkage throughout, as env_device.h: each
 // translation unit compiles its own copy, and env.hip's kernels compile to the code they compiled to with the two structs in the file.
 #pragma once
 #include "ddrl_common.h"
@@ -54,6 +55,33 @@ struct RolloutArgs {
     ddrl_replay_dev::RingPtrs ring;
     // optional mirrors for the host-side objects
     float *act_out, *next_obs_out;
+};
+
+// The DISCRETE fused rollout step's arguments: k_env_step_q (env.hip, the one-body lander) and k_env3_step_q (rollout3_q.hip, the
+// articulated lander) take the same struct, as the continuous pair takes RolloutArgs.
+struct RolloutQArgs {
+    float *S;
+    long long n;
+    uint32_t seed;
+    float max_ep_len;
+    EnvStats *stats;
+    float *obs;            // [n][8] in / out (the forward's buffer)
+    const float *hp;       // [8][n][16]
+    const float *b_lo, *b_hi;
+    int A, half, nt2, sqn, deterministic;
+    float greedy_prob, alpha;
+    uint32_t noise_seed;
+    unsigned long long noise_ctr;
+    ddrl_replay_dev::RingState *rs;
+    ddrl_replay_dev::RingPtrs ring;
+    float *act_out, *q_out, *next_obs_out;   // mirrors: [n], [n][A], [n][8] (k_env_step_q: each optional; k_env3_step_q: the env handle's block)
+    // version store of the acting forward (k_env_step_q<.., true> only; behind everything the plain kernel reads): env i acts on slot[i]
+    // (b_lo / b_hi are slot 0's then, slot s is vstride floats further) and adopts the newest version where its episode ends — the
+    // reference worker's pull at the episode boundary (algos/dqn/train.py:249-252) — and the NEXT forward's plan (vp.vcnt nullable)
+    int *slot;
+    const int *newest;
+    long long vstride;
+    VerPlan vp;
 };
 
 // get_action's last step for env i, in two halves so that a kernel can issue its other loads between them: k_env_step_pi's own
@@ -116,3 +144,6 @@ __device__ __forceinline__ float2 head_action(const RolloutArgs &a, long long i,
 // iteration counts.  ddrl_rollout3_launch_obs writes Env3::obs of every env's state into obs_d[n][8] (no reset, no step).
 int ddrl_rollout3_launch_step(const void *args, int vit, int pit, void *stream);
 int ddrl_rollout3_launch_obs(const float *S, long long n, float *obs_d, void *stream);
+// ... and the discrete step (rollout3_q.hip): `args` points to a RolloutQArgs whose three mirrors are set; versioned selects the
+// instantiation with the version store (slot / newest / vp are read then only)
+int ddrl_rollout3_launch_step_q(const void *args, int versioned, int vit, int pit, void *stream);

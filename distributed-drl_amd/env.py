@@ -27,9 +27,11 @@ class VecLunarLander:
     def __init__(self, n_envs, seed=0, max_ep_len=1000, device=None, model="simple", velocity_iterations=180, position_iterations=60):
         """model: "simple" — the one-body lander (ddrl_env_create) — or "articulated" — hull and two jointed legs on Box2D's island
         solve with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default; ddrl_env_create_ex).
-        The articulated env has reset / step / stats / get_state / set_state; step_wrapped and the fused rollout launches refuse it.
-        (Those are ddrl_rollout_step and its discrete and n-step siblings; the continuous worker's pair for this model,
-        ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated, is reached through workers.RolloutDevice.)"""
+        The articulated env has reset / step / stats / get_state / set_state; step_wrapped, the one-body fused rollout launches
+        (ddrl_rollout_step, ddrl_rollout_step_discrete) and the n-step fused step refuse it.  This model's own fused pairs are
+        ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated, reached through workers.RolloutDevice, and
+        ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated, reached through workers.RolloutDeviceDQN
+        (its mirrors: rollout_mirrors()); there is no n-step fused step and no wrapped step on this model."""
         _lib.require_gpu()
         self._lib = _lib.load()
         self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)
@@ -108,6 +110,19 @@ class VecLunarLander:
         if tuple(s.shape) != (self.state_fields, self.n):
             raise ValueError("state block must be [%d, %d] for this env's model, got %s" % (self.state_fields, self.n, tuple(s.shape)))
         _lib.check(self._lib.ddrl_env_set_state(self._h, _lib.dptr(s), _lib.stream_ptr()))
+
+    def rollout_mirrors(self):
+        """(act [n], q [n, A], next_obs [n, 8]): device views of the block the env handle owns for the articulated lander's fused
+        discrete rollout step (ddrl_env_rollout_mirrors) — the last step's action indices, its Q rows and the observations to act on
+        next.  No copy and no synchronisation: the views are stream-ordered like any tensor, and valid for the handle's life (the
+        block is never moved).  Before any ddrl_rollout_begin_discrete_articulated on this env the library refuses (ValueError)."""
+        act, q, nxt = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        n, A = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self._lib.ddrl_env_rollout_mirrors(self._h, ctypes.byref(act), ctypes.byref(q), ctypes.byref(nxt), ctypes.byref(n),
+                                                      ctypes.byref(A)))
+        n, A = int(n.value), int(A.value)
+        return (_device_view(act.value, n, "<f4", self.device), _device_view(q.value, n * A, "<f4", self.device).view(n, A),
+                _device_view(nxt.value, n * 8, "<f4", self.device).view(n, 8))
 
 
 class VecLunarLanderDiscrete(VecLunarLander):
@@ -285,6 +300,13 @@ class DeviceLunarLanderDiscrete(DeviceLunarLander):
                            "dqn.Actor.test); use env.make(\"LunarLander-v2\") for an env to step from the host")
 
 
+def _device_view(ptr, count, typestr, device):
+    """`count` elements of device memory the library owns as a flat tensor (a __cuda_array_interface__ view: no copy, no ownership)."""
+    class _Holder:
+        __cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(_Holder(), device=device)
+
+
 def eval_results(vec, want_row):
     """The results of the last ddrl_env_eval_policy / ddrl_env_eval_q on `vec` (a VecLunarLander) as NumPy: dict(ret float64 [n],
     len int32 [n]) and, where that call kept a trace, `trace` float32 [n, max_ep_len, want_row].  Read from the block the env handle
@@ -294,11 +316,7 @@ def eval_results(vec, want_row):
     _lib.check(vec._lib.ddrl_env_eval_results(vec._h, ctypes.byref(ret), ctypes.byref(ln), ctypes.byref(tr), ctypes.byref(n),
                                               ctypes.byref(L), ctypes.byref(row)))
     n, L, row = int(n.value), int(L.value), int(row.value)
-
-    def view(ptr, count, typestr):
-        class _Holder:
-            __cuda_array_interface__ = {"shape": (count,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-        return torch.as_tensor(_Holder(), device=vec.device)
+    view = lambda ptr, count, typestr: _device_view(ptr, count, typestr, vec.device)
     torch.cuda.current_stream().synchronize()
     out = {"ret": view(ret.value, n, "<f8").cpu().numpy(), "len": view(ln.value, n, "<i4").cpu().numpy()}
     if row:

@@ -606,9 +606,10 @@ def worker_train_nstep(ps, replay_buffer, opt, learner_index, make_agent=None, m
 def _env_model_kw(opt):
     """The env-model arguments of a rollout worker's envs: `opt.env_model` ("simple", the default, or "articulated") and, for the
     articulated lander, `opt.env_velocity_iterations` / `opt.env_position_iterations` (gym's 180 / 60 unless set).  On the articulated
-    model the workers run their unfused sequence (act, env.step, store): the fused launches of ddrl_rollout_step and its discrete
-    and n-step siblings hold the one-body lander.  The continuous worker alone (RolloutDevice) has a fused step on that model, behind
-    `opt.fused_rollout_articulated` (default False): that flag is RolloutDevice's, and changes nothing here."""
+    model the workers run their unfused sequence (act, env.step, store) by default: the fused launches of ddrl_rollout_step and its
+    discrete and n-step siblings hold the one-body lander.  The continuous worker (RolloutDevice) has a fused step on that model
+    behind `opt.fused_rollout_articulated`, the discrete worker (RolloutDeviceDQN) behind `opt.fused_discrete_rollout_articulated`
+    (both default False); the n-step worker has none.  The flags are the workers', and change nothing here."""
     model = getattr(opt, "env_model", "simple")
     if model == "simple":
         return {}
@@ -787,8 +788,16 @@ class RolloutDeviceDQN(_RolloutWorker):
     VecLunarLanderDiscrete — this project's own one-body lander behind gym's discrete action table — one dqn.Actor / ActorSQN
     (`opt.variant` "sqn" or `opt.make_actor`; default Double-DQN), a device replay ring (ReplayBufferDQN, not compact) and a
     ParameterServer, pulled key by key.  `t` counts this worker's transitions (the reference's gate is on actor_steps, train.py:255).
-    Fused pair: ddrl_rollout_begin_discrete / ddrl_rollout_step_discrete (the one-body lander only); adoption defaults to "step",
-    "episode" has horizon max_ep_len.  Works with TrainDeviceDQN under ActorLearnerLoop as RolloutDevice does with TrainDevice."""
+    Fused pair: ddrl_rollout_begin_discrete / ddrl_rollout_step_discrete on the one-body lander; adoption defaults to "step",
+    "episode" has horizon max_ep_len.  Works with TrainDeviceDQN under ActorLearnerLoop as RolloutDevice does with TrainDevice.
+
+    The articulated lander (`opt.env_model = "articulated"`) runs the unfused sequence — and so adopts per step — unless
+    `opt.fused_discrete_rollout_articulated` is set (default False): then the worker takes ddrl_rollout_begin_discrete_articulated /
+    ddrl_rollout_step_discrete_articulated, the same launch pair with the three-body solver in the env-step kernel, and "episode"
+    adoption holds on that model too.  That pair takes handles only and writes the step's mirrors into a block the env handle owns:
+    once the worker has decided for it, `env.obs` and `act` ARE views of that block (VecLunarLander.rollout_mirrors; no copy launch
+    behind a step, and the unfused sequence of the random-action phase writes the same memory), and a `q_out` tensor is filled by a
+    copy of the Q mirror.  The one-body worker ignores the flag."""
 
     _flat_pull = False
 
@@ -814,19 +823,37 @@ class RolloutDeviceDQN(_RolloutWorker):
 
     def _fused_eligible(self):
         from .replay import ReplayBuffer
-        return (isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
-                and self.env.model == "simple")
+        ok = isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
+        # ddrl_rollout_begin_discrete holds the one-body lander and refuses the other; the articulated pair is opt-in
+        return ok and (self.env.model == "simple" or
+                       (self.env.model == "articulated" and bool(getattr(self.opt, "fused_discrete_rollout_articulated", False))))
 
     def _fused_begin(self):
         from . import _lib
-        return self.actor._lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr())
+        lib = self.actor._lib
+        if self.env.model == "articulated":
+            return lib.ddrl_rollout_begin_discrete_articulated(self.env._h, self.actor._h, _lib.stream_ptr())
+        return lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr())
+
+    def _fused_decided(self, ok):
+        if ok and self.env.model == "articulated":
+            # the begin call has put the envs' observations into the next-observation mirror: from here on env.obs and act are the
+            # handle's own mirrors, whichever sequence steps the envs (`_q_mirror`: the source of the copy into q_out)
+            self.act, self._q_mirror, self.env.obs = self.env.rollout_mirrors()
+        super()._fused_decided(ok)
 
     def _fused_step(self, n_steps):
         from . import _lib
         env, a = self.env, self.actor
-        _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
-                                                     a._noise_seed, a._noise_ctr, _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs),
-                                                     _lib.stream_ptr()))
+        if env.model == "articulated":
+            _lib.check(a._lib.ddrl_rollout_step_discrete_articulated(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
+                                                                     a._noise_seed, a._noise_ctr, _lib.stream_ptr()))
+            if self.q_out is not None:
+                self.q_out.copy_(self._q_mirror)
+        else:
+            _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
+                                                         a._noise_seed, a._noise_ctr, _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs),
+                                                         _lib.stream_ptr()))
         a._noise_ctr += n_steps * 2 * env.n
 
 

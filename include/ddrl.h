@@ -490,8 +490,11 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /*                         solve with create-time iteration counts (tests/lander3_oracle.py)*/
 /*                         — ddrl_env_create_ex; reset / step / step_discrete / stats /     */
 /*                         get_state / set_state, the continuous fused rollout step behind  */
-/*                         ddrl_rollout_begin_articulated / _step_articulated, and the      */
-/*                         evaluation episodes of ddrl_env_eval_policy / ddrl_env_eval_q.   */
+/*                         ddrl_rollout_begin_articulated / _step_articulated, the discrete */
+/*                         one behind ddrl_rollout_begin_discrete_articulated /             */
+/*                         _step_discrete_articulated, and the evaluation episodes of       */
+/*                         ddrl_env_eval_policy / ddrl_env_eval_q.  The n-step fused step   */
+/*                         and the wrapped step hold the one-body model only.               */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
 
@@ -501,8 +504,9 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
  * arguments of Box2D's world.Step (gym: 6*30 and 2*30), each >= 1.  An unknown kind or an iteration count < 1: DDRL_ERR_BAD_ARG.
  * Given an articulated handle, ddrl_env_step_wrapped, ddrl_rollout_begin / ddrl_rollout_step and ddrl_rollout_begin_discrete /
  * ddrl_rollout_step_discrete return DDRL_ERR_UNSUPPORTED (reason in ddrl_last_error()) and change nothing: their kernels hold the
- * one-body model.  The unfused sequence (act + ddrl_env_step[_discrete] + store) works on both; the continuous fused step on an
- * articulated handle is ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated. */
+ * one-body model, and so do ddrl_rollout_begin_nstep / ddrl_rollout_step_nstep.  The unfused sequence (act + ddrl_env_step[_discrete]
+ * + store) works on both; the continuous fused step on an articulated handle is ddrl_rollout_begin_articulated /
+ * ddrl_rollout_step_articulated, the discrete one ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated. */
 #define DDRL_ENV_ONE_BODY 0
 #define DDRL_ENV_ARTICULATED 1
 typedef struct { int32_t kind, velocity_iterations, position_iterations; } ddrl_env_model_t;
@@ -750,6 +754,34 @@ int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, vo
 int ddrl_rollout_begin_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream);
 int ddrl_rollout_step_discrete(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode, float greedy_prob,
                                uint32_t seed, uint64_t ctr, float *act_out_d, float *q_out_d, float *next_obs_out_d, void *stream);
+/* The same pair on the ARTICULATED lander (an env handle of ddrl_env_create_ex, kind = DDRL_ENV_ARTICULATED): one vector step of
+ * worker_rollout_dqn's policy phase as the Q-forward launch and ONE launch that sums the Q row, selects the action (ddrl_dqn_act's rules
+ * and uniforms: step k of n_steps draws from ctr + k*2n), runs the three-body solver with the handle's iteration counts on the discrete
+ * action table, appends (o, a, r, o2, d) to the ring, resets the ended envs and — with a version store (ddrl_dqn_versions_enable) —
+ * moves an env to the newest version where its episode ends (algos/dqn/train.py:249-252).  Given the same head partials the Q row and
+ * the action are those ddrl_rollout_step_discrete computes, and the transition is bit for bit ddrl_env_step_discrete's on that action.
+ * n_steps, mode, greedy_prob, seed, ctr and the version store mean what they mean in ddrl_rollout_step_discrete.
+ * The entry points take HANDLES ONLY.  The mirrors of the LAST step — action indices [n] (as float32), Q rows [n][n_actions], the
+ * observations to act on next [n][8] (16-byte aligned) — go to a block the env handle owns: allocated by the first
+ * ddrl_rollout_begin_discrete_articulated that passes the envelope (that call allocates device memory and cannot be captured into a
+ * graph), never resized, freed by ddrl_env_destroy; the env's state block and statistics are never reallocated.  The step's launch
+ * always writes all three (stream-ordered on `stream`).  ddrl_env_rollout_mirrors hands out their addresses (host outs, each nullable;
+ * it writes no device memory and does not synchronise; n_actions is that of the dqn handle the last begin / step call took); before
+ * any begin call on the handle: DDRL_ERR_BAD_ARG.
+ * ddrl_rollout_begin_discrete_articulated writes the envs' current observations into the dqn handle's rows and into the
+ * next-observation mirror (no reset, no step): call it once, and again after any ddrl_env_step_discrete / ddrl_env_reset /
+ * ddrl_env_set_state issued outside this path.  A step call on a handle that has seen no begin call: DDRL_ERR_BAD_ARG.
+ * Envelope: ddrl_rollout_step_discrete's — an acting forward (obs_dim 8, n_actions <= 8, hidden sizes multiples of 4 within the
+ * direct-operand limits), n_envs a multiple of 32 and <= cfg.batch (exactly the acting forward's rows with a version store), a five-array
+ * float32 ring (obs1[8], obs2[8], acts, rews, done), not compact, everything on one device.  Outside it, and on a one-body handle (use
+ * ddrl_rollout_begin_discrete / ddrl_rollout_step_discrete there): DDRL_ERR_UNSUPPORTED, the function's name and the reason in
+ * ddrl_last_error(), nothing launched, allocated or written.  n_steps < 1 or an unknown mode: DDRL_ERR_BAD_ARG.
+ * ddrl_rollout_begin_discrete / ddrl_rollout_step_discrete keep refusing an articulated handle. */
+int ddrl_rollout_begin_discrete_articulated(ddrl_env_t *h, ddrl_dqn_t *dqn, void *stream);
+int ddrl_rollout_step_discrete_articulated(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_replay_t *replay, int32_t n_steps, int mode,
+                                           float greedy_prob, uint32_t seed, uint64_t ctr, void *stream);
+int ddrl_env_rollout_mirrors(ddrl_env_t *h, const float **act, const float **q, const float **next_obs,
+                             int32_t *n_envs, int32_t *n_actions);
 /* The DQN / SQN test worker's evaluation episodes as ONE launch: Actor.test (algos/dqn/actor_learner.py:230-251,
  * algos/sqn/actor_learner.py:229-250) — n episodes of get_action(o) + env.step(a) on the discrete lander — with one workgroup per
  * episode and no host round trip per step: the discrete counterpart of ddrl_policy_eval.  q_flat_d is the flat main vector in variable
