@@ -108,6 +108,7 @@ class Lander3Oracle:
         self.S = np.zeros((NF3, self.n), dtype=F)
         self.env_ids = np.arange(self.n, dtype=np.uint32)
         self.episodes, self.ret_sum, self.len_sum = 0, 0.0, 0
+        self.last = None   # what the last step() / _physics() call did, per env (see _physics); the step inside reset() is not recorded
         self.reset()
 
     # -- RNG: the one-body model's streams (oracle/env_oracle.py: LanderOracle._rng) --------------------------------------
@@ -150,7 +151,14 @@ class Lander3Oracle:
         return (h0 + dh * t).astype(F)
 
     # -- one physics step for every env; returns (reward, done_env, obs) ----------------------------------------------------
-    def _physics(self, act):
+    def _physics(self, act, record=True):
+        """RECORDING (no arithmetic statement depends on it): with `record`, self.last becomes a dict of per-env arrays for this step —
+        on [8, n] contact mask, seg [8, n] terrain segment under each corner, dh [8, n] that segment's rise, friction_clamp [8, n] the
+        tangent clamp cut an increment in some sweep, sweeps [n] position sweeps executed, solved [n], per leg [2, n] motor_hi /
+        motor_lo (the motor clamp cut at +0.8 / -0.8 in some sweep) and limit_lo / limit_up (that row left with a positive accumulated
+        impulse), main / side the two engine impulses (ix, iy) on the hull with their arms main_r / side_r about its centre of mass
+        and m_power / s_power, crash, out (crash or viewport), asleep, and state: a copy of the block as this function leaves it (before
+        step()'s episode bookkeeping and reset)."""
         S, n = self.S, self.n
         a0 = np.clip(act[:, 0].astype(F), F(-1.0), F(1.0))
         a1 = np.clip(act[:, 1].astype(F), F(-1.0), F(1.0))
@@ -173,6 +181,7 @@ class Lander3Oracle:
         iy = -oy * MAIN_POWER * m_power
         rx = ox - lx
         ry = oy - ly
+        rec = {"main": (ix, iy), "main_r": (rx, ry), "m_power": m_power}
         hull.vx = hull.vx + ix * INV_MH
         hull.vy = hull.vy + iy * INV_MH
         hull.om = hull.om + (rx * iy - ry * ix) * INV_IH
@@ -186,6 +195,7 @@ class Lander3Oracle:
         iy = -oy * SIDE_POWER * s_power
         rx = (ox - tip0 * F(0.56666666)) - lx
         ry = (oy + tip1 * SIDE_H) - ly
+        rec.update(side=(ix, iy), side_r=(rx, ry), s_power=s_power)
         hull.vx = hull.vx + ix * INV_MH
         hull.vy = hull.vy + iy * INV_MH
         hull.om = hull.om + (rx * iy - ry * ix) * INV_IH
@@ -208,6 +218,7 @@ class Lander3Oracle:
                 x0, h0, dh = self._segment(px)
                 ln = np.sqrt(dh * dh + F(4.0))
                 c["x0"], c["h0"] = x0, h0
+                c["seg"], c["dh"], c["fclamp"] = (x0 * F(0.5)).astype(np.int64), dh, np.zeros(n, bool)
                 c["nx"] = -dh / ln
                 c["ny"] = F(2.0) / ln
                 sep = ((px - x0) * c["nx"] + (py - h0) * c["ny"]) - RADIUS
@@ -233,7 +244,7 @@ class Lander3Oracle:
             lg = legs[b]
             sb, cb = sincos32(lg.ang)
             ax = SIGN[b] * ANCX
-            j = {"b": b}
+            j = {"b": b, "mhi": np.zeros(n, bool), "mlo": np.zeros(n, bool)}
             j["rBx"] = cb * ax - sb * ANCY
             j["rBy"] = sb * ax + cb * ANCY
             j["k11"] = ((INV_MH + INV_ML) + (rAy * rAy) * INV_IH) + (j["rBy"] * j["rBy"]) * INV_IL
@@ -260,6 +271,8 @@ class Lander3Oracle:
                 imp = -AXM * cdot
                 old = j["m"]
                 j["m"] = _clamp(old + imp, -MAX_MOTOR_IMP, MAX_MOTOR_IMP)
+                j["mhi"] |= (old + imp) > MAX_MOTOR_IMP
+                j["mlo"] |= (old + imp) < -MAX_MOTOR_IMP
                 imp = j["m"] - old
                 hull.om = hull.om - INV_IH * imp
                 lg.om = lg.om + INV_IL * imp
@@ -305,6 +318,7 @@ class Lander3Oracle:
                 lam = c["tmass"] * -(dvx * tx + dvy * ty)
                 lim = MU * c["an"]
                 new = _clamp(c["at"] + lam, -lim, lim)
+                c["fclamp"] |= on & (np.abs(c["at"] + lam) > lim)
                 lam = new - c["at"]
                 c["at"] = np.where(on, new, c["at"]).astype(F)
                 Px = lam * tx
@@ -331,9 +345,11 @@ class Lander3Oracle:
             bd.ang = bd.ang + DT * bd.om
         # ---- position sweeps: contacts, then joints; a solved env leaves the loop (mask) ----
         live = np.ones(n, bool)
+        sweeps = np.zeros(n, np.int64)
         for _ in range(self.pit):
             if not live.any():
                 break
+            sweeps += live
             minsep = np.zeros(n, F)
             for c in con:
                 lg = legs[c["b"]]
@@ -439,6 +455,13 @@ class Lander3Oracle:
         rew = (rew - m_power * F(0.30)) - s_power * F(0.03)
         out = crash | (np.abs(o[:, 0]) >= F(1.0))
         rew = np.where(out, F(-100.0), np.where(asleep, F(100.0), rew)).astype(F)
+        if record:
+            rec.update(on=np.stack([c["on"] for c in con]), seg=np.stack([c["seg"] for c in con]), dh=np.stack([c["dh"] for c in con]),
+                       friction_clamp=np.stack([c["fclamp"] for c in con]), sweeps=sweeps, solved=solved,
+                       motor_hi=np.stack([j["mhi"] for j in jn]), motor_lo=np.stack([j["mlo"] for j in jn]),
+                       limit_lo=np.stack([j["lo"] > F(0.0) for j in jn]), limit_up=np.stack([j["up"] > F(0.0) for j in jn]),
+                       crash=crash, out=out, asleep=asleep, state=S.copy())
+            self.last = rec
         return rew, (out | asleep), o
 
     # -- env.reset() for masked envs (gym: build terrain, create the bodies, random initial force, one no-op step) -------------
@@ -463,7 +486,7 @@ class Lander3Oracle:
             S[L0 + 6 * b + 0] = F(10.0) - SIGN[b] * LEG_X0
             S[L0 + 6 * b + 1] = H
             S[L0 + 6 * b + 4] = SIGN[b] * LEG_A0
-        self._physics(np.zeros((self.n, 2), F))
+        self._physics(np.zeros((self.n, 2), F), record=False)
         S[:, ~m] = keep[:, ~m]
         return self.obs()
 

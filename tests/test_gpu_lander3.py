@@ -50,8 +50,13 @@ def _oracle(n, seed=0, max_ep_len=1000, vit=VIT, pit=PIT):
     return Lander3Oracle(n, seed=seed, max_ep_len=max_ep_len, velocity_iterations=vit, position_iterations=pit)
 
 
-# 64 / heuristic: contacts, rest attempts and the time limit; 33: not a multiple of a wave; 1: one lane; 4096: 64 workgroups, and a
-# time limit inside the run so that every lane goes through its reset (no crash can happen within 20 steps of the start height)
+# 64 / heuristic: contacts and the time limit; 33: not a multiple of a wave; 1: one lane; 4096: 64 workgroups, and a time limit
+# inside the run so that every lane goes through its reset (no crash can happen within 20 steps of the start height).
+# What this matrix reaches (profiles/lander3_census.txt, first table): contact on the legs' bottom corners (the top ones in a handful
+# of env-steps), the near side of both joint limits, crashes by the hull's bottom vertices, viewport exits, the time limit.  It
+# never reaches rest: at 8 / 3 the SLEEP counter stays at 0, so neither the sleep test nor the +100 exit runs, and the far side of
+# the joint limits, the hull's top vertices and sloped or clamped terrain segments are touched in single env-steps at most.  Those
+# branches are held by the crafted states of tests/test_gpu_lander3_scenarios.py.
 @pytest.mark.parametrize("n,seed,policy,steps,max_len", [(64, 1, "heuristic", 300, 160), (33, 7, "random", 200, 1000),
                                                          (1, 3, "zero", 150, 1000), (4096, 11, "random", 20, 12)])
 def test_env3_bit_exact_vs_live_oracle(ddrl, n, seed, policy, steps, max_len):

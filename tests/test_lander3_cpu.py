@@ -3,7 +3,6 @@ file regenerates bit for bit, and gym's heuristic controller lands the model.  N
 and the same golden file in tests/test_gpu_lander3.py."""
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -19,22 +18,7 @@ import lander3_oracle as L3   # noqa: E402
 GOLDEN = os.path.join(HERE, "golden", "lander3_heuristic.npz")
 
 
-def _float64_restatement():
-    """The SAME step in float64: the oracle's source with its working type switched and exact sin / cos.  Every constant is set back
-    to the float32 oracle's value (mass data, limits, tolerances), the random numbers are the same 24-bit values: the same model,
-    finer arithmetic."""
-    src = open(L3.__file__).read()
-    assert src.count("F = np.float32") == 1
-    mod = types.ModuleType("lander3_oracle_f64")
-    mod.__file__ = L3.__file__
-    exec(compile(src.replace("F = np.float32", "F = np.float64"), L3.__file__, "exec"), mod.__dict__)
-    for name, v in vars(L3).items():
-        if isinstance(v, np.float32):
-            setattr(mod, name, np.float64(v))
-        elif isinstance(v, tuple) and v and isinstance(v[0], np.float32):
-            setattr(mod, name, tuple(np.float64(x) for x in v))
-    mod.sincos32 = lambda x: (np.sin(np.asarray(x, np.float64)), np.cos(np.asarray(x, np.float64)))
-    return mod
+from _lander3_scenarios import float64_restatement as _float64_restatement   # noqa: E402  (moved there; shared with the scenario tests)
 
 
 def _momentum(S, mod=L3):
