@@ -1148,6 +1148,116 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             if (tid + 256 < glen) jb.gw_snap[tid + 256] = gv1;
         }
     }
+    // ---- epilogue operands: requested from inside the K loop (behind the MFMAs of the first groups), so that the first
+    // MFMA does not queue behind up to 16 more wave-loads per wave.  A wave's loads return in order, and the optimizer state is
+    // cold (it comes over the fabric): whatever waits behind it in the K loop waits a round trip.  That cost did not depend on
+    // WHERE the state was requested (DGMID 1 - 8: flat), because of how the waits were counted, not because of the queue: the
+    // requests sat in branches (job type, do_adam) inside the one K loop of all job types, and where paths with different
+    // numbers of loads in flight join, the compiler's wait counts assume the shortest one — the very next MFMA group waited for
+    // all but the four newest loads (vmcnt(5) / (4) where the stepping J4 path had 13 behind the operand it needed), i.e. for
+    // the whole state wherever it stood; and the four bias-correction powers were used where they were loaded, a vmcnt(0) in the
+    // middle of the loop of EVERY tile of a stepping launch, dgrads included, which never use them.
+    // So the tiles that step the optimizer run a K loop of their own per epilogue mapping (k_loop_step, KIND 1 - 3 below: no load
+    // of theirs under a branch, the waits count exactly: vmcnt(13) there now), request the state behind the last operand group
+    // of a 256-deep contraction (DGST) and first use it, and the powers, behind the combine barrier; the other tiles keep the
+    // loop they had and no longer load the powers.  (All four kinds through ONE generic loop: the compiler then turns the
+    // generated-operand branches of the dgrads into selects, +0.9 k cycles of K loop in launch "bq".)  tools/upd_bench, us per
+    // update: 43.9 -> 42.7 (K loop of the stepping J4 tiles 16.6 k -> 14.7 k cycles in launch "mid", 11.4 k -> 9.8 k in "pi";
+    // their epilogue 2.8 k -> 3.3 k; the policy dgrad beside them 9.7 k -> 9.1 k); DGST 3 / 4 / 5 / 6 / 7: 43.0 - 43.4 against
+    // 44.1, flat — with exact waits the position hardly matters, the rest of the K loop's excess is the arrival of its own
+    // operands (profiles/optstate_queue_before_after.txt).  Closed before that: a fifth "helper" wave per
+    // workgroup that fetches the state into LDS before the combine barrier — the dispatcher then fits one 5-wave workgroup
+    // per CU at 131 VGPRs (59.5 us per update), and capping the kernel at 128 VGPRs spills (55.7 us) against 52.5 us.
+    const bool rm_like = type == DG_WGRAD_RM || type == DG_WGRAD_W1Y;  // element-addressed gradient: row-major, or the layer-1 block layout
+    int kind;   // block-uniform: the tile's KIND (below)
+    {
+        const bool dgrad = type == DG_DGRAD_Q || type == DG_DGRAD;
+        const bool step = jobs.ad.on && (type == DG_WGRAD_J4 || rm_like) && jb.adam_off >= 0;
+        kind = step ? (type == DG_WGRAD_J4 ? 1 : (hot_N > 8 ? 2 : 3)) : !dgrad ? 0 : type == DG_DGRAD ? 6 : jb.da_part ? 5 : 4;
+        kind = __builtin_amdgcn_readfirstlane(kind);
+        asm volatile("" : "+s"(kind));   // one scalar through the tile, not a 64-bit mask per predicate it stands for
+    }
+    const bool is_dgrad = kind >= 4;
+    float4 mk = make_float4(1.f, 1.f, 1.f, 1.f);
+    float wa_v = 0.f;  // staged into LDS after the K loop
+    const bool has_da = kind == 5 || (kind == 6 && jb.da_part);  // block-uniform
+    auto wa_ok = [&]() { return (tid >> 5) < jb.nact && n0 + (tid & 31) < jb.N; };   // this thread's element of the action rows exists
+    const bool do_adam = kind >= 1 && kind <= 3;
+    const bool narrow = kind == 3 || (kind == 0 && rm_like && hot_N <= 8);   // block-uniform
+    float al_pi = 0.f, al_q = 0.f;
+    float b1p_pi = 0.f, b2p_pi = 0.f, b1p_q = 0.f, b2p_q = 0.f;   // stepping tiles: the powers as loaded, al_pi / al_q from them in the epilogue
+    // optimizer state of this tile: J4 — thread (col r, row group cg) owns rows 4cg..4cg+3 of column r as one float4;
+    // RM — thread owns elements (o >> 5, o & 31), o = tid + 256 q
+    float4 j_m, j_v, j_p, j_t;
+    float bm = 0.f, bv = 0.f, bp = 0.f, bt = 0.f;
+    float am[4], av[4], ap[4], at[4];
+    bool okv[4];
+    long long j_idx = 0, b_idx = 0;
+    bool j_ok = false, b_ok = false;
+    // KIND = which loads a tile's K loop carries beside its operand groups (block-uniform, chosen once in front of the FIRST operand
+    // request).  0: none (wgrads of the split API, which do not step the optimizer) — 1 / 2 / 3: the optimizer state of a stepping J4 /
+    // element-addressed / narrow element-addressed tile — 4: a Q dgrad (DG_DGRAD_Q), its relu mask — 5: a Q dgrad that also leaves
+    // dQ/da partials, the mask and the layer-1 action rows — 6: a DG_DGRAD tile (the policy's: A generated with bgen = 3, or plain), the
+    // mask (the rows too, under a branch, should such a job ever carry dQ/da partials: none does).  The dgrads are split by job type as
+    // well because the Q prologue's partials and the policy's row math otherwise hold their registers through each other's code: one
+    // instance for both needs 179 VGPRs (two waves per SIMD) against 168.
+    // Mask and rows are kept AS LOADED: a compare or a select on them is placed at the load by the compiler,
+    // with a vmcnt(0) in front — a drain of the whole queue in the middle of the loop, one cold round trip each (the mask was written by
+    // the forward launch) while the operand groups in flight land unused.  The mask is tested behind the combine barrier, the rows are
+    // masked where they are staged (profiles/dg_queue_drains_before_after.txt).
+    auto epilogue_operands = [&](auto kind) {
+        constexpr int KIND = decltype(kind)::value;
+        if (KIND >= 4) {
+            mk = *reinterpret_cast<const float4 *>(jb.mask + ((long long)(m0 / 4 + cg) * jb.ldmask + n0 + r) * 4);  // mapping C: (col r, row group cg)
+            if (KIND == 5 || (KIND == 6 && has_da)) wa_v = jb.wa[wa_ok() ? w1y_index(jb.wa_d0 + (tid >> 5), n0 + (tid & 31)) : 0];
+        } else if (KIND >= 1) {
+            b1p_pi = jobs.ad.opt->b1p_pi; b2p_pi = jobs.ad.opt->b2p_pi; b1p_q = jobs.ad.opt->b1p_q; b2p_q = jobs.ad.opt->b2p_q;
+        }
+        if (KIND == 1 || (KIND == 0 && type == DG_WGRAD_J4)) {
+            j_ok = m0 + 4 * cg < jb.bias_row && n0 + r < jb.N;
+            j_idx = jb.adam_off + ((long long)(m0 / 4 + cg) * jb.ldc + n0 + r) * 4;
+            b_ok = m0 + 4 * cg == jb.bias_row && n0 + r < jb.N;  // (hidden1 % 4 == 0: the bias row opens a group)
+            b_idx = jb.bias_off + n0 + r;
+            if (KIND == 1) {
+                const long long ic = j_ok ? j_idx : jb.adam_off;
+                j_m = *reinterpret_cast<const float4 *>(jobs.ad.m + ic); j_v = *reinterpret_cast<const float4 *>(jobs.ad.v + ic);
+                j_p = *reinterpret_cast<const float4 *>(jobs.ad.p + ic); j_t = *reinterpret_cast<const float4 *>(jobs.ad.t + ic);
+                const long long bc = b_ok ? b_idx : jb.bias_off;
+                bm = jobs.ad.m[bc]; bv = jobs.ad.v[bc]; bp = jobs.ad.p[bc]; bt = jobs.ad.t[bc];
+            }
+        } else if (KIND == 2 || KIND == 3 || (KIND == 0 && rm_like)) {
+            // narrow outputs (the head kernels: N = act or 1 column): 32 rows x 8 columns = one element per thread instead of four —
+            // a quarter of the optimizer-state loads
+            const bool nar = KIND == 3 || (KIND == 0 && narrow);   // block-uniform
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (nar && q > 0) { okv[q] = false; continue; }
+                const int o = tid + 256 * q;
+                const int gi = m0 + (nar ? (o >> 3) : (o >> 5)), gj = n0 + (nar ? (o & 7) : (o & 31));
+                okv[q] = gi < jb.M && gj < jb.N;
+                if (KIND == 2 || KIND == 3) {
+                    const long long idx = !okv[q] ? jb.adam_off : jb.adam_off + (type == DG_WGRAD_W1Y ? w1y_index(gi, gj) : (long long)gi * jb.ldc + gj);
+                    am[q] = jobs.ad.m[idx]; av[q] = jobs.ad.v[idx]; ap[q] = jobs.ad.p[idx]; at[q] = jobs.ad.t[idx];
+                }
+            }
+        }
+    };
+    floatx16 acc;
+    // ---- from the first operand request to the last MFMA: one instance per KIND, each with operand registers of its own.  With the
+    // up-front requests in front of the dispatch, the loops shared a4[] / b4[] across a join, and the compiler copied components of
+    // b4[0] and b4[1] into the registers one of the loops wanted — behind vmcnt(2) and vmcnt(0): every GEMM tile waited for BOTH
+    // up-front groups before it requested the third, a round trip with nothing new in flight.  (The code between the requests and
+    // the loop — generated-operand row math, LDS staging, the loss prologue — is written once and compiled per kind.)
+    auto gemm_tile = [&](auto kind) {
+    constexpr int KIND = decltype(kind)::value;
+    constexpr bool STEP = KIND >= 1 && KIND <= 3, DGQ = KIND == 4 || KIND == 5;
+    // (a marker that differs per kind: the instances begin with the same requests, which the compiler otherwise hoists back in front
+    // of the dispatch as common code — and with them the join)
+    asm volatile("; k_dg tile kind %0" ::"n"(KIND));
+    // what the kind says about the job type (`kind` is opaque to the compiler): predicates of the other types fold away
+    if (DGQ) __builtin_assume(type == DG_DGRAD_Q);
+    else if (KIND == 6) __builtin_assume(type == DG_DGRAD);
+    else __builtin_assume(type != DG_DGRAD_Q && type != DG_DGRAD);
     // both operand streams of this wave: unconditional loads, groups beyond ng re-read the last one (a branch or a
     // select in front of a load makes the compiler wait for the previous load before issuing the next)
     float4 a4[GMAX], b4[GMAX];
@@ -1171,7 +1281,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     // over, off this chain).  The dgrad no longer waits for a launch between the dQ/da partials and itself, and the layer-1 wgrad of
     // the policy becomes a plain job of the last launch instead of a hand-off at the end of the update's longest chain.
     float pdm[4] = {0.f, 0.f, 0.f, 0.f}, pdl[4] = {0.f, 0.f, 0.f, 0.f};
-    if (agen) {
+    if (KIND == 6 && agen) {
         __builtin_amdgcn_sched_barrier(0);
         const int act = jb.nact, row = m0 + l31;
         float4 dp[16];
@@ -1240,92 +1350,11 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     const bool agen2 = agen && jb.nact <= 2;   // block-uniform
     ktouch(kl);
     DST(kid, 1);
-    // ---- epilogue operands: requested from inside the K loop (behind the MFMAs of the first groups), so that the first
-    // MFMA does not queue behind up to 16 more wave-loads per wave.  A wave's loads return in order, and the optimizer state is
-    // cold (it comes over the fabric): whatever waits behind it in the K loop waits a round trip.  That cost did not depend on
-    // WHERE the state was requested (DGMID 1 - 8: flat), because of how the waits were counted, not because of the queue: the
-    // requests sat in branches (job type, do_adam) inside the one K loop of all job types, and where paths with different
-    // numbers of loads in flight join, the compiler's wait counts assume the shortest one — the very next MFMA group waited for
-    // all but the four newest loads (vmcnt(5) / (4) where the stepping J4 path had 13 behind the operand it needed), i.e. for
-    // the whole state wherever it stood; and the four bias-correction powers were used where they were loaded, a vmcnt(0) in the
-    // middle of the loop of EVERY tile of a stepping launch, dgrads included, which never use them.
-    // So the tiles that step the optimizer run a K loop of their own per epilogue mapping (k_loop_step, KIND 1 - 3 below: no load
-    // of theirs under a branch, the waits count exactly: vmcnt(13) there now), request the state behind the last operand group
-    // of a 256-deep contraction (DGST) and first use it, and the powers, behind the combine barrier; the other tiles keep the
-    // loop they had and no longer load the powers.  (All four kinds through ONE generic loop: the compiler then turns the
-    // generated-operand branches of the dgrads into selects, +0.9 k cycles of K loop in launch "bq".)  tools/upd_bench, us per
-    // update: 43.9 -> 42.7 (K loop of the stepping J4 tiles 16.6 k -> 14.7 k cycles in launch "mid", 11.4 k -> 9.8 k in "pi";
-    // their epilogue 2.8 k -> 3.3 k; the policy dgrad beside them 9.7 k -> 9.1 k); DGST 3 / 4 / 5 / 6 / 7: 43.0 - 43.4 against
-    // 44.1, flat — with exact waits the position hardly matters, the rest of the K loop's excess is the arrival of its own
-    // operands (profiles/optstate_queue_before_after.txt).  Closed before that: a fifth "helper" wave per
-    // workgroup that fetches the state into LDS before the combine barrier — the dispatcher then fits one 5-wave workgroup
-    // per CU at 131 VGPRs (59.5 us per update), and capping the kernel at 128 VGPRs spills (55.7 us) against 52.5 us.
-    const bool is_dgrad = type == DG_DGRAD_Q || type == DG_DGRAD;
-    float4 mk = make_float4(1.f, 1.f, 1.f, 1.f);
-    float wa_v = 0.f;  // staged into LDS after the K loop
-    const bool has_da = is_dgrad && jb.da_part;  // block-uniform
-    const bool rm_like = type == DG_WGRAD_RM || type == DG_WGRAD_W1Y;  // element-addressed gradient: row-major, or the layer-1 block layout
-    const bool do_adam = jobs.ad.on && (type == DG_WGRAD_J4 || rm_like) && jb.adam_off >= 0;
-    const bool narrow = rm_like && hot_N <= 8;   // block-uniform
-    float al_pi = 0.f, al_q = 0.f;
-    float b1p_pi = 0.f, b2p_pi = 0.f, b1p_q = 0.f, b2p_q = 0.f;   // stepping tiles: the powers as loaded, al_pi / al_q from them in the epilogue
-    // optimizer state of this tile: J4 — thread (col r, row group cg) owns rows 4cg..4cg+3 of column r as one float4;
-    // RM — thread owns elements (o >> 5, o & 31), o = tid + 256 q
-    float4 j_m, j_v, j_p, j_t;
-    float bm = 0.f, bv = 0.f, bp = 0.f, bt = 0.f;
-    float am[4], av[4], ap[4], at[4];
-    bool okv[4];
-    long long j_idx = 0, b_idx = 0;
-    bool j_ok = false, b_ok = false;
-    // KIND 0: a tile that does not step the optimizer (dgrads; wgrads of the split API) — 1 / 2 / 3: a stepping J4 / element-addressed /
-    // narrow element-addressed tile (block-uniform, chosen once in front of the K loop)
-    auto epilogue_operands = [&](auto kind) {
-        constexpr int KIND = decltype(kind)::value;
-        if (KIND == 0) {
-            if (is_dgrad) mk = *reinterpret_cast<const float4 *>(jb.mask + ((long long)(m0 / 4 + cg) * jb.ldmask + n0 + r) * 4);  // mapping C: (col r, row group cg)
-            if (has_da) {
-                const int c = tid >> 5, col = n0 + (tid & 31);
-                const bool ok = c < jb.nact && col < jb.N;
-                const float v = jb.wa[ok ? w1y_index(jb.wa_d0 + c, col) : 0];
-                wa_v = ok ? v : 0.f;
-            }
-        } else {
-            b1p_pi = jobs.ad.opt->b1p_pi; b2p_pi = jobs.ad.opt->b2p_pi; b1p_q = jobs.ad.opt->b1p_q; b2p_q = jobs.ad.opt->b2p_q;
-        }
-        if (KIND == 1 || (KIND == 0 && type == DG_WGRAD_J4)) {
-            j_ok = m0 + 4 * cg < jb.bias_row && n0 + r < jb.N;
-            j_idx = jb.adam_off + ((long long)(m0 / 4 + cg) * jb.ldc + n0 + r) * 4;
-            b_ok = m0 + 4 * cg == jb.bias_row && n0 + r < jb.N;  // (hidden1 % 4 == 0: the bias row opens a group)
-            b_idx = jb.bias_off + n0 + r;
-            if (KIND == 1) {
-                const long long ic = j_ok ? j_idx : jb.adam_off;
-                j_m = *reinterpret_cast<const float4 *>(jobs.ad.m + ic); j_v = *reinterpret_cast<const float4 *>(jobs.ad.v + ic);
-                j_p = *reinterpret_cast<const float4 *>(jobs.ad.p + ic); j_t = *reinterpret_cast<const float4 *>(jobs.ad.t + ic);
-                const long long bc = b_ok ? b_idx : jb.bias_off;
-                bm = jobs.ad.m[bc]; bv = jobs.ad.v[bc]; bp = jobs.ad.p[bc]; bt = jobs.ad.t[bc];
-            }
-        } else if (KIND >= 2 || (KIND == 0 && rm_like)) {
-            // narrow outputs (the head kernels: N = act or 1 column): 32 rows x 8 columns = one element per thread instead of four —
-            // a quarter of the optimizer-state loads
-            const bool nar = KIND == 3 || (KIND == 0 && narrow);   // block-uniform
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (nar && q > 0) { okv[q] = false; continue; }
-                const int o = tid + 256 * q;
-                const int gi = m0 + (nar ? (o >> 3) : (o >> 5)), gj = n0 + (nar ? (o & 7) : (o & 31));
-                okv[q] = gi < jb.M && gj < jb.N;
-                if (KIND >= 2) {
-                    const long long idx = !okv[q] ? jb.adam_off : jb.adam_off + (type == DG_WGRAD_W1Y ? w1y_index(gi, gj) : (long long)gi * jb.ldc + gj);
-                    am[q] = jobs.ad.m[idx]; av[q] = jobs.ad.v[idx]; ap[q] = jobs.ad.p[idx]; at[q] = jobs.ad.t[idx];
-                }
-            }
-        }
-    };
     // ---- DGRAD_Q prologue: q1, q2, q1(x,pi), the target backup, the per-row loss terms and dq = dLoss/dq (actor_learner.py:58-69)
     float dqr = m0 + l31 < Bv ? jb.gconst : 0.f;
     if (has_gen && !agen) { s_gw[tid] = gv0; s_gw[tid + 256] = gv1; }
     if (has_gen && !need_q) __syncthreads();
-    if (type == DG_DGRAD_Q) {
+    if (DGQ) {
         if (need_q) {
             float qsum = zero_here();
 #pragma unroll
@@ -1381,57 +1410,33 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             dqr = s_g[l31];
         }
     }
-    // ---- K loop
+    // ---- K loop.  No load of a kind stands under a branch (a join with a path that has fewer loads in flight makes the compiler
+    // count the shorter queue), so the waits in front of every MFMA group count exactly; the generated-operand branches of the
+    // tiles that do not step stay branches (as selects: +0.9 k cycles in launch "bq").
     DST(kid, 2);
-    floatx16 acc;
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    // the tiles that step the optimizer (wgrads: a plain or a generated B operand): one loop per epilogue mapping, no load under a branch
-    auto k_loop_step = [&](auto kind) {
-#pragma unroll
-        for (int g = 0; g < GMAX; ++g) {
-            if (g + DGP < GMAX) {
-                fetch_group(g + DGP);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (g == DGST) {
-                epilogue_operands(kind);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (g < ng) {
-                float4 av4 = a4[g], bv4 = b4[g];
-                if (jb.bgen) {
-                    const float4 d4 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
-                    bv4 = make_float4(bv4.x > 0.f ? d4.x * gwn : 0.f, bv4.y > 0.f ? d4.y * gwn : 0.f, bv4.z > 0.f ? d4.z * gwn : 0.f, bv4.w > 0.f ? d4.w * gwn : 0.f);
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.x, bv4.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.y, bv4.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.z, bv4.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.w, bv4.w, acc, 0, 0, 0);
-            }
-        }
-    };
-    if (do_adam) {   // block-uniform
-        if (type == DG_WGRAD_J4) k_loop_step(DGKind<1>{});
-        else if (!narrow) k_loop_step(DGKind<2>{});
-        else k_loop_step(DGKind<3>{});
-    } else {
 #pragma unroll
     for (int g = 0; g < GMAX; ++g) {
         if (g + DGP < GMAX) {
             fetch_group(g + DGP);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (g == DGMID) {
-            epilogue_operands(DGKind<0>{});
+        if (g == (STEP ? DGST : DGMID)) {
+            epilogue_operands(kind);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (g < ng) {
             float4 av4 = a4[g], bv4 = b4[g];
-            if (type == DG_DGRAD_Q) {
+            if (STEP) {   // wgrads: a plain or a generated B operand
+                if (jb.bgen) {
+                    const float4 d4 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
+                    bv4 = make_float4(bv4.x > 0.f ? d4.x * gwn : 0.f, bv4.y > 0.f ? d4.y * gwn : 0.f, bv4.z > 0.f ? d4.z * gwn : 0.f, bv4.w > 0.f ? d4.w * gwn : 0.f);
+                }
+            } else if (DGQ) {
                 const float4 w3 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
                 av4 = make_float4(av4.x > 0.f ? dqr * w3.x : 0.f, av4.y > 0.f ? dqr * w3.y : 0.f, av4.z > 0.f ? dqr * w3.z : 0.f, av4.w > 0.f ? dqr * w3.w : 0.f);
-            } else if (agen2) {
+            } else if (KIND == 6 && agen2) {
                 // act <= 2: rows [Wmu0 Wmu1 Wls0 Wls1]; the terms of the action slots 2, 3 are exact zeros and add nothing (fma(0, 0, acc) == acc)
                 const float *wk = &s_w8[(8 * (g0 + g) + 4 * h) * 4];
                 float z4[4];
@@ -1443,7 +1448,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
                     z4[e] = acc;
                 }
                 av4 = make_float4(av4.x > 0.f ? z4[0] : 0.f, av4.y > 0.f ? z4[1] : 0.f, av4.z > 0.f ? z4[2] : 0.f, av4.w > 0.f ? z4[3] : 0.f);
-            } else if (agen) {
+            } else if (KIND == 6 && agen) {
                 const float *wk = &s_w8[(8 * (g0 + g) + 4 * h) * 8];
                 float z4[4];
 #pragma unroll
@@ -1456,7 +1461,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
                     z4[e] = acc;
                 }
                 av4 = make_float4(av4.x > 0.f ? z4[0] : 0.f, av4.y > 0.f ? z4[1] : 0.f, av4.z > 0.f ? z4[2] : 0.f, av4.w > 0.f ? z4[3] : 0.f);
-            } else if (jb.bgen) {
+            } else if (KIND == 0 && jb.bgen) {   // (a generated B operand is a wgrad's)
                 const float4 d4 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
                 bv4 = make_float4(bv4.x > 0.f ? d4.x * gwn : 0.f, bv4.y > 0.f ? d4.y * gwn : 0.f, bv4.z > 0.f ? d4.z * gwn : 0.f, bv4.w > 0.f ? d4.w * gwn : 0.f);
             }
@@ -1466,10 +1471,19 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.w, bv4.w, acc, 0, 0, 0);
         }
     }
+    };
+    switch (kind) {   // block-uniform
+    case 0: gemm_tile(DGKind<0>{}); break;
+    case 1: gemm_tile(DGKind<1>{}); break;
+    case 2: gemm_tile(DGKind<2>{}); break;
+    case 3: gemm_tile(DGKind<3>{}); break;
+    case 4: gemm_tile(DGKind<4>{}); break;
+    case 5: gemm_tile(DGKind<5>{}); break;
+    default: gemm_tile(DGKind<6>{}); break;
     }
     // ---- split-K combine.  D layout: col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)
     DST(kid, 3);
-    if (has_da && tid < 128) s_wa[tid >> 5][tid & 31] = wa_v;
+    if (has_da && tid < 128) s_wa[tid >> 5][tid & 31] = wa_ok() ? wa_v : 0.f;
 #pragma unroll
     for (int q = 0; q < 16; ++q) red[w][(q & 3) + 8 * (q >> 2) + 4 * h][l31] = acc[q];
     __syncthreads();
@@ -1478,6 +1492,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     if (is_dgrad) {
         // mapping C: thread (col r, row group cg): rows m0 + 4cg .. + 3 of column n0 + r
         float o4[4];
+        asm volatile("" : "+v"(mk.x), "+v"(mk.y), "+v"(mk.z), "+v"(mk.w));   // the mask as loaded up to HERE: its test is not to move to the load
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float s = ((red[0][4 * cg + i][r] + red[1][4 * cg + i][r]) + red[2][4 * cg + i][r]) + red[3][4 * cg + i][r];
