@@ -415,18 +415,18 @@ int ddrl_sac1_stage_time(ddrl_sac1_t *h, int stage, int reps, float *ms_per_laun
 /*   `while True: batch = sample_batch(B); agent.train(batch)`                              */
 /*   (algos/sac1/sac1.py:146-148; example/dsac.py:142-144 + example/model.py:92-101)        */
 /* sample (MT19937 indices + gather, straight into the learner's buffers) -> update, n times, */
-/* with no host work per update: the sequence for `updates_per_graph` updates is captured     */
-/* once into a hipGraph (all cursors, RNG state and Adam state are device-resident) and       */
-/* replayed.  Consecutive updates alternate between the learner's two input sets; with         */
-/* DDRL_LOOP_FORK=1 the sampler runs on a forked graph branch so that sample(u+1) overlaps      */
-/* update(u) — the role of the reference's `Cache` prefetch process (sac1.py:103-130); measured */
-/* slower than inline on MI355X, hence opt-in.                                      */
+/* with no host work per update: the sequences for `updates_per_graph` updates and every power */
+/* of two below it are captured once into hipGraphs (all cursors, RNG state and Adam state are */
+/* device-resident) and replayed.  Consecutive updates alternate between the learner's two      */
+/* input sets, and the sampler of update u+1 rides inside update u — the role of the            */
+/* reference's `Cache` prefetch process (sac1.py:103-130).                                      */
 /* ===================================================================================== */
 typedef struct ddrl_loop ddrl_loop_t;
 int ddrl_loop_create(ddrl_loop_t **out, ddrl_sac1_t *learner, ddrl_replay_t *replay, int32_t updates_per_graph,
                      uint32_t noise_seed);
 int ddrl_loop_destroy(ddrl_loop_t *h);
-/* Enqueue n_updates sample+train iterations on `stream` (graph replays + an eager remainder).
+/* Enqueue n_updates sample+train iterations on `stream`.  The first call of at least updates_per_graph updates runs one update
+ * eagerly and captures; from then on every update of a call runs from a graph replay (updates_per_graph == 0: all eager).
  * Returns DDRL_ERR_EMPTY_BUFFER if the ring is empty.  On an n-step window ring (algos/sac1/sac_ray.py:40-51) every draw is
  * ddrl_replay_sample_nstep with the learner's gamma. */
 int ddrl_loop_run(ddrl_loop_t *h, int64_t n_updates, void *stream);
