@@ -159,6 +159,7 @@ SIGNATURES = {
     "ddrl_rollout_begin_articulated": (c_int, [_P, _P, _P]),
     "ddrl_rollout_step_articulated": (c_int, [_P, _P, _P, c_int32, c_uint32, c_uint64, c_int, _P, _P, _P]),
     "ddrl_env_step_wrapped": (c_int, [_P, _P, c_float, c_float, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "ddrl_env_step_wrapped_articulated": (c_int, [_P, _P, c_float, c_float, c_float, c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
     "ddrl_env_step_discrete": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ddrl_rollout_begin_discrete": (c_int, [_P, _P, _P]),
     "ddrl_rollout_step_discrete": (c_int, [_P, _P, _P, c_int32, c_int, c_float, c_uint32, c_uint64, _P, _P, _P, _P]),
@@ -212,6 +213,9 @@ SIGNATURES = {
     "ddrl_rollout_begin_nstep": (c_int, [_P, _P, _P, _P]),
     "ddrl_rollout_step_nstep": (c_int, [_P, _P, _P, _P, c_int32, c_float, c_float, c_float, c_int32, c_int32, c_int32, c_uint32, c_uint64,
                                         _P, _P]),
+    "ddrl_rollout_begin_nstep_articulated": (c_int, [_P, _P, _P, _P]),
+    "ddrl_rollout_step_nstep_articulated": (c_int, [_P, _P, _P, _P, c_int32, c_float, c_float, c_float, c_int32, c_int32, c_int32, c_uint32,
+                                                    c_uint64, _P, _P]),
     "ddrl_normal_fill": (c_int, [_P, c_int64, c_uint32, c_uint64, _P]),
     "ddrl_uniform_fill": (c_int, [_P, c_int64, c_float, c_float, c_uint32, c_uint64, _P]),
 }

@@ -689,6 +689,21 @@ int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float ob
     return DDRL_OK;
 }
 
+// ... on the articulated lander (kernel: rollout3_nstep.hip, k_env3_step_wrapped); the iteration counts are the handle's
+int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale,
+                                      int32_t action_repeat, int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d,
+                                      float *next_obs_d, uint8_t *ended_d, void *stream) {
+    DDRL_REQUIRE(h != nullptr && act_d != nullptr, "NULL pointer");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_env_step_wrapped_articulated", "ddrl_env_step_wrapped");
+    DDRL_REQUIRE_ALIGNED(act_d, 8);
+    DDRL_REQUIRE_ALIGNED(obs2_d, 16);
+    DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
+    DDRL_REQUIRE(action_repeat >= 1 && limit_steps >= 1, "action_repeat and limit_steps must be >= 1");
+    ddrl::DeviceGuard g(h->device);
+    return ddrl_env3_launch_step_wrapped(h->S, h->n, h->seed, limit_steps, h->vit, h->pit, act_d, act_noise, obs_noise, reward_scale,
+                                         action_repeat, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats, stream);
+}
+
 int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream) {
     DDRL_REQUIRE(h != nullptr && actor != nullptr, "NULL handle");
     DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin");
@@ -930,22 +945,21 @@ static int rollout_nstep_ring_check(ddrl_env_t *h, const ddrl_winq_view &q, cons
     return DDRL_OK;
 }
 
-int ddrl_rollout_begin_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream) {
-    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr, "NULL handle");
-    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin_nstep");
+// ---- what the two n-step pairs (one-body: rollout_nstep.hip; articulated: rollout3_nstep.hip) share behind their own kind test:
+// the begin call — envelope, then the observation rows and the readiness bytes from the queues (no env state is read) ...
+static int rollout_nstep_begin(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream) {
     const ddrl_actor_rollout_view v = ddrl_actor_internal_view(actor);
     const ddrl_winq_view q = ddrl_winq_internal_view(winq);
     if (const int rc = rollout_nstep_check(h, v, q)) return rc;
     ddrl::DeviceGuard g(h->device);
     return ddrl_nstep_launch_begin(q.o, h->n, q.Ln, v.obs, q.t, q.save_freq, q.rdy[*q.parity], stream);
 }
-
-int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
-                            float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
-                            int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr, const ddrl_rollout_nstep_out_t *out,
-                            void *stream) {
-    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr && window_ring != nullptr, "NULL handle");
-    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step_nstep");
+// ... and the step driver: argument checks, envelope, then n_steps times the loop body of worker_rollout — the versioned / plain
+// forward choice, the env-step kernel of the handle's model on the filled NStepLaunch, the parity flip
+static int rollout_nstep_step_loop(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
+                                   float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
+                                   int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr,
+                                   const ddrl_rollout_nstep_out_t *out, void *stream) {
     DDRL_REQUIRE(n_steps >= 1 && action_repeat >= 1 && limit_steps >= 1, "n_steps, action_repeat and limit_steps must be >= 1");
     if (out) {
         DDRL_REQUIRE_ALIGNED(out->act, 8);
@@ -982,7 +996,8 @@ int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *win
             if (const int frc = ddrl_actor_internal_forward(actor, h->n, stream, versioned ? 1 : 0)) return frc;
             a.noise_ctr = noise_ctr + (uint64_t)k * (uint64_t)h->n * 2ull;
             a.rdy_in = q.rdy[*q.parity]; a.rdy_out = q.rdy[1 - *q.parity];
-            if (const int lrc = ddrl_nstep_launch_step(a, stream)) return lrc;
+            const int lrc = h->kind == DDRL_ENV_ARTICULATED ? ddrl_nstep3_launch_step(a, h->vit, h->pit, stream) : ddrl_nstep_launch_step(a, stream);
+            if (lrc) return lrc;
             *q.parity = 1 - *q.parity;
             if (!versioned && store && a.adopt) *v.ver.plan_fresh = false;   // an unplanned launch moved envs: the next forward plans
             return DDRL_OK;
@@ -991,6 +1006,40 @@ int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *win
         ddrl_replay_note_masked_store(window_ring);   // the row count is known on the device only
     }
     return DDRL_OK;
+}
+
+int ddrl_rollout_begin_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_begin_nstep");
+    return rollout_nstep_begin(h, actor, winq, stream);
+}
+
+int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
+                            float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
+                            int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr, const ddrl_rollout_nstep_out_t *out,
+                            void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr && window_ring != nullptr, "NULL handle");
+    DDRL_ONE_BODY_ONLY(h, "ddrl_rollout_step_nstep");
+    return rollout_nstep_step_loop(h, actor, winq, window_ring, n_steps, act_noise, obs_noise, reward_scale, action_repeat, limit_steps,
+                                   adopt_at_episode_end, noise_seed, noise_ctr, out, stream);
+}
+
+// ---- the same pair on the articulated lander (kernel: rollout3_nstep.hip): only the kind test is its own: the envelope, the begin
+// launch (it reads the queues only) and the step driver, which launches the kernel of the handle's model, are the one-body pair's
+int ddrl_rollout_begin_nstep_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr, "NULL handle");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_begin_nstep_articulated", "ddrl_rollout_begin_nstep");
+    return rollout_nstep_begin(h, actor, winq, stream);
+}
+
+int ddrl_rollout_step_nstep_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
+                                        float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
+                                        int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr,
+                                        const ddrl_rollout_nstep_out_t *out, void *stream) {
+    DDRL_REQUIRE(h != nullptr && actor != nullptr && winq != nullptr && window_ring != nullptr, "NULL handle");
+    DDRL_ARTICULATED_ONLY(h, "ddrl_rollout_step_nstep_articulated", "ddrl_rollout_step_nstep");
+    return rollout_nstep_step_loop(h, actor, winq, window_ring, n_steps, act_noise, obs_noise, reward_scale, action_repeat, limit_steps,
+                                   adopt_at_episode_end, noise_seed, noise_ctr, out, stream);
 }
 
 int ddrl_env_stats(ddrl_env_t *h, int64_t *episodes_h, double *ret_sum_h, int64_t *len_sum_h, void *stream) {

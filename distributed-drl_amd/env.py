@@ -27,11 +27,12 @@ class VecLunarLander:
     def __init__(self, n_envs, seed=0, max_ep_len=1000, device=None, model="simple", velocity_iterations=180, position_iterations=60):
         """model: "simple" — the one-body lander (ddrl_env_create) — or "articulated" — hull and two jointed legs on Box2D's island
         solve with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default; ddrl_env_create_ex).
-        The articulated env has reset / step / stats / get_state / set_state; step_wrapped, the one-body fused rollout launches
-        (ddrl_rollout_step, ddrl_rollout_step_discrete) and the n-step fused step refuse it.  This model's own fused pairs are
-        ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated, reached through workers.RolloutDevice, and
+        The articulated env has reset / step / step_wrapped_articulated / stats / get_state / set_state; step_wrapped and the one-body
+        fused rollout launches (ddrl_rollout_step, ddrl_rollout_step_discrete, ddrl_rollout_step_nstep) refuse it.  This model's own
+        fused pairs are ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated, reached through workers.RolloutDevice,
         ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated, reached through workers.RolloutDeviceDQN
-        (its mirrors: rollout_mirrors()); there is no n-step fused step and no wrapped step on this model."""
+        (its mirrors: rollout_mirrors()), and ddrl_rollout_begin_nstep_articulated / ddrl_rollout_step_nstep_articulated, reached
+        through workers.RolloutDeviceNStep.  Like the one-body model it is not pinned against gym (tests/lander3_oracle.py)."""
         _lib.require_gpu()
         self._lib = _lib.load()
         self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)
@@ -83,6 +84,19 @@ class VecLunarLander:
         _lib.check(self._lib.ddrl_env_step_wrapped(self._h, _lib.dptr(act), float(act_noise), float(obs_noise), float(reward_scale),
                                                    int(action_repeat), limit, _lib.dptr(self.obs2), _lib.dptr(self.rew),
                                                    _lib.dptr(self.done), _lib.dptr(self.obs), _lib.dptr(self.ended), _lib.stream_ptr()))
+        return self.obs2, self.rew, self.done, self.obs, self.ended
+
+    def step_wrapped_articulated(self, act, act_noise=0.0, obs_noise=0.0, reward_scale=1.0, action_repeat=3, limit_steps=None):
+        """step_wrapped on the articulated lander (ddrl_env_step_wrapped_articulated, csrc/rollout3_nstep.hip): the same Wrapper and
+        bookkeeping around the three-body solver with this env's iteration counts; same arguments and outputs, `act` updated in place.
+        On model="simple" the library refuses (DdrlUnsupported naming step_wrapped's entry point); step_wrapped is unchanged and keeps
+        refusing this model."""
+        act = act.to(device=self.device, dtype=torch.float32).contiguous()
+        limit = int(limit_steps if limit_steps is not None else self.max_ep_len)
+        _lib.check(self._lib.ddrl_env_step_wrapped_articulated(self._h, _lib.dptr(act), float(act_noise), float(obs_noise),
+                                                               float(reward_scale), int(action_repeat), limit, _lib.dptr(self.obs2),
+                                                               _lib.dptr(self.rew), _lib.dptr(self.done), _lib.dptr(self.obs),
+                                                               _lib.dptr(self.ended), _lib.stream_ptr()))
         return self.obs2, self.rew, self.done, self.obs, self.ended
 
     def sample_actions(self, out=None):

@@ -607,9 +607,10 @@ def _env_model_kw(opt):
     """The env-model arguments of a rollout worker's envs: `opt.env_model` ("simple", the default, or "articulated") and, for the
     articulated lander, `opt.env_velocity_iterations` / `opt.env_position_iterations` (gym's 180 / 60 unless set).  On the articulated
     model the workers run their unfused sequence (act, env.step, store) by default: the fused launches of ddrl_rollout_step and its
-    discrete and n-step siblings hold the one-body lander.  The continuous worker (RolloutDevice) has a fused step on that model
-    behind `opt.fused_rollout_articulated`, the discrete worker (RolloutDeviceDQN) behind `opt.fused_discrete_rollout_articulated`
-    (both default False); the n-step worker has none.  The flags are the workers', and change nothing here."""
+    discrete and n-step siblings hold the one-body lander.  Every worker has a fused step on that model behind a flag of its own: the
+    continuous worker (RolloutDevice) behind `opt.fused_rollout_articulated`, the discrete worker (RolloutDeviceDQN) behind
+    `opt.fused_discrete_rollout_articulated`, the n-step worker (RolloutDeviceNStep) behind `opt.fused_nstep_rollout_articulated`
+    (all default False).  The flags are the workers', and change nothing here."""
     model = getattr(opt, "env_model", "simple")
     if model == "simple":
         return {}
@@ -907,7 +908,14 @@ class RolloutDeviceNStep(_RolloutWorker):
     Fused pair: ddrl_rollout_begin_nstep / ddrl_rollout_step_nstep, for the policy phase with the version store on.  Adoption defaults
     to "episode" with horizon limit_steps, the store is enabled in the constructor, and an env adopts at `d or ep_len * action_repeat >=
     max_ep_len` only once the buffer's steps exceed start_steps (`_learning`, sac_ray.py:252-262).  Its step() is its own: the
-    filling phase counts filling_steps, not t, and every step pushes the window queues."""
+    filling phase counts filling_steps, not t, and every step pushes the window queues.
+
+    The articulated lander (`opt.env_model = "articulated"`, iteration counts as _env_model_kw reads them) steps through
+    VecLunarLander.step_wrapped_articulated on the unfused sequence, which is what this worker runs on that model unless
+    `opt.fused_nstep_rollout_articulated` is set (default False): then — with the rest of the envelope holding as on the one-body model —
+    it takes ddrl_rollout_begin_nstep_articulated / ddrl_rollout_step_nstep_articulated, the same launch pair with the three-body solver
+    inside the Wrapper's repeat loop (csrc/rollout3_nstep.hip).  `_learning`, adoption at the episode end, ps=None and _fused_refresh
+    behave as on the one-body model; the one-body worker ignores the flag."""
 
     WRAPPER_REPEAT = 3  # the literal in sac_ray.py:189 (opt.action_repeat only scales the episode limit)
 
@@ -919,7 +927,7 @@ class RolloutDeviceNStep(_RolloutWorker):
         self.opt = opt
         self.rbs = list(replay_buffers) if isinstance(replay_buffers, (list, tuple)) else [replay_buffers]
         n = int(opt.num_envs)
-        self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23)
+        self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23, **_env_model_kw(opt))
         self.limit_steps = -(-int(opt.max_ep_len) // int(opt.action_repeat))   # ep_len * action_repeat >= max_ep_len (sac_ray.py:252)
         self.actor = Actor(opt, job="worker", max_rows=n, index=worker_index)
         self.filling_steps = 0
@@ -950,13 +958,23 @@ class RolloutDeviceNStep(_RolloutWorker):
         store is part of the envelope, so that the two paths stay bit-identical.  The C entry point checks the rest."""
         from . import _lib
         from .replay import ReplayBufferNStep
-        ok = self._versions and self.env.model == "simple" and all(isinstance(rb, ReplayBufferNStep) for rb in self.rbs)
+        # ddrl_rollout_begin_nstep holds the one-body lander and refuses the other; the articulated pair is opt-in
+        ok = self.env.model == "simple" or (self.env.model == "articulated" and
+                                            bool(getattr(self.opt, "fused_nstep_rollout_articulated", False)))
+        ok = ok and self._versions and all(isinstance(rb, ReplayBufferNStep) for rb in self.rbs)
         ok = ok and self.env.n % 32 == 0 and self.winq.Ln <= _lib.DDRL_NSTEP_FUSED_MAX_LN
         return ok and all(rb.max_size < (1 << 31) and rb.Ln == self.winq.Ln and (rb.obs_dim, rb.act_dim) == (8, 2) for rb in self.rbs)
 
+    def _rollout_calls(self):
+        """The fused pair of the envs' model: (begin, step) of the C library."""
+        lib = self.actor._lib
+        if self.env.model == "articulated":
+            return lib.ddrl_rollout_begin_nstep_articulated, lib.ddrl_rollout_step_nstep_articulated
+        return lib.ddrl_rollout_begin_nstep, lib.ddrl_rollout_step_nstep
+
     def _fused_begin(self):
         from . import _lib
-        return self.actor._lib.ddrl_rollout_begin_nstep(self.env._h, self.actor._h, self.winq._h, _lib.stream_ptr())
+        return self._rollout_calls()[0](self.env._h, self.actor._h, self.winq._h, _lib.stream_ptr())
 
     def _fused_decided(self, ok):
         if ok:
@@ -965,16 +983,17 @@ class RolloutDeviceNStep(_RolloutWorker):
             self._out = _lib.RolloutNStepOut(act=_lib.dptr(self.act), next_obs=_lib.dptr(env.obs), ended=_lib.dptr(env.ended))
 
     def _step_fused(self):
-        """The policy phase of _step_once as the forward + ONE launch (csrc/rollout_nstep.hip); same bits as the sequence below."""
+        """The policy phase of _step_once as the forward + ONE launch (csrc/rollout_nstep.hip; on the articulated lander
+        csrc/rollout3_nstep.hip); same bits as the sequence below."""
         import ctypes
         from . import _lib
         env, opt, a = self.env, self.opt, self.actor
         rb = self.rbs[int(self.pick.choice(len(self.rbs), 1)[0])]   # replay_buffer[np.random.choice(opt.num_buffers, 1)[0]]
         self._fused_refresh()        # (observation rows and readiness bytes anew, where the unfused path has touched the env or the queues)
-        _lib.check(a._lib.ddrl_rollout_step_nstep(env._h, a._h, self.winq._h, rb._h, 1, float(getattr(opt, "act_noise", 0.0)),
-                                                  float(getattr(opt, "obs_noise", 0.0)), float(getattr(opt, "reward_scale", 1.0)),
-                                                  self.WRAPPER_REPEAT, self.limit_steps, 1 if self._learning else 0, a._noise_seed,
-                                                  a._noise_ctr, ctypes.byref(self._out), _lib.stream_ptr()))
+        _lib.check(self._rollout_calls()[1](env._h, a._h, self.winq._h, rb._h, 1, float(getattr(opt, "act_noise", 0.0)),
+                                            float(getattr(opt, "obs_noise", 0.0)), float(getattr(opt, "reward_scale", 1.0)),
+                                            self.WRAPPER_REPEAT, self.limit_steps, 1 if self._learning else 0, a._noise_seed,
+                                            a._noise_ctr, ctypes.byref(self._out), _lib.stream_ptr()))
         a._noise_ctr += env.n * a.cfg.act_dim
         if not self._learning:       # sac_ray.py:255-259, as below: the counters after this step's store decide about THIS step's episode ends
             self._learning = self.rbs[0].get_counts()[1] > opt.start_steps
@@ -998,8 +1017,9 @@ class RolloutDeviceNStep(_RolloutWorker):
         else:
             env.sample_actions(out=self.act)
             self.filling_steps += 1
-        o2, r, d, next_obs, ended = env.step_wrapped(self.act, getattr(opt, "act_noise", 0.0), getattr(opt, "obs_noise", 0.0),
-                                                     getattr(opt, "reward_scale", 1.0), self.WRAPPER_REPEAT, self.limit_steps)
+        wrapped = env.step_wrapped_articulated if env.model == "articulated" else env.step_wrapped
+        o2, r, d, next_obs, ended = wrapped(self.act, getattr(opt, "act_noise", 0.0), getattr(opt, "obs_noise", 0.0),
+                                            getattr(opt, "reward_scale", 1.0), self.WRAPPER_REPEAT, self.limit_steps)
         ready = self.winq.push(o2, self.act, r, d)
         rb = self.rbs[int(self.pick.choice(len(self.rbs), 1)[0])]   # replay_buffer[np.random.choice(opt.num_buffers, 1)[0]]
         rb.store_masked(*self.winq.arrays, ready)

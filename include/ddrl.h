@@ -25,7 +25,7 @@
  * Memory contract (tests/test_gpu_abi_memory.py holds every entry point to it, between guard bands)
  *   - an output is written exactly in its documented extent [rows, width]: every element of it, and no byte before or behind it;
  *     where a comment says an output is left untouched (a refused call, a fed plan entry's idx_d) not one byte of it changes.
- *   - an input is never written, unless its comment says so (today: act_d of ddrl_env_step_wrapped), and a result depends on the
+ *   - an input is never written, unless its comment says so (today: act_d of ddrl_env_step_wrapped and of its _articulated twin), and a result depends on the
  *     documented extent of the inputs alone — never on what lies next to them.
  *   - a *_d pointer needs the alignment of its element type (4 bytes for float32 / int32, 8 for int64 / double) and no more, unless
  *     its comment states a stricter one.  Stricter today: the [n,8] observation and [n,2] action pointers of the ddrl_env_* steps and
@@ -483,8 +483,8 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /* absent; the dynamics are this build's own Box2D-style models, validated  */
 /* against their NumPy oracles, not against Box2D ("parity unpinned").  Two models:        */
 /*   DDRL_ENV_ONE_BODY     one rigid body, two rigid leg contact points, 4 contact sweeps   */
-/*                         (oracle/env_oracle.py) — ddrl_env_create, every fused rollout    */
-/*                         launch, the wrapped step, ddrl_policy_eval and ddrl_dqn_eval;     */
+/*                         (oracle/env_oracle.py) — ddrl_env_create, every entry point     */
+/*                         without _articulated in its name, ddrl_policy_eval, ddrl_dqn_eval; */
 /*   DDRL_ENV_ARTICULATED  hull + two legs on revolute joints (limits, spring-like motor),  */
 /*                         leg-corner contacts against the terrain segments, Box2D's island */
 /*                         solve with create-time iteration counts (tests/lander3_oracle.py)*/
@@ -493,8 +493,10 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /*                         ddrl_rollout_begin_articulated / _step_articulated, the discrete */
 /*                         one behind ddrl_rollout_begin_discrete_articulated /             */
 /*                         _step_discrete_articulated, and the evaluation episodes of       */
-/*                         ddrl_env_eval_policy / ddrl_env_eval_q.  The n-step fused step   */
-/*                         and the wrapped step hold the one-body model only.               */
+/*                         ddrl_env_eval_policy / ddrl_env_eval_q, the wrapped step behind  */
+/*                         ddrl_env_step_wrapped_articulated and the n-step fused step      */
+/*                         behind ddrl_rollout_begin_nstep_articulated /                    */
+/*                         _step_nstep_articulated.  Not pinned against gym either.         */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
 
@@ -506,7 +508,9 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
  * ddrl_rollout_step_discrete return DDRL_ERR_UNSUPPORTED (reason in ddrl_last_error()) and change nothing: their kernels hold the
  * one-body model, and so do ddrl_rollout_begin_nstep / ddrl_rollout_step_nstep.  The unfused sequence (act + ddrl_env_step[_discrete]
  * + store) works on both; the continuous fused step on an articulated handle is ddrl_rollout_begin_articulated /
- * ddrl_rollout_step_articulated, the discrete one ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated. */
+ * ddrl_rollout_step_articulated, the discrete one ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated,
+ * the wrapped step ddrl_env_step_wrapped_articulated and the n-step fused step ddrl_rollout_begin_nstep_articulated /
+ * ddrl_rollout_step_nstep_articulated: every one-body entry point has its twin, and each twin refuses a one-body handle likewise. */
 #define DDRL_ENV_ONE_BODY 0
 #define DDRL_ENV_ARTICULATED 1
 typedef struct { int32_t kind, velocity_iterations, position_iterations; } ddrl_env_model_t;
@@ -543,6 +547,17 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
 int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale,
                           int32_t action_repeat, int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d,
                           float *next_obs_d, uint8_t *ended_d, void *stream);
+/* The same step on the ARTICULATED lander (an env handle of ddrl_env_create_ex, kind = DDRL_ENV_ARTICULATED): the Wrapper — action
+ * noise, the repeat loop with the dropped reward, observation noise, reward scale, the bare step at action_repeat == 1 — and the
+ * n-step rollout's bookkeeping statement for statement as ddrl_env_step_wrapped has them, around the three-body solver with the
+ * handle's iteration counts; every physics step inside the repeat is bit for bit ddrl_env_step's, the noise streams and the reset
+ * noise are the one-body step's.  Arguments, outputs, the in-place update of act_d and the alignment rules (act_d 8 bytes, obs2_d and
+ * next_obs_d 16 bytes, else DDRL_ERR_BAD_ARG naming the pointer before any launch) mean what they mean there.  On a one-body handle
+ * (use ddrl_env_step_wrapped there): DDRL_ERR_UNSUPPORTED, the function's name and the reason in ddrl_last_error(), nothing launched or
+ * written.  ddrl_env_step_wrapped keeps refusing an articulated handle. */
+int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale,
+                                      int32_t action_repeat, int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d,
+                                      float *next_obs_d, uint8_t *ended_d, void *stream);
 /* RolloutDevice.step fused: ONE vector step of worker_rollout's policy phase (example/dsac.py:96-130; SAC1 flavour
  * algos/sac1/sac1.py:177-213) for all n envs, as two launches with no host work in between:
  *   a = agent.get_action(o)  (Actor.get_action, actor_learner.py:195-197; noise element i*act+c of the counter stream
@@ -890,7 +905,8 @@ int ddrl_winq_buffers(ddrl_winq_t *h, float **arrays_h, int32_t **t_queue_h);
  * Envelope: one-body lander, obs_dim 8, act_dim 2, n_envs % 32 == 0 within the actor's max_rows (== max_rows with a version store), a
  * direct-operand actor, a float32 four-array window ring {(Ln+1)*8, Ln*2, Ln, Ln} with capacity < 2^31, a queue handle of the same
  * n_envs, Ln and dims, Ln <= DDRL_NSTEP_FUSED_MAX_LN, everything on one device.  Outside it: DDRL_ERR_UNSUPPORTED (an articulated env
- * handle, a ring or queue of another shape, n_envs, Ln) or DDRL_ERR_BAD_ARG (NULL handles, n_steps / action_repeat / limit_steps < 1)
+ * handle — its pair is ddrl_rollout_begin_nstep_articulated / ddrl_rollout_step_nstep_articulated below —, a ring or queue of another
+ * shape, n_envs, Ln) or DDRL_ERR_BAD_ARG (NULL handles, n_steps / action_repeat / limit_steps < 1)
  * with the reason in ddrl_last_error(), and nothing is changed. */
 #define DDRL_NSTEP_FUSED_MAX_LN 16
 typedef struct {
@@ -906,6 +922,25 @@ int ddrl_rollout_step_nstep(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *win
                             float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
                             int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr, const ddrl_rollout_nstep_out_t *out,
                             void *stream);
+/* The same pair on the ARTICULATED lander (an env handle of ddrl_env_create_ex, kind = DDRL_ENV_ARTICULATED): one vector step of the
+ * n-step driver's worker_rollout as the policy-forward launch and ONE launch that does, per env and in the order listed above, what
+ * ddrl_actor_act_versioned's head, ddrl_env_step_wrapped_articulated, ddrl_winq_push, ddrl_replay_store_masked_ex,
+ * ddrl_actor_versions_adopt and ddrl_winq_begin(ended) do as launches of their own, bit for bit, with the three-body solver at the
+ * handle's iteration counts inside the Wrapper's repeat loop.  Arguments, noise words, `out` and its alignment rules, n_steps, the
+ * readiness parity and the version store mean what they mean in ddrl_rollout_begin_nstep / ddrl_rollout_step_nstep; the queue handle,
+ * the window ring and ddrl_rollout_nstep_out_t are the same objects, and a queue handle may change between the two pairs' step calls
+ * only across a begin call (as between a fused and an unfused step).
+ * ddrl_rollout_begin_nstep_articulated does what ddrl_rollout_begin_nstep does (it reads the queues, not the env state): call it under
+ * the same conditions.
+ * Envelope: that of the one-body pair with an articulated handle in place of the one-body one, with the same statuses and reasons.
+ * On a one-body handle (use ddrl_rollout_begin_nstep / ddrl_rollout_step_nstep there): DDRL_ERR_UNSUPPORTED, the function's name and
+ * the reason in ddrl_last_error().  A refused call launches nothing and changes nothing.  ddrl_rollout_begin_nstep /
+ * ddrl_rollout_step_nstep keep refusing an articulated handle. */
+int ddrl_rollout_begin_nstep_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, void *stream);
+int ddrl_rollout_step_nstep_articulated(ddrl_env_t *h, ddrl_actor_t *actor, ddrl_winq_t *winq, ddrl_replay_t *window_ring, int32_t n_steps,
+                                        float act_noise, float obs_noise, float reward_scale, int32_t action_repeat, int32_t limit_steps,
+                                        int32_t adopt_at_episode_end, uint32_t noise_seed, uint64_t noise_ctr,
+                                        const ddrl_rollout_nstep_out_t *out, void *stream);
 
 /* ===================================================================================== */
 /* Counter-based noise (stands in for tf.random_normal, core.py:77, and                    */
