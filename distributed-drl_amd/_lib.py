@@ -88,6 +88,7 @@ SIGNATURES = {
     "ddrl_replay_create_ex": (c_int, [POINTER(_P), c_int, c_int64, c_int32, POINTER(c_int32), c_int64, c_int64]),
     "ddrl_replay_store_ex": (c_int, [_P, POINTER(_P), c_int64, _P]),
     "ddrl_replay_store_masked_ex": (c_int, [_P, POINTER(_P), _P, c_int64, _P]),
+    "ddrl_replay_append_ring": (c_int, [_P, _P, _P]),
     "ddrl_replay_sample_ex": (c_int, [_P, c_int64, POINTER(_P), _P, _P]),
     "ddrl_replay_sample_many": (c_int, [_P, c_int64, c_int64, POINTER(_P), _P]),
     "ddrl_replay_set_feed": (c_int, [_P, _P, c_int32, c_int32, c_int32, POINTER(_P), POINTER(c_int32), _P]),

@@ -149,6 +149,59 @@ __global__ void __launch_bounds__(256) k_store_masked(RingState *st, RingPtrs ri
 }
 
 // ------------------------------------------------------------------------------------------
+// ring append: store() of every row ring `src` holds, oldest first, into ring `dst`; then `src` is emptied.  The row count is
+// src's own `size`, read on the device: a staging ring filled by masked stores (k_store_masked, the fused n-step step's cursor
+// commit) is committed without the host ever learning how many rows it held, and a captured node follows the counts at replay.
+// grid = (blocks, n_arr), k_store's float path with a second ring in place of the flat source: source row i is
+// (src.ptr - src.size + i) mod src.capacity, rows i < size - dst.capacity are skipped as in k_store.
+// Ticket: dst's own done_counter, through ring_commit — the launch is one more store into dst, and nothing else may store into
+// dst while it runs.  Every block reads the three cursors before its ticket; the block that draws the last ticket commits dst
+// and only then zeroes src's cursor, so no block can see the emptied source.  No grid barrier, no spin.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_append_ring(RingState *st, RingPtrs ring, RingState *sst, RingPtrs sring) {
+    __shared__ long long s_c[3];
+    if (threadIdx.x == 0) { s_c[0] = st->ptr; s_c[1] = sst->ptr; s_c[2] = sst->size; }
+    __syncthreads();
+    const long long ptr = s_c[0], cap = ring.capacity, scap = sring.capacity;
+    const long long n = s_c[2];
+    const long long skip = n > cap ? n - cap : 0;
+    const int which = blockIdx.y;
+    const float *src = sring.a[which];
+    float *dst = ring.a[which];
+    const int width = ring.w[which];
+    const bool v4 = (width & 3) == 0 && aligned16(dst, src);
+    const int wv = v4 ? width >> 2 : width;
+    const long long total = (n - skip) * wv;
+    const long long base_row = (ptr + skip) % cap;                       // ring row of the first row that lands
+    const long long sbase = ((s_c[1] - n + skip) % scap + scap) % scap;  // source row of it: oldest row + skip (n <= scap, ptr < scap)
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (scap * wv < 0x7fffffffll) {   // total <= scap * wv: decided by the capacity, the count is not known where the grid is sized
+        const unsigned tot = (unsigned)total, uw = (unsigned)wv, ustride = (unsigned)stride;
+        for (unsigned e = (unsigned)t0; e < tot; e += ustride) {
+            const unsigned ri = e / uw, c = e - ri * uw;
+            long long row = base_row + ri, srow = sbase + ri;   // ri < min(cap, scap): one conditional subtraction is the modulo
+            if (row >= cap) row -= cap;
+            if (srow >= scap) srow -= scap;
+            const long long so = srow * wv + c, dof = row * wv + c;
+            if (v4) reinterpret_cast<float4 *>(dst)[dof] = reinterpret_cast<const float4 *>(src)[so];
+            else dst[dof] = src[so];
+        }
+    } else {
+        for (long long e = t0; e < total; e += stride) {
+            const long long ri = e / wv;
+            const int c = (int)(e - ri * wv);
+            const long long row = (base_row + ri) % cap, srow = (sbase + ri) % scap;
+            const long long so = srow * wv + c, dof = row * wv + c;
+            if (v4) reinterpret_cast<float4 *>(dst)[dof] = reinterpret_cast<const float4 *>(src)[so];
+            else dst[dof] = src[so];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && ring_commit(st, ring, ptr, n)) { sst->ptr = 0; sst->size = 0; }
+}
+
+// ------------------------------------------------------------------------------------------
 // MT19937 (NumPy legacy RandomState): seed == init_genrand
 // ------------------------------------------------------------------------------------------
 __global__ void k_mt_seed(RingState *st, uint32_t seed) {
@@ -625,6 +678,45 @@ int ddrl_replay_store_masked_ex(ddrl_replay_t *h, const float *const *src_h, con
     k_store_masked<<<dim3((unsigned)blocks, (unsigned)h->ring.n_arr), 256, 0, s>>>(h->state, h->ring, srcs, h->rank_buf, n);
     DDRL_LAUNCH_CHECK();
     h->h_dirty = true;
+    return DDRL_OK;
+}
+
+int ddrl_replay_append_ring(ddrl_replay_t *dst, ddrl_replay_t *src, void *stream) {
+    DDRL_REQUIRE(dst != nullptr && src != nullptr, "NULL handle");
+    const char *why = nullptr;
+    if (dst == src) why = "source and destination are the same ring";
+    else if (dst->device != src->device) why = "the two rings live on different devices";
+    else if (has_compact(dst) || has_compact(src)) why = "a compact (uint8) ring on either side is not built (commit it with ddrl_replay_store_ex)";
+    else if (dst->ring.n_arr != src->ring.n_arr) why = "the rings differ in their number of arrays";
+    for (int j = 0; !why && j < dst->ring.n_arr; ++j)
+        if (dst->ring.w[j] != src->ring.w[j]) why = "the rings differ in a row width";
+    if (why) {
+        ddrl::set_error("ddrl_replay_append_ring: %s", why);
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    ddrl::DeviceGuard g(dst->device);
+    int widest = 1;
+    for (int j = 0; j < dst->ring.n_arr; ++j) {
+        const int wv = (dst->ring.w[j] & 3) == 0 ? dst->ring.w[j] / 4 : dst->ring.w[j];
+        if (wv > widest) widest = wv;
+    }
+    // the rows src holds are counted on the device: the grid is sized for a full source (at most dst.capacity rows land) and capped;
+    // the blocks beyond the true count find nothing to copy and take their ticket.  Cap 512 (x n_arr: a full wave of workgroups on
+    // every CU), a quarter of k_store's: a block costs its ticket whether it copies or not, and here the host cannot shrink the
+    // grid for a nearly empty source (profiles/free_running_workers.txt)
+    const long long rows = src->ring.capacity > dst->ring.capacity ? dst->ring.capacity : src->ring.capacity;
+    long long blocks = (rows * widest + 255) / 256;
+    if (blocks > 512) blocks = 512;
+    if (blocks < 1) blocks = 1;
+    k_append_ring<<<dim3((unsigned)blocks, (unsigned)dst->ring.n_arr), 256, 0, ddrl::as_stream(stream)>>>(dst->state, dst->ring, src->state,
+                                                                                                         src->ring);
+    DDRL_LAUNCH_CHECK();
+    // host mirrors.  src is empty behind this launch whatever it held.  dst's new counters are on the device only; between two
+    // refreshes the mirror is asked one thing — are there rows to draw from (require_rows, ddrl_replay_can_fuse) — and an append
+    // takes none away: a ring known to hold rows needs no re-read (which would be a stream sync in front of the learner's next
+    // eager draw), an empty one re-reads before it reports EMPTY_BUFFER.  ddrl_replay_counts always reads the device.
+    src->h_ptr = src->h_size = 0;
+    if (dst->h_size <= 0) dst->h_dirty = true;
     return DDRL_OK;
 }
 

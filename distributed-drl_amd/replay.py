@@ -63,6 +63,18 @@ class _Ring:
         _lib.check(self._lib.ddrl_replay_counts(self._h, *[ctypes.byref(x) for x in c], _lib.stream_ptr()))
         return tuple(int(x.value) for x in c)  # (ptr, size, steps, sample_times)
 
+    def append_from(self, src):
+        """Commit a staging ring (ddrl_replay_append_ring): every row `src` holds, oldest first, is appended as that many store()
+        calls would, and `src` is left empty (its steps / sample_times / sampler state untouched).  How many rows that is stays on
+        the device — no host read, no sync, legal under graph capture: the commit for a ring filled by store_masked or by the fused
+        n-step rollout step.  Rings of another shape, compact rings and `src is self` raise DdrlUnsupported."""
+        order = getattr(self, "_pf_order_store", None)   # (the five-array rings: ordered against an own-stream prefetch as every store is)
+        if order:
+            order(True)
+        _lib.check(self._lib.ddrl_replay_append_ring(self._h, src._h, _lib.stream_ptr()))
+        if order:
+            order(False)
+
     def set_feed(self, plan, batch_size, regions):
         """Attach a per-update feed plan (int32 device tensor: -1 = local draw, r << 24 | i = batch i of regions[r]) to
         this ring's sampler; regions = [(packed block tensor, batches in it)].  plan=None detaches."""

@@ -675,6 +675,23 @@ class _RolloutWorker:
             self.actor.set_weights(self.keys, self.ps.pull_device(self.keys))
         return True
 
+    # -- what FreeRunningLoop asks of a worker: where its stores belong, a staging ring of that kind, how to store into it ------------
+    _free_append = False  # the commit of a staging ring: store_batch of its rows (False: every vector step stores num_envs rows, the
+                          # host knows the count) or _Ring.append_from (True: the count is in the staging ring's device state only)
+
+    def _free_target(self, trainer):
+        """The ring a segment's transitions are committed to; ValueError where this worker / trainer pair cannot free-run."""
+        return trainer.rb
+
+    def _free_staging(self, rows):
+        """An empty ring of `rows` rows, of the kind this worker's stores take."""
+        from .replay import ReplayBufferSAC1
+        return ReplayBufferSAC1(self.opt.obs_dim, self.opt.act_dim, rows)
+
+    def _free_store_into(self, ring):
+        """From the next step on the worker stores into `ring` (a staging ring, or the commit target again)."""
+        self.rb = ring
+
     def _enable_versions(self, horizon):
         """Every env on the weights held now; later pulls become versions adopted at episode ends."""
         self.actor.enable_versions(min(2048, min(self.env.n, int(horizon)) + 2))
@@ -822,6 +839,19 @@ class RolloutDeviceDQN(_RolloutWorker):
         if self.adopt == "episode":
             self._fused_ready()   # the version store starts from the initial pull, before any step
 
+    def _free_target(self, trainer):
+        if not any(rb is self.rb for node in trainer.node_buffer for rb in node):
+            raise ValueError("FreeRunningLoop: the rollout worker's ring is not one of the trainer's node_buffer rings: "
+                             "nothing would ever train on what the loop commits")
+        return self.rb
+
+    def _free_staging(self, rows):
+        import copy
+        from .replay import ReplayBufferDQN
+        o = copy.copy(self.opt)
+        o.buffer_size = int(rows)
+        return ReplayBufferDQN(o, 0, compact_obs=False)   # float32 whatever the target is: the commit's store_batch converts
+
     def _fused_eligible(self):
         from .replay import ReplayBuffer
         ok = isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
@@ -952,6 +982,32 @@ class RolloutDeviceNStep(_RolloutWorker):
         for _ in range(int(n_steps)):
             self._step_once()
 
+    _free_append = True   # a step stores a window only for the envs whose queue is full: the count is in the ring's device state
+
+    def _policy_phase(self):
+        return bool(self.filling_steps > self.opt.start_steps or getattr(self.opt, "weights_file", ""))
+
+    def _free_target(self, trainer):
+        if len(self.rbs) != 1:
+            raise ValueError("FreeRunningLoop: the n-step rollout worker must store into exactly one ring, it has %d" % len(self.rbs))
+        if not (self._policy_phase() and self._learning):
+            raise ValueError("FreeRunningLoop: the n-step rollout worker is still filling (policy phase: %s, _learning: %s) — that phase "
+                             "reads the ring's counters on the host after every step, which would be a staging ring's; fill the buffer "
+                             "with ordinary step() calls first" % (self._policy_phase(), self._learning))
+        if trainer.rb is not self.rbs[0]:
+            raise ValueError("FreeRunningLoop: the n-step rollout worker's ring is not the ring the trainer draws from")
+        return self.rbs[0]
+
+    def _free_staging(self, rows):
+        import copy
+        from .replay import ReplayBufferNStep
+        o = copy.copy(self.rbs[0].opt)   # the same Ln, shapes and num_buffers (the counter increments)
+        o.buffer_size = int(rows)
+        return ReplayBufferNStep(o)
+
+    def _free_store_into(self, ring):
+        self.rbs = [ring]
+
     def _fused_eligible(self):
         """The fused step evaluates the direct-operand forward, which is what the unfused sequence runs only with the version store on
         (get_actions_versioned; without it get_actions runs the row-major kernels, whose float32 sums are ordered differently): the
@@ -1003,7 +1059,7 @@ class RolloutDeviceNStep(_RolloutWorker):
     def _step_once(self):
         """One vector step = num_envs iterations of sac_ray.py:208-262."""
         env, opt = self.env, self.opt
-        if self._versions:
+        if self._versions and self.auto_pull:
             self.pull()              # what the server holds now is what an env ending its episode in this step would pull
         if (self.filling_steps > opt.start_steps or getattr(opt, "weights_file", "")) and self._fused_ready():
             return self._step_fused()
@@ -1029,7 +1085,7 @@ class RolloutDeviceNStep(_RolloutWorker):
             if self._learning:
                 self.actor.adopt_where_ended(ended)
         self.winq.begin(next_obs, ended)
-        if not self._versions:
+        if not self._versions and self.auto_pull:
             self.pull()
 
 
@@ -1260,21 +1316,43 @@ class FreeRunningLoop:
     (its pushes) and the commit waits for the rollout's segment.  With both segment lengths about equal in time both streams stay
     busy.  The index streams stay exactly the replay ring's own (one MT19937 draw per update, in update order); which transitions
     the ring holds at a given update is timing-free too (commits sit at fixed points of the update sequence), so a run is
-    reproducible — unlike the reference's."""
+    reproducible — unlike the reference's.
+
+    The three worker families.  The loop asks the rollout worker where its stores belong (_free_target), for a staging ring of K x
+    num_envs rows of that kind (_free_staging) and to store into one (_free_store_into); the learner half is trainer.run(n):
+      * (RolloutDevice, TrainDevice): as above; the target is the trainer's ring.
+      * (RolloutDeviceDQN, TrainDeviceDQN) — algos/dqn/train.py starts its tasks the same way: the target is the worker's ring, which
+        must be one of the trainer's node_buffer rings; staging rings are float32 ReplayBufferDQNs; trainer.run(n) with
+        updates_per_graph 0 or > 0.  The commit is store_batch, as for SAC1: every vector step stores exactly num_envs rows, so the
+        host knows the count, store_batch keeps the target's host-side counters exact (append_from leaves them to the next
+        refresh), and it is the one commit that converts into a compact (uint8) target.  TrainDeviceDQN's push goes through the
+        host, so every push_freq-th update blocks the issuing thread until the learner stream has drained: a cost in time
+        (profiles/free_running_workers.txt), never in results.
+      * (RolloutDeviceNStep, TrainDevice on a ReplayBufferNStep): the worker has exactly one ring, the trainer's, and is past its
+        filling phase (policy phase, `_learning` true — the filling phase reads the ring's counters on the host after every step;
+        fill the buffer with ordinary step() calls first).  A step stores a window only for the envs whose queue is full, so how
+        many rows a segment leaves in its staging ring is in that ring's device state only — the fused step's cursor commit and
+        the unfused store_masked leave it the same way — and the commit is append_from (ddrl_replay_append_ring): it reads the count
+        on the device and empties the staging ring.  `env_steps` counts K x num_envs per segment; the windows stored are not
+        known on the host and run() never reads them.
+    `opt.env_model = "articulated"` and the workers' fused flags are the workers' business: the loop does not look at them.
+    ValueError: a pair outside the above; a segment that does not fit the target ring."""
 
     def __init__(self, rollout, trainer, opt, steps_per_segment=64, updates_per_segment=None, timing=False, streams=None):
         import torch
-        from .replay import ReplayBufferSAC1
         self.rollout, self.trainer, self.opt = rollout, trainer, opt
         self.timing, self.marks = bool(timing), []
         self.K = int(steps_per_segment)
         self.n = int(self.K if updates_per_segment is None else updates_per_segment)
-        self.rb = trainer.rb
+        self.rb = rollout._free_target(trainer)
         n_env = int(opt.num_envs)
         self.rows = self.K * n_env
-        assert self.rows <= self.rb.max_size, "a segment's transitions must fit the replay ring"
-        self.stage = [ReplayBufferSAC1(opt.obs_dim, opt.act_dim, self.rows) for _ in range(2)]
-        self.views = [st.rings() for st in self.stage]
+        if self.rows > self.rb.max_size:
+            raise ValueError("FreeRunningLoop: a segment's transitions (%d) must fit the replay ring (%d rows)" % (self.rows, self.rb.max_size))
+        self.stage = [rollout._free_staging(self.rows) for _ in range(2)]
+        self.append = bool(rollout._free_append)
+        self.views = None if self.append else [st.rings() for st in self.stage]
+        self._auto_pull = rollout.auto_pull
         # streams=(s, s): both halves on ONE stream — the same launches in the order [pull, K vector steps, n updates, commit] per
         # segment: what the two-stream run must equal bit for bit (tests)
         # (the pair is created once per device and reused: the runtime multiplexes streams onto a handful of hardware queues —
@@ -1308,7 +1386,7 @@ class FreeRunningLoop:
                 self.ev_pull[s].record()
                 if s - 2 in self.ev_commit:
                     self.sR.wait_event(self.ev_commit.pop(s - 2))  # this staging ring's last commit has read it
-                ro.rb = self.stage[s % 2]
+                ro._free_store_into(self.stage[s % 2])
                 ro.step(self.K)
                 self.ev_roll[s] = mk() if mk else torch.cuda.Event()
                 self.ev_roll[s].record()
@@ -1324,8 +1402,11 @@ class FreeRunningLoop:
                 self.sL.wait_event(self.ev_roll.pop(s))
                 if mk:
                     m["c0"] = mk(); m["c0"].record()
-                v = self.views[s % 2]
-                self.rb.store_batch(v["obs1_buf"], v["acts_buf"], v["rews_buf"], v["obs2_buf"], v["done_buf"])
+                if self.append:
+                    self.rb.append_from(self.stage[s % 2])         # what the segment's masked stores left, counted on the device
+                else:
+                    v = self.views[s % 2]
+                    self.rb.store_batch(v["obs1_buf"], v["acts_buf"], v["rews_buf"], v["obs2_buf"], v["done_buf"])
                 self.ev_commit[s] = mk() if mk else torch.cuda.Event()
                 self.ev_commit[s].record()
                 m["c1"] = self.ev_commit[s]
@@ -1355,6 +1436,7 @@ class FreeRunningLoop:
                 "segments": len(ms)}
 
     def close(self):
-        """Back to one stream: the rollout stores into the replay ring again and looks at the server itself."""
+        """Back to one stream: the rollout stores into the replay ring again and looks at the server itself, as before the loop."""
         self.drain()
-        self.rollout.rb, self.rollout.auto_pull = self.rb, True
+        self.rollout._free_store_into(self.rb)
+        self.rollout.auto_pull = self._auto_pull

@@ -134,6 +134,17 @@ int ddrl_replay_store_ex(ddrl_replay_t *h, const float *const *src_h, int64_t n,
  * a window only for the envs whose deque is full (algos/sac1/sac_ray.py:243-246).  The row count
  * stays on the device; host-side counters are refreshed by the next ddrl_replay_counts. */
 int ddrl_replay_store_masked_ex(ddrl_replay_t *h, const float *const *src_h, const uint8_t *mask_d, int64_t n, void *stream);
+/* Commit a staging ring: append to `dst` every row `src` holds, oldest first — source rows (ptr - size + i) mod capacity, i = 0 ..
+ * size-1 — exactly as `size` sequential store() calls of those rows would (the same destination rows with the wrap of dst's cursor;
+ * with size > dst's capacity only the last capacity rows land; dst's ptr / size advance by size and steps by size * dst's own
+ * steps_inc), and then empty `src`: ptr = size = 0, its steps, sample_times, MT19937 state, feed plan and arrays untouched.
+ * src's ptr / size and dst's ptr are read ON THE DEVICE by the one launch this is: no host read, no synchronisation, legal under
+ * stream capture, and a captured node follows whatever counts the rings hold at replay — which is what a ring filled by
+ * ddrl_replay_store_masked_ex or the fused n-step rollout step needs, whose row count the host never learns.  An empty source is a
+ * no-op.  Nothing else may store into either ring while the launch runs.  Host-side counters of dst are refreshed by the next
+ * ddrl_replay_counts.  DDRL_ERR_UNSUPPORTED (reason in ddrl_last_error(), nothing launched): the rings differ in n_arrays or in a
+ * width, either one has a compact (uint8) array, dst == src, or they live on different devices. */
+int ddrl_replay_append_ring(ddrl_replay_t *dst, ddrl_replay_t *src, void *stream);
 int ddrl_replay_sample_ex(ddrl_replay_t *h, int64_t batch, float *const *out_h, int64_t *idx_d, void *stream);
 int ddrl_replay_gather_ex(ddrl_replay_t *h, const int64_t *idx_d, int64_t batch, float *const *out_h, void *stream);
 /* The index draw of sample_batch alone: idx_d[batch] = np.random.randint(0, size, batch) on the ring's stream (advances it and
