@@ -23,7 +23,16 @@ int ddrl_ps_create(ddrl_ps_t **out, int device, int64_t count) {
         delete h;
         return DDRL_ERR_NOMEM;
     }
-    DDRL_HIP_CHECK(hipMemset(h->buf, 0, (size_t)count * sizeof(float)));
+    // hipMemset of device memory only ENQUEUES on the null stream: without the sync a push on a non-blocking stream could land
+    // in front of the clear (tests/test_gpu_abi_stream.py, "a handle is ready when create returns")
+    hipError_t e = hipMemset(h->buf, 0, (size_t)count * sizeof(float));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        ddrl::set_error("clearing the parameter server failed in ddrl_ps_create: %s", hipGetErrorString(e));
+        (void)hipFree(h->buf);
+        delete h;
+        return DDRL_ERR_HIP;
+    }
     *out = h;
     return DDRL_OK;
 }

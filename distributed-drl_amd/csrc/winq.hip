@@ -96,6 +96,12 @@ int ddrl_winq_create(ddrl_winq_t **out, int device, int64_t n_envs, int32_t Ln, 
             return DDRL_ERR_NOMEM;
         }
     }
+    // the clears above are only enqueued on the null stream: the handle is usable on a non-blocking stream once they have landed
+    if (hipError_t e = hipStreamSynchronize(nullptr); e != hipSuccess) {
+        ddrl::set_error("clearing the queues failed in ddrl_winq_create: %s", hipGetErrorString(e));
+        ddrl_winq_destroy(h);
+        return DDRL_ERR_HIP;
+    }
     *out = h;
     return DDRL_OK;
 }

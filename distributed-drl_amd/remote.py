@@ -15,8 +15,13 @@ replay, learner and environments live in the same device's HBM).  Semantics kept
     device work on a HIP stream of its own (non-blocking), so a replay actor's `sample_batch` (gather + copy down) runs beside
     the learner's update instead of behind it on the shared default stream — what lets the reference's `Cache` prefetch
     (algos/sac1/sac1.py:103-130) hide the sample behind the train on the host-buffer surface.  Arguments and results cross as
-    in Ray, by value: a CUDA tensor handed to an actor is waited for (event) before the method runs, and an actor drains its
-    stream before a result that holds CUDA tensors is published.
+    in Ray, by value: a CUDA tensor handed to an actor is waited for (event) before the method runs and is recorded on the
+    actor's stream (Tensor.record_stream), so that a caller who drops it right after a fire-and-forget `.remote(...)` does not
+    get its block back from the caching allocator before the actor's stream has read it; an actor drains its stream before a
+    result that holds CUDA tensors is published, and the result is recorded on the default stream.  A result handed on to
+    another actor is an argument there and is protected the same way.  What is NOT a copy: a tensor the actor object itself
+    keeps and rewrites (ReplayBuffer.sample_batch_device without fresh=True returns the buffer's cached output block, which the
+    next draw overwrites in place) — ask for fresh tensors when a device result has to outlive the actor's next call.
 If a real Ray is present the same classes can be wrapped by `ray.remote` unchanged.
 """
 import queue
@@ -36,16 +41,21 @@ def _has_cuda(x, depth=0):
     return False
 
 
-def _record_default(x, depth=0):
-    """Device tensors an actor hands out were allocated on ITS stream; the caller most likely reads them on the default stream:
-    tell the caching allocator, so that the block is not given out again before that stream has passed the reads."""
-    import torch
+def _record_stream(x, stream=None, depth=0):
+    """Tell the caching allocator that `stream` (None: the default stream of each tensor's own device) uses the device tensors in x:
+    their blocks are not given out again before that stream has passed the work issued so far at the moment they are freed."""
     if hasattr(x, "is_cuda"):
         if x.is_cuda:
-            x.record_stream(torch.cuda.default_stream(x.device))
+            import torch
+            x.record_stream(torch.cuda.default_stream(x.device) if stream is None else stream)
     elif depth < 2:
         for v in (x.values() if isinstance(x, dict) else x if isinstance(x, (list, tuple)) else ()):
-            _record_default(v, depth + 1)
+            _record_stream(v, stream, depth + 1)
+
+
+def _record_default(x):
+    """Device tensors an actor hands out were allocated on ITS stream; the caller most likely reads them on the default stream."""
+    _record_stream(x, None)
 
 
 class _ActorMethod:
@@ -106,6 +116,8 @@ class ActorHandle:
             try:
                 if ev is not None:
                     self._stream.wait_event(ev)
+                    _record_stream(a, self._stream)      # the method's launches read them on this stream, whenever it gets there
+                    _record_stream(k, self._stream)
                 res = getattr(self._obj, name)(*a, **k)
                 if self._stream is not None and _has_cuda(res):
                     self._stream.synchronize()
@@ -113,6 +125,7 @@ class ActorHandle:
                 fut.set_result(res)
             except BaseException as e:  # noqa
                 fut.set_exception(e)
+            item = a = k = res = fut = None              # (the loop holds nobody's tensors while it waits for the next message)
 
     def __getattr__(self, name):
         if name.startswith("_"):

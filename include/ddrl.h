@@ -18,7 +18,8 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  All device work is
  *     enqueued on it; no call synchronises the device except where documented (counts /
  *     *_to_host helpers).  Inputs are borrowed until the stream reaches the enqueued work;
- *     outputs are caller-allocated; handles own all persistent device memory.
+ *     outputs are caller-allocated; handles own all persistent device memory.  A handle is ready for any stream when its
+ *     create call returns.  (tests/test_gpu_abi_stream.py holds every entry point that takes a stream to this, on a side stream.)
  *   - handles are not thread-safe (the reference's actors execute methods serially,
  *     algos/sac1/sac_ray.py:316-317); the Python actor shim serialises calls per handle.
  *
@@ -363,8 +364,9 @@ int ddrl_sac1_compute_grads_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t
  * exactly as three ddrl_normal_fill calls at noise_ctr, noise_ctr + B*act, noise_ctr + 2*B*act would, then one ddrl_sac1_step on that
  * set.  The block must have room for TWO more floats behind the n_floats: the call writes the noise counter there and the device reads
  * it from there — which is what lets the whole sequence (batch up + noise, the update's launches) replay as ONE captured graph of
- * kernel launches per (block, state-copy parity) from the second use of a block on: on this surface the host's launch calls, not the
- * device, set the rate (DDRL_HOST_GRAPH=0: always eager).  The block must stay untouched until the work issued by the call has run.
+ * kernel launches per (block, state-copy parity), captured at a key's first use and replayed from its second use on, when `stream` is
+ * a caller's stream (the null stream cannot be captured: every call on it is issued eagerly; ddrl_sac1_host_graphs counts the graphs
+ * held): on this surface the host's launch calls, not the device, set the rate (DDRL_HOST_GRAPH=0: always eager).  The block must stay untouched until the work issued by the call has run.
  * The block may be rewritten once work queued on `stream` behind this call has started (record an event after the call and wait for
  * it). */
 int ddrl_sac1_step_host(ddrl_sac1_t *h, float *block_h, int64_t n_floats, uint32_t noise_seed, uint64_t noise_ctr, float *losses_d,
@@ -397,6 +399,10 @@ int ddrl_sac1_batch(ddrl_sac1_t *h);
 /* 1 when this handle's shape runs the five-launch direct-operand update (csrc/sac1_direct.h: hidden sizes % 4 == 0 and
  * <= 512, obs + act <= 12, act <= 4), 0 on the generic 9-launch path (k_l1 / k_gemm / k_rows_* / k_adam_polyak). */
 int ddrl_sac1_is_fused(ddrl_sac1_t *h);
+/* How many captured graphs ddrl_sac1_step_host holds for this handle (one per (block, losses_d, seed, state-copy parity) it has
+ * met; at most 16, further keys run eagerly).  0 on a handle that has only seen the null stream — which cannot be captured: every
+ * call there is issued eagerly —, on the generic path, with DDRL_HOST_GRAPH=0 and for pageable blocks. */
+int ddrl_sac1_host_graphs(ddrl_sac1_t *h);
 /* Arm noise generation for the NEXT ddrl_sac1_step / compute_grads: its first kernel fills the
  * three noise buffers of the input set in use with N(0,1) from the counter generator
  * (hash(seed, counter+i), same values as ddrl_normal_fill over a flat [3][B*act] buffer); the

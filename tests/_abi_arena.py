@@ -13,7 +13,11 @@ its inputs and outputs at chosen byte offsets; the library gets raw addresses (a
 
 A case is a function fn(ctx) that builds its handles, declares its buffers through ctx.inp / ctx.out and returns the closure that makes
 the call under test; run_case drives it once on a PlainCtx and several times on ArenaCtx and collects every failed comparison before
-raising anything."""
+raising anything.  The closure hands the call ctx.stream_arg as its stream — NULL in all of these runs; run_stream_case (second half
+of this file, "S") runs the same case once more on a side stream, for the header's stream contract."""
+import contextlib
+import ctypes
+
 import numpy as np
 import torch
 
@@ -130,10 +134,34 @@ class Checks:
 
 
 class _Ctx:
-    def __init__(self, device, lib=None):
+    def __init__(self, device, lib=None, stream=None):
         self.device, self.lib = torch.device(device), lib
         self.bufs, self._keep, self._defer = {}, [], []
         self.expect_rc = 0
+        self.stream = stream       # None: the null stream (PlainCtx, ArenaCtx on the GPU); StreamCtx: the side stream of its run
+
+    @property
+    def stream_arg(self):
+        """What a closure hands the call under test as `void *stream`: NULL, the side stream's hipStream_t, or — for the CPU
+        stand-ins of tests/test_abi_table_cpu.py — the model stream itself."""
+        if self.stream is None:
+            return None
+        return ctypes.c_void_p(self.stream.cuda_stream) if hasattr(self.stream, "cuda_stream") else self.stream
+
+    def host(self, name, n, ctype):
+        """A HOST output of n elements (the *_h scalars of counts / mt_state / opt_steps / opt_state_get / env_stats): a ctypes array
+        filled with 0xA5 bytes; read when the call returns — such a call is documented to synchronise its stream — and compared
+        with the plain twin's."""
+        arr = (ctype * int(n))()
+        ctypes.memset(arr, SENT_BYTE, ctypes.sizeof(arr))
+        self.bufs[name] = dict(kind="host", arr=arr)
+        return arr
+
+    def read_host(self):
+        """Called as soon as the call under test has returned, before anything else synchronises."""
+        for b in self.bufs.values():
+            if b["kind"] == "host":
+                b["got"] = bytes(b["arr"])
 
     # -- what a case uses -------------------------------------------------------------------------------------------------------
     def tmp(self, x, dtype=None):
@@ -200,8 +228,8 @@ class ArenaCtx(_Ctx):
     sentinel.  misalign: names of the pointers to offset by one float (only those the case declares ma=True take the offset)."""
     capacity = 48 << 20
 
-    def __init__(self, device, lib=None, in_fill="nan", misalign=(), capacity=None):
-        super().__init__(device, lib)
+    def __init__(self, device, lib=None, in_fill="nan", misalign=(), capacity=None, stream=None):
+        super().__init__(device, lib, stream)
         self.arena, self.in_fill, self.misalign = Arena(device, capacity or self.capacity), in_fill, set(misalign)
         self.ma_names = []
 
@@ -244,6 +272,7 @@ def _run(fn, ctx, checks, tag):
     call = fn(ctx)
     ctx.arm()
     rc = call()
+    ctx.read_host()
     ctx.sync()
     rcs = list(rc) if isinstance(rc, (list, tuple)) else [rc]
     for v in rcs:
@@ -257,6 +286,9 @@ def _check_arena(ctx, plain, checks, tag):
         checks.add("P1", False, "%s: a guard word around `%s` was overwritten" % (tag, name))
     res = {}
     for name, b in ctx.bufs.items():
+        if b["kind"] == "host":
+            checks.add("S-sync", b["got"] == plain.bufs[name]["got"], "%s: host output `%s` differs from the plain twin's" % (tag, name))
+            continue
         r = b["r"]
         if b["kind"] == "out":
             if b["untouched"]:
@@ -299,5 +331,267 @@ def run_case(name, fn, device, lib=None, misaligned=True, capacity=None):
             for k, v in got.items():
                 checks.add("ALIGN", torch.equal(v, runs["nan"][k]), "%s: `%s` differs from the aligned run" % (tag, k))
             ctx.finish()
+    plain.finish()
+    return checks
+
+
+# ---- S: the stream contract (include/ddrl.h, "Conventions": all device work is enqueued on `stream`) ------------------------------------
+# One more arena run (`nan` fill, aligned) on a non-blocking side stream s.  Every device input is carved holding a DECOY — its own
+# elements rotated by one position: an index, mask or flag array stays in range, weights and observations stay valid values that give
+# another result — while the true value waits in a device-side staging image.  On s, in this order: a bounded GATE that holds the
+# stream, the LATE WRITES (the true value of every input over its decoy, the sentinel over every output extent), the closure called with
+# s.  Then s.synchronize() — not a device sync — and the arena is read.  P1 / P2 / P3 hold as they stand against the plain twin, and
+#     S-early  work that did not go to s ran during the gate: it read decoys and the late sentinel erased what it wrote — a sentinel is
+#              left or the output differs from the twin's, and still does once the whole device has drained
+#     S-late   work left unjoined on another stream had not landed at s.synchronize(): the same failures, gone after a device sync
+#     S-sync   a host output read behind a sync of the wrong stream is stale (ctx.host, read when the call returns)
+#     VOID     the gate, measured with events in every run, came out shorter than intended, or it held the null stream as well (streams
+#              that share a hardware queue run one behind the other: side_stream picks one that is seen to run beside the null stream,
+#              and every run checks with a marker on the null stream): the run proves nothing and fails
+# The side a run uses is an object with stream / on() / gate() / enqueue(fn) / synchronize() / drain() / measured_ms() / gate_ms:
+# TorchSide on the GPU, ModelSide for the NumPy stand-ins of tests/test_abi_table_cpu.py (a stream is a deferred queue there).
+_CYCLES_PER_MS = {}
+
+
+def cycles_per_ms(device):
+    """torch.cuda._sleep's cycles per millisecond, measured once per process with two events (a few bounded sleeps)."""
+    key = str(device)
+    if key not in _CYCLES_PER_MS:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        n, ms = 100000, 0.0
+        for _ in range(16):
+            torch.cuda.synchronize(device)
+            e0.record()
+            torch.cuda._sleep(n)
+            e1.record()
+            e1.synchronize()
+            ms = e0.elapsed_time(e1)
+            if ms >= 2.0:
+                break
+            n *= 4
+        assert ms >= 2.0, "torch.cuda._sleep(%d) took %.3f ms: no usable gate on this device" % (n, ms)
+        _CYCLES_PER_MS[key] = n / ms
+    return _CYCLES_PER_MS[key]
+
+
+def runs_beside(gated, other, device):
+    """Does work on stream `other` run while a gate holds stream `gated`?  Two non-blocking streams have no ORDER between them, but the
+    runtime maps its streams onto a few hardware queues, and two streams that share one run one behind the other: a gate on one of
+    them then holds the other as well, and whatever the gate is meant to expose waits politely.  One bounded probe (a 5 ms gate)."""
+    device = torch.device(device)
+    torch.cuda.synchronize(device)
+    end, mark = torch.cuda.Event(), torch.cuda.Event()
+    with torch.cuda.stream(gated):
+        torch.cuda._sleep(int(cycles_per_ms(device) * 5.0))
+        end.record()
+    with torch.cuda.stream(other):
+        torch.zeros(1, device=device)
+        mark.record()
+    mark.synchronize()
+    beside = not end.query()
+    torch.cuda.synchronize(device)
+    return beside
+
+
+_SIDE_STREAM = {}
+
+
+def side_stream(device):
+    """A stream of torch's pool that is seen to run beside the null stream, both ways (found once per process; at most 16 probes)."""
+    device = torch.device(device)
+    if str(device) not in _SIDE_STREAM:
+        null = torch.cuda.default_stream(device)
+        for _ in range(16):
+            s = torch.cuda.Stream(device)
+            if runs_beside(s, null, device) and runs_beside(null, s, device):
+                _SIDE_STREAM[str(device)] = s
+                break
+        else:
+            raise AssertionError("no stream of the pool runs beside the null stream on %s: the gate cannot expose anything" % device)
+    return _SIDE_STREAM[str(device)]
+
+
+class TorchSide:
+    def __init__(self, device, gate_ms):
+        self.device, self.gate_ms = torch.device(device), float(gate_ms)
+        self.cycles = int(cycles_per_ms(self.device) * self.gate_ms * 1.1)
+        self.stream = side_stream(self.device)                # torch's pool streams are non-blocking: no implicit order against NULL
+        self.e0, self.e1, self.mark = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+
+    def on(self):
+        return torch.cuda.stream(self.stream)
+
+    def gate(self):
+        self.e0.record(self.stream)
+        torch.cuda._sleep(self.cycles)
+        self.e1.record(self.stream)
+        null = torch.cuda.default_stream(self.device)         # a marker on the null stream: it must pass while the gate still holds
+        with torch.cuda.stream(null):
+            torch.zeros(1, device=self.device)
+            self.mark.record()
+
+    def beside_ms(self):
+        """How long before the gate's end the null stream's marker passed (what a launch misplaced there would have had)."""
+        return self.mark.elapsed_time(self.e1)
+
+    def enqueue(self, fn):
+        fn()                                                   # torch work issued under on() lands on the stream
+
+    def synchronize(self):
+        self.stream.synchronize()
+
+    def drain(self):
+        torch.cuda.synchronize(self.device)
+
+    def measured_ms(self):
+        return self.e0.elapsed_time(self.e1)
+
+
+class ModelDevice:
+    """The CPU model of a device: its streams are deferred queues; eager=True is the twin's device, on which everything runs at once."""
+
+    def __init__(self, eager=False):
+        self.eager, self.streams = eager, []
+
+    def new_stream(self):
+        s = ModelStream(self, not self.eager)
+        self.streams.append(s)
+        return s
+
+    def null_stream(self):
+        return ModelStream(self, False)
+
+    def synchronize(self):
+        for s in self.streams:
+            s.synchronize()
+
+
+class ModelStream:
+    def __init__(self, device, deferred):
+        self.device, self.deferred, self.q = device, deferred, []
+
+    def enqueue(self, fn):
+        if self.deferred:
+            self.q.append(fn)
+        else:
+            fn()
+
+    def synchronize(self):
+        while self.q:
+            self.q.pop(0)()
+
+
+class ModelSide:
+    def __init__(self, gate_ms=10.0, measured_ms=None):
+        self.dev = ModelDevice()
+        self.stream, self.gate_ms, self._measured = self.dev.new_stream(), gate_ms, gate_ms if measured_ms is None else measured_ms
+
+    def on(self):
+        return contextlib.nullcontext()
+
+    def gate(self):
+        pass        # whatever bypasses a deferred queue has run before the queue does: the gate is the model itself
+
+    def enqueue(self, fn):
+        self.stream.enqueue(fn)
+
+    def synchronize(self):
+        self.stream.synchronize()
+
+    def drain(self):
+        self.dev.synchronize()
+
+    def measured_ms(self):
+        return self._measured
+
+    def beside_ms(self):
+        return self._measured
+
+
+class StreamCtx(ArenaCtx):
+    """The S run.  The case's setup (fn(ctx): handles, setup calls, the carving) runs on the null stream as in every other run and
+    arm() drains the device; from the gate on everything is issued under side.on()."""
+
+    def __init__(self, device, lib, side, capacity=None):
+        super().__init__(device, lib, "nan", (), capacity, stream=side.stream)
+        self.side, self._true = side, []
+
+    def inp(self, name, x, dtype=None, ma=False, modified=False, align=256):
+        t = _as_tensor(x, dtype)
+        r = self.arena.carve(t.numel() * t.element_size(), align, 0, name, t.dtype, FILLS[self.in_fill])
+        true = t.to(self.device).reshape(-1)
+        self.arena.write(r, torch.roll(true, 1))                 # the decoy
+        self._true.append((r, true.clone()))
+        self.bufs[name] = dict(kind="in", r=r, dtype=t.dtype, modified=modified)
+        return self.arena.ptr(r)
+
+    def arm(self):
+        """pristine becomes the staging image: the true value of every input (what P3 compares with), the sentinel in every output."""
+        self.sync()
+        ar = self.arena
+        ar.arm()
+        for r, true in self._true:
+            ar.pristine[r.off:r.off + r.nbytes].copy_(true.view(torch.uint8))
+        self.sync()
+
+    def late_writes(self):
+        ar = self.arena
+        for b in self.bufs.values():
+            if b["kind"] != "host":
+                r = b["r"]
+                ar.buf[r.off:r.off + r.nbytes].copy_(ar.pristine[r.off:r.off + r.nbytes])
+
+    def image(self):
+        return self.arena.buf[:self.arena.cursor].to("cpu", copy=True)
+
+
+def _check_image(ctx, image, pristine, plain, checks, tag):
+    """_check_arena on a host image of the arena (what was there at s.synchronize(); what was there once the device had drained)."""
+    ar = ctx.arena
+    keep = ar.buf, ar.pristine
+    ar.buf, ar.pristine = image, pristine
+    try:
+        return _check_arena(ctx, plain, checks, tag)
+    finally:
+        ar.buf, ar.pristine = keep
+
+
+def run_stream_case(name, fn, device, lib, side, plain_stream=None, capacity=None):
+    """The plain twin (null stream) and ONE S run of the case on `side`.  Returns the Checks; the caller reports."""
+    checks = Checks(name)
+    plain = _run(fn, PlainCtx(device, lib, plain_stream), checks, "plain")
+    ctx = StreamCtx(device, lib, side, capacity)
+    call = fn(ctx)
+    ctx.arm()
+    pristine = ctx.arena.pristine.to("cpu", copy=True)
+    with side.on():
+        side.gate()
+        side.enqueue(ctx.late_writes)
+        rc = call()
+        ctx.read_host()
+        side.synchronize()
+        first = ctx.image()
+    side.drain()
+    drained = ctx.image()
+    for v in (list(rc) if isinstance(rc, (list, tuple)) else [rc]):
+        checks.add("RC", v is None or v == ctx.expect_rc, "S: call returned %r, expected %r" % (v, ctx.expect_rc))
+    got, want = side.measured_ms(), side.gate_ms
+    checks.add("VOID", got >= want, "S: the gate held the stream for %.2f ms, %.2f ms intended: the run is void" % (got, want))
+    got = side.beside_ms()
+    checks.add("VOID", got >= 0.5 * want, "S: the null stream passed its marker %.2f ms before the gate's end (%.2f ms intended): the gate "
+               "held the null stream too, the run is void" % (got, want))
+    c1 = Checks(name)
+    _check_image(ctx, first, pristine, plain, c1, "S")
+    checks.failed += c1.failed
+    if any(p in ("P2", "P3") for p, _ in c1.failed):
+        c2 = Checks(name)
+        _check_image(ctx, drained, pristine, plain, c2, "drained")
+        if any(p in ("P2", "P3") for p, _ in c2.failed):
+            checks.add("S-early", False, "S: the failures above remain after a device sync: work that did not go to the caller's "
+                       "stream ran during the gate (it read decoys, or the late sentinel erased its output)")
+        else:
+            checks.add("S-late", False, "S: the failures above are gone after a device sync: work left on another stream had not "
+                       "landed when the caller's stream was synchronised")
+    ctx.finish()
     plain.finish()
     return checks

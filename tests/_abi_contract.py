@@ -9,7 +9,7 @@ untouched=...) — extents as the header's comment states them, ma=True where th
 returns the closure that makes the call under test.  Where a call's effect stays inside a handle (store, import, set_state, adopt) the
 closure reads it back through the export entry of the same family into an output, so that P2 / P4 see it."""
 import ctypes
-from ctypes import byref, c_void_p as P
+from ctypes import POINTER, byref, c_double, c_int32, c_int64, c_uint32, c_uint64, c_void_p as P
 
 import numpy as np
 import torch
@@ -103,7 +103,7 @@ def _ring5(ctx, obs, act, flags=0, cap=CAP, fill=0, seed=3):
 def _export5(ctx, h, widths, cap, ma=False):
     """Closure part: the whole ring, array by array, into outputs ring0.. (ddrl_replay_rows_export)."""
     outs = [ctx.out("ring%d" % j, cap * w, F32, ma=ma) for j, w in enumerate(widths)]
-    return lambda: [ctx.lib.ddrl_replay_rows_export(h, j, 0, cap, P(p), None) for j, p in enumerate(outs)]
+    return lambda: [ctx.lib.ddrl_replay_rows_export(h, j, 0, cap, P(p), ctx.stream_arg) for j, p in enumerate(outs)]
 
 
 def _mk_store(shape, n):
@@ -114,7 +114,7 @@ def _mk_store(shape, n):
         o1, a, r, o2, d = _rows5(obs, act, n, 5, flags & 2)
         p = [ctx.inp(k, x, ma=True) for k, x in (("obs_d", o1), ("act_d", a), ("rew_d", r), ("obs2_d", o2), ("done_d", d))]
         exp = _export5(ctx, h, (obs, obs, act, 1, 1), CAP)
-        return lambda: [ctx.lib.ddrl_replay_store(h, P(p[0]), P(p[1]), P(p[2]), P(p[3]), P(p[4]), n, None)] + exp()
+        return lambda: [ctx.lib.ddrl_replay_store(h, P(p[0]), P(p[1]), P(p[2]), P(p[3]), P(p[4]), n, ctx.stream_arg)] + exp()
     return fn
 
 
@@ -132,9 +132,9 @@ def _mk_sample(shape, B, gather):
         o = [ctx.out(k, B * w, F32, ma=True) for k, w in (("obs1_d", obs), ("obs2_d", obs), ("acts_d", act), ("rews_d", 1), ("done_d", 1))]
         if gather:
             idx = ctx.inp("idx_d", _rs(B).randint(0, 37, B).astype(np.int64))
-            return lambda: L.ddrl_replay_gather(h, P(idx), B, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), None)
+            return lambda: L.ddrl_replay_gather(h, P(idx), B, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), ctx.stream_arg)
         idx = ctx.out("idx_d", B, I64)
-        return lambda: L.ddrl_replay_sample(h, B, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(idx), None)
+        return lambda: L.ddrl_replay_sample(h, B, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(idx), ctx.stream_arg)
     return fn
 
 
@@ -148,7 +148,7 @@ for _s in RING_SHAPES:
 def _sample_idx_null(ctx):
     h = _ring5(ctx, 8, 2, fill=37)
     o = [ctx.out(k, 5 * w, F32) for k, w in (("obs1_d", 8), ("obs2_d", 8), ("acts_d", 2), ("rews_d", 1), ("done_d", 1))]
-    return lambda: ctx.lib.ddrl_replay_sample(h, 5, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), None, None)
+    return lambda: ctx.lib.ddrl_replay_sample(h, 5, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), None, ctx.stream_arg)
 
 
 @case("replay_sample-empty_ring_refused", "ddrl_replay_sample")
@@ -158,21 +158,21 @@ def _sample_refused(ctx):
     ctx.expect_rc = -2
     o = [ctx.out(k, 5 * w, F32, untouched=True) for k, w in (("obs1_d", 8), ("obs2_d", 8), ("acts_d", 2), ("rews_d", 1), ("done_d", 1))]
     idx = ctx.out("idx_d", 5, I64, untouched=True)
-    return lambda: ctx.lib.ddrl_replay_sample(h, 5, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(idx), None)
+    return lambda: ctx.lib.ddrl_replay_sample(h, 5, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(idx), ctx.stream_arg)
 
 
 @case("replay_sample_indices", "ddrl_replay_sample_indices")
 def _sample_indices(ctx):
     h = _ring5(ctx, 8, 2, fill=37)
     idx = ctx.out("idx_d", 37, I64)
-    return lambda: ctx.lib.ddrl_replay_sample_indices(h, 37, P(idx), None)
+    return lambda: ctx.lib.ddrl_replay_sample_indices(h, 37, P(idx), ctx.stream_arg)
 
 
 @case("replay_take_error", "ddrl_replay_take_error")
 def _take_error(ctx):
     h = _ring5(ctx, 8, 2, fill=5)
     w = ctx.out("out_d", 1, I32)
-    return lambda: ctx.lib.ddrl_replay_take_error(h, P(w), None)
+    return lambda: ctx.lib.ddrl_replay_take_error(h, P(w), ctx.stream_arg)
 
 
 def _mk_rows(shape, imp):
@@ -184,9 +184,9 @@ def _mk_rows(shape, imp):
         if imp:
             src = ctx.inp("src_d", _rows5(obs, act, 7, 9, flags & 2)[0], ma=True)
             exp = _export5(ctx, h, (obs, obs, act, 1, 1), CAP)
-            return lambda: [L.ddrl_replay_rows_import(h, 0, 3, 7, P(src), None)] + exp()
+            return lambda: [L.ddrl_replay_rows_import(h, 0, 3, 7, P(src), ctx.stream_arg)] + exp()
         out = ctx.out("out_d", 7 * obs, F32, ma=True)
-        return lambda: L.ddrl_replay_rows_export(h, 1, 3, 7, P(out), None)
+        return lambda: L.ddrl_replay_rows_export(h, 1, 3, 7, P(out), ctx.stream_arg)
     return fn
 
 
@@ -202,7 +202,7 @@ def _mk_sample_many(shape):
         h = _ring5(ctx, obs, act, flags, fill=37)
         o = [ctx.out("out_h[%d]" % j, 3 * 5 * w, F32, ma=True) for j, w in enumerate((obs, obs, act, 1, 1))]
         arr = _ptrs(*o)
-        return lambda: ctx.lib.ddrl_replay_sample_many(h, 5, 3, arr, None)
+        return lambda: ctx.lib.ddrl_replay_sample_many(h, 5, 3, arr, ctx.stream_arg)
     return fn
 
 
@@ -245,14 +245,14 @@ def _mk_store_ex(win, n, mask):
         src = _ptrs(*[ctx.inp("src_h[%d]" % j, x, ma=True) for j, x in enumerate(_wrows(Ln, obs, n, 5))])
         exp = _export5(ctx, h, _wwidths(Ln, obs), CAP)
         if mask is None:
-            return lambda: [L.ddrl_replay_store_ex(h, src, n, None)] + exp()
+            return lambda: [L.ddrl_replay_store_ex(h, src, n, ctx.stream_arg)] + exp()
         m = np.zeros(n, np.uint8)
         if mask == "one":
             m[n // 2] = 1
         elif mask == "all":
             m[:] = 1
         md = ctx.inp("mask_d", m)
-        return lambda: [L.ddrl_replay_store_masked_ex(h, src, P(md), n, None)] + exp()
+        return lambda: [L.ddrl_replay_store_masked_ex(h, src, P(md), n, ctx.stream_arg)] + exp()
     return fn
 
 
@@ -273,16 +273,16 @@ def _mk_sample_ex(win, B, mode):
             o = _ptrs(*[ctx.out("out_h[%d]" % j, B * w, F32, ma=True) for j, w in enumerate(_wwidths(Ln, obs))])
             if mode == "gather_ex":
                 idx = ctx.inp("idx_d", _rs(B).randint(0, 37, B).astype(np.int64))
-                return lambda: L.ddrl_replay_gather_ex(h, P(idx), B, o, None)
+                return lambda: L.ddrl_replay_gather_ex(h, P(idx), B, o, ctx.stream_arg)
             idx = ctx.out("idx_d", B, I64)
-            return lambda: L.ddrl_replay_sample_ex(h, B, o, P(idx), None)
+            return lambda: L.ddrl_replay_sample_ex(h, B, o, P(idx), ctx.stream_arg)
         names = (("obs1_d", obs), ("obs2_d", obs), ("acts_d", WACT), ("rews_d", 1), ("done_d", 1))
         if mode == "sample_nstep":
             o = [ctx.out(k, B * w, F32, ma=True) for k, w in names]
             idx = ctx.out("idx_d", B, I64)
-            return lambda: L.ddrl_replay_sample_nstep(h, B, GAMMA, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(idx), None)
+            return lambda: L.ddrl_replay_sample_nstep(h, B, GAMMA, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(idx), ctx.stream_arg)
         o = _ptrs(*[ctx.out("out_h[%d]" % j, 3 * B * w, F32, ma=True) for j, (_, w) in enumerate(names)])
-        return lambda: L.ddrl_replay_sample_many_nstep(h, B, 3, GAMMA, o, None)
+        return lambda: L.ddrl_replay_sample_many_nstep(h, B, 3, GAMMA, o, ctx.stream_arg)
     return fn
 
 
@@ -301,7 +301,7 @@ def _mk_fold(win, B):
         w = [ctx.inp(k, x, ma=True) for k, x in zip(("obs_w_d", "acts_w_d", "rews_w_d", "done_w_d"), _wrows(Ln, obs, B, 11))]
         o = [ctx.out(k, B * n, F32, ma=True) for k, n in (("obs1_d", obs), ("obs2_d", obs), ("acts_d", WACT), ("rews_d", 1), ("done_d", 1))]
         return lambda: ctx.lib.ddrl_nstep_fold(P(w[0]), P(w[1]), P(w[2]), P(w[3]), B, Ln, obs, WACT, GAMMA,
-                                               P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), None)
+                                               P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), ctx.stream_arg)
     return fn
 
 
@@ -329,10 +329,10 @@ def _set_feed(ctx):
     loc_idx = ctx.out("local.idx_d", B, I64)
 
     def call():
-        rcs = [L.ddrl_replay_set_feed(h, P(plan), 2, B, 1, base, cnt, None), L.ddrl_replay_sample_ex(h, B, fed, P(fed_idx), None),
-               L.ddrl_replay_sample_ex(h, B, loc, P(loc_idx), None)]
+        rcs = [L.ddrl_replay_set_feed(h, P(plan), 2, B, 1, base, cnt, ctx.stream_arg), L.ddrl_replay_sample_ex(h, B, fed, P(fed_idx), ctx.stream_arg),
+               L.ddrl_replay_sample_ex(h, B, loc, P(loc_idx), ctx.stream_arg)]
         ctx.sync()
-        return rcs + [L.ddrl_replay_set_feed(h, None, 0, B, 0, None, None, None)]
+        return rcs + [L.ddrl_replay_set_feed(h, None, 0, B, 0, None, None, ctx.stream_arg)]
     return call
 
 
@@ -348,10 +348,10 @@ def _mk_ps(off, cnt, pull):
         _ok(ctx, L.ddrl_ps_push(h, _tp(base), 0, PS_N, None))
         if pull:
             dst = ctx.out("dst_d", cnt, F32, ma=True)
-            return lambda: L.ddrl_ps_pull(h, P(dst), off, cnt, None)
+            return lambda: L.ddrl_ps_pull(h, P(dst), off, cnt, ctx.stream_arg)
         src = ctx.inp("src_d", _f32(_rs(2).randn(cnt)), ma=True)
         allp = ctx.out("server", PS_N, F32)
-        return lambda: [L.ddrl_ps_push(h, P(src), off, cnt, None), L.ddrl_ps_pull(h, P(allp), 0, PS_N, None)]
+        return lambda: [L.ddrl_ps_push(h, P(src), off, cnt, ctx.stream_arg), L.ddrl_ps_pull(h, P(allp), 0, PS_N, ctx.stream_arg)]
     return fn
 
 
@@ -367,8 +367,8 @@ def _mk_fill(n, uniform):
     def fn(ctx):
         o = ctx.out("out_d", n, F32, ma=True)
         if uniform:
-            return lambda: ctx.lib.ddrl_uniform_fill(P(o), n, -1.0, 1.0, 7, ctr, None)
-        return lambda: ctx.lib.ddrl_normal_fill(P(o), n, 7, ctr, None)
+            return lambda: ctx.lib.ddrl_uniform_fill(P(o), n, -1.0, 1.0, 7, ctr, ctx.stream_arg)
+        return lambda: ctx.lib.ddrl_normal_fill(P(o), n, 7, ctr, ctx.stream_arg)
     return fn
 
 
@@ -427,7 +427,7 @@ def _mk_sac_step(shape, variant, grads, rows):
         per = [P(ctx.out(k, B, F32)) if rows else None for k in ("q1_d", "q2_d", "logp_pi_d")]
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in ((4,) if grads else (0, 1, 2, 3))]
         f = L.ddrl_sac1_compute_grads if grads else L.ddrl_sac1_step
-        return lambda: [f(h, *ins, losses, *per, None)] + [L.ddrl_sac1_export(h, w, p, None) for w, p in exp]
+        return lambda: [f(h, *ins, losses, *per, ctx.stream_arg)] + [L.ddrl_sac1_export(h, w, p, ctx.stream_arg) for w, p in exp]
     return fn
 
 
@@ -444,20 +444,20 @@ def _mk_sac_io(shape, variant, mode):
         h, n = _sac(ctx, shape, variant)
         if mode == "get_weights":
             o = ctx.out("flat_main_d", n, F32, ma=True)
-            return lambda: L.ddrl_sac1_get_weights(h, P(o), None)
+            return lambda: L.ddrl_sac1_get_weights(h, P(o), ctx.stream_arg)
         if mode == "set_weights":
             src = ctx.inp("flat_main_d", _weights(n, 77), ma=True)
             o = [P(ctx.out("export%d" % w, n, F32)) for w in (0, 1)]
-            return lambda: [L.ddrl_sac1_set_weights(h, P(src), None)] + [L.ddrl_sac1_export(h, w, p, None) for w, p in enumerate(o)]
+            return lambda: [L.ddrl_sac1_set_weights(h, P(src), ctx.stream_arg)] + [L.ddrl_sac1_export(h, w, p, ctx.stream_arg) for w, p in enumerate(o)]
         which = int(mode[-1])
         if mode.startswith("export"):
             ins = [_tp(ctx.tmp(x)) for _, x in _sac_batch(shape, 31)]      # one update first: moments, target and gradient are not the initial ones
             _ok(ctx, L.ddrl_sac1_step(h, *ins, _tp(ctx.tmp(np.zeros(4, np.float32))), None, None, None, None))
             o = ctx.out("flat_d", n, F32, ma=True)
-            return lambda: L.ddrl_sac1_export(h, which, P(o), None)
+            return lambda: L.ddrl_sac1_export(h, which, P(o), ctx.stream_arg)
         src = ctx.inp("flat_d", np.abs(_weights(n, 78)) if which == 3 else _weights(n, 78), ma=True)
         o = ctx.out("export", n, F32)
-        return lambda: [L.ddrl_sac1_import(h, which, P(src), None), L.ddrl_sac1_export(h, which, P(o), None)]
+        return lambda: [L.ddrl_sac1_import(h, which, P(src), ctx.stream_arg), L.ddrl_sac1_export(h, which, P(o), ctx.stream_arg)]
     return fn
 
 
@@ -486,8 +486,8 @@ def _mk_sac_step_host(shape):
             hv[off[j]:off[j] + x.size] = x.reshape(-1)
         losses = ctx.out("losses_d", 3, F32)
         exp = [P(ctx.out("export%d" % w, n, F32)) for w in (0, 2)]
-        return lambda: [L.ddrl_sac1_step_host(h, P(host.data_ptr()), span, 5, 1000, P(losses), None)] + [
-            L.ddrl_sac1_export(h, w, e, None) for w, e in zip((0, 2), exp)]
+        return lambda: [L.ddrl_sac1_step_host(h, P(host.data_ptr()), span, 5, 1000, P(losses), ctx.stream_arg)] + [
+            L.ddrl_sac1_export(h, w, e, ctx.stream_arg) for w, e in zip((0, 2), exp)]
     return fn
 
 
@@ -518,7 +518,7 @@ def _mk_actor_act(shape, n, det):
         obs = ctx.inp("obs_d", _f32(r.randn(n, o)), ma=True)
         eps = None if det else ctx.inp("eps_d", _f32(r.randn(n, a)), ma=True)
         act = ctx.out("act_d", n * a, F32, ma=True)       # the rows of act_d beyond n are guard, not extent
-        return lambda: ctx.lib.ddrl_actor_act(h, P(obs), P(eps) if eps else None, n, det, P(act), None)
+        return lambda: ctx.lib.ddrl_actor_act(h, P(obs), P(eps) if eps else None, n, det, P(act), ctx.stream_arg)
     return fn
 
 
@@ -535,7 +535,7 @@ def _mk_actor_one(shape, det):
         h, _ = _actor(ctx, shape)
         obs = ctx.inp("obs_d", _f32(_rs(4).randn(o)), ma=True)
         act = ctx.out("act_d", a, F32, ma=True)
-        return lambda: ctx.lib.ddrl_actor_act_one(h, P(obs), 9, (1 << 32) - 1, det, P(act), None)
+        return lambda: ctx.lib.ddrl_actor_act_one(h, P(obs), 9, (1 << 32) - 1, det, P(act), ctx.stream_arg)
     return fn
 
 
@@ -551,9 +551,9 @@ def _mk_actor_weights(setw):
         if setw:
             src = ctx.inp("flat_pi_d", _weights(n_pi, 79), ma=True)
             o = ctx.out("get_weights", n_pi, F32)
-            return lambda: [L.ddrl_actor_set_weights(h, P(src), None), L.ddrl_actor_get_weights(h, P(o), None)]
+            return lambda: [L.ddrl_actor_set_weights(h, P(src), ctx.stream_arg), L.ddrl_actor_get_weights(h, P(o), ctx.stream_arg)]
         o = ctx.out("flat_pi_d", n_pi, F32, ma=True)
-        return lambda: L.ddrl_actor_get_weights(h, P(o), None)
+        return lambda: L.ddrl_actor_get_weights(h, P(o), ctx.stream_arg)
     return fn
 
 
@@ -580,7 +580,7 @@ def _act_versioned(ctx):
     r = _rs(6)
     obs, eps = ctx.inp("obs_d", _f32(r.randn(MAX_ROWS, 8)), ma=True), ctx.inp("eps_d", _f32(r.randn(MAX_ROWS, 2)), ma=True)
     act = ctx.out("act_d", MAX_ROWS * 2, F32, ma=True)
-    return lambda: L.ddrl_actor_act_versioned(h, P(obs), P(eps), MAX_ROWS, 0, 1000, P(act), None)
+    return lambda: L.ddrl_actor_act_versioned(h, P(obs), P(eps), MAX_ROWS, 0, 1000, P(act), ctx.stream_arg)
 
 
 @case("actor_versions_adopt_and_state", "ddrl_actor_versions_adopt", "ddrl_actor_versions_state")
@@ -590,7 +590,7 @@ def _versions_adopt(ctx):
     e = ctx.inp("ended_d", ended)
     slots = ctx.out("slot_of_env_d", MAX_ROWS, I32)
     st = ctx.keep((ctypes.c_int32 * 4)())
-    return lambda: [L.ddrl_actor_versions_adopt(h, P(e), MAX_ROWS, None), L.ddrl_actor_versions_state(h, P(slots), st, None)]
+    return lambda: [L.ddrl_actor_versions_adopt(h, P(e), MAX_ROWS, ctx.stream_arg), L.ddrl_actor_versions_state(h, P(slots), st, ctx.stream_arg)]
 
 
 # ---- evaluation -----------------------------------------------------------------------------------------------------------------------
@@ -604,7 +604,7 @@ def _mk_policy_eval(trace):
         w = ctx.inp("pi_flat_d", _weights(n_pi, 41))
         ret, ln = ctx.out("ret_d", EPISODES, F64), ctx.out("len_d", EPISODES, I32)
         tr = ctx.out("trace_d", EPISODES * EP_LEN * 12, F32) if trace else None     # rows past an episode's end: zeros (header)
-        return lambda: ctx.lib.ddrl_policy_eval(byref(cfg), P(w), EPISODES, 5, 2, EP_LEN, P(ret), P(ln), P(tr) if tr else None, None)
+        return lambda: ctx.lib.ddrl_policy_eval(byref(cfg), P(w), EPISODES, 5, 2, EP_LEN, P(ret), P(ln), P(tr) if tr else None, ctx.stream_arg)
     return fn
 
 
@@ -654,9 +654,9 @@ def _mk_env_step(model, n, kind, present):
         outs = _env_outs(ctx, n, present)
         st = P(ctx.out("state_d", fields * n, F32))
         if kind == "wrapped":
-            return lambda: [L.ddrl_env_step_wrapped(h, P(act), 0.3, 0.1, 5.0, 2, 2, *outs, None), L.ddrl_env_get_state(h, st, None)]
+            return lambda: [L.ddrl_env_step_wrapped(h, P(act), 0.3, 0.1, 5.0, 2, 2, *outs, ctx.stream_arg), L.ddrl_env_get_state(h, st, ctx.stream_arg)]
         f = L.ddrl_env_step_discrete if kind == "discrete" else L.ddrl_env_step
-        return lambda: [f(h, P(act), *outs, None), L.ddrl_env_get_state(h, st, None)]
+        return lambda: [f(h, P(act), *outs, ctx.stream_arg), L.ddrl_env_get_state(h, st, ctx.stream_arg)]
     return fn
 
 
@@ -678,7 +678,7 @@ def _mk_env_reset(model, n, mask, obs):
         m = P(ctx.inp("mask_d", (np.arange(n) % 3 == 0).astype(np.uint8))) if mask else None
         o = P(ctx.out("obs_d", n * 8, F32)) if obs else None
         st = P(ctx.out("state_d", fields * n, F32))
-        return lambda: [L.ddrl_env_reset(h, m, o, None), L.ddrl_env_get_state(h, st, None)]
+        return lambda: [L.ddrl_env_reset(h, m, o, ctx.stream_arg), L.ddrl_env_get_state(h, st, ctx.stream_arg)]
     return fn
 
 
@@ -700,7 +700,7 @@ def _mk_env_state(model, n):
         ctx.sync()
         s = P(ctx.inp("state_d(set)", src.cpu().numpy(), ma=True))
         o = P(ctx.out("state_d(get)", fields * n, F32, ma=True))
-        return lambda: [L.ddrl_env_set_state(h, s, None), L.ddrl_env_get_state(h, o, None)]
+        return lambda: [L.ddrl_env_set_state(h, s, ctx.stream_arg), L.ddrl_env_get_state(h, o, ctx.stream_arg)]
     return fn
 
 
@@ -727,7 +727,7 @@ def _mk_rollout(model, n_steps, act_m, obs_m):
         om = P(ctx.out("next_obs_out_d", RN * 8, F32)) if obs_m else None
         st = P(ctx.out("state_d", fields * RN, F32))
         exp = _export5(ctx, ring, (8, 8, 2, 1, 1), RCAP)
-        return lambda: [step(h, a, ring, n_steps, 5, 1000, 0, am, om, None), L.ddrl_env_get_state(h, st, None)] + exp()
+        return lambda: [step(h, a, ring, n_steps, 5, 1000, 0, am, om, ctx.stream_arg), L.ddrl_env_get_state(h, st, ctx.stream_arg)] + exp()
     return fn
 
 
@@ -757,8 +757,8 @@ def _mk_rollout_nstep(n_steps, present):
         out = ctx.keep(_lib.RolloutNStepOut(*[P(ctx.out("out->" + k, RN * w, t)) if k in present else None for k, w, t in names]))
         st = P(ctx.out("state_d", fields * RN, F32))
         exp = _export5(ctx, ring, _wwidths(Ln, 8), RCAP)
-        return lambda: [L.ddrl_rollout_step_nstep(h, a, q, ring, n_steps, *args, 4000, byref(out) if present else None, None),
-                        L.ddrl_env_get_state(h, st, None)] + exp()
+        return lambda: [L.ddrl_rollout_step_nstep(h, a, q, ring, n_steps, *args, 4000, byref(out) if present else None, ctx.stream_arg),
+                        L.ddrl_env_get_state(h, st, ctx.stream_arg)] + exp()
     return fn
 
 
@@ -789,11 +789,11 @@ def _mk_winq(win, push):
                 _ok(ctx, L.ddrl_winq_push(q, *[_tp(x) for x in t], _tp(ctx.tmp(np.zeros(n, np.uint8))), None))
             ins = [P(ctx.inp(k, _f32(r.randn(n, w)))) for k, w in (("obs2_d", obs), ("act_d", WACT), ("rew_d", 1), ("done_d", 1))]
             ready = P(ctx.out("ready_d", n, U8))
-            call = lambda: L.ddrl_winq_push(q, *ins, ready, None)
+            call = lambda: L.ddrl_winq_push(q, *ins, ready, ctx.stream_arg)
         else:
             m = P(ctx.inp("mask_d", (np.arange(n) % 2).astype(np.uint8)))
             o = P(ctx.inp("obs_d", _f32(r.randn(n, obs))))
-            call = lambda: L.ddrl_winq_begin(q, m, o, None)
+            call = lambda: L.ddrl_winq_begin(q, m, o, ctx.stream_arg)
         # the queues live in the handle: the closure copies the observation windows and t_queue (int32 bits) out, device to device
         ctx.out("o_queue", n * (Ln + 1) * obs, F32)
         ctx.out("t_queue", n, F32)
@@ -852,7 +852,7 @@ def _mk_dqn_step(shape, variant, outs):
         loss = P(ctx.out("loss_d", 1, F32)) if outs else None
         q = P(ctx.out("q_d", B * A, F32)) if outs else None
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3, 4)]
-        return lambda: [L.ddrl_dqn_step(h, *ins, loss, q, None)] + [L.ddrl_dqn_export(h, w, p, None) for w, p in exp]
+        return lambda: [L.ddrl_dqn_step(h, *ins, loss, q, ctx.stream_arg)] + [L.ddrl_dqn_export(h, w, p, ctx.stream_arg) for w, p in exp]
     return fn
 
 
@@ -871,16 +871,16 @@ def _mk_dqn_io(shape, variant, mode):
         if mode == "set_weights":
             src = ctx.inp("flat_main_d", _weights(n, 80) * 0.25, ma=True)
             o = [P(ctx.out("export%d" % w, n, F32)) for w in (0, 1)]
-            return lambda: [L.ddrl_dqn_set_weights(h, P(src), None)] + [L.ddrl_dqn_export(h, w, p, None) for w, p in enumerate(o)]
+            return lambda: [L.ddrl_dqn_set_weights(h, P(src), ctx.stream_arg)] + [L.ddrl_dqn_export(h, w, p, ctx.stream_arg) for w, p in enumerate(o)]
         which = int(mode[-1])
         if mode.startswith("export"):
             ins = [_tp(ctx.tmp(x)) for _, x in _dqn_batch(shape, 61)]      # one update first: moments, target and gradient are not the initial ones
             _ok(ctx, L.ddrl_dqn_step(h, *ins, None, None, None))
             o = ctx.out("flat_d", n, F32, ma=True)
-            return lambda: L.ddrl_dqn_export(h, which, P(o), None)
+            return lambda: L.ddrl_dqn_export(h, which, P(o), ctx.stream_arg)
         src = ctx.inp("flat_d", np.abs(_weights(n, 81)) if which == 3 else _weights(n, 81), ma=True)
         o = ctx.out("export", n, F32)
-        return lambda: [L.ddrl_dqn_import(h, which, P(src), None), L.ddrl_dqn_export(h, which, P(o), None)]
+        return lambda: [L.ddrl_dqn_import(h, which, P(src), ctx.stream_arg), L.ddrl_dqn_export(h, which, P(o), ctx.stream_arg)]
     return fn
 
 
@@ -900,10 +900,10 @@ def _mk_dqn_q(shape, variant, n, act):
         obs = P(ctx.inp("obs_d", _f32(_rs(n).randn(n, o)), ma=True))
         if act is None:
             q = P(ctx.out("q_d", n * A, F32, ma=True))
-            return lambda: L.ddrl_dqn_q(h, obs, n, q, None)
+            return lambda: L.ddrl_dqn_q(h, obs, n, q, ctx.stream_arg)
         a = P(ctx.out("act_d", n, F32, ma=True))
         q = P(ctx.out("q_out_d", n * A, F32, ma=True)) if act == "q" else None
-        return lambda: L.ddrl_dqn_act(h, obs, n, 0, 0.5, 9, (1 << 32) - 2, a, q, None)
+        return lambda: L.ddrl_dqn_act(h, obs, n, 0, 0.5, 9, (1 << 32) - 2, a, q, ctx.stream_arg)
     return fn
 
 
@@ -930,7 +930,7 @@ def _mk_dqn_step_ring(outs):
         q = P(ctx.out("q_d", B * A, F32)) if outs else None
         idx = P(ctx.out("idx_out_d", B, I64)) if outs else None
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 2)]
-        return lambda: [L.ddrl_dqn_step_ring(h, ring, loss, q, idx, None)] + [L.ddrl_dqn_export(h, w, p, None) for w, p in exp]
+        return lambda: [L.ddrl_dqn_step_ring(h, ring, loss, q, idx, ctx.stream_arg)] + [L.ddrl_dqn_export(h, w, p, ctx.stream_arg) for w, p in exp]
     return fn
 
 
@@ -952,7 +952,7 @@ def _mk_dqn_loop(variant, loss):
         ld = P(ctx.out("loss_d", 1, F32)) if loss else None
         loop = _handle(ctx, L.ddrl_dqn_loop_destroy, L.ddrl_dqn_loop_create, h, ring, 2, ld)   # updates_per_graph 2: loss_d is baked into the graphs
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 2)]
-        return lambda: [L.ddrl_dqn_loop_run(loop, 5, None)] + [L.ddrl_dqn_export(h, w, p, None) for w, p in exp]
+        return lambda: [L.ddrl_dqn_loop_run(loop, 5, ctx.stream_arg)] + [L.ddrl_dqn_export(h, w, p, ctx.stream_arg) for w, p in exp]
     return fn
 
 
@@ -975,7 +975,7 @@ def _dqn_versions(ctx):
     e = ctx.inp("ended_d", ended)
     slots = ctx.out("slot_of_env_d", 64, I32)
     st = ctx.keep((ctypes.c_int32 * 4)())
-    return lambda: [L.ddrl_dqn_versions_adopt(h, P(e), 64, None), L.ddrl_dqn_versions_state(h, P(slots), st, None)]
+    return lambda: [L.ddrl_dqn_versions_adopt(h, P(e), 64, ctx.stream_arg), L.ddrl_dqn_versions_state(h, P(slots), st, ctx.stream_arg)]
 
 
 def _mk_rollout_discrete(variant, n_steps, present):
@@ -991,8 +991,8 @@ def _mk_rollout_discrete(variant, n_steps, present):
         om = P(ctx.out("next_obs_out_d", RN * 8, F32)) if "obs" in present else None
         st = P(ctx.out("state_d", fields * RN, F32))
         exp = _export5(ctx, ring, (8, 8, 1, 1, 1), RCAP)
-        return lambda: [L.ddrl_rollout_step_discrete(h, d, ring, n_steps, 0, 0.5, 5, 1000, am, qm, om, None),
-                        L.ddrl_env_get_state(h, st, None)] + exp()
+        return lambda: [L.ddrl_rollout_step_discrete(h, d, ring, n_steps, 0, 0.5, 5, 1000, am, qm, om, ctx.stream_arg),
+                        L.ddrl_env_get_state(h, st, ctx.stream_arg)] + exp()
     return fn
 
 
@@ -1014,7 +1014,7 @@ def _mk_dqn_eval(variant, mode, trace):
         ret, ln = ctx.out("ret_d", EPISODES, F64), ctx.out("len_d", EPISODES, I32)
         tr = ctx.out("trace_d", EPISODES * EP_LEN * 20, F32) if trace else None
         return lambda: ctx.lib.ddrl_dqn_eval(byref(cfg), P(w), EPISODES, 5, 2, EP_LEN, mode, 0.5, 9, 100, P(ret), P(ln),
-                                             P(tr) if tr else None, None)
+                                             P(tr) if tr else None, ctx.stream_arg)
     return fn
 
 
@@ -1036,3 +1036,515 @@ REFUSALS = [
     ("ddrl_rollout_step_nstep", "out->act"), ("ddrl_rollout_step_nstep", "out->obs2"), ("ddrl_rollout_step_nstep", "out->next_obs"),
     ("ddrl_policy_eval", "trace_d"), ("ddrl_dqn_eval", "trace_d"),
 ]
+
+
+# ---- the stream contract's rows: the functions that take `void *stream` and no caller device memory ----------------------------------
+# tests/test_gpu_abi_stream.py runs every case above AND these on a side stream (tests/_abi_arena.run_stream_case); the memory suite
+# keeps CASES.  STREAM_TABLE() = TABLE + STREAM_ROWS is what tests/test_abi_table_cpu.py parses the header's stream parameters against.
+# Each effect is read back into a declared output through the family's export entry; the *_h scalars are host outputs (ctx.host).
+#
+# A call that reads and writes handle memory only would, misplaced on another stream, simply finish during the gate: the setup settled
+# that memory before the gate, and the read-back queued on `s` behind it finds what the twin finds.  So in every closure a call on `s`
+# that does NOT COMMUTE with the call under test stands ahead of it (the "call ahead"): one that takes a declared input (a decoy until
+# the late writes) and changes the handle state the call under test reads or writes — a store into the ring it draws from, a
+# set_weights of the network it runs, a set_state of the env it reads, a winq_begin of the queue it reads — or a draw from the
+# generator it reseeds.  The call ahead waits behind the gate; a call under test that ran during the gate acted on the state from
+# before it, and the read-back differs from the twin's.
+STREAM_EXEMPT = {
+    "ddrl_comm_bcast_params": EXEMPT["ddrl_comm_bcast_params"],
+    "ddrl_comm_allreduce_grads": EXEMPT["ddrl_comm_allreduce_grads"],
+    "ddrl_comm_send_batch": EXEMPT["ddrl_comm_send_batch"],
+    "ddrl_comm_recv_batch": EXEMPT["ddrl_comm_recv_batch"],
+    "ddrl_dqn_step_timed": "profiling entry: it times the launches of ddrl_dqn_step, which has a row, between events and returns host means",
+    "ddrl_sac1_stage_time": "profiling entry: it times one launch of ddrl_sac1_step, which has a row, between events and returns a host mean",
+}
+STREAM_CASES = {}   # id -> (fn, (functions covered))
+STREAM_ROWS = {}    # function -> [case ids]
+
+
+def stream_case(cid, *functions):
+    def deco(fn):
+        assert cid not in CASES and cid not in STREAM_CASES, cid
+        STREAM_CASES[cid] = (fn, functions)
+        for f in functions:
+            STREAM_ROWS.setdefault(f, []).append(cid)
+        return fn
+    return deco
+
+
+def STREAM_TABLE():
+    t = {f: list(c) for f, c in TABLE.items()}
+    for f, c in STREAM_ROWS.items():
+        t.setdefault(f, []).extend(c)
+    return t
+
+
+def _at(arr, i=0):
+    """Element i of a ctx.host array as the pointer the binding's prototype wants."""
+    return ctypes.cast(ctypes.addressof(arr) + i * ctypes.sizeof(arr._type_), POINTER(arr._type_))
+
+
+def _counts(ctx, name, h):
+    c = ctx.host(name, 4, c_int64)
+    return lambda: ctx.lib.ddrl_replay_counts(h, _at(c, 0), _at(c, 1), _at(c, 2), _at(c, 3), ctx.stream_arg)
+
+
+def _copy_out(ctx, name, ptr, n_f32):
+    """Closure part: n_f32 32-bit words of handle-owned device memory into output `name`, device to device on the current stream."""
+    from distributed_drl_amd.replay import _view
+    ctx.tensor(name).view(F32).copy_(_view(ptr, (n_f32,), ctx.device))
+
+
+def _store_ahead(ctx, h, rows):
+    """Call ahead: ddrl_replay_store of `rows` (obs1, acts, rews, obs2, done; declared inputs) on the caller's stream."""
+    n = len(rows[2])
+    p = [P(ctx.inp("ahead.%s" % k, x)) for k, x in zip(("obs_d", "act_d", "rew_d", "obs2_d", "done_d"), rows)]
+    return lambda: ctx.lib.ddrl_replay_store(h, *p, n, ctx.stream_arg)
+
+
+def _other_state(ctx, n, model, max_ep_len, discrete=False):
+    """The state of a second env (another seed, one step taken), as the array that ddrl_env_set_state takes."""
+    h2, fields = _env(ctx, n, model, seed=8, max_ep_len=max_ep_len)
+    _env_warm(ctx, h2, n, discrete)
+    src = ctx.tmp(torch.empty(fields * n, dtype=torch.float32))
+    _ok(ctx, ctx.lib.ddrl_env_get_state(h2, _tp(src), None))
+    ctx.sync()
+    return src.cpu().numpy()
+
+
+@stream_case("replay_seed", "ddrl_replay_seed")
+def _seed(ctx):
+    """Call ahead: a draw.  A seed that ran during the gate is followed by two draws, not one."""
+    L = ctx.lib
+    h = _ring5(ctx, 8, 2, fill=37)
+    idx0, idx = ctx.out("idx0_d", 37, I64), ctx.out("idx_d", 37, I64)
+    return lambda: [L.ddrl_replay_sample_indices(h, 37, P(idx0), ctx.stream_arg), L.ddrl_replay_seed(h, 99, ctx.stream_arg),
+                    L.ddrl_replay_sample_indices(h, 37, P(idx), ctx.stream_arg)]
+
+
+@stream_case("replay_counts-behind_masked_store", "ddrl_replay_counts")
+def _counts_masked(ctx):
+    """The masked store's row count stays on the device: counts reads it behind a sync of `stream`, on which the store still waits."""
+    L, (Ln, obs), n = ctx.lib, WINDOWS["Ln3o5"], 37
+    h = _wring(ctx, Ln, obs, fill=7)
+    src = _ptrs(*[ctx.inp("src_h[%d]" % j, x) for j, x in enumerate(_wrows(Ln, obs, n, 5))])
+    md = ctx.inp("mask_d", (np.arange(n) % 3 == 0).astype(np.uint8))
+    cnt = _counts(ctx, "counts_h", h)
+    exp = _export5(ctx, h, _wwidths(Ln, obs), CAP)
+    return lambda: [L.ddrl_replay_store_masked_ex(h, src, P(md), n, ctx.stream_arg), cnt()] + exp()
+
+
+@stream_case("replay_set_counts", "ddrl_replay_set_counts", "ddrl_replay_counts")
+def _set_counts(ctx):
+    """Call ahead: a store of three rows.  Counters set during the gate are moved on by the store."""
+    L = ctx.lib
+    h = _ring5(ctx, 8, 2, fill=37)
+    ahead = _store_ahead(ctx, h, _rows5(8, 2, 3, 9, 0))
+    idx = ctx.out("idx_d", 16, I64)
+    cnt = _counts(ctx, "counts_h", h)
+    return lambda: [ahead(), L.ddrl_replay_set_counts(h, 5, 20, 100, 7, ctx.stream_arg),
+                    L.ddrl_replay_sample_indices(h, 16, P(idx), ctx.stream_arg), cnt()]
+
+
+@stream_case("replay_mt_state", "ddrl_replay_mt_state")
+def _mt_state(ctx):
+    L = ctx.lib
+    h = _ring5(ctx, 8, 2, fill=37)
+    idx = ctx.out("idx_d", 37, I64)
+    key, pos = ctx.host("key_h", 624, c_uint32), ctx.host("pos_h", 1, c_int32)
+    return lambda: [L.ddrl_replay_sample_indices(h, 37, P(idx), ctx.stream_arg), L.ddrl_replay_mt_state(h, key, _at(pos), ctx.stream_arg)]
+
+
+@stream_case("replay_append_ring", "ddrl_replay_append_ring")
+def _append_ring(ctx):
+    """45 rows in a ring of 50 take 13 more: the append wraps; the staging ring is emptied (its counts are host outputs).
+    Call ahead: the store of the staging ring's last three rows.  An append that ran during the gate moved ten rows and left three."""
+    L = ctx.lib
+    dst, src = _ring5(ctx, 8, 2, fill=45), _ring5(ctx, 8, 2, cap=16, fill=10, seed=4)
+    ahead = _store_ahead(ctx, src, _rows5(8, 2, 3, 9, 0))
+    exp = _export5(ctx, dst, (8, 8, 2, 1, 1), CAP)
+    cd, cs = _counts(ctx, "dst.counts_h", dst), _counts(ctx, "src.counts_h", src)
+    return lambda: [ahead(), L.ddrl_replay_append_ring(dst, src, ctx.stream_arg)] + exp() + [cd(), cs()]
+
+
+LSHAPE = "o8a2h64x48B37"     # SAC_SHAPES' direct-operand one
+
+
+def _sac_ring(ctx, cap=CAP, fill=37):
+    return _ring5(ctx, 8, 2, cap=cap, fill=fill)
+
+
+def _sac_sets(ctx, h):
+    L, sets = ctx.lib, []
+    for s in (0, 1):
+        b = (P * 8)()
+        _ok(ctx, L.ddrl_sac1_input_buffers(h, s, b))
+        sets.append([int(b[i]) for i in range(8)])
+    return sets
+
+
+def _mk_sac_two_phase(variant):
+    def fn(ctx):
+        L = ctx.lib
+        h, n = _sac(ctx, LSHAPE, variant)
+        ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31)]
+        losses = P(ctx.out("losses_d", 4 if variant else 3, F32))
+        exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3)]
+        s = lambda: ctx.stream_arg
+        return lambda: [L.ddrl_sac1_compute_grads(h, *ins, losses, None, None, None, s()), L.ddrl_sac1_grad_finalize(h, s()),
+                        L.ddrl_sac1_apply_grads(h, s())] + [L.ddrl_sac1_export(h, w, p, s()) for w, p in exp]
+    return fn
+
+
+stream_case("sac1_grad_finalize_apply_grads", "ddrl_sac1_grad_finalize", "ddrl_sac1_apply_grads")(_mk_sac_two_phase(0))
+stream_case("sacv_grad_finalize_apply_grads", "ddrl_sac1_grad_finalize", "ddrl_sac1_apply_grads")(_mk_sac_two_phase(1))
+
+
+@stream_case("sac1_opt_state_set_get_steps", "ddrl_sac1_opt_state_set", "ddrl_sac1_opt_state_get", "ddrl_sac1_opt_steps")
+def _opt_state(ctx):
+    """One update (the call ahead: it takes the batch and moves the counts) -> set(3, 4, ctr) -> one update (its lr_t depends on the
+    counts) -> the counts read back both ways, behind the update.  A set that ran during the gate is counted on by two updates."""
+    L = ctx.lib
+    h, n = _sac(ctx, LSHAPE)
+    ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31)]
+    losses = P(ctx.out("losses_d", 3, F32))
+    e0 = P(ctx.out("export0", n, F32))
+    t, g, c = ctx.host("opt_steps_h", 2, c_int64), ctx.host("opt_state_h", 2, c_int64), ctx.host("noise_ctr_h", 1, c_uint64)
+    s = lambda: ctx.stream_arg
+    return lambda: [L.ddrl_sac1_step(h, *ins, losses, None, None, None, s()),
+                    L.ddrl_sac1_opt_state_set(h, 3, 4, 1234, s()), L.ddrl_sac1_step(h, *ins, losses, None, None, None, s()),
+                    L.ddrl_sac1_export(h, 0, e0, s()), L.ddrl_sac1_opt_steps(h, _at(t, 0), _at(t, 1), s()),
+                    L.ddrl_sac1_opt_state_get(h, _at(g, 0), _at(g, 1), _at(c), s())]
+
+
+def _mk_sac_and_sample(mode):
+    """The learner's own input sets: set 0 holds a drawn batch (setup), the call under test updates from it while its sampler draws
+    the next batch into set 1; both sets' transition arrays and the generated noise of set 0 are copied out.
+    Calls ahead: a set_weights of the learner and a store of three rows into the ring the sampler draws from (ddrl_sac1_fill_noise
+    launches nothing: it arms the next update's first kernel)."""
+    o, a, _, _, B = SAC_SHAPES[LSHAPE]
+
+    def fn(ctx):
+        L = ctx.lib
+        h, n = _sac(ctx, LSHAPE)
+        ring = _sac_ring(ctx)
+        sets = _sac_sets(ctx, h)
+        _ok(ctx, L.ddrl_replay_sample(ring, B, *[P(x) for x in sets[0][:5]], None, None))
+        flat, store = P(ctx.inp("ahead.flat_d", _weights(n, 23))), _store_ahead(ctx, ring, _rows5(8, 2, 3, 9, 0))
+        # (the two fused entries take no losses pointer: the loss words stay in the handle)
+        losses = P(ctx.out("losses_d", 3, F32)) if mode == "apply_grads_and_sample" else None
+        exp =[(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 2)]
+        widths = (o, o, a, 1, 1, a, a, a)
+        for k in (0, 1):
+            for j in range(8 if k == 0 else 5):
+                ctx.out("set%d[%d]" % (k, j), B * widths[j], F32)
+        s = lambda: ctx.stream_arg
+
+        def call():
+            ahead = [L.ddrl_sac1_set_weights(h, flat, s()), store()]
+            if mode == "step_and_sample":
+                rc = [L.ddrl_sac1_fill_noise(h, 11, s()), L.ddrl_sac1_step_and_sample(h, 0, ring, 1, s())]
+            elif mode == "compute_grads_and_sample":
+                rc = [L.ddrl_sac1_fill_noise(h, 11, s()), L.ddrl_sac1_compute_grads_and_sample(h, 0, ring, 1, s()),
+                      L.ddrl_sac1_grad_finalize(h, s()), L.ddrl_sac1_apply_grads(h, s())]
+            else:
+                rc = [L.ddrl_sac1_fill_noise(h, 11, s()),
+                      L.ddrl_sac1_compute_grads(h, *[P(x) for x in sets[0]], losses, None, None, None, s()),
+                      L.ddrl_sac1_apply_grads_and_sample(h, ring, 1, s())]
+            rc = ahead + rc + [L.ddrl_sac1_export(h, w, p, s()) for w, p in exp]
+            for k in (0, 1):
+                for j in range(8 if k == 0 else 5):
+                    _copy_out(ctx, "set%d[%d]" % (k, j), sets[k][j], B * widths[j])
+            return rc
+        return call
+    return fn
+
+
+for _m, _f in (("step_and_sample", ("ddrl_sac1_step_and_sample", "ddrl_sac1_fill_noise")),
+               ("compute_grads_and_sample", ("ddrl_sac1_compute_grads_and_sample", "ddrl_sac1_fill_noise")),
+               ("apply_grads_and_sample", ("ddrl_sac1_apply_grads_and_sample", "ddrl_sac1_fill_noise"))):
+    stream_case("sac1_%s" % _m, *_f)(_mk_sac_and_sample(_m))
+
+
+@stream_case("sac1_graph_sync", "ddrl_sac1_graph_sync")
+def _graph_sync(ctx):
+    """One update leaves the double-buffered optimizer state on copy 1; graph_sync puts it back on copy 0 (a copy node on `stream`);
+    the update behind it continues from there."""
+    L = ctx.lib
+    h, n = _sac(ctx, LSHAPE)
+    ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31)]
+    losses = P(ctx.out("losses_d", 3, F32))
+    exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3)]
+    s = lambda: ctx.stream_arg
+    return lambda: [L.ddrl_sac1_step(h, *ins, losses, None, None, None, s()), L.ddrl_sac1_graph_sync(h, s()),
+                    L.ddrl_sac1_step(h, *ins, losses, None, None, None, s())] + [L.ddrl_sac1_export(h, w, p, s()) for w, p in exp]
+
+
+LOOP_ROWS = 64
+
+
+def _mk_loop_run(per_graph):
+    """Two calls: per_graph - 1 updates (below the capture threshold: eager), then 2 per_graph + 1 (one eager update, the capture, replays).
+    Calls ahead: a set_weights of the learner and a store of three rows into the ring the loop draws from."""
+    def fn(ctx):
+        L = ctx.lib
+        h, n = _sac(ctx, LSHAPE)
+        ring = _sac_ring(ctx, cap=LOOP_ROWS, fill=LOOP_ROWS)
+        flat, store = P(ctx.inp("ahead.flat_d", _weights(n, 23))), _store_ahead(ctx, ring, _rows5(8, 2, 3, 9, 0))
+        loop = _handle(ctx, L.ddrl_loop_destroy, L.ddrl_loop_create, h, ring, per_graph, 13)
+        exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3)]
+        t = ctx.host("opt_steps_h", 2, c_int64)
+        cnt = _counts(ctx, "counts_h", ring)
+        s = lambda: ctx.stream_arg
+        return lambda: [L.ddrl_sac1_set_weights(h, flat, s()), store(), L.ddrl_loop_run(loop, per_graph - 1, s()),
+                        L.ddrl_loop_run(loop, 2 * per_graph + 1, s())] + [
+            L.ddrl_sac1_export(h, w, p, s()) for w, p in exp] + [L.ddrl_sac1_opt_steps(h, _at(t, 0), _at(t, 1), s()), cnt()]
+    return fn
+
+
+def _mk_dqn_loop_run(per_graph):
+    shape = "o8A2h64x48B37"
+    o, A, _, _, B = DQN_SHAPES[shape]
+
+    def fn(ctx):
+        L = ctx.lib
+        h, n, _ = _dqn(ctx, shape, 0)
+        ring = _ring5(ctx, o, 1, 0, cap=LOOP_ROWS, fill=0)
+        r = _rs(72)
+        rows = [_f32(r.randn(LOOP_ROWS, o)), _f32(r.randint(0, A, (LOOP_ROWS, 1))), _f32(r.randn(LOOP_ROWS)), _f32(r.randn(LOOP_ROWS, o)),
+                _f32(r.rand(LOOP_ROWS) < 0.2)]
+        _ok(ctx, L.ddrl_replay_store(ring, *[_tp(ctx.tmp(x)) for x in rows], LOOP_ROWS, None))
+        flat = P(ctx.inp("ahead.flat_d", _weights(n, 57) * 0.25))
+        store = _store_ahead(ctx, ring, [_f32(r.randn(3, o)), _f32(r.randint(0, A, (3, 1))), _f32(r.randn(3)), _f32(r.randn(3, o)),
+                                         _f32(r.rand(3) < 0.2)])
+        ld = P(ctx.out("loss_d", 1, F32))
+        loop = _handle(ctx, L.ddrl_dqn_loop_destroy, L.ddrl_dqn_loop_create, h, ring, per_graph, ld)
+        exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3)]
+        cnt = _counts(ctx, "counts_h", ring)
+        s = lambda: ctx.stream_arg
+        return lambda: [L.ddrl_dqn_set_weights(h, flat, s()), store(), L.ddrl_dqn_loop_run(loop, per_graph - 1, s()),
+                        L.ddrl_dqn_loop_run(loop, 2 * per_graph + 1, s())] + [
+            L.ddrl_dqn_export(h, w, p, s()) for w, p in exp] + [cnt()]
+    return fn
+
+
+for _pg in (2, 3):
+    stream_case("loop_run-per_graph%d" % _pg, "ddrl_loop_run")(_mk_loop_run(_pg))
+    stream_case("dqn_loop_run-per_graph%d" % _pg, "ddrl_dqn_loop_run")(_mk_dqn_loop_run(_pg))
+
+
+@stream_case("actor_versions_enable", "ddrl_actor_versions_enable")
+def _actor_enable(ctx):
+    """A set_weights (the call ahead: what enable keeps as the first version) -> enable -> a second install -> three envs adopt it:
+    the slot words and the action of every env against its version."""
+    L = ctx.lib
+    h, n_pi = _actor(ctx)
+    src0 = P(ctx.inp("ahead.flat_pi_d", _weights(n_pi, 44)))
+    src = P(ctx.inp("flat_pi_d", _weights(n_pi, 43)))
+    ended = np.zeros(MAX_ROWS, np.uint8)
+    ended[[0, 3, 40]] = 1
+    e = P(ctx.inp("ended_d", ended))
+    r = _rs(6)
+    obs, eps = P(ctx.inp("obs_d", _f32(r.randn(MAX_ROWS, 8)))), P(ctx.inp("eps_d", _f32(r.randn(MAX_ROWS, 2))))
+    slots, act = P(ctx.out("slot_of_env_d", MAX_ROWS, I32)), P(ctx.out("act_d", MAX_ROWS * 2, F32))
+    st = ctx.host("state_h", 4, c_int32)
+    s = lambda: ctx.stream_arg
+    return lambda: [L.ddrl_actor_set_weights(h, src0, s()), L.ddrl_actor_versions_enable(h, 8, s()), L.ddrl_actor_set_weights(h, src, s()),
+                    L.ddrl_actor_versions_adopt(h, e, MAX_ROWS, s()), L.ddrl_actor_act_versioned(h, obs, eps, MAX_ROWS, 0, 1000, act, s()),
+                    L.ddrl_actor_versions_state(h, slots, st, s())]
+
+
+@stream_case("dqn_versions_enable", "ddrl_dqn_versions_enable")
+def _dqn_enable(ctx):
+    """_actor_enable's on the Q network; the Q values of every env against its version come out of one fused rollout step (the only
+    versioned forward of this family)."""
+    L = ctx.lib
+    h, n, _ = _dqn(ctx, DSHAPE)
+    env, _ = _env(ctx, RN, "one_body", max_ep_len=3)
+    ring = _ring5(ctx, 8, 1, cap=RCAP, fill=7)
+    src0 = P(ctx.inp("ahead.flat_main_d", _weights(n, 54) * 0.25))
+    src = P(ctx.inp("flat_main_d", _weights(n, 53) * 0.25))
+    ended = np.zeros(RN, np.uint8)
+    ended[[0, 3, 40]] = 1
+    e = P(ctx.inp("ended_d", ended))
+    slots = P(ctx.out("slot_of_env_d", RN, I32))
+    am, qm = P(ctx.out("act_out_d", RN, F32)), P(ctx.out("q_out_d", RN * 4, F32))
+    st = ctx.host("state_h", 4, c_int32)
+    s = lambda: ctx.stream_arg
+    return lambda: [L.ddrl_dqn_set_weights(h, src0, s()), L.ddrl_dqn_versions_enable(h, 8, s()), L.ddrl_dqn_set_weights(h, src, s()),
+                    L.ddrl_dqn_versions_adopt(h, e, RN, s()), L.ddrl_rollout_begin_discrete(env, h, s()),
+                    L.ddrl_rollout_step_discrete(env, h, ring, 1, 0, 0.5, 5, 1000, am, qm, None, s()),
+                    L.ddrl_dqn_versions_state(h, slots, st, s())]
+
+
+def _mk_rollout_begin(model):
+    """Two fused steps, then a step outside the fused path: the actor's rows are stale, the begin call under test refreshes them and
+    the fused step behind it acts on what it copied.  Call ahead: a set_state with the state of another env; a begin that ran during
+    the gate copied the observations of the state before it."""
+    def fn(ctx):
+        L = ctx.lib
+        h, fields = _env(ctx, RN, model, max_ep_len=3)
+        ahead = P(ctx.inp("ahead.state_d", _other_state(ctx, RN, model, 3)))
+        a, _ = _actor(ctx)
+        ring = _ring5(ctx, 8, 2, cap=RCAP, fill=7)
+        begin, step = ((L.ddrl_rollout_begin_articulated, L.ddrl_rollout_step_articulated) if model == "articulated"
+                       else (L.ddrl_rollout_begin, L.ddrl_rollout_step))
+        _ok(ctx, begin(h, a, None))
+        _ok(ctx, step(h, a, ring, 2, 5, 0, 0, None, None, None))
+        _env_warm(ctx, h, RN)
+        am, om = P(ctx.out("act_out_d", RN * 2, F32)), P(ctx.out("next_obs_out_d", RN * 8, F32))
+        st = P(ctx.out("state_d", fields * RN, F32))
+        exp = _export5(ctx, ring, (8, 8, 2, 1, 1), RCAP)
+        s = lambda: ctx.stream_arg
+        return lambda: [L.ddrl_env_set_state(h, ahead, s()), begin(h, a, s()), step(h, a, ring, 1, 5, 1000, 0, am, om, s()),
+                        L.ddrl_env_get_state(h, st, s())] + exp()
+    return fn
+
+
+stream_case("rollout_begin", "ddrl_rollout_begin")(_mk_rollout_begin("one_body"))
+stream_case("rollout_begin_articulated", "ddrl_rollout_begin_articulated")(_mk_rollout_begin("articulated"))
+
+
+def _mk_rollout_begin_discrete(model):
+    """The discrete pair likewise, the set_state ahead included.  The articulated pair takes handles only: its mirrors live in the env
+    handle and are copied out."""
+    artic = model == "articulated"
+
+    def fn(ctx):
+        L = ctx.lib
+        h, fields = _env(ctx, RN, model, max_ep_len=3)
+        ahead = P(ctx.inp("ahead.state_d", _other_state(ctx, RN, model, 3, discrete=True)))
+        d, _, _ = _dqn(ctx, DSHAPE)
+        ring = _ring5(ctx, 8, 1, cap=RCAP, fill=7)
+        s = lambda: ctx.stream_arg
+        st = P(ctx.out("state_d", fields * RN, F32))
+        if artic:
+            begin, step = L.ddrl_rollout_begin_discrete_articulated, L.ddrl_rollout_step_discrete_articulated
+            _ok(ctx, begin(h, d, None))
+            _ok(ctx, step(h, d, ring, 2, 0, 0.5, 5, 0, None))
+            mir = [P(), P(), P()]
+            _ok(ctx, L.ddrl_env_rollout_mirrors(h, byref(mir[0]), byref(mir[1]), byref(mir[2]), None, None))
+            sizes = (("act_mirror", RN), ("q_mirror", RN * 4), ("next_obs_mirror", RN * 8))
+            for k, w in sizes:
+                ctx.out(k, w, F32)
+        else:
+            begin, step = L.ddrl_rollout_begin_discrete, L.ddrl_rollout_step_discrete
+            _ok(ctx, begin(h, d, None))
+            _ok(ctx, step(h, d, ring, 2, 0, 0.5, 5, 0, None, None, None, None))
+            am, qm, om = P(ctx.out("act_out_d", RN, F32)), P(ctx.out("q_out_d", RN * 4, F32)), P(ctx.out("next_obs_out_d", RN * 8, F32))
+        _env_warm(ctx, h, RN, discrete=True)
+        exp = _export5(ctx, ring, (8, 8, 1, 1, 1), RCAP)
+
+        def call():
+            if artic:
+                rc = [L.ddrl_env_set_state(h, ahead, s()), begin(h, d, s()), step(h, d, ring, 1, 0, 0.5, 5, 1000, s()),
+                      L.ddrl_env_get_state(h, st, s())] + exp()
+                for (k, w), p in zip(sizes, mir):
+                    _copy_out(ctx, k, p.value, w)
+                return rc
+            return [L.ddrl_env_set_state(h, ahead, s()), begin(h, d, s()), step(h, d, ring, 1, 0, 0.5, 5, 1000, am, qm, om, s()),
+                    L.ddrl_env_get_state(h, st, s())] + exp()
+        return call
+    return fn
+
+
+stream_case("rollout_begin_discrete", "ddrl_rollout_begin_discrete")(_mk_rollout_begin_discrete("one_body"))
+stream_case("rollout_discrete_articulated", "ddrl_rollout_begin_discrete_articulated",
+            "ddrl_rollout_step_discrete_articulated")(_mk_rollout_begin_discrete("articulated"))
+
+
+def _mk_rollout_begin_nstep(model):
+    """_mk_rollout_nstep's setup, then reset + winq_begin outside the fused path: the actor's rows and the readiness bytes are stale and
+    the begin call under test rebuilds them; the fused step behind it shows what it wrote.  Call ahead: a winq_begin with other
+    observations (the begin launch reads the queues only); a begin that ran during the gate copied the rows from before it."""
+    Ln, artic = 4, model == "articulated"
+
+    def fn(ctx):
+        from distributed_drl_amd import _lib
+        L = ctx.lib
+        h, fields = _env(ctx, RN, model, max_ep_len=1 << 20)
+        a, _ = _actor(ctx)
+        ring = _wring(ctx, Ln, 8, cap=RCAP)
+        q = _handle(ctx, L.ddrl_winq_destroy, L.ddrl_winq_create, _dev(ctx), RN, Ln, 8, 2, 1)
+        begin, step = ((L.ddrl_rollout_begin_nstep_articulated, L.ddrl_rollout_step_nstep_articulated) if artic
+                       else (L.ddrl_rollout_begin_nstep, L.ddrl_rollout_step_nstep))
+        obs = ctx.tmp(torch.empty(RN * 8, dtype=torch.float32))
+        args = (0.3, 0.1, 5.0, 2, 3, 0, 5)
+        _ok(ctx, L.ddrl_env_reset(h, None, _tp(obs), None))
+        _ok(ctx, L.ddrl_winq_begin(q, None, _tp(obs), None))
+        _ok(ctx, begin(h, a, q, None))
+        _ok(ctx, step(h, a, q, ring, 4, *args, 0, None, None))
+        _ok(ctx, L.ddrl_env_reset(h, None, _tp(obs), None))
+        _ok(ctx, L.ddrl_winq_begin(q, None, _tp(obs), None))
+        ahead = P(ctx.inp("ahead.obs_d", _f32(_rs(12).randn(RN, 8))))
+        names = (("act", 2, F32), ("obs2", 8, F32), ("rew", 1, F32), ("done", 1, F32), ("next_obs", 8, F32), ("ended", 1, U8))
+        out = ctx.keep(_lib.RolloutNStepOut(*[P(ctx.out("out->" + k, RN * w, t)) for k, w, t in names]))
+        st = P(ctx.out("state_d", fields * RN, F32))
+        exp = _export5(ctx, ring, _wwidths(Ln, 8), RCAP)
+        s = lambda: ctx.stream_arg
+        return lambda: [L.ddrl_winq_begin(q, None, ahead, s()), begin(h, a, q, s()), step(h, a, q, ring, 1, *args, 4000, byref(out), s()),
+                        L.ddrl_env_get_state(h, st, s())] + exp()
+    return fn
+
+
+stream_case("rollout_begin_nstep", "ddrl_rollout_begin_nstep")(_mk_rollout_begin_nstep("one_body"))
+stream_case("rollout_begin_nstep_articulated", "ddrl_rollout_begin_nstep_articulated")(_mk_rollout_begin_nstep("articulated"))
+
+
+def _mk_env_stats(model):
+    """max_ep_len 2 and one step taken: the step under test ends every episode at the limit; the statistics are read behind it."""
+    n = 33
+
+    def fn(ctx):
+        L = ctx.lib
+        h, _ = _env(ctx, n, model)
+        _env_warm(ctx, h, n)
+        act = P(ctx.inp("act_d", _f32(_rs(2).uniform(-1.2, 1.2, (n, 2)))))
+        rew = P(ctx.out("rew_d", n, F32))
+        ep, ret, ln = ctx.host("episodes_h", 1, c_int64), ctx.host("ret_sum_h", 1, c_double), ctx.host("len_sum_h", 1, c_int64)
+        s = lambda: ctx.stream_arg
+        return lambda: [L.ddrl_env_step(h, act, None, rew, None, None, None, s()), L.ddrl_env_stats(h, _at(ep), _at(ret), _at(ln), s())]
+    return fn
+
+
+for _m in MODELS:
+    stream_case("env_stats-%s" % _m, "ddrl_env_stats")(_mk_env_stats(_m))
+
+
+def _mk_env_eval(model, discrete):
+    """The evaluation entries fed from handles: the results live in a block of the env handle (ddrl_env_eval_results) and are copied
+    out.  A first evaluation of the same size (setup) has allocated that block, so that the call under test only launches.
+    Call ahead: a set_weights of the network that the episodes are played with."""
+    row = 20 if discrete else 12
+
+    def fn(ctx):
+        L = ctx.lib
+        h, _ = _env(ctx, 1, model, seed=5, max_ep_len=EP_LEN)
+        src, n, _ = _dqn(ctx, DSHAPE) if discrete else _actor(ctx) + (None,)
+        flat = P(ctx.inp("ahead.flat_d", _weights(n, 58) * (0.25 if discrete else 1.0)))
+        setw = L.ddrl_dqn_set_weights if discrete else L.ddrl_actor_set_weights
+        s = lambda: ctx.stream_arg
+        if discrete:
+            ev = lambda first, st: L.ddrl_env_eval_q(h, src, EPISODES, first, 0, 0.5, 9, 100, 1, st)
+        else:
+            ev = lambda first, st: L.ddrl_env_eval_policy(h, src, EPISODES, first, 1, st)
+        _ok(ctx, ev(0, None))
+        ctx.out("ret", EPISODES, F64), ctx.out("len", EPISODES, I32), ctx.out("trace", EPISODES * EP_LEN * row, F32)
+
+        def call():
+            rc = [setw(src, flat, s()), ev(2, s())]
+            ret, ln, tr = P(), P(), P()
+            ne, ml, tw = c_int32(), c_int32(), c_int32()
+            _ok(ctx, L.ddrl_env_eval_results(h, byref(ret), byref(ln), byref(tr), byref(ne), byref(ml), byref(tw)))
+            assert (ne.value, ml.value, tw.value) == (EPISODES, EP_LEN, row), (ne.value, ml.value, tw.value)
+            _copy_out(ctx, "ret", ret.value, 2 * EPISODES)
+            _copy_out(ctx, "len", ln.value, EPISODES)
+            _copy_out(ctx, "trace", tr.value, EPISODES * EP_LEN * row)
+            return rc
+        return call
+    return fn
+
+
+for _m in MODELS:
+    stream_case("env_eval_policy-%s" % _m, "ddrl_env_eval_policy")(_mk_env_eval(_m, False))
+    stream_case("env_eval_q-%s" % _m, "ddrl_env_eval_q")(_mk_env_eval(_m, True))

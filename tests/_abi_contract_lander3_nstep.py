@@ -5,9 +5,11 @@ tests/test_gpu_abi_lander3_nstep.py runs them between guard bands (tests/_abi_ar
 parametrisation over _abi_contract.CASES does not depend on whether this module has been imported.
 The ROWS are different: importing this module enters them in _abi_contract.TABLE, the one table tests/test_abi_table_cpu.py parses the
 header against.  _abi_contract.py itself holds no row for the two functions, so that check finds them only once this module has been
-imported — which every collection of the suite does (tests/test_gpu_abi_lander3_nstep.py and tests/test_lander3_wrapped_cpu.py import
-it), while tests/test_abi_table_cpu.py collected on its own reports the two functions as uncovered.
-tests/test_lander3_wrapped_cpu.py repeats the header check with this module imported, whatever else was collected."""
+imported — which every collection of the suite does (tests/test_gpu_abi_lander3_nstep.py, tests/test_lander3_wrapped_cpu.py and, for
+the stream table, tests/test_abi_table_cpu.py itself import it).
+tests/test_lander3_wrapped_cpu.py repeats the header check with this module imported, whatever else was collected.
+The closures hand the call under test ctx.stream_arg: tests/test_gpu_abi_stream.py runs these cases on a side stream as well; the
+stream row of ddrl_rollout_begin_nstep_articulated stands with the other begin calls' in _abi_contract.STREAM_CASES."""
 from ctypes import byref, c_void_p as P
 
 import torch
@@ -41,7 +43,7 @@ def _mk_env_step_wrapped(n, present):
         act = ctx.inp("act_d", ac._f32(ac._rs(2).uniform(-1.2, 1.2, (n, 2))), modified=True)
         outs = ac._env_outs(ctx, n, present)
         st = P(ctx.out("state_d", fields * n, F32))
-        return lambda: [L.ddrl_env_step_wrapped_articulated(h, P(act), 0.3, 0.1, 5.0, 2, 2, *outs, None), L.ddrl_env_get_state(h, st, None)]
+        return lambda: [L.ddrl_env_step_wrapped_articulated(h, P(act), 0.3, 0.1, 5.0, 2, 2, *outs, ctx.stream_arg), L.ddrl_env_get_state(h, st, ctx.stream_arg)]
     return fn
 
 
@@ -72,8 +74,8 @@ def _mk_rollout_nstep(n_steps, present):
         out = ctx.keep(_lib.RolloutNStepOut(*[P(ctx.out("out->" + k, ac.RN * w, t)) if k in present else None for k, w, t in names]))
         st = P(ctx.out("state_d", fields * ac.RN, F32))
         exp = ac._export5(ctx, ring, ac._wwidths(Ln, 8), ac.RCAP)
-        return lambda: [L.ddrl_rollout_step_nstep_articulated(h, a, q, ring, n_steps, *args, 4000, byref(out) if present else None, None),
-                        L.ddrl_env_get_state(h, st, None)] + exp()
+        return lambda: [L.ddrl_rollout_step_nstep_articulated(h, a, q, ring, n_steps, *args, 4000, byref(out) if present else None, ctx.stream_arg),
+                        L.ddrl_env_get_state(h, st, ctx.stream_arg)] + exp()
     return fn
 
 
