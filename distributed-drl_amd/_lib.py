@@ -26,6 +26,8 @@ DDRL_ENV_STATE_FIELDS = 32
 DDRL_NSTEP_FUSED_MAX_LN = 16   # include/ddrl.h: the fused n-step rollout step stages a workgroup's windows in LDS
 DDRL_ENV3_STATE_FIELDS = 66   # the articulated model's block (ddrl_env_state_fields tells which a handle holds)
 DDRL_ENV_ONE_BODY, DDRL_ENV_ARTICULATED = 0, 1   # ddrl_env_model_t.kind
+DDRL_ENV_WALKER = 3                              # ... the bipedal walker ([n,24] observations, [n,4] actions); 2 is not a model
+DDRL_ENVW_STATE_FIELDS = 286                     # its block: bodies, joint and contact impulses, bookkeeping, 200 terrain heights
 SAC1_STAGES = 12
 DQN_STAGES = 9   # include/ddrl.h: DDRL_DQN_STAGES
 SAC1_MAIN, SAC1_TARGET, SAC1_ADAM_M, SAC1_ADAM_V, SAC1_GRAD = range(5)

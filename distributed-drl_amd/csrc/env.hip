@@ -417,6 +417,10 @@ __global__ void __launch_bounds__(256) k_env_obs(float *S, long long n, uint32_t
 int ddrl_env3_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
 int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d,
                           float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+// the walker's launches (walker.hip): [n,24] observations, [n,4] actions
+int ddrl_walker_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
+int ddrl_walker_launch_step(float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d,
+                            float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
 
 // Memory contract (include/ddrl.h): the env family's kernels move an observation row as two float4 and a continuous action row as one
 // float2, so caller pointers to [n,8] observations must be 16-byte aligned and to [n,2] actions 8-byte aligned.  Checked here, before
@@ -427,6 +431,7 @@ int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, in
 // the entry points whose kernels hold the one-body model refuse an articulated handle before they touch anything
 #define DDRL_ONE_BODY_ONLY(h, what)                                                                                                   \
     do {                                                                                                                              \
+        DDRL_REFUSE_WALKER(h, what);                                                                                                  \
         if ((h)->kind != DDRL_ENV_ONE_BODY) {                                                                                         \
             ::ddrl::set_error("%s: not built for the articulated lander (DDRL_ENV_ARTICULATED); its kernel holds the one-body model — " \
                               "use ddrl_env_step / ddrl_env_step_discrete with the unfused act and store calls", what);                \
@@ -437,6 +442,7 @@ int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, in
 // the articulated pair (ddrl_rollout_begin_articulated / _step_articulated) refuses a one-body handle before it touches anything
 #define DDRL_ARTICULATED_ONLY(h, what, instead)                                                                                       \
     do {                                                                                                                              \
+        DDRL_REFUSE_WALKER(h, what);                                                                                                  \
         if ((h)->kind != DDRL_ENV_ARTICULATED) {                                                                                      \
             ::ddrl::set_error("%s: built for the articulated lander (DDRL_ENV_ARTICULATED); this handle holds the one-body model — " \
                               "use %s", what, instead);                                                                               \
@@ -591,17 +597,18 @@ int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t se
     DDRL_REQUIRE(out != nullptr && n_envs > 0 && max_ep_len > 0, "bad out/n_envs/max_ep_len");
     DDRL_REQUIRE(max_ep_len < (1 << 24), "max_ep_len must stay exact in float32");
     const int kind = model ? model->kind : DDRL_ENV_ONE_BODY;
-    DDRL_REQUIRE(kind == DDRL_ENV_ONE_BODY || kind == DDRL_ENV_ARTICULATED, "model kind must be DDRL_ENV_ONE_BODY or DDRL_ENV_ARTICULATED");
+    DDRL_REQUIRE(kind == DDRL_ENV_ONE_BODY || kind == DDRL_ENV_ARTICULATED || kind == DDRL_ENV_WALKER,
+                 "model kind must be DDRL_ENV_ONE_BODY, DDRL_ENV_ARTICULATED or DDRL_ENV_WALKER");
     DDRL_REQUIRE(kind == DDRL_ENV_ONE_BODY || (model->velocity_iterations >= 1 && model->position_iterations >= 1),
-                 "the articulated model needs velocity_iterations >= 1 and position_iterations >= 1");
-    const int NF = kind == DDRL_ENV_ARTICULATED ? DDRL_ENV3_STATE_FIELDS : DDRL_ENV_STATE_FIELDS;
+                 "the articulated model and the walker need velocity_iterations >= 1 and position_iterations >= 1");
+    const int NF = kind == DDRL_ENV_WALKER ? DDRL_ENVW_STATE_FIELDS : kind == DDRL_ENV_ARTICULATED ? DDRL_ENV3_STATE_FIELDS : DDRL_ENV_STATE_FIELDS;
     ddrl::DeviceGuard g(device);
     if (!g.ok) { ddrl::set_error("cannot select device %d", device); return DDRL_ERR_HIP; }
     ddrl_env *h = new ddrl_env();
     h->device = device; h->n = n_envs; h->seed = seed; h->max_ep_len = max_ep_len; h->S = nullptr; h->stats = nullptr;
     h->kind = kind; h->fields = NF;
-    h->vit = kind == DDRL_ENV_ARTICULATED ? model->velocity_iterations : 0;
-    h->pit = kind == DDRL_ENV_ARTICULATED ? model->position_iterations : 0;
+    h->vit = kind != DDRL_ENV_ONE_BODY ? model->velocity_iterations : 0;
+    h->pit = kind != DDRL_ENV_ONE_BODY ? model->position_iterations : 0;
     if (hipMalloc((void **)&h->S, (size_t)NF * n_envs * sizeof(float)) != hipSuccess ||
         hipMalloc((void **)&h->stats, sizeof(EnvStats)) != hipSuccess) {
         ddrl::set_error("hipMalloc failed for %lld envs", (long long)n_envs);
@@ -610,7 +617,9 @@ int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t se
     }
     DDRL_HIP_CHECK(hipMemset(h->S, 0, (size_t)NF * n_envs * sizeof(float)));
     DDRL_HIP_CHECK(hipMemset(h->stats, 0, sizeof(EnvStats)));
-    if (kind == DDRL_ENV_ARTICULATED) {
+    if (kind == DDRL_ENV_WALKER) {
+        if (const int rc = ddrl_walker_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, nullptr, nullptr, nullptr)) return rc;
+    } else if (kind == DDRL_ENV_ARTICULATED) {
         if (const int rc = ddrl_env3_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, nullptr, nullptr, nullptr)) return rc;
     } else {
         k_env_reset<<<(unsigned)((n_envs + 255) / 256), 256, 0, nullptr>>>(h->S, h->n, h->seed, nullptr, nullptr);
@@ -635,6 +644,7 @@ int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *str
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     DDRL_REQUIRE_ALIGNED(obs_d, 16);
     ddrl::DeviceGuard g(h->device);
+    if (h->kind == DDRL_ENV_WALKER) return ddrl_walker_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, mask_d, obs_d, stream);
     if (h->kind == DDRL_ENV_ARTICULATED) return ddrl_env3_launch_reset(h->S, h->n, h->seed, h->vit, h->pit, mask_d, obs_d, stream);
     k_env_reset<<<(unsigned)((h->n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->S, h->n, h->seed, mask_d, obs_d);
     DDRL_LAUNCH_CHECK();
@@ -648,6 +658,11 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
     DDRL_REQUIRE_ALIGNED(obs2_d, 16);
     DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
     ddrl::DeviceGuard g(h->device);
+    if (h->kind == DDRL_ENV_WALKER) {   // an [n,4] action row moves as one float4
+        DDRL_REQUIRE_ALIGNED(act_d, 16);
+        return ddrl_walker_launch_step(h->S, h->n, h->seed, h->max_ep_len, h->vit, h->pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d,
+                                       h->stats, stream);
+    }
     if (h->kind == DDRL_ENV_ARTICULATED)
         return ddrl_env3_launch_step(0, h->S, h->n, h->seed, h->max_ep_len, h->vit, h->pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d,
                                      h->stats, stream);
@@ -660,6 +675,7 @@ int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d
 int ddrl_env_step_discrete(ddrl_env_t *h, const float *act_idx_d, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d,
                            uint8_t *ended_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && act_idx_d != nullptr, "NULL handle or action pointer");
+    DDRL_REFUSE_WALKER(h, "ddrl_env_step_discrete");
     DDRL_REQUIRE_ALIGNED(obs2_d, 16);
     DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
     ddrl::DeviceGuard g(h->device);
@@ -880,6 +896,7 @@ int ddrl_rollout_step_discrete_articulated(ddrl_env_t *h, ddrl_dqn_t *dqn, ddrl_
 
 int ddrl_env_rollout_mirrors(ddrl_env_t *h, const float **act, const float **q, const float **next_obs, int32_t *n_envs, int32_t *n_actions) {
     DDRL_REQUIRE(h != nullptr, "ddrl_env_rollout_mirrors: handle is NULL");
+    DDRL_REFUSE_WALKER(h, "ddrl_env_rollout_mirrors");
     DDRL_REQUIRE(h->ro_block != nullptr, "ddrl_env_rollout_mirrors: no ddrl_rollout_begin_discrete_articulated on this env handle yet");
     const float *b = h->ro_block;
     if (next_obs) *next_obs = b;

@@ -12,8 +12,8 @@ struct ddrl_env {
     int max_ep_len;
     float *S;
     EnvStats *stats;
-    int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's only
-    int fields;           // rows of S: DDRL_ENV_STATE_FIELDS or DDRL_ENV3_STATE_FIELDS
+    int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's and the walker's
+    int fields;           // rows of S: DDRL_ENV_STATE_FIELDS, DDRL_ENV3_STATE_FIELDS or DDRL_ENVW_STATE_FIELDS
     // ---- evaluation episodes (ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_results, eval3.hip).  Everything below is
     // allocated at the first evaluation, grows when a call needs more, and is freed by ddrl_env_destroy; S and stats above are
     // neither read nor written by an evaluation.
@@ -31,4 +31,14 @@ struct ddrl_env {
     float *ro_block;           // nullptr: no begin call yet
     int ro_actions;            // n_actions of the handle the last begin / step call took: the row width of the Q mirror
 };
+// A walker handle (DDRL_ENV_WALKER: [n,24] observations, [n,4] actions) is taken by reset / step / stats / get_state / set_state only:
+// every other entry point that takes an env handle refuses it with its own name, before it touches anything.
+#define DDRL_REFUSE_WALKER(h, what)                                                                                                   \
+    do {                                                                                                                              \
+        if ((h)->kind == DDRL_ENV_WALKER) {                                                                                           \
+            ::ddrl::set_error("%s: not built for the walker (DDRL_ENV_WALKER: 24 observations, 4 actions); its kernels hold a lander — " \
+                              "use ddrl_actor_act + ddrl_env_step + ddrl_replay_store", what);                                         \
+            return DDRL_ERR_UNSUPPORTED;                                                                                              \
+        }                                                                                                                             \
+    } while (0)
 constexpr int DDRL_ROLLOUT_MIRROR_Q = 8;   // ddrl_sel::MAXQ: the widest Q row the fused discrete step takes

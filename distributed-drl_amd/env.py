@@ -139,6 +139,56 @@ class VecLunarLander:
                 _device_view(nxt.value, n * 8, "<f4", self.device).view(n, 8))
 
 
+class VecBipedalWalker(VecLunarLander):
+    """n bipedal walkers stepped by one kernel launch (ddrl_env_create_ex, kind DDRL_ENV_WALKER; csrc/walker.hip): gym's BipedalWalker
+    shape — hull, two two-segment legs on four motorised joints, 10 lidar rays, 24 observations, 4 actions — on the articulated
+    lander's solver with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default).  Specification,
+    and what is gym's, Box2D's and this build's own: tests/walker_oracle.py.  NOT pinned against gym.  It has reset / step /
+    sample_actions / stats / get_state / set_state; the wrapped steps, every fused rollout launch and the on-device evaluation hold a
+    lander, and the library refuses this env there (DdrlUnsupported naming the entry point and the walker)."""
+
+    obs_dim, act_dim, act_high = 24, 4, 1.0
+    model = "walker"
+
+    def __init__(self, n_envs, seed=0, max_ep_len=1600, device=None, velocity_iterations=180, position_iterations=60):
+        _lib.require_gpu()
+        self._lib = _lib.load()
+        self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        h = ctypes.c_void_p()
+        m = _lib.EnvModel(_lib.DDRL_ENV_WALKER, int(velocity_iterations), int(position_iterations))
+        _lib.check(self._lib.ddrl_env_create_ex(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len, ctypes.byref(m)))
+        self._h = h
+        self.state_fields = int(self._lib.ddrl_env_state_fields(h))
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
+        self.obs = e(self.n, self.obs_dim)        # observation to act on next
+        self.obs2 = e(self.n, self.obs_dim)       # o2 of the last transition
+        self.rew, self.done = e(self.n), e(self.n)
+        self.ended = e(self.n, dt=torch.uint8)
+        self._sample_ctr = 0
+        self.reset()
+
+    def step(self, act):
+        """env.step(a) for every env (a: [n, 4], gym's hip / knee / hip / knee motor commands) + the bookkeeping of VecLunarLander.step;
+        same outputs, observations [n, 24]."""
+        act = act.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(act.shape) != (self.n, self.act_dim):
+            raise ValueError("the walker's actions are [%d, %d], got %s" % (self.n, self.act_dim, tuple(act.shape)))
+        act = _lib.aligned(act, 16)   # ddrl.h: a walker's act_d is read as float4 rows
+        _lib.check(self._lib.ddrl_env_step(self._h, _lib.dptr(act), _lib.dptr(self.obs2), _lib.dptr(self.rew),
+                                           _lib.dptr(self.done), _lib.dptr(self.obs), _lib.dptr(self.ended),
+                                           _lib.stream_ptr()))
+        return self.obs2, self.rew, self.done, self.obs, self.ended
+
+    def sample_actions(self, out=None):
+        """env.action_space.sample() for every env: U[-1, 1) from the counter generator."""
+        out = out if out is not None else torch.empty(self.n, self.act_dim, dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.ddrl_uniform_fill(_lib.dptr(out), self.n * self.act_dim, -1.0, 1.0, self.seed ^ 0x5EED5EED,
+                                               self._sample_ctr, _lib.stream_ptr()))
+        self._sample_ctr += self.n * self.act_dim
+        return out
+
+
 class VecLunarLanderDiscrete(VecLunarLander):
     """The same n landers behind gym's discrete LunarLander-v2 action table (ddrl_env_step_discrete): 0 noop, 1 left engine,
     2 main engine, 3 right engine — under the continuous step's clip rules exactly gym's discrete powers, so no new dynamics.  The env
@@ -201,6 +251,37 @@ class LunarLander:
 
     def step(self, a):
         act = torch.as_tensor(np.asarray(a, np.float32).reshape(1, 2))
+        o2, r, d, _, ended = self._vec.step(act)
+        ended = bool(ended[0].item())
+        self._fresh = ended
+        return o2[0].cpu().numpy().astype(np.float64), float(r[0].item()), ended, {}
+
+
+class _WalkerActionSpace(_ActionSpace):
+    def __init__(self, env):
+        self._env = env
+        self.high = np.ones(4, dtype=np.float32)
+        self.low = -self.high
+        self.shape = (4,)
+
+
+class _WalkerObsSpace:
+    shape = (24,)
+
+
+class BipedalWalker(LunarLander):
+    """One walker with the gym call shape (env.make("BipedalWalker-v2", model="walker")): reset() -> o[24]; step(a[4]) -> (o2, r, d,
+    info), `d` True at the time limit too (gym's TimeLimit of 1600 is max_ep_len)."""
+
+    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60):
+        self._vec = VecBipedalWalker(1, seed=seed, max_ep_len=max_ep_len, velocity_iterations=velocity_iterations,
+                                     position_iterations=position_iterations)
+        self.action_space = _WalkerActionSpace(self)
+        self.observation_space = _WalkerObsSpace()
+        self._fresh = True
+
+    def step(self, a):
+        act = torch.as_tensor(np.asarray(a, np.float32).reshape(1, 4))
         o2, r, d, _, ended = self._vec.step(act)
         ended = bool(ended[0].item())
         self._fresh = ended
@@ -378,10 +459,38 @@ class Wrapper(object):
         return self._noisy(obs_), self.reward_scale * r, done_, info_
 
 
+def _walker_door(env_name, kw, who):
+    """None for a lander name; for "BipedalWalker-v2" the BipedalWalker's keyword arguments.  The walker is asked for by name AND by
+    model="walker": the bare name keeps raising ValueError, as it did before this env existed, because what stands behind it is this
+    build's own model, unpinned against gym's (tests/walker_oracle.py) — a driver that names gym's env says so once, in its make call.
+    "BipedalWalkerHardcore-v2" (pits, stumps, stairs) is not built."""
+    if "BipedalWalker" not in env_name:
+        if kw.get("model") == "walker":
+            raise ValueError("%s(%r, model=\"walker\"): the walker's name is \"BipedalWalker-v2\"" % (who, env_name))
+        return None
+    if "Hardcore" in env_name:
+        raise ValueError("%s(%r): the Hardcore terrain (pits, stumps, stairs) is not built; \"BipedalWalker-v2\" with model=\"walker\" is"
+                         % (who, env_name))
+    if env_name != "BipedalWalker-v2":
+        raise ValueError("%s(%r): the walker that is built is \"BipedalWalker-v2\"" % (who, env_name))
+    if kw.get("model") != "walker":
+        raise ValueError("%s(\"BipedalWalker-v2\") needs model=\"walker\": the env behind the name is this build's own five-body model, "
+                         "not pinned against gym's (only the LunarLanderContinuous-v2 stand-in is built without one; SURVEY §8(a) A7)" % who)
+    return {k: v for k, v in kw.items() if k != "model"}
+
+
 def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     """gym.make stand-in (example/dsac.py:78).  model="simple" | "articulated" (+ velocity_iterations, position_iterations) is passed on to the env.  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
     `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)
-    on the one-body lander; the articulated model's marker is built by make_device."""
+    on the one-body lander; the articulated model's marker is built by make_device.
+    "BipedalWalker-v2" with model="walker" (+ seed, max_ep_len, velocity_iterations, position_iterations): the BipedalWalker facade
+    (_walker_door); on_device=True raises, no evaluation kernel holds that model."""
+    walker = _walker_door(env_name, kw, "env.make")
+    if walker is not None:
+        if on_device:
+            raise ValueError("env.make(%r, on_device=True): no evaluation kernel holds the walker (ddrl_env_eval_policy / ddrl_env_eval_q, "
+                             "csrc/eval3.hip, run landers) — evaluate on a host-stepped env.make(%r, model=\"walker\")" % (env_name, env_name))
+        return BipedalWalker(**walker)
     if on_device and _check_model(kw.get("model", "simple")) != "simple":
         raise ValueError("env.make(on_device=True, model=%r): this door builds the one-body lander's marker only (ddrl_policy_eval, csrc/eval.hip; "
                          "ddrl_dqn_eval, csrc/eval_q.hip) — the evaluation kernel for the articulated model (ddrl_env_eval_policy / "
@@ -400,6 +509,9 @@ def make_device(env_name="LunarLanderContinuous-v2", **kw):
     """The test-env marker of an on-device evaluation for EITHER model: seed, max_ep_len and model="simple" | "articulated"
     (+ velocity_iterations, position_iterations) as env.make takes them.  "LunarLander-v2": DeviceLunarLanderDiscrete (dqn.Actor.test /
     ActorSQN.test), else DeviceLunarLander (Actor.test / Model.test_agent).  The one-body marker is what make(on_device=True) returns."""
+    if _walker_door(env_name, kw, "env.make_device") is not None:
+        raise ValueError("env.make_device(%r): no evaluation kernel holds the walker (ddrl_env_eval_policy / ddrl_env_eval_q, "
+                         "csrc/eval3.hip, run landers) — evaluate on a host-stepped env.make(%r, model=\"walker\")" % (env_name, env_name))
     _check_model(kw.get("model", "simple"))
     if env_name == "LunarLander-v2":
         return DeviceLunarLanderDiscrete(**kw)

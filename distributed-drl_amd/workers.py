@@ -610,12 +610,20 @@ def _env_model_kw(opt):
     discrete and n-step siblings hold the one-body lander.  Every worker has a fused step on that model behind a flag of its own: the
     continuous worker (RolloutDevice) behind `opt.fused_rollout_articulated`, the discrete worker (RolloutDeviceDQN) behind
     `opt.fused_discrete_rollout_articulated`, the n-step worker (RolloutDeviceNStep) behind `opt.fused_nstep_rollout_articulated`
-    (all default False).  The flags are the workers', and change nothing here."""
+    (all default False).  The flags are the workers', and change nothing here.
+    "walker" (env.VecBipedalWalker, 24 observations / 4 actions) is RolloutDevice's alone and always unfused: _no_walker() is what the
+    other two workers say to it."""
     model = getattr(opt, "env_model", "simple")
     if model == "simple":
         return {}
     return dict(model=model, velocity_iterations=int(getattr(opt, "env_velocity_iterations", 180)),
                 position_iterations=int(getattr(opt, "env_position_iterations", 60)))
+
+
+def _no_walker(opt, who, why):
+    if getattr(opt, "env_model", "simple") == "walker":
+        raise ValueError("%s: opt.env_model = \"walker\" is not built for this worker (%s); workers.RolloutDevice steps the walker on "
+                         "its unfused sequence" % (who, why))
 
 
 class _RolloutWorker:
@@ -758,19 +766,28 @@ class RolloutDevice(_RolloutWorker):
     The articulated lander (`opt.env_model = "articulated"`) runs the unfused sequence — and so adopts per step — unless
     `opt.fused_rollout_articulated` is set (default False): then the worker takes ddrl_rollout_begin_articulated /
     ddrl_rollout_step_articulated, the same launch pair with the three-body solver in the env-step kernel, and "episode" adoption
-    holds on that model too.  The one-body worker ignores the flag."""
+    holds on that model too.  The one-body worker ignores the flag.
+
+    The walker (`opt.env_model = "walker"`: env.VecBipedalWalker with the same iteration options) sets `opt.obs_dim, opt.act_dim =
+    24, 4` and always runs the unfused sequence: no fused launch holds it (ddrl_rollout_begin* refuse a walker handle), and an actor of
+    obs + act = 28 has no direct-operand policy anyway."""
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
         from .agent import Actor
-        from .env import VecLunarLander
+        from .env import VecBipedalWalker, VecLunarLander
         self.rb, self.opt = replay_buffer, opt
-        self.env = VecLunarLander(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index),
-                                  max_ep_len=opt.max_ep_len, **_env_model_kw(opt))
+        kw = _env_model_kw(opt)
+        if kw.get("model") == "walker":
+            del kw["model"]
+            opt.obs_dim, opt.act_dim = VecBipedalWalker.obs_dim, VecBipedalWalker.act_dim
+            self.env = VecBipedalWalker(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len, **kw)
+        else:
+            self.env = VecLunarLander(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len, **kw)
         self.actor = Actor(opt, job="worker", max_rows=opt.num_envs, index=worker_index)
         self.t = 0
         self.o = torch.empty_like(self.env.obs)
-        self.act = torch.empty(opt.num_envs, 2, dtype=torch.float32, device=self.env.device)
+        self.act = torch.empty(opt.num_envs, self.env.act_dim, dtype=torch.float32, device=self.env.device)
         self._start(ps, getattr(opt, "fused_rollout", True), "episode")
         if self.adopt == "episode":
             self._fused_ready()   # the version store starts from the initial pull, before any step
@@ -823,6 +840,7 @@ class RolloutDeviceDQN(_RolloutWorker):
         import torch
         from . import dqn
         from .env import VecLunarLanderDiscrete
+        _no_walker(opt, "RolloutDeviceDQN", "the walker's actions are continuous")
         self.rb, self.opt = replay_buffer, opt
         self.env = VecLunarLanderDiscrete(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len,
                                           **_env_model_kw(opt))
@@ -954,6 +972,7 @@ class RolloutDeviceNStep(_RolloutWorker):
         import torch
         from .agent import Actor
         from .env import VecLunarLander
+        _no_walker(opt, "RolloutDeviceNStep", "no wrapped step holds the walker: ddrl_env_step_wrapped* refuse its handle")
         self.opt = opt
         self.rbs = list(replay_buffers) if isinstance(replay_buffers, (list, tuple)) else [replay_buffers]
         n = int(opt.num_envs)

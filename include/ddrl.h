@@ -514,6 +514,12 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /*                         ddrl_env_step_wrapped_articulated and the n-step fused step      */
 /*                         behind ddrl_rollout_begin_nstep_articulated /                    */
 /*                         _step_nstep_articulated.  Not pinned against gym either.         */
+/*   DDRL_ENV_WALKER       gym's BipedalWalker shape: hull + two two-segment legs on four    */
+/*                         motorised revolute joints, feet and knees against 199 terrain    */
+/*                         segments, ten lidar rays, the same island solve                  */
+/*                         (tests/walker_oracle.py) — ddrl_env_create_ex; reset / step /    */
+/*                         stats / get_state / set_state only, with [n,24] observations and */
+/*                         [n,4] actions.  Not pinned against gym either.                   */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
 
@@ -527,17 +533,26 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
  * + store) works on both; the continuous fused step on an articulated handle is ddrl_rollout_begin_articulated /
  * ddrl_rollout_step_articulated, the discrete one ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated,
  * the wrapped step ddrl_env_step_wrapped_articulated and the n-step fused step ddrl_rollout_begin_nstep_articulated /
- * ddrl_rollout_step_nstep_articulated: every one-body entry point has its twin, and each twin refuses a one-body handle likewise. */
+ * ddrl_rollout_step_nstep_articulated: every one-body entry point has its twin, and each twin refuses a one-body handle likewise.
+ * kind == DDRL_ENV_WALKER: the five-body walker, iteration counts as for the articulated lander (each >= 1).  A walker handle is taken
+ * by ddrl_env_state_fields, ddrl_env_reset, ddrl_env_step, ddrl_env_stats, ddrl_env_get_state, ddrl_env_set_state and
+ * ddrl_env_destroy; wherever those comments say [n,8] observations and [n,2] actions, a walker handle's are [n,24] and [n,4], all three
+ * pointers 16-byte aligned.  Every other entry point that takes an env handle (ddrl_env_step_discrete, both wrapped steps, the six
+ * rollout begin / step pairs, ddrl_env_eval_policy / ddrl_env_eval_q, ddrl_env_rollout_mirrors) returns DDRL_ERR_UNSUPPORTED for it,
+ * with its own name and the word "walker" in ddrl_last_error(), and launches and writes nothing.  (Value 2 is not a model.) */
 #define DDRL_ENV_ONE_BODY 0
 #define DDRL_ENV_ARTICULATED 1
+#define DDRL_ENV_WALKER 3
 typedef struct { int32_t kind, velocity_iterations, position_iterations; } ddrl_env_model_t;
 int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len,
                        const ddrl_env_model_t *model);
-/* Rows of the handle's state block: DDRL_ENV_STATE_FIELDS (one-body) or DDRL_ENV3_STATE_FIELDS (articulated). */
+/* Rows of the handle's state block: DDRL_ENV_STATE_FIELDS (one-body), DDRL_ENV3_STATE_FIELDS (articulated) or DDRL_ENVW_STATE_FIELDS
+ * (walker). */
 int ddrl_env_state_fields(ddrl_env_t *h);
 int ddrl_env_destroy(ddrl_env_t *h);
 /* env.reset() for every env (mask_d == NULL) or for envs with mask_d[i] != 0 (device uint8[n]).
- * obs_d[n,8] receives the current observation of every env (may be NULL; 16-byte aligned, else DDRL_ERR_BAD_ARG). */
+ * obs_d[n,8] ([n,24] for a walker handle) receives the current observation of every env (may be NULL; 16-byte aligned, else
+ * DDRL_ERR_BAD_ARG). */
 int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *stream);
 /* One env.step(a) per env followed by the reference's episode bookkeeping
  * (example/dsac.py:102-127): outputs the transition as it is stored —
@@ -549,7 +564,9 @@ int ddrl_env_reset(ddrl_env_t *h, const uint8_t *mask_d, float *obs_d, void *str
  *   ended_d[n]       (uint8, may be NULL) 1 where an episode ended this step.
  * act_d[n,2] device float32.  Every output may be NULL (that one is then not written).
  * Alignment: act_d 8 bytes, obs2_d and next_obs_d 16 bytes (rows move as float2 / float4); rew_d, done_d, ended_d that of their
- * element.  A pointer off that grid: DDRL_ERR_BAD_ARG naming it, before any launch — state, statistics and outputs unchanged. */
+ * element.  A pointer off that grid: DDRL_ERR_BAD_ARG naming it, before any launch — state, statistics and outputs unchanged.
+ * A walker handle (DDRL_ENV_WALKER): obs2_d and next_obs_d are [n,24], act_d is [n,4] and 16-byte aligned like them (a row moves as
+ * one float4); the action is gym's four motor commands (hip, knee, hip, knee), not clipped beyond the torque's clip(|a|, 0, 1). */
 int ddrl_env_step(ddrl_env_t *h, const float *act_d, float *obs2_d, float *rew_d, float *done_d,
                   float *next_obs_d, uint8_t *ended_d, void *stream);
 /* env.step through `Wrapper(env, obs_noise, act_noise, reward_scale, action_repeat)`
@@ -645,6 +662,7 @@ int ddrl_env_stats(ddrl_env_t *h, int64_t *episodes_h, double *ret_sum_h, int64_
  * to / from a device buffer. */
 #define DDRL_ENV_STATE_FIELDS 32
 #define DDRL_ENV3_STATE_FIELDS 66
+#define DDRL_ENVW_STATE_FIELDS 286
 int ddrl_env_get_state(ddrl_env_t *h, float *state_d, void *stream);
 int ddrl_env_set_state(ddrl_env_t *h, const float *state_d, void *stream);
 
