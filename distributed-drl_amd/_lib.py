@@ -235,6 +235,12 @@ class DdrlUnsupported(DdrlError):
     """DDRL_ERR_UNSUPPORTED: the call has no kernel for this shape (callers with another path catch this one)."""
 
 
+# include/ddrl_walker.h: the entry points declared beside include/ddrl.h (SIGNATURES is that header's set, name for name)
+SIGNATURES_WALKER = {
+    "ddrl_env_step_wrapped_walker": SIGNATURES["ddrl_env_step_wrapped"],   # the arguments of its one-body twin
+}
+
+
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
     global _lib
@@ -248,7 +254,7 @@ def load():
             "libddrl_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C distributed-drl_amd/csrc`; there is no CPU fallback for the product path" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

@@ -9,6 +9,7 @@
 // contraction (-ffp-contract=off), correctly rounded sqrt/divide, polynomial sin/cos shared with
 // the oracle, counter-hash RNG.  Every arithmetic statement below mirrors one line of the oracle.
 #include "ddrl_common.h"
+#include "../../include/ddrl_walker.h"
 #include "policy_row.h"
 #include "replay_device.h"
 #include "env_device.h"
@@ -421,6 +422,10 @@ int ddrl_env3_launch_step(int discrete, float *S, long long n, uint32_t seed, in
 int ddrl_walker_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
 int ddrl_walker_launch_step(float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d,
                             float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+// ... and its wrapped step (walker_nstep.hip)
+int ddrl_walker_launch_step_wrapped(float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d, float act_noise,
+                                    float obs_noise, float reward_scale, int action_repeat, float *obs2_d, float *rew_d, float *done_d,
+                                    float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
 
 // Memory contract (include/ddrl.h): the env family's kernels move an observation row as two float4 and a continuous action row as one
 // float2, so caller pointers to [n,8] observations must be 16-byte aligned and to [n,2] actions 8-byte aligned.  Checked here, before
@@ -718,6 +723,26 @@ int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noi
     ddrl::DeviceGuard g(h->device);
     return ddrl_env3_launch_step_wrapped(h->S, h->n, h->seed, limit_steps, h->vit, h->pit, act_d, act_noise, obs_noise, reward_scale,
                                          action_repeat, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats, stream);
+}
+
+// ... on the walker (kernel: walker_nstep.hip, k_walker_step_wrapped): [n,4] actions as one float4, [n,24] observations as six
+int ddrl_env_step_wrapped_walker(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale, int32_t action_repeat,
+                                 int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d,
+                                 void *stream) {
+    DDRL_REQUIRE(h != nullptr && act_d != nullptr, "ddrl_env_step_wrapped_walker: NULL handle or act_d");
+    if (h->kind != DDRL_ENV_WALKER) {
+        ::ddrl::set_error("ddrl_env_step_wrapped_walker: built for the walker (DDRL_ENV_WALKER); this handle holds %s — use %s",
+                          h->kind == DDRL_ENV_ARTICULATED ? "the articulated lander" : "the one-body model",
+                          h->kind == DDRL_ENV_ARTICULATED ? "ddrl_env_step_wrapped_articulated" : "ddrl_env_step_wrapped");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    DDRL_REQUIRE_ALIGNED(act_d, 16);
+    DDRL_REQUIRE_ALIGNED(obs2_d, 16);
+    DDRL_REQUIRE_ALIGNED(next_obs_d, 16);
+    DDRL_REQUIRE(action_repeat >= 1 && limit_steps >= 1, "ddrl_env_step_wrapped_walker: action_repeat and limit_steps must be >= 1");
+    ddrl::DeviceGuard g(h->device);
+    return ddrl_walker_launch_step_wrapped(h->S, h->n, h->seed, limit_steps, h->vit, h->pit, act_d, act_noise, obs_noise, reward_scale,
+                                           action_repeat, obs2_d, rew_d, done_d, next_obs_d, ended_d, h->stats, stream);
 }
 
 int ddrl_rollout_begin(ddrl_env_t *h, ddrl_actor_t *actor, void *stream) {

@@ -144,8 +144,9 @@ class VecBipedalWalker(VecLunarLander):
     shape — hull, two two-segment legs on four motorised joints, 10 lidar rays, 24 observations, 4 actions — on the articulated
     lander's solver with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default).  Specification,
     and what is gym's, Box2D's and this build's own: tests/walker_oracle.py.  NOT pinned against gym.  It has reset / step /
-    sample_actions / stats / get_state / set_state; the wrapped steps, every fused rollout launch and the on-device evaluation hold a
-    lander, and the library refuses this env there (DdrlUnsupported naming the entry point and the walker)."""
+    step_wrapped_walker (the n-step worker's step, csrc/walker_nstep.hip) / sample_actions / stats / get_state / set_state; the
+    landers' wrapped steps (the inherited step_wrapped and step_wrapped_articulated), every fused rollout launch and the on-device
+    evaluation hold a lander, and the library refuses this env there (DdrlUnsupported naming the entry point and the walker)."""
 
     obs_dim, act_dim, act_high = 24, 4, 1.0
     model = "walker"
@@ -178,6 +179,29 @@ class VecBipedalWalker(VecLunarLander):
         _lib.check(self._lib.ddrl_env_step(self._h, _lib.dptr(act), _lib.dptr(self.obs2), _lib.dptr(self.rew),
                                            _lib.dptr(self.done), _lib.dptr(self.obs), _lib.dptr(self.ended),
                                            _lib.stream_ptr()))
+        return self.obs2, self.rew, self.done, self.obs, self.ended
+
+    def step_wrapped_walker(self, act, act_noise=0.0, obs_noise=0.0, reward_scale=1.0, action_repeat=3, limit_steps=None):
+        """step_wrapped on the walker (ddrl_env_step_wrapped_walker, csrc/walker_nstep.hip; specification
+        tests/walker_wrapped_oracle.py): the same Wrapper and bookkeeping around the five-body solver with this env's iteration counts;
+        same arguments and outputs as step_wrapped_articulated, observations [n, 24], done the raw d.  `act` ([n, 4], a contiguous
+        float32 device tensor) receives the noisy action in place.  The library reads and writes an action row as one float4, so `act`
+        goes through _lib.aligned(act, 16) as in step(): a view that starts off the 16-byte grid is staged in an aligned copy, and the
+        noisy action is copied back into the view on the same stream — the caller sees the in-place update either way, at the cost of
+        two copies for such a view.  (A tensor on another device or of another dtype is converted first and is NOT written back, as in
+        step_wrapped.)  The inherited step_wrapped and step_wrapped_articulated keep raising DdrlUnsupported on this env."""
+        given = act
+        act = act.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(act.shape) != (self.n, self.act_dim):
+            raise ValueError("the walker's actions are [%d, %d], got %s" % (self.n, self.act_dim, tuple(act.shape)))
+        a = _lib.aligned(act, 16)
+        limit = int(limit_steps if limit_steps is not None else self.max_ep_len)
+        _lib.check(self._lib.ddrl_env_step_wrapped_walker(self._h, _lib.dptr(a), float(act_noise), float(obs_noise), float(reward_scale),
+                                                          int(action_repeat), limit, _lib.dptr(self.obs2), _lib.dptr(self.rew),
+                                                          _lib.dptr(self.done), _lib.dptr(self.obs), _lib.dptr(self.ended),
+                                                          _lib.stream_ptr()))
+        if act is given and a is not act:
+            act.copy_(a)
         return self.obs2, self.rew, self.done, self.obs, self.ended
 
     def sample_actions(self, out=None):

@@ -611,8 +611,8 @@ def _env_model_kw(opt):
     continuous worker (RolloutDevice) behind `opt.fused_rollout_articulated`, the discrete worker (RolloutDeviceDQN) behind
     `opt.fused_discrete_rollout_articulated`, the n-step worker (RolloutDeviceNStep) behind `opt.fused_nstep_rollout_articulated`
     (all default False).  The flags are the workers', and change nothing here.
-    "walker" (env.VecBipedalWalker, 24 observations / 4 actions) is RolloutDevice's alone and always unfused: _no_walker() is what the
-    other two workers say to it."""
+    "walker" (env.VecBipedalWalker, 24 observations / 4 actions) is RolloutDevice's and RolloutDeviceNStep's, always unfused (the
+    n-step worker steps it through VecBipedalWalker.step_wrapped_walker): _no_walker() is what the discrete worker says to it."""
     model = getattr(opt, "env_model", "simple")
     if model == "simple":
         return {}
@@ -622,8 +622,8 @@ def _env_model_kw(opt):
 
 def _no_walker(opt, who, why):
     if getattr(opt, "env_model", "simple") == "walker":
-        raise ValueError("%s: opt.env_model = \"walker\" is not built for this worker (%s); workers.RolloutDevice steps the walker on "
-                         "its unfused sequence" % (who, why))
+        raise ValueError("%s: opt.env_model = \"walker\" is not built for this worker (%s); workers.RolloutDevice and "
+                         "workers.RolloutDeviceNStep step the walker on their unfused sequences" % (who, why))
 
 
 class _RolloutWorker:
@@ -770,7 +770,7 @@ class RolloutDevice(_RolloutWorker):
 
     The walker (`opt.env_model = "walker"`: env.VecBipedalWalker with the same iteration options) sets `opt.obs_dim, opt.act_dim =
     24, 4` and always runs the unfused sequence: no fused launch holds it (ddrl_rollout_begin* refuse a walker handle), and an actor of
-    obs + act = 28 has no direct-operand policy anyway."""
+    obs + act = 28 has no direct-operand policy anyway.  The n-step driver's worker on this env is RolloutDeviceNStep."""
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
@@ -963,7 +963,15 @@ class RolloutDeviceNStep(_RolloutWorker):
     `opt.fused_nstep_rollout_articulated` is set (default False): then — with the rest of the envelope holding as on the one-body model —
     it takes ddrl_rollout_begin_nstep_articulated / ddrl_rollout_step_nstep_articulated, the same launch pair with the three-body solver
     inside the Wrapper's repeat loop (csrc/rollout3_nstep.hip).  `_learning`, adoption at the episode end, ps=None and _fused_refresh
-    behave as on the one-body model; the one-body worker ignores the flag."""
+    behave as on the one-body model; the one-body worker ignores the flag.
+
+    The walker (`opt.env_model = "walker"`: env.VecBipedalWalker with the same iteration options — the env sac_ray.py itself names)
+    sets `opt.obs_dim, opt.act_dim = 24, 4`, as RolloutDevice does, and steps through VecBipedalWalker.step_wrapped_walker
+    (ddrl_env_step_wrapped_walker, csrc/walker_nstep.hip).  Every ring handed to it must be a ReplayBufferNStep of 24 / 4: the
+    constructor checks that before it allocates anything and raises ValueError otherwise.  The worker is always unfused there — no
+    fused launch holds the walker — and has no version store: an actor of 24 observations lies outside the direct-operand envelope,
+    _enable_versions' ValueError is caught as for any such actor, and weight adoption is the whole-vector swap after the step
+    (`adopt = "step"` behaviour whatever opt.adopt says: never staler than the reference, not identical to it)."""
 
     WRAPPER_REPEAT = 3  # the literal in sac_ray.py:189 (opt.action_repeat only scales the episode limit)
 
@@ -971,19 +979,31 @@ class RolloutDeviceNStep(_RolloutWorker):
         import numpy as np
         import torch
         from .agent import Actor
-        from .env import VecLunarLander
-        _no_walker(opt, "RolloutDeviceNStep", "no wrapped step holds the walker: ddrl_env_step_wrapped* refuse its handle")
+        from .env import VecBipedalWalker, VecLunarLander
         self.opt = opt
         self.rbs = list(replay_buffers) if isinstance(replay_buffers, (list, tuple)) else [replay_buffers]
         n = int(opt.num_envs)
-        self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23, **_env_model_kw(opt))
+        kw = _env_model_kw(opt)
+        if kw.get("model") == "walker":
+            from .replay import ReplayBufferNStep
+            dims = (VecBipedalWalker.obs_dim, VecBipedalWalker.act_dim)
+            for rb in self.rbs:     # before anything is allocated: the window rings must hold the walker's rows
+                if not isinstance(rb, ReplayBufferNStep) or (rb.obs_dim, rb.act_dim) != dims:
+                    raise ValueError("RolloutDeviceNStep: opt.env_model = \"walker\" stores windows of %d observations / %d actions and "
+                                     "needs ReplayBufferNStep rings of that shape, got %s%s"
+                                     % (dims + (type(rb).__name__, " of %s / %s" % (getattr(rb, "obs_dim", "?"), getattr(rb, "act_dim", "?")))))
+            del kw["model"]
+            opt.obs_dim, opt.act_dim = dims
+            self.env = VecBipedalWalker(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23, **kw)
+        else:
+            self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23, **kw)
         self.limit_steps = -(-int(opt.max_ep_len) // int(opt.action_repeat))   # ep_len * action_repeat >= max_ep_len (sac_ray.py:252)
         self.actor = Actor(opt, job="worker", max_rows=n, index=worker_index)
         self.filling_steps = 0
         self.winq = WindowQueue(n, opt.Ln, opt.obs_dim, opt.act_dim, getattr(opt, "save_freq", 1), device=self.env.device.index)
         self.winq.begin(self.env.obs)
         self.o = torch.empty_like(self.env.obs)
-        self.act = torch.empty(n, 2, dtype=torch.float32, device=self.env.device)
+        self.act = torch.empty(n, self.env.act_dim, dtype=torch.float32, device=self.env.device)
         self.pick = np.random.RandomState(int(opt.seed) + 7919 * int(worker_index))
         # `opt.fused_nstep_rollout`, default True: the measurement behind the default is profiles/nstep_rollout.txt.  _fused_live covers
         # the queues' readiness bytes too: a caller that rewrites the queues or t_queue by hand between two fused steps clears it
@@ -1092,7 +1112,8 @@ class RolloutDeviceNStep(_RolloutWorker):
         else:
             env.sample_actions(out=self.act)
             self.filling_steps += 1
-        wrapped = env.step_wrapped_articulated if env.model == "articulated" else env.step_wrapped
+        wrapped = (env.step_wrapped_walker if env.model == "walker" else
+                   env.step_wrapped_articulated if env.model == "articulated" else env.step_wrapped)
         o2, r, d, next_obs, ended = wrapped(self.act, getattr(opt, "act_noise", 0.0), getattr(opt, "obs_noise", 0.0),
                                             getattr(opt, "reward_scale", 1.0), self.WRAPPER_REPEAT, self.limit_steps)
         ready = self.winq.push(o2, self.act, r, d)

@@ -518,7 +518,9 @@ int ddrl_policy_eval(const ddrl_sac1_config_t *cfg, const float *pi_flat_d, int3
 /*                         motorised revolute joints, feet and knees against 199 terrain    */
 /*                         segments, ten lidar rays, the same island solve                  */
 /*                         (tests/walker_oracle.py) — ddrl_env_create_ex; reset / step /    */
-/*                         stats / get_state / set_state only, with [n,24] observations and */
+/*                         stats / get_state / set_state and the wrapped step behind        */
+/*                         ddrl_env_step_wrapped_walker (ddrl_walker.h) only, with [n,24]   */
+/*                         observations and                                                 */
 /*                         [n,4] actions.  Not pinned against gym either.                   */
 /* ===================================================================================== */
 typedef struct ddrl_env ddrl_env_t;
@@ -537,7 +539,8 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
  * kind == DDRL_ENV_WALKER: the five-body walker, iteration counts as for the articulated lander (each >= 1).  A walker handle is taken
  * by ddrl_env_state_fields, ddrl_env_reset, ddrl_env_step, ddrl_env_stats, ddrl_env_get_state, ddrl_env_set_state and
  * ddrl_env_destroy; wherever those comments say [n,8] observations and [n,2] actions, a walker handle's are [n,24] and [n,4], all three
- * pointers 16-byte aligned.  Every other entry point that takes an env handle (ddrl_env_step_discrete, both wrapped steps, the six
+ * pointers 16-byte aligned.  Its wrapped step is ddrl_env_step_wrapped_walker (include/ddrl_walker.h), which takes no other handle.
+ * Every other entry point that takes an env handle (ddrl_env_step_discrete, both landers' wrapped steps, the six
  * rollout begin / step pairs, ddrl_env_eval_policy / ddrl_env_eval_q, ddrl_env_rollout_mirrors) returns DDRL_ERR_UNSUPPORTED for it,
  * with its own name and the word "walker" in ddrl_last_error(), and launches and writes nothing.  (Value 2 is not a model.) */
 #define DDRL_ENV_ONE_BODY 0
@@ -592,6 +595,8 @@ int ddrl_env_step_wrapped(ddrl_env_t *h, float *act_d, float act_noise, float ob
 int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale,
                                       int32_t action_repeat, int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d,
                                       float *next_obs_d, uint8_t *ended_d, void *stream);
+/* The same step on the WALKER (kind = DDRL_ENV_WALKER) is ddrl_env_step_wrapped_walker, declared with its memory contract in
+ * include/ddrl_walker.h: this header's set of declarations is closed, and entry points added since live in headers beside it. */
 /* RolloutDevice.step fused: ONE vector step of worker_rollout's policy phase (example/dsac.py:96-130; SAC1 flavour
  * algos/sac1/sac1.py:177-213) for all n envs, as two launches with no host work in between:
  *   a = agent.get_action(o)  (Actor.get_action, actor_learner.py:195-197; noise element i*act+c of the counter stream
