@@ -241,7 +241,10 @@ constexpr int DGMID = DDRL_DGMID;   // k_dg: the group behind whose MFMAs the ep
 // k_dg, tiles that step the optimizer: the group in front of whose MFMAs the state is requested.  With DGP0 = 2 that is right
 // behind the request of group DGST + 2: group 7, the last one a wave has of a 256-deep contraction (the batch).
 constexpr int DGST10 = DDRL_DGST;
-template <int V> struct DGKind { static constexpr int value = V; };
+// k_dg's compile-time tile kind: `value` = the loads a K loop carries (0 - 6, at the dispatch), `gen` = how the generated MFMA operand
+// is made (0: none, both operands as loaded — 1: from s_gw (the B of a J4 wgrad, the A of a Q dgrad) or, KIND 6, from the [k][8] rows
+// of s_w8 — 2: KIND 6 with the packed [k][4] rows, act <= 2)
+template <int V, int G = 0> struct DGKind { static constexpr int value = V, gen = G; };
 struct DSrc {
     const float *W1, *W2p;
     int Np, b0, nb, n0;
@@ -1177,6 +1180,15 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
         kind = __builtin_amdgcn_readfirstlane(kind);
         asm volatile("" : "+s"(kind));   // one scalar through the tile, not a 64-bit mask per predicate it stands for
     }
+    // ... and how its generated operand is made (DGKind::gen): part of the compile-time kind, so that no K loop tests bgen / agen /
+    // nact between its MFMA groups (each test was a scalar load from the kernarg segment, a wait and a branch, in every group).
+    // A generated B operand is a J4 wgrad's (dg_add), stepping or not.
+    int ksel;
+    {
+        const int gen = kind >= 6 ? (agen ? (jb.nact <= 2 ? 2 : 1) : 0) : kind >= 4 ? 1 : kind <= 1 ? (hot_bgen == 1 ? 1 : 0) : 0;
+        ksel = __builtin_amdgcn_readfirstlane(kind + 8 * gen);
+        asm volatile("" : "+s"(ksel));
+    }
     const bool is_dgrad = kind >= 4;
     float4 mk = make_float4(1.f, 1.f, 1.f, 1.f);
     float wa_v = 0.f;  // staged into LDS after the K loop
@@ -1250,10 +1262,13 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     // the loop — generated-operand row math, LDS staging, the loss prologue — is written once and compiled per kind.)
     auto gemm_tile = [&](auto kind) {
     constexpr int KIND = decltype(kind)::value;
+    constexpr int GEN = decltype(kind)::gen;
     constexpr bool STEP = KIND >= 1 && KIND <= 3, DGQ = KIND == 4 || KIND == 5;
+    constexpr bool GW = GEN == 1 && KIND != 6, AG = KIND == 6 && GEN == 1, AG2 = KIND == 6 && GEN == 2;
+    static_assert(!DGQ || GEN == 1, "a Q dgrad generates its A operand");
     // (a marker that differs per kind: the instances begin with the same requests, which the compiler otherwise hoists back in front
     // of the dispatch as common code — and with them the join)
-    asm volatile("; k_dg tile kind %0" ::"n"(KIND));
+    asm volatile("; k_dg tile kind %0 gen %1" ::"n"(KIND), "n"(GEN));
     // what the kind says about the job type (`kind` is opaque to the compiler): predicates of the other types fold away
     if (DGQ) __builtin_assume(type == DG_DGRAD_Q);
     else if (KIND == 6) __builtin_assume(type == DG_DGRAD);
@@ -1281,7 +1296,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     // over, off this chain).  The dgrad no longer waits for a launch between the dQ/da partials and itself, and the layer-1 wgrad of
     // the policy becomes a plain job of the last launch instead of a hand-off at the end of the update's longest chain.
     float pdm[4] = {0.f, 0.f, 0.f, 0.f}, pdl[4] = {0.f, 0.f, 0.f, 0.f};
-    if (KIND == 6 && agen) {
+    if (AG || AG2) {
         __builtin_amdgcn_sched_barrier(0);
         const int act = jb.nact, row = m0 + l31;
         float4 dp[16];
@@ -1341,19 +1356,18 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
         for (int u = 0; u < 2; ++u) {
             const int k = tid + 256 * u;
             if (k < 8 * G) {
-                if (act <= 2) *reinterpret_cast<float4 *>(&s_w8[k * 4]) = make_float4(wm4[u].x, wm4[u].y, wl4[u].x, wl4[u].y);   // packed rows: half the LDS reads
+                if (AG2) *reinterpret_cast<float4 *>(&s_w8[k * 4]) = make_float4(wm4[u].x, wm4[u].y, wl4[u].x, wl4[u].y);   // packed rows: half the LDS reads
                 else { *reinterpret_cast<float4 *>(&s_w8[k * 8]) = wm4[u]; *reinterpret_cast<float4 *>(&s_w8[k * 8 + 4]) = wl4[u]; }
             }
         }
         DST(kid, 8);
     }
-    const bool agen2 = agen && jb.nact <= 2;   // block-uniform
     ktouch(kl);
     DST(kid, 1);
     // ---- DGRAD_Q prologue: q1, q2, q1(x,pi), the target backup, the per-row loss terms and dq = dLoss/dq (actor_learner.py:58-69)
     float dqr = m0 + l31 < Bv ? jb.gconst : 0.f;
-    if (has_gen && !agen) { s_gw[tid] = gv0; s_gw[tid + 256] = gv1; }
-    if (has_gen && !need_q) __syncthreads();
+    if (GW) { s_gw[tid] = gv0; s_gw[tid + 256] = gv1; }
+    if (GEN && !need_q) __syncthreads();
     if (DGQ) {
         if (need_q) {
             float qsum = zero_here();
@@ -1411,8 +1425,54 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
         }
     }
     // ---- K loop.  No load of a kind stands under a branch (a join with a path that has fewer loads in flight makes the compiler
-    // count the shorter queue), so the waits in front of every MFMA group count exactly; the generated-operand branches of the
-    // tiles that do not step stay branches (as selects: +0.9 k cycles in launch "bq").
+    // count the shorter queue), so the waits in front of every MFMA group count exactly.  How a generated operand is made is
+    // compile-time too (GEN): as run-time tests of jb.bgen / agen / nact every group of a stepping or policy-dgrad tile opened with
+    // a scalar load from the kernarg segment, its wait and a branch — 4 k of the 9.1 k cycles of the policy layer-2 wgrad's K loop,
+    // which generates nothing, and 6 k of the 14 k of the Q layer-2 wgrads' (profiles/generated_operands_before_after.txt).
+    // Making group g + 1's values under the MFMAs of group g on top of that was built and measured: +0.13 us per update — with two
+    // waves per SIMD the other wave's MFMAs already cover this VALU and LDS work — and is not in.
+    // ---- generated operands: element e of a group's operand is (loaded element > 0) ? z[e] : 0.  The LDS reads of a group are made
+    // first, whole, and the four z values from them; the tests and selects on the loaded operand come last.  (Written as
+    // `loaded > 0 ? read * factor : 0` per element, the compiler moved the reads under the tests: the 16 bytes of s_gw came as a
+    // ds_read2_b32, a ds_read_b32 and a fourth read under an exec branch with a wait of its own, in front of every group's MFMAs.)
+    // Same operations on the same values in the same order per element either way.
+    constexpr bool GA = DGQ || KIND == 6;   // the generated operand is A (dgrads) or B (wgrads)
+    constexpr int NLD = AG ? 8 : AG2 ? 4 : 1;
+    float4 ld[NLD];
+    float zc[4] = {0.f, 0.f, 0.f, 0.f};
+    auto gen_read = [&](int g) {
+        const int gg = g0 + g < glast ? g0 + g : glast;   // (= g0 + g for the groups a wave runs)
+        if (GW) ld[0] = *reinterpret_cast<const float4 *>(&s_gw[8 * gg + 4 * h]);
+        if (AG2) {   // rows [Wmu0 Wmu1 Wls0 Wls1]
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ld[e] = *reinterpret_cast<const float4 *>(&s_w8[(8 * gg + 4 * h + e) * 4]);
+        }
+        if (AG) {    // rows [Wmu 0..3 | Wls 0..3]
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ld[e] = *reinterpret_cast<const float4 *>(&s_w8[(8 * gg + 4 * h) * 8 + 4 * e]);
+        }
+    };
+    auto gen_pair = [&](int e0) {   // elements e0, e0 + 1 of the group last read -> zc
+#pragma unroll
+        for (int e = e0; e < e0 + 2; ++e) {
+            if (GW) zc[e] = DGQ ? dqr * f4e(ld[0], e) : f4e(ld[0], e) * gwn;
+            if (AG2) {
+                // act <= 2: the terms of the action slots 2, 3 are exact zeros and add nothing (fma(0, 0, acc) == acc)
+                const float4 w4 = ld[e];
+                float s = fmaf(pdl[0], w4.z, pdm[0] * w4.x);
+                s = fmaf(pdm[1], w4.y, s); s = fmaf(pdl[1], w4.w, s);
+                zc[e] = s;
+            }
+            if (AG) {
+                const float4 m4 = ld[2 * e], l4 = ld[2 * e + 1];
+                float s = fmaf(pdl[0], l4.x, pdm[0] * m4.x);     // (the summation order of the DG_ROWS_C tiles)
+                s = fmaf(pdm[1], m4.y, s); s = fmaf(pdl[1], l4.y, s);
+                s = fmaf(pdm[2], m4.z, s); s = fmaf(pdl[2], l4.z, s);
+                s = fmaf(pdm[3], m4.w, s); s = fmaf(pdl[3], l4.w, s);
+                zc[e] = s;
+            }
+        }
+    };
     DST(kid, 2);
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.f;
@@ -1427,59 +1487,37 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             __builtin_amdgcn_sched_barrier(0);
         }
         if (g < ng) {
-            float4 av4 = a4[g], bv4 = b4[g];
-            if (STEP) {   // wgrads: a plain or a generated B operand
-                if (jb.bgen) {
-                    const float4 d4 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
-                    bv4 = make_float4(bv4.x > 0.f ? d4.x * gwn : 0.f, bv4.y > 0.f ? d4.y * gwn : 0.f, bv4.z > 0.f ? d4.z * gwn : 0.f, bv4.w > 0.f ? d4.w * gwn : 0.f);
-                }
-            } else if (DGQ) {
-                const float4 w3 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
-                av4 = make_float4(av4.x > 0.f ? dqr * w3.x : 0.f, av4.y > 0.f ? dqr * w3.y : 0.f, av4.z > 0.f ? dqr * w3.z : 0.f, av4.w > 0.f ? dqr * w3.w : 0.f);
-            } else if (KIND == 6 && agen2) {
-                // act <= 2: rows [Wmu0 Wmu1 Wls0 Wls1]; the terms of the action slots 2, 3 are exact zeros and add nothing (fma(0, 0, acc) == acc)
-                const float *wk = &s_w8[(8 * (g0 + g) + 4 * h) * 4];
-                float z4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float4 w4 = *reinterpret_cast<const float4 *>(wk + 4 * e);
-                    float acc = fmaf(pdl[0], w4.z, pdm[0] * w4.x);
-                    acc = fmaf(pdm[1], w4.y, acc); acc = fmaf(pdl[1], w4.w, acc);
-                    z4[e] = acc;
-                }
-                av4 = make_float4(av4.x > 0.f ? z4[0] : 0.f, av4.y > 0.f ? z4[1] : 0.f, av4.z > 0.f ? z4[2] : 0.f, av4.w > 0.f ? z4[3] : 0.f);
-            } else if (KIND == 6 && agen) {
-                const float *wk = &s_w8[(8 * (g0 + g) + 4 * h) * 8];
-                float z4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float4 m4 = *reinterpret_cast<const float4 *>(wk + 8 * e), l4 = *reinterpret_cast<const float4 *>(wk + 8 * e + 4);
-                    float acc = fmaf(pdl[0], l4.x, pdm[0] * m4.x);     // (the summation order of the DG_ROWS_C tiles)
-                    acc = fmaf(pdm[1], m4.y, acc); acc = fmaf(pdl[1], l4.y, acc);
-                    acc = fmaf(pdm[2], m4.z, acc); acc = fmaf(pdl[2], l4.z, acc);
-                    acc = fmaf(pdm[3], m4.w, acc); acc = fmaf(pdl[3], l4.w, acc);
-                    z4[e] = acc;
-                }
-                av4 = make_float4(av4.x > 0.f ? z4[0] : 0.f, av4.y > 0.f ? z4[1] : 0.f, av4.z > 0.f ? z4[2] : 0.f, av4.w > 0.f ? z4[3] : 0.f);
-            } else if (KIND == 0 && jb.bgen) {   // (a generated B operand is a wgrad's)
-                const float4 d4 = *reinterpret_cast<const float4 *>(&s_gw[8 * (g0 + g) + 4 * h]);
-                bv4 = make_float4(bv4.x > 0.f ? d4.x * gwn : 0.f, bv4.y > 0.f ? d4.y * gwn : 0.f, bv4.z > 0.f ? d4.z * gwn : 0.f, bv4.w > 0.f ? d4.w * gwn : 0.f);
+            const float4 av4 = a4[g], bv4 = b4[g];
+            if (!GEN) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.x, bv4.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.y, bv4.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.z, bv4.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.w, bv4.w, acc, 0, 0, 0);
+            } else {
+                gen_read(g);
+                gen_pair(0); gen_pair(2);
+                const float4 ld4 = GA ? av4 : bv4;
+                const float x0 = ld4.x > 0.f ? zc[0] : 0.f, x1 = ld4.y > 0.f ? zc[1] : 0.f, x2 = ld4.z > 0.f ? zc[2] : 0.f, x3 = ld4.w > 0.f ? zc[3] : 0.f;
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(GA ? x0 : av4.x, GA ? bv4.x : x0, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(GA ? x1 : av4.y, GA ? bv4.y : x1, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(GA ? x2 : av4.z, GA ? bv4.z : x2, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(GA ? x3 : av4.w, GA ? bv4.w : x3, acc, 0, 0, 0);
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.x, bv4.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.y, bv4.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.z, bv4.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av4.w, bv4.w, acc, 0, 0, 0);
         }
     }
     };
-    switch (kind) {   // block-uniform
+    switch (ksel) {   // block-uniform
     case 0: gemm_tile(DGKind<0>{}); break;
+    case 8: gemm_tile(DGKind<0, 1>{}); break;
     case 1: gemm_tile(DGKind<1>{}); break;
+    case 9: gemm_tile(DGKind<1, 1>{}); break;
     case 2: gemm_tile(DGKind<2>{}); break;
     case 3: gemm_tile(DGKind<3>{}); break;
-    case 4: gemm_tile(DGKind<4>{}); break;
-    case 5: gemm_tile(DGKind<5>{}); break;
-    default: gemm_tile(DGKind<6>{}); break;
+    case 12: gemm_tile(DGKind<4, 1>{}); break;
+    case 13: gemm_tile(DGKind<5, 1>{}); break;
+    case 6: gemm_tile(DGKind<6>{}); break;
+    case 14: gemm_tile(DGKind<6, 1>{}); break;
+    default: gemm_tile(DGKind<6, 2>{}); break;
     }
     // ---- split-K combine.  D layout: col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)
     DST(kid, 3);
@@ -1582,6 +1620,11 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
 }
 
 static void dg_add(DGJobs &js, DGJob j) {
+    // (k_dg compiles a generated operand only into the K loops of the job types that have one)
+    if (j.bgen && !(j.bgen == 1 && j.type == DG_WGRAD_J4) && !(j.bgen == 3 && j.type == DG_DGRAD)) {
+        fprintf(stderr, "dg_add: bgen = %d on a job of type %d (1: a J4 wgrad's B, 3: the policy dgrad's A)\n", j.bgen, j.type);
+        abort();
+    }
     j.gp = j.type == DG_DGRAD_Q ? j.gw : j.gdq;
     j.tiles_m = (j.M + 31) / 32;
     j.ntiles = j.type == DG_LOSS ? 1 : j.tiles_m * ((j.N + 31) / 32);
