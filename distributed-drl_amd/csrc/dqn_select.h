@@ -1,5 +1,5 @@
 // Row-local action selection of the discrete actors, shared by the selection kernel of ddrl_dqn_act (dqn.hip) and the fused
-// discrete rollout step (env.hip: k_env_step_q), so that the two paths cannot drift:
+// discrete rollout step (lander.hip: k_env_step_q), so that the two paths cannot drift:
 //   Double-DQN  algos/dqn/actor_learner.py:194-201   argmax q with probability greedy_prob, a uniform random action otherwise
 //   SQN         algos/sqn/core.py:30-42              argmax of / one draw from softmax(q1 / alpha) (tf.random.multinomial there, an
 //                                                    inverse CDF in float32 on the counter generator's uniform here)

@@ -6,10 +6,11 @@
 // contact points), so the launch is latency-bound: one wave per workgroup spreads the envs over as many CUs as there are waves, and
 // __launch_bounds__(64) leaves the register allocator the whole file (the bodies, joint rows and contact points stay in VGPRs: no
 // scratch — profiles/lander3_resource_usage.txt).
-// These kernels live in a translation unit of their own so that env.hip's kernels compile exactly as before.
+// These kernels live in a translation unit of their own so that lander.hip's kernels compile exactly as before.
 #include "ddrl_common.h"
 #include "env3_device.h"
 #include "dqn_select.h"
+#include "env_launch.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// The lander itself, shared by the batched env kernels (env.hip) and the on-device evaluation episodes (eval.hip): state fields,
+// The lander itself, shared by the batched env kernels (lander.hip) and the on-device evaluation episodes (eval.hip): state fields,
 // constants, the polynomial sin/cos, the counter-hash stream of one (seed, env id, episode) and one env's reset / physics step.
 // Specification: oracle/env_oracle.py (every arithmetic statement of Env mirrors one line of it; float32, no FMA contraction).
 // Internal linkage throughout: every translation unit that includes this compiles its own copy (-fno-gpu-rdc).

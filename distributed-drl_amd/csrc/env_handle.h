@@ -1,5 +1,5 @@
-// The env handle behind ddrl_env_* as the translation units that reach into it see it: env.hip (create / destroy, the step and the
-// fused rollout entry points) and eval3.hip (the evaluation episodes, which borrow the handle's model and own its results block).
+// The env handle behind ddrl_env_* as the translation units that reach into it see it: env.hip (create / destroy, the model table, the
+// step and the fused rollout entry points) and eval3.hip (the evaluation episodes, which borrow the handle's model and own its results block).
 // Host side only: never a kernel argument.
 #pragma once
 #include "ddrl_common.h"
@@ -13,7 +13,7 @@ struct ddrl_env {
     float *S;
     EnvStats *stats;
     int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's and the walker's
-    int fields;           // rows of S: DDRL_ENV_STATE_FIELDS, DDRL_ENV3_STATE_FIELDS or DDRL_ENVW_STATE_FIELDS
+    const struct EnvModel *model;   // the kind's row of env.hip's model table (widths, state fields, launches), set at create
     // ---- evaluation episodes (ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_results, eval3.hip).  Everything below is
     // allocated at the first evaluation, grows when a call needs more, and is freed by ddrl_env_destroy; S and stats above are
     // neither read nor written by an evaluation.
@@ -31,14 +31,11 @@ struct ddrl_env {
     float *ro_block;           // nullptr: no begin call yet
     int ro_actions;            // n_actions of the handle the last begin / step call took: the row width of the Q mirror
 };
-// A walker handle (DDRL_ENV_WALKER: [n,24] observations, [n,4] actions) is taken by reset / step / stats / get_state / set_state only:
-// every other entry point that takes an env handle refuses it with its own name, before it touches anything.
-#define DDRL_REFUSE_WALKER(h, what)                                                                                                   \
-    do {                                                                                                                              \
-        if ((h)->kind == DDRL_ENV_WALKER) {                                                                                           \
-            ::ddrl::set_error("%s: not built for the walker (DDRL_ENV_WALKER: 24 observations, 4 actions); its kernels hold a lander — " \
-                              "use ddrl_actor_act + ddrl_env_step + ddrl_replay_store", what);                                         \
-            return DDRL_ERR_UNSUPPORTED;                                                                                              \
-        }                                                                                                                             \
-    } while (0)
+// Which kinds an entry point takes, as the mask of 1u << DDRL_ENV_*, and the one guard behind every entry point that does not take
+// them all (env.hip, beside the model table): DDRL_OK for a handle of a taken kind, else DDRL_ERR_UNSUPPORTED with `what` — the entry
+// point's name — the two models and what to use instead in ddrl_last_error(), before anything is touched.  `family`: the one-body
+// entry point of the same family (the handle's own model's is named from it); nullptr where only the walker is refused.
+// A walker handle ([n,24] observations, [n,4] actions) is taken by reset / step / step_wrapped_walker / stats / get_state / set_state only.
+constexpr unsigned DDRL_TAKES_LANDERS = 1u << DDRL_ENV_ONE_BODY | 1u << DDRL_ENV_ARTICULATED;
+int ddrl_env_refuse(const ddrl_env *h, unsigned takes, const char *what, const char *family);
 constexpr int DDRL_ROLLOUT_MIRROR_Q = 8;   // ddrl_sel::MAXQ: the widest Q row the fused discrete step takes

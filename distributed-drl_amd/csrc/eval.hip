@@ -10,7 +10,7 @@
 // bias; head partials per group of 16 columns in column order from zero, the groups added in group order, then the head bias; then
 // ddrl_pol::policy_row with eps = 0.  Only the assignment of (column, slice) sums to threads differs: a wave takes 64 consecutive
 // columns of one contraction row per load (256 contiguous bytes) instead of 16 columns of four slices.
-// The env step is Env::physics plus the bookkeeping of k_env_step (env.hip), run by one lane with the env state in registers.
+// The env step is Env::physics plus the bookkeeping of k_env_step (lander.hip), run by one lane with the env state in registers.
 // The kernel body is a template over the env type (eval_episodes.h); this file instantiates it for Env, the one-body lander.
 #include "eval_episodes.h"
 

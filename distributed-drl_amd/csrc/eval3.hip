@@ -55,7 +55,7 @@ int eval_common_check(const char *what, ddrl_env *h, const void *agent, int32_t 
         ddrl::set_error("%s: bad argument: NULL handle", what);
         return DDRL_ERR_BAD_ARG;
     }
-    DDRL_REFUSE_WALKER(h, what);   // no evaluation kernel holds the walker
+    if (const int rc = ddrl_env_refuse(h, DDRL_TAKES_LANDERS, what, nullptr)) return rc;   // no evaluation kernel holds the walker
     if (n_episodes < 1) {
         ddrl::set_error("%s: bad argument: n_episodes must be >= 1 (got %d)", what, (int)n_episodes);
         return DDRL_ERR_BAD_ARG;

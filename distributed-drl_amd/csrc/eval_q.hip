@@ -15,7 +15,7 @@
 // the layer-1 operands and the env state stay in registers, the hidden layers and the partials live in LDS.
 // Selection is ddrl_sel::select_row<8> (dqn_select.h), the function k_dqn_select and k_env_step_q call: step t of episode e of the call
 // owns u0 = U(seed, ctr + 2 (e * max_ep_len + t)) and u1 = U(seed, ctr + 2 (e * max_ep_len + t) + 1) of ddrl_uniform_fill's generator.
-// The env step is ddrl_sel::lander_action, then Env::physics plus the bookkeeping of k_env_step (env.hip), run by one lane.
+// The env step is ddrl_sel::lander_action, then Env::physics plus the bookkeeping of k_env_step (lander.hip), run by one lane.
 // The kernel body is a template over the env type (eval_episodes.h); this file instantiates it for Env, the one-body lander.
 #include "eval_episodes.h"
 

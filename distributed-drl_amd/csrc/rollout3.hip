@@ -1,5 +1,5 @@
 // Fused rollout step on the ARTICULATED lander (ddrl_rollout_begin_articulated / ddrl_rollout_step_articulated): k_env_step_pi's
-// (env.hip) vector step of worker_rollout's policy phase (example/dsac.py:96-130) with Env3's solver (env3_device.h) in the middle —
+// (lander.hip) vector step of worker_rollout's policy phase (example/dsac.py:96-130) with Env3's solver (env3_device.h) in the middle —
 //   a = agent.get_action(o)      the forward launch's head partials, summed in column-tile order, plus the head bias of the env's own
 //                                version slot, through ddrl_pol::policy_row: head_load / head_action (rollout_args.h),
 //                                k_env_step_pi's statements in its order, so the same partials give the same action
@@ -11,10 +11,11 @@
 // for it: everything of the policy phase is consumed BEFORE the env state is loaded — the ring row is known before the step, so o1 and
 // the action go to the ring and to the act mirror first — and only i, the row, the slot and the step's outputs cross physics();
 // o2, r and d are written behind it.  profiles/lander3_rollout_resource_usage.txt holds the compiler's report (no scratch, no spill).
-// A translation unit of its own, as env3.hip: env.hip's and env3.hip's kernels compile exactly as before.
+// A translation unit of its own, as env3.hip: lander.hip's and env3.hip's kernels compile exactly as before.
 #include "ddrl_common.h"
 #include "env3_device.h"
 #include "rollout_args.h"
+#include "env_launch.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // The n-step worker's two env launches on the ARTICULATED lander (ddrl_env_step_wrapped_articulated, ddrl_rollout_step_nstep_articulated):
-//   k_env3_step_wrapped   k_env_step_wrapped (env.hip) statement for statement over Env3 (env3_device.h): `Wrapper(env, obs_noise,
+//   k_env3_step_wrapped   k_env_step_wrapped (lander.hip) statement for statement over Env3 (env3_device.h): `Wrapper(env, obs_noise,
 //                         act_noise, reward_scale, action_repeat)` of algos/sac1/hyperparams.py:107-134 around env.step plus the n-step
 //                         rollout's episode bookkeeping (algos/sac1/sac_ray.py:212-216, 238-258).  One lane per env, one wave per
 //                         workgroup as k_env3_step (env3.hip): the sweeps are one serial chain per env.
@@ -17,7 +17,7 @@
 // The repeat loop is a run-time loop around ONE inlined Env3::physics (a second one sits in Env3::reset, as in every step kernel of this
 // model).  profiles/lander3_nstep_rollout_resource_usage.txt holds the compiler's report (no scratch).
 // As in k_env_step_nstep only the ring ticket and the version counts (ver_plan_tail) cross workgroups: no spin, no fence.
-// A translation unit of its own: the kernels of env.hip, env3.hip, rollout_nstep.hip and rollout3.hip compile exactly as before.
+// A translation unit of its own: the kernels of lander.hip, env3.hip, rollout_nstep.hip and rollout3.hip compile exactly as before.
 #include "ddrl_common.h"
 #include "policy_row.h"
 #include "replay_device.h"
@@ -25,10 +25,11 @@
 #include "version_plan.h"
 #include "rollout_nstep.h"
 #include "rollout_nstep_device.h"
+#include "env_launch.h"
 
 namespace {
 
-constexpr uint32_t RESET_NOISE_STREAM = 0xFFFFFFEFu;   // as env.hip: the Wrapper's reset-observation noise (hyperparams.py:119-121)
+constexpr uint32_t RESET_NOISE_STREAM = 0xFFFFFFEFu;   // as lander.hip: the Wrapper's reset-observation noise (hyperparams.py:119-121)
 
 __device__ __forceinline__ void put_obs(float *dst, long long i, const float *o) {
     float4 *p = reinterpret_cast<float4 *>(dst + i * 8);

@@ -1,5 +1,5 @@
 // Fused DISCRETE rollout step on the ARTICULATED lander (ddrl_rollout_begin_discrete_articulated / ddrl_rollout_step_discrete_articulated):
-// k_env_step_q's (env.hip) vector step of worker_rollout_dqn's policy phase (algos/dqn/train.py:253-274) with Env3's solver
+// k_env_step_q's (lander.hip) vector step of worker_rollout_dqn's policy phase (algos/dqn/train.py:253-274) with Env3's solver
 // (env3_device.h) in the middle, as k_env3_step_pi (rollout3.hip) is k_env_step_pi's —
 //   a = agent.get_action(o)      the Q-head partials of the forward launch in front of this kernel summed in column-tile order, plus the
 //                                head bias of the env's own version slot (ddrl_sel::q_row_from_partials), two uniforms of the counter
@@ -22,6 +22,7 @@
 #include "env3_device.h"
 #include "dqn_select.h"
 #include "rollout_args.h"
+#include "env_launch.h"
 
 namespace {
 

@@ -1,8 +1,8 @@
-// What the continuous fused rollout step's two kernels share: k_env_step_pi (env.hip, the one-body lander) and k_env3_step_pi
+// What the continuous fused rollout step's two kernels share: k_env_step_pi (lander.hip, the one-body lander) and k_env3_step_pi
 // (rollout3.hip, the articulated lander) take the same arguments, finish get_action from the forward's head partials by the same
 // statements and pass the same ring ticket to ver_plan_tail (version_plan.h) — and what the DISCRETE step's two kernels share likewise:
-// k_env_step_q (env.hip) and k_env3_step_q (rollout3_q.hip) take one RolloutQArgs and the same ticket.  Internal linkage throughout, as env_device.h: each
-// translation unit compiles its own copy, and env.hip's kernels compile to the code they compiled to with the two structs in the file.
+// k_env_step_q (lander.hip) and k_env3_step_q (rollout3_q.hip) take one RolloutQArgs and the same ticket.  Internal linkage throughout, as env_device.h: each
+// translation unit compiles its own copy, and lander.hip's kernels compile to the code they compiled to with the two structs in the file.
 #pragma once
 #include "ddrl_common.h"
 #include "policy_row.h"
@@ -57,7 +57,7 @@ struct RolloutArgs {
     float *act_out, *next_obs_out;
 };
 
-// The DISCRETE fused rollout step's arguments: k_env_step_q (env.hip, the one-body lander) and k_env3_step_q (rollout3_q.hip, the
+// The DISCRETE fused rollout step's arguments: k_env_step_q (lander.hip, the one-body lander) and k_env3_step_q (rollout3_q.hip, the
 // articulated lander) take the same struct, as the continuous pair takes RolloutArgs.
 struct RolloutQArgs {
     float *S;
@@ -86,7 +86,7 @@ struct RolloutQArgs {
 
 // get_action's last step for env i, in two halves so that a kernel can issue its other loads between them: k_env_step_pi's own
 // statements in k_env_step_pi's order, so that the same partials give the same action.  (k_env_step_pi keeps them inline: calling
-// these two functions there changed that kernel's register allocation, and env.hip's kernels are to compile as they did.)
+// these two functions there changed that kernel's register allocation, and lander.hip's kernels are to compile as they did.)
 // head_load: the forward launch's head partials (mu heads 0..act-1, log_std heads act..2act-1), NA = 2 (act_dim <= 2) or 4 action
 // columns.  (Two statically indexed register arrays: one array indexed by `c + act` would live in scratch memory.)
 template <int NA>
@@ -139,11 +139,4 @@ __device__ __forceinline__ float2 head_action(const RolloutArgs &a, long long i,
 
 }  // namespace
 
-// The articulated model's fused launches (rollout3.hip) as env.hip's entry points reach them.  `args` points to a RolloutArgs: the
-// struct has internal linkage in each translation unit (above), so it crosses the boundary as bytes; vit / pit are the handle's
-// iteration counts.  ddrl_rollout3_launch_obs writes Env3::obs of every env's state into obs_d[n][8] (no reset, no step).
-int ddrl_rollout3_launch_step(const void *args, int vit, int pit, void *stream);
-int ddrl_rollout3_launch_obs(const float *S, long long n, float *obs_d, void *stream);
-// ... and the discrete step (rollout3_q.hip): `args` points to a RolloutQArgs whose three mirrors are set; versioned selects the
-// instantiation with the version store (slot / newest / vp are read then only)
-int ddrl_rollout3_launch_step_q(const void *args, int versioned, int vit, int pit, void *stream);
+// (The launch functions that take these structs as bytes: env_launch.h.)

@@ -61,13 +61,4 @@ struct NStepLaunch {
     float *act_out, *obs2_out, *rew_out, *done_out, *next_obs_out;
     uint8_t *ended_out;
 };
-int ddrl_nstep_launch_step(const NStepLaunch &a, void *stream);
-// obs_d[n][8] = the newest entry of every env's o_queue (the observation its worker holds); rdy_d[i] = readiness of t_queue[i] (i < n)
-int ddrl_nstep_launch_begin(const float *qo, long long n, int Ln, float *obs_d, const int *t_queue, int save_freq, uint8_t *rdy_d, void *stream);
-// ... and the same two launches of the articulated lander (rollout3_nstep.hip): the n-step fused step with Env3's solver in the middle
-// (the begin call's launch is ddrl_nstep_launch_begin above: it reads the queues only), and the wrapped step of an articulated handle.
-// vit / pit: the handle's iteration counts.
-int ddrl_nstep3_launch_step(const NStepLaunch &a, int vit, int pit, void *stream);
-int ddrl_env3_launch_step_wrapped(float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d, float act_noise,
-                                  float obs_noise, float reward_scale, int repeat, float *obs2_d, float *rew_d, float *done_d,
-                                  float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+// (ddrl_nstep_launch_step / ddrl_nstep_launch_begin and the articulated lander's ddrl_nstep3_launch_step: env_launch.h.)

@@ -1,9 +1,9 @@
 // Fused n-step rollout step (RolloutDeviceNStep._step_once = num_envs iterations of worker_rollout of the n-step driver,
-// algos/sac1/sac_ray.py:208-262, in the policy phase), the sibling of k_env_step_pi / k_env_step_q (env.hip) for the window-queue worker.
+// algos/sac1/sac_ray.py:208-262, in the policy phase), the sibling of k_env_step_pi / k_env_step_q (lander.hip) for the window-queue worker.
 // Behind the actor's forward launch, ONE kernel does per env, in this order, what the unfused sequence does in seven launches:
 //   a.  a = agent.get_action(o)       head partials summed in n-tile order + the bias of the env's version slot, counter-hash noise,
 //                                     ddrl_pol::policy_row (k_actor_finish of sac1.hip; the head of k_env_step_pi)
-//   b.  o2, r, d = Wrapper.step(a)    k_env_step_wrapped of env.hip, statement for statement (hyperparams.py:122-134, sac_ray.py:212-221)
+//   b.  o2, r, d = Wrapper.step(a)    k_env_step_wrapped of lander.hip, statement for statement (hyperparams.py:122-134, sac_ray.py:212-221)
 //   c.  the queues                    k_winq_push of winq.hip: the o / a / r / d windows slide by one and take (o2, noisy a, r, d);
 //                                     ready = t >= Ln && t % save_freq == 0; t += 1 (sac_ray.py:229-248)
 //   d.  replay_buffer.store(queues)   ready envs: the window becomes ring row (ptr + rank) % capacity, rank = ready envs of smaller index
@@ -32,10 +32,11 @@
 #include "version_plan.h"
 #include "rollout_nstep.h"
 #include "rollout_nstep_device.h"
+#include "env_launch.h"
 
 namespace {
 
-constexpr uint32_t RESET_NOISE_STREAM = 0xFFFFFFEFu;   // as env.hip: the Wrapper's reset-observation noise (hyperparams.py:119-121)
+constexpr uint32_t RESET_NOISE_STREAM = 0xFFFFFFEFu;   // as lander.hip: the Wrapper's reset-observation noise (hyperparams.py:119-121)
 // (NStepTicket, slide_store and the env-agnostic phases: rollout_nstep_device.h, shared with k_env3_step_nstep of rollout3_nstep.hip)
 __global__ void __launch_bounds__(64) k_env_step_nstep(NStepLaunch a) {
     extern __shared__ float4 s_win[];            // 64 x (Ln + 1) x 2 float4

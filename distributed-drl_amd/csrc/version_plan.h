@@ -1,4 +1,4 @@
-// The version store's side of an env-step launch, shared by the continuous and the discrete fused rollout step (env.hip: k_env_step_pi,
+// The version store's side of an env-step launch, shared by the continuous and the discrete fused rollout step (lander.hip: k_env_step_pi,
 // k_env_step_q<.., true>) so that the two paths cannot drift.  The tables it writes are those of policy_row.h (VerTile, VerState, ver_split),
 // read by the versioned policy / Q forward (k_actor_fwd<.., true>, sac1_direct.h).
 #pragma once

@@ -7,9 +7,10 @@
 // __launch_bounds__(64) leaves the register allocator the whole file.  What does not fit it lives in LDS, never in scratch memory
 // (profiles/walker_resource_usage.txt).  The step kernel holds ONE instance of the physics step: the reset of an env whose episode ended
 // is a second trip through the same loop body, not a second inlined copy.
-// These kernels live in a translation unit of their own so that env.hip's and env3.hip's kernels compile exactly as before.
+// These kernels live in a translation unit of their own so that lander.hip's and env3.hip's kernels compile exactly as before.
 #include "ddrl_common.h"
 #include "walker_device.h"
+#include "env_launch.h"
 
 namespace {
 

@@ -13,13 +13,14 @@
 // on the last action trip (every earlier assignment of hyperparams.py:134 is overwritten), and "no observation noise" is the uniform
 // test repeat == 1 (:132-133 is the only branch that clears it).  The Wrapper's scalars are wave-uniform.
 // profiles/walker_wrapped_resource_usage.txt holds the compiler's report (no scratch, no VGPR spill).
-// A translation unit of its own: the kernels of walker.hip, env.hip, env3.hip and rollout*.hip compile exactly as before.
+// A translation unit of its own: the kernels of walker.hip, lander.hip, env3.hip and rollout*.hip compile exactly as before.
 #include "ddrl_common.h"
 #include "walker_device.h"
+#include "env_launch.h"
 
 namespace {
 
-constexpr uint32_t RESET_NOISE_STREAM = 0xFFFFFFEFu;   // as env.hip: the Wrapper's reset-observation noise (hyperparams.py:119-121)
+constexpr uint32_t RESET_NOISE_STREAM = 0xFFFFFFEFu;   // as lander.hip: the Wrapper's reset-observation noise (hyperparams.py:119-121)
 // The observation noise behind PSTEP st1 is drawn at "step" OBS_NOISE_STEP0 + 2 st1, indices 0..23: 32 hash inputs per PSTEP value in a
 // range of their own (0x40000000 + 32 st1 + k).  The landers' layout (indices 4.. of step st1) does not carry over to 24 observations:
 // the block would reach into step st1 + 1, where an early break draws again under the same episode seed (tests/walker_wrapped_oracle.py).

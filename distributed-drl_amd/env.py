@@ -2,7 +2,7 @@
 
 Stands where the reference calls `gym.make('LunarLanderContinuous-v2')`, `env.reset()`,
 `env.step(a)` and `env.action_space.sample()` (example/dsac.py:78-79,99,102,127).  gym/Box2D are
-not available; the dynamics are this build's own Box2D-style model (csrc/env.hip; specification
+not available; the dynamics are this build's own Box2D-style model (csrc/lander.hip; specification
 and caveats in oracle/env_oracle.py's header and DESIGN.md §env).
 """
 import ctypes
@@ -151,7 +151,9 @@ class VecBipedalWalker(VecLunarLander):
     obs_dim, act_dim, act_high = 24, 4, 1.0
     model = "walker"
 
-    def __init__(self, n_envs, seed=0, max_ep_len=1600, device=None, velocity_iterations=180, position_iterations=60):
+    def __init__(self, n_envs, seed=0, max_ep_len=1600, device=None, velocity_iterations=180, position_iterations=60, model="walker"):
+        if model != "walker":   # (taken so that every class of MODELS is built with the same keywords)
+            raise ValueError("VecBipedalWalker is the env of model=\"walker\": %r" % (model,))
         _lib.require_gpu()
         self._lib = _lib.load()
         self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)
@@ -238,6 +240,25 @@ class VecLunarLanderDiscrete(VecLunarLander):
         _lib.check(self._lib.ddrl_uniform_fill(_lib.dptr(out), self.n, 0.0, 4.0, self.seed ^ 0x5EED5EED, self._sample_ctr, _lib.stream_ptr()))
         self._sample_ctr += self.n
         return torch.floor_(out)
+
+
+# The C entry points of each env model, by `env.model`: what workers.py reads where a worker's calls depend on the model (the library's
+# side of this table is csrc/env.hip's model table).  cls: the vectorised env of the continuous workers; dims: the (obs_dim, act_dim) its
+# worker writes into its options (None: the options keep theirs — a lander's policy may have one action or two); wrapped: the env's wrapped-step method; fused: per fused family — "pi" (RolloutDevice), "q" (RolloutDeviceDQN), "nstep"
+# (RolloutDeviceNStep) — the (begin, step) entry-point NAMES, whether the pair is opt-in (taken only where the worker's own
+# `opt.fused_*_articulated` flag is set) and whether the step takes handles only, its mirrors being a block the env handle owns (rollout_mirrors).  A
+# family is missing where no fused launch holds the model.
+MODELS = {
+    "simple": dict(cls=VecLunarLander, dims=None, wrapped="step_wrapped", fused={
+        "pi": ("ddrl_rollout_begin", "ddrl_rollout_step", False, False),
+        "q": ("ddrl_rollout_begin_discrete", "ddrl_rollout_step_discrete", False, False),
+        "nstep": ("ddrl_rollout_begin_nstep", "ddrl_rollout_step_nstep", False, False)}),
+    "articulated": dict(cls=VecLunarLander, dims=None, wrapped="step_wrapped_articulated", fused={
+        "pi": ("ddrl_rollout_begin_articulated", "ddrl_rollout_step_articulated", True, False),
+        "q": ("ddrl_rollout_begin_discrete_articulated", "ddrl_rollout_step_discrete_articulated", True, True),
+        "nstep": ("ddrl_rollout_begin_nstep_articulated", "ddrl_rollout_step_nstep_articulated", True, False)}),
+    "walker": dict(cls=VecBipedalWalker, dims=(24, 4), wrapped="step_wrapped_walker", fused={}),
+}
 
 
 class _ActionSpace:

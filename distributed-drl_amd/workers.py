@@ -620,6 +620,17 @@ def _env_model_kw(opt):
                 position_iterations=int(getattr(opt, "env_position_iterations", 60)))
 
 
+def _vec_env(opt, worker_index, max_ep_len):
+    """The envs of a continuous worker: `opt.num_envs` of the class env.MODELS names for `opt.env_model`, seeded per worker.  Where the
+    model fixes the policy's shape (the walker) `opt.obs_dim, opt.act_dim` are set from it."""
+    from .env import MODELS
+    kw = _env_model_kw(opt)
+    m = MODELS[kw.get("model", "simple")]
+    if m["dims"] is not None:
+        opt.obs_dim, opt.act_dim = m["dims"]
+    return m["cls"](int(opt.num_envs), seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=max_ep_len, **kw)
+
+
 def _no_walker(opt, who, why):
     if getattr(opt, "env_model", "simple") == "walker":
         raise ValueError("%s: opt.env_model = \"walker\" is not built for this worker (%s); workers.RolloutDevice and "
@@ -648,7 +659,24 @@ class _RolloutWorker:
     `auto_pull`: step() looks at the server itself; FreeRunningLoop turns it off and pulls at segment boundaries."""
 
     _flat_pull = True     # pull() takes the actor's keys as one span of the server's flat table where it has one
+    _family = None        # the worker's fused family in env.MODELS[model]["fused"]: "pi", "q" or "nstep"
     _t_per_step = 1       # what one vector step adds to `t`
+
+    def _fused_pair(self):
+        """env.MODELS' entry of this worker's fused family on its envs' model: (begin name, step name, opt-in, handles only), or
+        None where no fused launch holds the model."""
+        from .env import MODELS
+        return MODELS[self.env.model]["fused"].get(self._family)
+
+    def _fused_on_model(self, opted_in):
+        """The envs' model has a fused pair for this worker, and where that pair is opt-in the worker's flag (`opted_in`) is set."""
+        pair = self._fused_pair()
+        return pair is not None and (not pair[2] or bool(opted_in))
+
+    def _rollout_calls(self):
+        """The fused pair of the envs' model: (begin, step) of the C library."""
+        begin, step = self._fused_pair()[:2]
+        return getattr(self.actor._lib, begin), getattr(self.actor._lib, step)
 
     def _start(self, ps, fused, adopt):
         """The shared state, then the initial pull (dsac.py:88-90).  fused: the worker's opt-out flag; adopt: its default."""
@@ -775,15 +803,8 @@ class RolloutDevice(_RolloutWorker):
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
         from .agent import Actor
-        from .env import VecBipedalWalker, VecLunarLander
         self.rb, self.opt = replay_buffer, opt
-        kw = _env_model_kw(opt)
-        if kw.get("model") == "walker":
-            del kw["model"]
-            opt.obs_dim, opt.act_dim = VecBipedalWalker.obs_dim, VecBipedalWalker.act_dim
-            self.env = VecBipedalWalker(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len, **kw)
-        else:
-            self.env = VecLunarLander(opt.num_envs, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=opt.max_ep_len, **kw)
+        self.env = _vec_env(opt, worker_index, opt.max_ep_len)
         self.actor = Actor(opt, job="worker", max_rows=opt.num_envs, index=worker_index)
         self.t = 0
         self.o = torch.empty_like(self.env.obs)
@@ -792,19 +813,13 @@ class RolloutDevice(_RolloutWorker):
         if self.adopt == "episode":
             self._fused_ready()   # the version store starts from the initial pull, before any step
 
-    def _rollout_calls(self):
-        """The fused pair of the envs' model: (begin, step) of the C library."""
-        lib = self.actor._lib
-        if self.env.model == "articulated":
-            return lib.ddrl_rollout_begin_articulated, lib.ddrl_rollout_step_articulated
-        return lib.ddrl_rollout_begin, lib.ddrl_rollout_step
+    _family = "pi"
 
     def _fused_eligible(self):
         from .replay import ReplayBuffer
         ok = isinstance(self.rb, ReplayBuffer) and not getattr(self.rb, "_acts_1d", False) and self.env.n % 32 == 0
         # ddrl_rollout_begin holds the one-body lander and refuses the other; the articulated pair is opt-in
-        return ok and (self.env.model == "simple" or
-                       (self.env.model == "articulated" and bool(getattr(self.opt, "fused_rollout_articulated", False))))
+        return ok and self._fused_on_model(getattr(self.opt, "fused_rollout_articulated", False))
 
     def _fused_begin(self):
         from . import _lib
@@ -835,6 +850,7 @@ class RolloutDeviceDQN(_RolloutWorker):
     copy of the Q mirror.  The one-body worker ignores the flag."""
 
     _flat_pull = False
+    _family = "q"
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
@@ -874,18 +890,18 @@ class RolloutDeviceDQN(_RolloutWorker):
         from .replay import ReplayBuffer
         ok = isinstance(self.rb, ReplayBuffer) and getattr(self.rb, "_acts_1d", False) and not getattr(self.rb, "compact_obs", False)
         # ddrl_rollout_begin_discrete holds the one-body lander and refuses the other; the articulated pair is opt-in
-        return ok and (self.env.model == "simple" or
-                       (self.env.model == "articulated" and bool(getattr(self.opt, "fused_discrete_rollout_articulated", False))))
+        return ok and self._fused_on_model(getattr(self.opt, "fused_discrete_rollout_articulated", False))
+
+    def _handle_mirrors(self):
+        """The fused pair of the envs' model takes handles only: its mirrors are the env handle's own block (the articulated lander)."""
+        return self._fused_pair()[3]
 
     def _fused_begin(self):
         from . import _lib
-        lib = self.actor._lib
-        if self.env.model == "articulated":
-            return lib.ddrl_rollout_begin_discrete_articulated(self.env._h, self.actor._h, _lib.stream_ptr())
-        return lib.ddrl_rollout_begin_discrete(self.env._h, self.actor._h, _lib.stream_ptr())
+        return self._rollout_calls()[0](self.env._h, self.actor._h, _lib.stream_ptr())
 
     def _fused_decided(self, ok):
-        if ok and self.env.model == "articulated":
+        if ok and self._handle_mirrors():
             # the begin call has put the envs' observations into the next-observation mirror: from here on env.obs and act are the
             # handle's own mirrors, whichever sequence steps the envs (`_q_mirror`: the source of the copy into q_out)
             self.act, self._q_mirror, self.env.obs = self.env.rollout_mirrors()
@@ -894,15 +910,15 @@ class RolloutDeviceDQN(_RolloutWorker):
     def _fused_step(self, n_steps):
         from . import _lib
         env, a = self.env, self.actor
-        if env.model == "articulated":
-            _lib.check(a._lib.ddrl_rollout_step_discrete_articulated(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
-                                                                     a._noise_seed, a._noise_ctr, _lib.stream_ptr()))
+        step = self._rollout_calls()[1]
+        if self._handle_mirrors():
+            _lib.check(step(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob), a._noise_seed, a._noise_ctr,
+                            _lib.stream_ptr()))
             if self.q_out is not None:
                 self.q_out.copy_(self._q_mirror)
         else:
-            _lib.check(a._lib.ddrl_rollout_step_discrete(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob),
-                                                         a._noise_seed, a._noise_ctr, _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs),
-                                                         _lib.stream_ptr()))
+            _lib.check(step(env._h, a._h, self.rb._h, n_steps, _lib.DDRL_ACT_SAMPLE, float(a.greedy_prob), a._noise_seed, a._noise_ctr,
+                            _lib.dptr(self.act), _lib.dptr(self.q_out), _lib.dptr(env.obs), _lib.stream_ptr()))
         a._noise_ctr += n_steps * 2 * env.n
 
 
@@ -979,24 +995,20 @@ class RolloutDeviceNStep(_RolloutWorker):
         import numpy as np
         import torch
         from .agent import Actor
-        from .env import VecBipedalWalker, VecLunarLander
+        from .env import MODELS
         self.opt = opt
         self.rbs = list(replay_buffers) if isinstance(replay_buffers, (list, tuple)) else [replay_buffers]
         n = int(opt.num_envs)
-        kw = _env_model_kw(opt)
-        if kw.get("model") == "walker":
+        model = getattr(opt, "env_model", "simple")
+        dims = MODELS[model]["dims"] if model in MODELS else None
+        if dims is not None:
             from .replay import ReplayBufferNStep
-            dims = (VecBipedalWalker.obs_dim, VecBipedalWalker.act_dim)
-            for rb in self.rbs:     # before anything is allocated: the window rings must hold the walker's rows
+            for rb in self.rbs:     # before anything is allocated: the window rings must hold the model's rows
                 if not isinstance(rb, ReplayBufferNStep) or (rb.obs_dim, rb.act_dim) != dims:
-                    raise ValueError("RolloutDeviceNStep: opt.env_model = \"walker\" stores windows of %d observations / %d actions and "
+                    raise ValueError("RolloutDeviceNStep: opt.env_model = \"%s\" stores windows of %d observations / %d actions and "
                                      "needs ReplayBufferNStep rings of that shape, got %s%s"
-                                     % (dims + (type(rb).__name__, " of %s / %s" % (getattr(rb, "obs_dim", "?"), getattr(rb, "act_dim", "?")))))
-            del kw["model"]
-            opt.obs_dim, opt.act_dim = dims
-            self.env = VecBipedalWalker(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23, **kw)
-        else:
-            self.env = VecLunarLander(n, seed=int(opt.seed) + 1000003 * int(worker_index), max_ep_len=1 << 23, **kw)
+                                     % ((model,) + dims + (type(rb).__name__, " of %s / %s" % (getattr(rb, "obs_dim", "?"), getattr(rb, "act_dim", "?")))))
+        self.env = _vec_env(opt, worker_index, 1 << 23)
         self.limit_steps = -(-int(opt.max_ep_len) // int(opt.action_repeat))   # ep_len * action_repeat >= max_ep_len (sac_ray.py:252)
         self.actor = Actor(opt, job="worker", max_rows=n, index=worker_index)
         self.filling_steps = 0
@@ -1054,18 +1066,12 @@ class RolloutDeviceNStep(_RolloutWorker):
         from . import _lib
         from .replay import ReplayBufferNStep
         # ddrl_rollout_begin_nstep holds the one-body lander and refuses the other; the articulated pair is opt-in
-        ok = self.env.model == "simple" or (self.env.model == "articulated" and
-                                            bool(getattr(self.opt, "fused_nstep_rollout_articulated", False)))
+        ok = self._fused_on_model(getattr(self.opt, "fused_nstep_rollout_articulated", False))
         ok = ok and self._versions and all(isinstance(rb, ReplayBufferNStep) for rb in self.rbs)
         ok = ok and self.env.n % 32 == 0 and self.winq.Ln <= _lib.DDRL_NSTEP_FUSED_MAX_LN
         return ok and all(rb.max_size < (1 << 31) and rb.Ln == self.winq.Ln and (rb.obs_dim, rb.act_dim) == (8, 2) for rb in self.rbs)
 
-    def _rollout_calls(self):
-        """The fused pair of the envs' model: (begin, step) of the C library."""
-        lib = self.actor._lib
-        if self.env.model == "articulated":
-            return lib.ddrl_rollout_begin_nstep_articulated, lib.ddrl_rollout_step_nstep_articulated
-        return lib.ddrl_rollout_begin_nstep, lib.ddrl_rollout_step_nstep
+    _family = "nstep"
 
     def _fused_begin(self):
         from . import _lib
@@ -1112,8 +1118,8 @@ class RolloutDeviceNStep(_RolloutWorker):
         else:
             env.sample_actions(out=self.act)
             self.filling_steps += 1
-        wrapped = (env.step_wrapped_walker if env.model == "walker" else
-                   env.step_wrapped_articulated if env.model == "articulated" else env.step_wrapped)
+        from .env import MODELS
+        wrapped = getattr(env, MODELS[env.model]["wrapped"])
         o2, r, d, next_obs, ended = wrapped(self.act, getattr(opt, "act_noise", 0.0), getattr(opt, "obs_noise", 0.0),
                                             getattr(opt, "reward_scale", 1.0), self.WRAPPER_REPEAT, self.limit_steps)
         ready = self.winq.push(o2, self.act, r, d)

@@ -1,7 +1,7 @@
 """ORACLE — TEST INFRASTRUCTURE ONLY.
 
 NumPy (float32, vectorised over envs) restatement of the build's batched lander environment
-(csrc/env.hip).  It stands where the reference calls gym's LunarLanderContinuous-v2
+(csrc/lander.hip).  It stands where the reference calls gym's LunarLanderContinuous-v2
 (example/dsac.py:78-79,102,127; algos/sac1/sac1.py:162,185,213).
 
 PARITY UNPINNED against the reference's environment: gym and Box2D are third-party, absent from

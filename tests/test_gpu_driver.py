@@ -488,7 +488,7 @@ def test_vectorised_rollout_never_acts_on_weights_older_than_the_reference_worke
     roll = RolloutDevice(ps, rb, opt)
     assert roll._fused_ready()
     push_after = {2: 1, 3: 2, 9: 3, 10: 4, 11: 5, 20: 6, 33: 7}          # step -> version pushed right after it
-    EPI = 13                                                          # csrc/env.hip: per-env episode counter
+    EPI = 13                                                          # csrc/env_device.h: per-env episode counter
     epi_before = roll.env.get_state()[EPI].cpu().numpy().copy()
     last_end = np.full(n, -1)                                         # the step in which env i last ended an episode (-1: the initial pull)
     pushed_by = lambda s: max([0] + [v for k, v in push_after.items() if k <= s])   # newest version pushed after a step <= s
@@ -556,7 +556,7 @@ def test_vectorised_rollout_equals_n_reference_workers_in_the_weights_each_env_a
         if s < 12 or (20 <= s < 20 + limit + 3) or (s >= 20 + 2 * limit + 12 and rs.rand() < 0.4):
             v += 1
             push_after[s] = v
-    EPLEN, EPI = 10, 13                                       # csrc/env.hip: per-env episode length / episode counter
+    EPLEN, EPI = 10, 13                                       # csrc/env_device.h: per-env episode length / episode counter
     st0 = roll.env.get_state()
     st0[EPLEN] = torch.arange(n, device="cuda").float() % limit   # stagger the time limits: episode ends in every step, env by env
     roll.env.set_state(st0)

@@ -32,7 +32,7 @@ import numpy as np
 
 from walker_oracle import ACT, EPI, EPLEN, EPRET, OBS, PSTEP, F, WalkerOracle
 
-RESET_NOISE_STREAM = 0xFFFFFFEF   # the value csrc/env.hip and csrc/rollout3_nstep.hip use for the Wrapper's reset-observation noise
+RESET_NOISE_STREAM = 0xFFFFFFEF   # the value csrc/lander.hip and csrc/rollout3_nstep.hip use for the Wrapper's reset-observation noise
 ACT_J0 = 2                        # first RNG index of the action noise
 OBS_NOISE_STEP0 = 0x04000000      # the observation noise of PSTEP st1 is drawn at "step" OBS_NOISE_STEP0 + 2 st1, indices 0..23
 
