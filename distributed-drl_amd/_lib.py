@@ -239,6 +239,10 @@ class DdrlUnsupported(DdrlError):
 SIGNATURES_WALKER = {
     "ddrl_env_step_wrapped_walker": SIGNATURES["ddrl_env_step_wrapped"],   # the arguments of its one-body twin
 }
+# include/ddrl_walker_eval.h, likewise
+SIGNATURES_WALKER_EVAL = {
+    "ddrl_env_eval_policy_walker": SIGNATURES["ddrl_env_eval_policy"],     # the arguments of the landers' entry point
+}
 
 
 def load():
@@ -254,7 +258,7 @@ def load():
             "libddrl_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C distributed-drl_amd/csrc`; there is no CPU fallback for the product path" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items()):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

@@ -550,15 +550,16 @@ class Model(Learner):
 
 def _device_episodes(actor, test_env, n, max_ep_len):
     """The episodes of Actor.test / Model.test_agent on an env.DeviceLunarLander: `actor.evaluate` from the env's episode count
-    on, which then advances by n (a marker of the articulated model: `actor.evaluate_env`, the handle-fed launch of that model).
+    on, which then advances by n (a marker of the articulated model or of the walker, env.DeviceBipedalWalker: `actor.evaluate_env`,
+    the handle-fed launch of that model).
     -> the n returns as Python floats, in episode order (what the host loop's `ep_ret`s are).
-    Outside the kernel's envelope (DDRL_ERR_UNSUPPORTED: a hidden width > 512) a host LunarLander of the same seed, positioned
-    at the same episode, is stepped instead."""
+    Outside the kernel's envelope (DDRL_ERR_UNSUPPORTED: a hidden width > 512) the marker's host_env() — a host env of the same seed
+    and model, positioned at the same episode — is stepped instead."""
     if int(test_env.max_ep_len) != int(max_ep_len):
         raise ValueError("the test env's max_ep_len (%d) must equal the agent's (%d): the device plays whole episodes"
                          % (test_env.max_ep_len, max_ep_len))
     try:
-        if getattr(test_env, "model", "simple") != "simple":   # the articulated lander: the handle-fed launch (ddrl_env_eval_policy)
+        if getattr(test_env, "model", "simple") != "simple":   # the articulated lander, the walker: the handle-fed launch of the model
             rets = [float(x) for x in actor.evaluate_env(test_env, n)["ret"]]
         else:
             rets = [float(x) for x in actor.evaluate(n, test_env.seed, test_env.episodes_played, max_ep_len)["ret"]]
@@ -701,18 +702,21 @@ class Actor(_Net):
         return out
 
     def evaluate_env(self, dev_env, n=25, first_episode=None, trace=False):
-        """n deterministic evaluation episodes of `dev_env`'s model — an env.DeviceLunarLander of either model — as one launch fed from
-        handles (ddrl_env_eval_policy, csrc/eval3.hip): episode e is the (first_episode + e)-th episode a host
-        `LunarLander(dev_env.seed, dev_env.max_ep_len, model=...)` plays (default: from dev_env.episodes_played on; the count is NOT
-        advanced here), acted on with this actor's current weights — the library reads them out of the actor handle — by
-        get_action(o, deterministic=True)'s arithmetic.  -> the dict `evaluate` returns, read from the results block the marker's
-        handle owns.  The actor's weights and noise counter and the lending handle's env state are untouched."""
+        """n deterministic evaluation episodes of `dev_env`'s model — an env.DeviceLunarLander of either lander model or an
+        env.DeviceBipedalWalker — as one launch fed from handles, through the model's entry point in env.MODELS (the landers:
+        ddrl_env_eval_policy, csrc/eval3.hip; the walker: ddrl_env_eval_policy_walker, csrc/walker_eval.hip): episode e is the
+        (first_episode + e)-th episode a host env of the marker's seed, max_ep_len and model plays (default: from
+        dev_env.episodes_played on; the count is NOT advanced here), acted on with this actor's current weights — the library reads them
+        out of the actor handle — by get_action(o, deterministic=True)'s arithmetic.  -> the dict `evaluate` returns, read from the
+        results block the marker's handle owns; a trace row is the model's: 12 floats on the landers, 32 on the walker (obs[24] acted
+        on, act[4], rew, ended, two zeros).  The actor's weights and noise counter and the lending handle's env state are untouched."""
+        from .env import MODELS, eval_results
         n = int(n)
         first = int(dev_env.episodes_played if first_episode is None else first_episode)
         vec = dev_env.handle()
-        _lib.check(self._lib.ddrl_env_eval_policy(vec._h, self._h, n, first, 1 if trace else 0, _lib.stream_ptr()))
-        from .env import eval_results
-        return eval_results(vec, 12)
+        entry, row = MODELS[dev_env.model]["eval"]
+        _lib.check(getattr(self._lib, entry)(vec._h, self._h, n, first, 1 if trace else 0, _lib.stream_ptr()))
+        return eval_results(vec, row)
 
     def test(self, test_env, replay_buffer=None, n=25):
         """Deterministic evaluation episodes (actor_learner.py:199-218); returns the mean return.  With opt.summary_dir set the

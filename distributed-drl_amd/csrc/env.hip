@@ -1,5 +1,5 @@
 // The C ABI of the env family: every ddrl_env_* and ddrl_rollout_* entry point that takes an env handle (the evaluation episodes:
-// eval3.hip), the fused-step drivers and their envelopes, behind ONE model table — a row per DDRL_ENV_* kind with the model's widths
+// eval3.hip, walker_eval.hip), the fused-step drivers and their envelopes, behind ONE model table — a row per DDRL_ENV_* kind with the model's widths
 // and its launch functions.  Host code only: every kernel lives in its model's own translation unit (lander.hip; env3.hip,
 // rollout3*.hip; walker*.hip; rollout_nstep.hip) and is reached through env_launch.h, so an edit here cannot change what a kernel
 // compiles to.
@@ -14,7 +14,7 @@
 #include "rollout_args.h"
 #include "env_launch.h"
 
-// struct ddrl_env: env_handle.h (shared with eval3.hip, whose evaluation entry points own the handle's results block)
+// struct ddrl_env: env_handle.h (shared with eval3.hip and walker_eval.hip, whose evaluation entry points own the handle's results block)
 
 // ---- the model table -----------------------------------------------------------------------------------------------------------
 // One row per kind.  A launch pointer is null where the model has no such kernel (the walker's fused family).
@@ -71,7 +71,8 @@ static const EnvModel *env_model_of(int kind) {
 
 // The one guard of the family (env_handle.h).  Three texts, as the entry points have always answered:
 // a walker handle at a lander's entry point; a lander handle at an entry point of the one-body model; a handle at an entry point
-// built for another model than the one-body one, which names the handle's own entry point of the same family.
+// built for another model than the one-body one, which names the handle's own entry point of the same family (`family` + the held
+// model's suffix — or `family` as it is where both landers share that one function).
 int ddrl_env_refuse(const ddrl_env *h, unsigned takes, const char *what, const char *family) {
     const EnvModel &held = *h->model;
     if (takes >> h->kind & 1u) return DDRL_OK;
@@ -86,8 +87,14 @@ int ddrl_env_refuse(const ddrl_env *h, unsigned takes, const char *what, const c
     if (built->kind == DDRL_ENV_ONE_BODY)
         ::ddrl::set_error("%s: not built for %s (%s); its kernel holds %s — "
                           "use ddrl_env_step / ddrl_env_step_discrete with the unfused act and store calls", what, held.noun, held.flag, built->noun);
-    else
-        ::ddrl::set_error("%s: built for %s (%s); this handle holds %s — use %s%s", what, built->noun, built->flag, held.noun, family, held.suffix);
+    else {
+        // a family whose lander entry point is ONE function for both landers (eval3.hip) is named as it is, without the model's suffix
+        static const char *const both_landers[] = {"ddrl_env_eval_policy"};
+        const char *suffix = held.suffix;
+        for (const char *f : both_landers)
+            if (strcmp(family, f) == 0) suffix = "";
+        ::ddrl::set_error("%s: built for %s (%s); this handle holds %s — use %s%s", what, built->noun, built->flag, held.noun, family, suffix);
+    }
     return DDRL_ERR_UNSUPPORTED;
 }
 

@@ -1,5 +1,6 @@
 // The env handle behind ddrl_env_* as the translation units that reach into it see it: env.hip (create / destroy, the model table, the
-// step and the fused rollout entry points) and eval3.hip (the evaluation episodes, which borrow the handle's model and own its results block).
+// step and the fused rollout entry points), eval3.hip and walker_eval.hip (the evaluation episodes, which borrow the handle's model and own
+// its results block; what the two share on the host: eval_host.h).
 // Host side only: never a kernel argument.
 #pragma once
 #include "ddrl_common.h"
@@ -14,7 +15,8 @@ struct ddrl_env {
     EnvStats *stats;
     int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's and the walker's
     const struct EnvModel *model;   // the kind's row of env.hip's model table (widths, state fields, launches), set at create
-    // ---- evaluation episodes (ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_results, eval3.hip).  Everything below is
+    // ---- evaluation episodes (ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_results, eval3.hip; ddrl_env_eval_policy_walker,
+    // walker_eval.hip).  Everything below is
     // allocated at the first evaluation, grows when a call needs more, and is freed by ddrl_env_destroy; S and stats above are
     // neither read nor written by an evaluation.
     unsigned char *ev_block;   // ret float64 [n] | len int32 [n] | trace float32 [n][max_ep_len][row], each part 256-byte aligned
@@ -35,7 +37,9 @@ struct ddrl_env {
 // them all (env.hip, beside the model table): DDRL_OK for a handle of a taken kind, else DDRL_ERR_UNSUPPORTED with `what` — the entry
 // point's name — the two models and what to use instead in ddrl_last_error(), before anything is touched.  `family`: the one-body
 // entry point of the same family (the handle's own model's is named from it); nullptr where only the walker is refused.
-// A walker handle ([n,24] observations, [n,4] actions) is taken by reset / step / step_wrapped_walker / stats / get_state / set_state only.
+// A walker handle ([n,24] observations, [n,4] actions) is taken by reset / step / step_wrapped_walker / eval_policy_walker / eval_results /
+// stats / get_state / set_state only.  Where both landers share ONE entry point of a family (ddrl_env_eval_policy), the guard names it
+// without the held model's suffix.
 constexpr unsigned DDRL_TAKES_LANDERS = 1u << DDRL_ENV_ONE_BODY | 1u << DDRL_ENV_ARTICULATED;
 int ddrl_env_refuse(const ddrl_env *h, unsigned takes, const char *what, const char *family);
 constexpr int DDRL_ROLLOUT_MIRROR_Q = 8;   // ddrl_sel::MAXQ: the widest Q row the fused discrete step takes

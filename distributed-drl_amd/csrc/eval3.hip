@@ -9,71 +9,22 @@
 // The env handle NAMES the model (kind, iteration counts, seed, max_ep_len, device) and owns the results block; its state block,
 // statistics and observations are neither read nor written.  The weights come out of the agent handle (ddrl_actor_get_weights: the
 // newest installed version; ddrl_dqn_export(MAIN): q1 leads the flat vector) into a staging vector the env handle owns, one pack
-// launch in front of the episodes' launch on the same stream.
+// launch in front of the episodes' launch on the same stream.  The results-block reservation and the common argument check are
+// eval_host.h's, shared with walker_eval.hip (the walker's episodes: ddrl_env_eval_policy_walker).
 // A translation unit of its own, as env3.hip and rollout3.hip: eval.hip's and eval_q.hip's kernels compile exactly as before.
 #include "ddrl_common.h"
 #include "env3_device.h"
 #include "env_handle.h"
 #include "eval_episodes.h"
-
-namespace {
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The results block for n episodes with a trace row of `row` floats (0: none), the weight staging for `w_floats`.  Grows by
-// free + allocate (never shrinks): such a call synchronises the device and cannot be captured.
-int eval_reserve(ddrl_env *h, const char *what, int n, int row, size_t w_floats) {
-    const size_t len_off = up256((size_t)n * sizeof(double));
-    const size_t trace_off = len_off + up256((size_t)n * sizeof(int));
-    const size_t bytes = trace_off + (size_t)n * (size_t)h->max_ep_len * (size_t)row * sizeof(float);
-    h->ev_n = 0;   // from here on the previous results are gone: ddrl_env_eval_results refuses until this call has launched
-    if (bytes > h->ev_bytes) {
-        unsigned char *p = nullptr;
-        if (hipMalloc((void **)&p, bytes) != hipSuccess) {
-            ddrl::set_error("%s: hipMalloc of the results block failed (%zu bytes)", what, bytes);
-            return DDRL_ERR_NOMEM;
-        }
-        (void)hipFree(h->ev_block);
-        h->ev_block = p; h->ev_bytes = bytes;
-    }
-    if (w_floats > h->ev_w_floats) {
-        float *p = nullptr;
-        if (hipMalloc((void **)&p, w_floats * sizeof(float)) != hipSuccess) {
-            ddrl::set_error("%s: hipMalloc of the weight staging vector failed (%zu floats)", what, w_floats);
-            return DDRL_ERR_NOMEM;
-        }
-        (void)hipFree(h->ev_w);
-        h->ev_w = p; h->ev_w_floats = w_floats;
-    }
-    h->ev_len_off = len_off; h->ev_trace_off = trace_off;
-    return DDRL_OK;
-}
-
-// what both entry points refuse before they look at the agent
-int eval_common_check(const char *what, ddrl_env *h, const void *agent, int32_t n_episodes, uint32_t first_episode) {
-    if (h == nullptr || agent == nullptr) {
-        ddrl::set_error("%s: bad argument: NULL handle", what);
-        return DDRL_ERR_BAD_ARG;
-    }
-    if (const int rc = ddrl_env_refuse(h, DDRL_TAKES_LANDERS, what, nullptr)) return rc;   // no evaluation kernel holds the walker
-    if (n_episodes < 1) {
-        ddrl::set_error("%s: bad argument: n_episodes must be >= 1 (got %d)", what, (int)n_episodes);
-        return DDRL_ERR_BAD_ARG;
-    }
-    if ((uint64_t)first_episode + (uint64_t)n_episodes > (1u << 24)) {
-        ddrl::set_error("%s: bad argument: first_episode + n_episodes must stay exact in float32 (<= 2^24)", what);
-        return DDRL_ERR_BAD_ARG;
-    }
-    return DDRL_OK;
-}
-
-}  // namespace
+#include "eval_host.h"
 
 extern "C" {
 
 int ddrl_env_eval_policy(ddrl_env_t *h, ddrl_actor_t *actor, int32_t n_episodes, uint32_t first_episode, int32_t want_trace, void *stream) {
     const char *what = "ddrl_env_eval_policy";
-    if (const int rc = eval_common_check(what, h, actor, n_episodes, first_episode)) return rc;
+    if (const int rc = eval_common_check(what, h, actor, n_episodes, first_episode, [&] {
+            return ddrl_env_refuse(h, DDRL_TAKES_LANDERS, what, nullptr);   // no lander kernel holds the walker: ddrl_env_eval_policy_walker
+        })) return rc;
     ddrl_sac1_config_t cfg;
     int adev = -1;
     if (const int rc = ddrl_actor_internal_config(actor, &cfg, &adev)) return rc;
@@ -115,7 +66,9 @@ int ddrl_env_eval_policy(ddrl_env_t *h, ddrl_actor_t *actor, int32_t n_episodes,
 int ddrl_env_eval_q(ddrl_env_t *h, ddrl_dqn_t *dqn, int32_t n_episodes, uint32_t first_episode, int mode, float greedy_prob,
                     uint32_t noise_seed, uint64_t noise_ctr, int32_t want_trace, void *stream) {
     const char *what = "ddrl_env_eval_q";
-    if (const int rc = eval_common_check(what, h, dqn, n_episodes, first_episode)) return rc;
+    if (const int rc = eval_common_check(what, h, dqn, n_episodes, first_episode, [&] {
+            return ddrl_env_refuse(h, DDRL_TAKES_LANDERS, what, nullptr);   // no Q-network evaluation holds the walker
+        })) return rc;
     ddrl_dqn_config_t cfg;
     int adev = -1;
     if (const int rc = ddrl_dqn_internal_config(dqn, &cfg, &adev)) return rc;

@@ -145,8 +145,10 @@ class VecBipedalWalker(VecLunarLander):
     lander's solver with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default).  Specification,
     and what is gym's, Box2D's and this build's own: tests/walker_oracle.py.  NOT pinned against gym.  It has reset / step /
     step_wrapped_walker (the n-step worker's step, csrc/walker_nstep.hip) / sample_actions / stats / get_state / set_state; the
-    landers' wrapped steps (the inherited step_wrapped and step_wrapped_articulated), every fused rollout launch and the on-device
-    evaluation hold a lander, and the library refuses this env there (DdrlUnsupported naming the entry point and the walker)."""
+    landers' wrapped steps (the inherited step_wrapped and step_wrapped_articulated), every fused rollout launch and the landers'
+    on-device evaluation (ddrl_env_eval_policy / ddrl_env_eval_q) hold a lander, and the library refuses this env there (DdrlUnsupported
+    naming the entry point and the walker).  Its evaluation episodes run on the device through a door of their own: the marker
+    DeviceBipedalWalker and Actor.evaluate_env (ddrl_env_eval_policy_walker, csrc/walker_eval.hip), which borrows a handle of this class."""
 
     obs_dim, act_dim, act_high = 24, 4, 1.0
     model = "walker"
@@ -247,17 +249,18 @@ class VecLunarLanderDiscrete(VecLunarLander):
 # worker writes into its options (None: the options keep theirs — a lander's policy may have one action or two); wrapped: the env's wrapped-step method; fused: per fused family — "pi" (RolloutDevice), "q" (RolloutDeviceDQN), "nstep"
 # (RolloutDeviceNStep) — the (begin, step) entry-point NAMES, whether the pair is opt-in (taken only where the worker's own
 # `opt.fused_*_articulated` flag is set) and whether the step takes handles only, its mirrors being a block the env handle owns (rollout_mirrors).  A
-# family is missing where no fused launch holds the model.
+# family is missing where no fused launch holds the model.  eval: the handle-fed evaluation of a continuous policy (Actor.evaluate_env) —
+# the entry point's NAME and the floats of its trace row, as eval_results reads them.
 MODELS = {
-    "simple": dict(cls=VecLunarLander, dims=None, wrapped="step_wrapped", fused={
+    "simple": dict(cls=VecLunarLander, dims=None, wrapped="step_wrapped", eval=("ddrl_env_eval_policy", 12), fused={
         "pi": ("ddrl_rollout_begin", "ddrl_rollout_step", False, False),
         "q": ("ddrl_rollout_begin_discrete", "ddrl_rollout_step_discrete", False, False),
         "nstep": ("ddrl_rollout_begin_nstep", "ddrl_rollout_step_nstep", False, False)}),
-    "articulated": dict(cls=VecLunarLander, dims=None, wrapped="step_wrapped_articulated", fused={
+    "articulated": dict(cls=VecLunarLander, dims=None, wrapped="step_wrapped_articulated", eval=("ddrl_env_eval_policy", 12), fused={
         "pi": ("ddrl_rollout_begin_articulated", "ddrl_rollout_step_articulated", True, False),
         "q": ("ddrl_rollout_begin_discrete_articulated", "ddrl_rollout_step_discrete_articulated", True, True),
         "nstep": ("ddrl_rollout_begin_nstep_articulated", "ddrl_rollout_step_nstep_articulated", True, False)}),
-    "walker": dict(cls=VecBipedalWalker, dims=(24, 4), wrapped="step_wrapped_walker", fused={}),
+    "walker": dict(cls=VecBipedalWalker, dims=(24, 4), wrapped="step_wrapped_walker", eval=("ddrl_env_eval_policy_walker", 32), fused={}),
 }
 
 
@@ -440,6 +443,43 @@ class DeviceLunarLanderDiscrete(DeviceLunarLander):
                            "dqn.Actor.test); use env.make(\"LunarLander-v2\") for an env to step from the host")
 
 
+class DeviceBipedalWalker(DeviceLunarLander):
+    """The same marker for the WALKER (model "walker"; 24 observations, 4 actions): `Actor.test` given one runs its episodes as one
+    launch — `Actor.evaluate_env` (ddrl_env_eval_policy_walker, csrc/walker_eval.hip), one workgroup per episode — and advances
+    `episodes_played`.  Episode e is the e-th a host `BipedalWalker(seed, max_ep_len, velocity_iterations, position_iterations)` plays.
+    handle() is a one-env VecBipedalWalker, created on first use, that names the model to the library and owns the results block;
+    host_env() is a `BipedalWalker` positioned at `episodes_played` (EPI is field 13 in this layout too: csrc/walker_device.h loads
+    and stores it by csrc/env_device.h's enum).  Built by name, not by env.make / env.make_device, which keep refusing the walker;
+    workers._default_test_env builds it for `opt.env_model = "walker"` under `opt.test_on_device`."""
+
+    _host_class = BipedalWalker
+
+    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60):
+        self.seed, self.max_ep_len, self.model = int(seed) & 0xFFFFFFFF, int(max_ep_len), "walker"
+        self.velocity_iterations, self.position_iterations = int(velocity_iterations), int(position_iterations)
+        self.episodes_played = 0
+        self.action_space = _WalkerActionSpace(self)
+        self.observation_space = _WalkerObsSpace()
+        self._lend = None
+
+    def _model_kw(self):   # BipedalWalker and VecBipedalWalker are the model: they take the iteration counts only
+        return dict(velocity_iterations=self.velocity_iterations, position_iterations=self.position_iterations)
+
+    def reset(self):
+        return np.zeros(24, np.float64)
+
+    def step(self, a):
+        raise RuntimeError("DeviceBipedalWalker is not steppable: its episodes run on the device (Actor.evaluate_env / Actor.test); "
+                           "use env.make(\"BipedalWalker-v2\", model=\"walker\") for an env to step from the host")
+
+    def handle(self):
+        """The one-env handle (a VecBipedalWalker of this marker's seed, max_ep_len and iteration counts) lent to
+        ddrl_env_eval_policy_walker; created on first use."""
+        if self._lend is None:
+            self._lend = VecBipedalWalker(1, seed=self.seed, max_ep_len=self.max_ep_len, **self._model_kw())
+        return self._lend
+
+
 def _device_view(ptr, count, typestr, device):
     """`count` elements of device memory the library owns as a flat tensor (a __cuda_array_interface__ view: no copy, no ownership)."""
     class _Holder:
@@ -448,7 +488,8 @@ def _device_view(ptr, count, typestr, device):
 
 
 def eval_results(vec, want_row):
-    """The results of the last ddrl_env_eval_policy / ddrl_env_eval_q on `vec` (a VecLunarLander) as NumPy: dict(ret float64 [n],
+    """The results of the last ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_policy_walker on `vec` (a VecLunarLander or a
+    VecBipedalWalker; want_row: 12, 20 or 32) as NumPy: dict(ret float64 [n],
     len int32 [n]) and, where that call kept a trace, `trace` float32 [n, max_ep_len, want_row].  Read from the block the env handle
     owns (ddrl_env_eval_results) through __cuda_array_interface__ views, as replay.py reads its rings; synchronises the stream."""
     ret, ln, tr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
@@ -529,12 +570,15 @@ def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)
     on the one-body lander; the articulated model's marker is built by make_device.
     "BipedalWalker-v2" with model="walker" (+ seed, max_ep_len, velocity_iterations, position_iterations): the BipedalWalker facade
-    (_walker_door); on_device=True raises, no evaluation kernel holds that model."""
+    (_walker_door); on_device=True raises: the walker's evaluation kernel is reached through env.DeviceBipedalWalker, not this door."""
     walker = _walker_door(env_name, kw, "env.make")
     if walker is not None:
         if on_device:
-            raise ValueError("env.make(%r, on_device=True): no evaluation kernel holds the walker (ddrl_env_eval_policy / ddrl_env_eval_q, "
-                             "csrc/eval3.hip, run landers) — evaluate on a host-stepped env.make(%r, model=\"walker\")" % (env_name, env_name))
+            raise ValueError("env.make(%r, on_device=True): this door builds the landers' markers only (ddrl_env_eval_policy / ddrl_env_eval_q, "
+                             "csrc/eval3.hip, run landers) — the evaluation kernel for the walker (ddrl_env_eval_policy_walker, "
+                             "csrc/walker_eval.hip) is reached through env.DeviceBipedalWalker(seed, max_ep_len, velocity_iterations, "
+                             "position_iterations) and Actor.test / Actor.evaluate_env; use on_device=False for a host-stepped "
+                             "env.make(%r, model=\"walker\")" % (env_name, env_name))
         return BipedalWalker(**walker)
     if on_device and _check_model(kw.get("model", "simple")) != "simple":
         raise ValueError("env.make(on_device=True, model=%r): this door builds the one-body lander's marker only (ddrl_policy_eval, csrc/eval.hip; "
@@ -553,10 +597,14 @@ def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
 def make_device(env_name="LunarLanderContinuous-v2", **kw):
     """The test-env marker of an on-device evaluation for EITHER model: seed, max_ep_len and model="simple" | "articulated"
     (+ velocity_iterations, position_iterations) as env.make takes them.  "LunarLander-v2": DeviceLunarLanderDiscrete (dqn.Actor.test /
-    ActorSQN.test), else DeviceLunarLander (Actor.test / Model.test_agent).  The one-body marker is what make(on_device=True) returns."""
+    ActorSQN.test), else DeviceLunarLander (Actor.test / Model.test_agent).  The one-body marker is what make(on_device=True) returns.
+    "BipedalWalker-v2" raises: the walker's marker is env.DeviceBipedalWalker."""
     if _walker_door(env_name, kw, "env.make_device") is not None:
-        raise ValueError("env.make_device(%r): no evaluation kernel holds the walker (ddrl_env_eval_policy / ddrl_env_eval_q, "
-                         "csrc/eval3.hip, run landers) — evaluate on a host-stepped env.make(%r, model=\"walker\")" % (env_name, env_name))
+        raise ValueError("env.make_device(%r): this door builds the landers' markers only (ddrl_env_eval_policy / ddrl_env_eval_q, "
+                         "csrc/eval3.hip, run landers) — the evaluation kernel for the walker (ddrl_env_eval_policy_walker, "
+                         "csrc/walker_eval.hip) is reached through env.DeviceBipedalWalker(seed, max_ep_len, velocity_iterations, "
+                         "position_iterations) and Actor.test / Actor.evaluate_env; a host-stepped env is env.make(%r, model=\"walker\")"
+                         % (env_name, env_name))
     _check_model(kw.get("model", "simple"))
     if env_name == "LunarLander-v2":
         return DeviceLunarLanderDiscrete(**kw)

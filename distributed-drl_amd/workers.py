@@ -43,12 +43,17 @@ def _default_env(name, args):
 
 def _default_test_env(name, args):
     """The test workers' env when the caller passes no make_env: the host env of _default_env — or, with `args.test_on_device` set
-    (default False), the device marker of `args.env_model` (env.make_device with _env_model_kw): a round's evaluation episodes then
-    run as one launch, on the one-body and on the articulated lander."""
+    (default False), the device marker of `args.env_model` (env.make_device with _env_model_kw; the walker's, which that door does not
+    build: env.DeviceBipedalWalker): a round's evaluation episodes then run as one launch, on the one-body lander, the articulated
+    lander and the walker."""
     if not getattr(args, "test_on_device", False):
         return _default_env(name, args)
     from . import env as _env
-    return _env.make_device(name, seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len), **_env_model_kw(args))
+    kw = _env_model_kw(args)
+    if kw.get("model") == "walker":
+        return _env.DeviceBipedalWalker(seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len),
+                                        velocity_iterations=kw["velocity_iterations"], position_iterations=kw["position_iterations"])
+    return _env.make_device(name, seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len), **kw)
 
 
 def _stop(args):
