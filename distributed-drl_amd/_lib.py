@@ -28,6 +28,8 @@ DDRL_ENV3_STATE_FIELDS = 66   # the articulated model's block (ddrl_env_state_fi
 DDRL_ENV_ONE_BODY, DDRL_ENV_ARTICULATED = 0, 1   # ddrl_env_model_t.kind
 DDRL_ENV_WALKER = 3                              # ... the bipedal walker ([n,24] observations, [n,4] actions); 2 is not a model
 DDRL_ENVW_STATE_FIELDS = 286                     # its block: bodies, joint and contact impulses, bookkeeping, 200 terrain heights
+DDRL_WALKER_TERRAIN_GRASS, DDRL_WALKER_TERRAIN_HARDCORE = 0, 1   # include/ddrl_walker_hardcore.h: the walker handle's terrain mode
+DDRL_ENVWH_STATE_FIELDS = 663                    # a Hardcore walker's block: the 286 rows, wall-slot impulses, box count / table / column index
 SAC1_STAGES = 12
 DQN_STAGES = 9   # include/ddrl.h: DDRL_DQN_STAGES
 SAC1_MAIN, SAC1_TARGET, SAC1_ADAM_M, SAC1_ADAM_V, SAC1_GRAD = range(5)
@@ -243,6 +245,10 @@ SIGNATURES_WALKER = {
 SIGNATURES_WALKER_EVAL = {
     "ddrl_env_eval_policy_walker": SIGNATURES["ddrl_env_eval_policy"],     # the arguments of the landers' entry point
 }
+# include/ddrl_walker_hardcore.h, likewise
+SIGNATURES_WALKER_HARDCORE = {
+    "ddrl_env_create_walker": (c_int, [POINTER(_P), c_int, c_int64, c_uint32, c_int32, c_int32, c_int32, c_int32]),
+}
 
 
 def load():
@@ -258,7 +264,7 @@ def load():
             "libddrl_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C distributed-drl_amd/csrc`; there is no CPU fallback for the product path" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items()) + list(SIGNATURES_WALKER_HARDCORE.items()):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

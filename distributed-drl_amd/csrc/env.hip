@@ -5,6 +5,7 @@
 // compiles to.
 #include "ddrl_common.h"
 #include "../../include/ddrl_walker.h"
+#include "../../include/ddrl_walker_hardcore.h"
 #include "policy_row.h"
 #include "replay_device.h"
 #include "env_handle.h"
@@ -62,6 +63,17 @@ static const EnvModel ENV_MODELS[] = {
      },
      ddrl_walker_launch_step_wrapped, nullptr, nullptr, nullptr, nullptr, nullptr},
 };
+// The walker on the HARDCORE terrain (ddrl_walker_hardcore.h) is no kind and no row of the table: a terrain mode of the walker kind.
+// Its launches and its state block's rows stand here, as the walker row with those four members exchanged; ddrl_env_create_walker
+// hands a handle this object by the handle's `terrain`, so every entry point above and below serves it through h->model unchanged.
+static const EnvModel ENV_WALKER_HARDCORE = {
+    DDRL_ENV_WALKER, DDRL_ENVWH_STATE_FIELDS, 24, 4, 16, true, "DDRL_ENV_WALKER", "the walker", "_walker",
+    ddrl_walker_hc_launch_reset,
+    [](int, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d, float *rew_d,
+       float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream) {
+        return ddrl_walker_hc_launch_step(S, n, seed, max_ep_len, vit, pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, stats_d, stream);
+    },
+    ddrl_walker_hc_launch_step_wrapped, nullptr, nullptr, nullptr, nullptr, nullptr};
 // the table lookup: the row of `kind`, nullptr where no model has it
 static const EnvModel *env_model_of(int kind) {
     for (const EnvModel &m : ENV_MODELS)
@@ -292,18 +304,21 @@ int ddrl_env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed,
     return ddrl_env_create_ex(out, device, n_envs, seed, max_ep_len, nullptr);
 }
 
-int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len, const ddrl_env_model_t *model) {
+// ddrl_env_create_ex and ddrl_env_create_walker: `terrain` is the handle's terrain mode, which picks the walker's launches
+static int env_create(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len, const ddrl_env_model_t *model,
+                      int terrain) {
     DDRL_REQUIRE(out != nullptr && n_envs > 0 && max_ep_len > 0, "bad out/n_envs/max_ep_len");
     DDRL_REQUIRE(max_ep_len < (1 << 24), "max_ep_len must stay exact in float32");
     const EnvModel *m = env_model_of(model ? model->kind : DDRL_ENV_ONE_BODY);
     DDRL_REQUIRE(m != nullptr, "model kind must be DDRL_ENV_ONE_BODY, DDRL_ENV_ARTICULATED or DDRL_ENV_WALKER");
     DDRL_REQUIRE(!m->iterates || (model->velocity_iterations >= 1 && model->position_iterations >= 1),
                  "the articulated model and the walker need velocity_iterations >= 1 and position_iterations >= 1");
+    if (terrain == DDRL_WALKER_TERRAIN_HARDCORE) m = &ENV_WALKER_HARDCORE;
     ddrl::DeviceGuard g(device);
     if (!g.ok) { ddrl::set_error("cannot select device %d", device); return DDRL_ERR_HIP; }
     ddrl_env *h = new ddrl_env();
     h->device = device; h->n = n_envs; h->seed = seed; h->max_ep_len = max_ep_len; h->S = nullptr; h->stats = nullptr;
-    h->kind = m->kind; h->model = m;
+    h->kind = m->kind; h->model = m; h->terrain = terrain;
     h->vit = m->iterates ? model->velocity_iterations : 0;
     h->pit = m->iterates ? model->position_iterations : 0;
     if (hipMalloc((void **)&h->S, (size_t)m->fields * n_envs * sizeof(float)) != hipSuccess ||
@@ -318,6 +333,19 @@ int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t se
     DDRL_HIP_CHECK(hipStreamSynchronize(nullptr));
     *out = h;
     return DDRL_OK;
+}
+
+int ddrl_env_create_ex(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len, const ddrl_env_model_t *model) {
+    return env_create(out, device, n_envs, seed, max_ep_len, model, DDRL_WALKER_TERRAIN_GRASS);
+}
+
+// ddrl_walker_hardcore.h: a walker handle with a terrain mode (GRASS: ddrl_env_create_ex's walker handle itself)
+int ddrl_env_create_walker(ddrl_env_t **out, int device, int64_t n_envs, uint32_t seed, int32_t max_ep_len, int32_t velocity_iterations,
+                           int32_t position_iterations, int32_t terrain) {
+    DDRL_REQUIRE(terrain == DDRL_WALKER_TERRAIN_GRASS || terrain == DDRL_WALKER_TERRAIN_HARDCORE,
+                 "ddrl_env_create_walker: terrain must be DDRL_WALKER_TERRAIN_GRASS or DDRL_WALKER_TERRAIN_HARDCORE");
+    const ddrl_env_model_t model = {DDRL_ENV_WALKER, velocity_iterations, position_iterations};
+    return env_create(out, device, n_envs, seed, max_ep_len, &model, terrain);
 }
 
 int ddrl_env_destroy(ddrl_env_t *h) {

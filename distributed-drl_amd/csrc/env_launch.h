@@ -40,10 +40,17 @@ int ddrl_rollout3_launch_step(const void *args, int vit, int pit, void *stream);
 int ddrl_rollout3_launch_step_q(const void *args, int versioned, int vit, int pit, void *stream);
 int ddrl_nstep3_launch_step(const NStepLaunch &a, int vit, int pit, void *stream);
 
-// ---- the walker (walker.hip; its wrapped step: walker_nstep.hip): [n,24] observations, [n,4] actions
+// ---- the walker (walker.hip; its wrapped step: walker_nstep.hip): [n,24] observations, [n,4] actions; on the Hardcore terrain
+// (walker_hardcore.hip, state block [DDRL_ENVWH_STATE_FIELDS][n]): the ddrl_walker_hc_* three, argument for argument
 int ddrl_walker_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
 int ddrl_walker_launch_step(float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d,
                             float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
 int ddrl_walker_launch_step_wrapped(float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d, float act_noise,
                                     float obs_noise, float reward_scale, int action_repeat, float *obs2_d, float *rew_d, float *done_d,
                                     float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+int ddrl_walker_hc_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
+int ddrl_walker_hc_launch_step(float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d,
+                               float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+int ddrl_walker_hc_launch_step_wrapped(float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d, float act_noise,
+                                       float obs_noise, float reward_scale, int action_repeat, float *obs2_d, float *rew_d, float *done_d,
+                                       float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);

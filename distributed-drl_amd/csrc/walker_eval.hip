@@ -21,6 +21,7 @@
 // Compiled with -ffp-contract=off; write no fmaf here.  A translation unit of its own: no other file's kernels depend on it.
 #include "ddrl_common.h"
 #include "../../include/ddrl_walker_eval.h"
+#include "../../include/ddrl_walker_hardcore.h"
 #include "policy_row.h"
 #include "walker_device.h"
 #include "env_handle.h"
@@ -198,8 +199,14 @@ extern "C" {
 int ddrl_env_eval_policy_walker(ddrl_env_t *h, ddrl_actor_t *actor, int32_t n_episodes, uint32_t first_episode, int32_t want_trace,
                                 void *stream) {
     const char *what = "ddrl_env_eval_policy_walker";
-    if (const int rc = eval_common_check(what, h, actor, n_episodes, first_episode, [&] {
-            return ddrl_env_refuse(h, 1u << DDRL_ENV_WALKER, what, "ddrl_env_eval_policy");   // a lander handle: the landers' entry point
+    if (const int rc = eval_common_check(what, h, actor, n_episodes, first_episode, [&]() -> int {
+            if (const int rc = ddrl_env_refuse(h, 1u << DDRL_ENV_WALKER, what, "ddrl_env_eval_policy")) return rc;   // a lander handle: the landers' entry point
+            if (h->terrain != DDRL_WALKER_TERRAIN_GRASS) {   // k_walker_eval keeps the episode's terrain in LDS and builds grass only
+                ddrl::set_error("%s: not built for the hardcore terrain (ddrl_env_create_walker, DDRL_WALKER_TERRAIN_HARDCORE): the "
+                                "evaluation kernel holds the grass terrain — step a host env instead", what);
+                return DDRL_ERR_UNSUPPORTED;
+            }
+            return DDRL_OK;
         })) return rc;
     ddrl_sac1_config_t cfg;
     int adev = -1;

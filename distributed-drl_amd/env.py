@@ -148,21 +148,35 @@ class VecBipedalWalker(VecLunarLander):
     landers' wrapped steps (the inherited step_wrapped and step_wrapped_articulated), every fused rollout launch and the landers'
     on-device evaluation (ddrl_env_eval_policy / ddrl_env_eval_q) hold a lander, and the library refuses this env there (DdrlUnsupported
     naming the entry point and the walker).  Its evaluation episodes run on the device through a door of their own: the marker
-    DeviceBipedalWalker and Actor.evaluate_env (ddrl_env_eval_policy_walker, csrc/walker_eval.hip), which borrows a handle of this class."""
+    DeviceBipedalWalker and Actor.evaluate_env (ddrl_env_eval_policy_walker, csrc/walker_eval.hip), which borrows a handle of this class.
+    terrain="hardcore" (ddrl_env_create_walker, include/ddrl_walker_hardcore.h; csrc/walker_hardcore.hip; specification
+    tests/walker_hardcore_oracle.py): gym's BipedalWalkerHardcore terrain generator — stumps, pits and stairs as boxes, a second (wall)
+    contact slot per leg corner, a hull that ends the episode inside a box, lidar rays that see box edges — behind every method above,
+    with a state block of `state_fields` = 663 rows; the on-device evaluation refuses it (DdrlUnsupported naming the hardcore terrain).
+    terrain="grass" is the env it always was, bit for bit."""
 
     obs_dim, act_dim, act_high = 24, 4, 1.0
     model = "walker"
+    TERRAINS = {"grass": _lib.DDRL_WALKER_TERRAIN_GRASS, "hardcore": _lib.DDRL_WALKER_TERRAIN_HARDCORE}
 
-    def __init__(self, n_envs, seed=0, max_ep_len=1600, device=None, velocity_iterations=180, position_iterations=60, model="walker"):
+    def __init__(self, n_envs, seed=0, max_ep_len=1600, device=None, velocity_iterations=180, position_iterations=60, model="walker",
+                 terrain="grass"):
         if model != "walker":   # (taken so that every class of MODELS is built with the same keywords)
             raise ValueError("VecBipedalWalker is the env of model=\"walker\": %r" % (model,))
+        if terrain not in self.TERRAINS:
+            raise ValueError("VecBipedalWalker: terrain must be \"grass\" or \"hardcore\", got %r" % (terrain,))
+        self.terrain = terrain
         _lib.require_gpu()
         self._lib = _lib.load()
         self.n, self.seed, self.max_ep_len = int(n_envs), int(seed) & 0xFFFFFFFF, int(max_ep_len)
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         h = ctypes.c_void_p()
-        m = _lib.EnvModel(_lib.DDRL_ENV_WALKER, int(velocity_iterations), int(position_iterations))
-        _lib.check(self._lib.ddrl_env_create_ex(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len, ctypes.byref(m)))
+        if terrain == "grass":
+            m = _lib.EnvModel(_lib.DDRL_ENV_WALKER, int(velocity_iterations), int(position_iterations))
+            _lib.check(self._lib.ddrl_env_create_ex(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len, ctypes.byref(m)))
+        else:
+            _lib.check(self._lib.ddrl_env_create_walker(ctypes.byref(h), self.device.index, self.n, self.seed, self.max_ep_len,
+                                                        int(velocity_iterations), int(position_iterations), self.TERRAINS[terrain]))
         self._h = h
         self.state_fields = int(self._lib.ddrl_env_state_fields(h))
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
@@ -319,11 +333,12 @@ class _WalkerObsSpace:
 
 class BipedalWalker(LunarLander):
     """One walker with the gym call shape (env.make("BipedalWalker-v2", model="walker")): reset() -> o[24]; step(a[4]) -> (o2, r, d,
-    info), `d` True at the time limit too (gym's TimeLimit of 1600 is max_ep_len)."""
+    info), `d` True at the time limit too (gym's TimeLimit of 1600 is max_ep_len).  terrain="hardcore"
+    (env.make("BipedalWalkerHardcore-v2", model="walker", terrain="hardcore")): VecBipedalWalker's Hardcore terrain."""
 
-    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60):
+    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60, terrain="grass"):
         self._vec = VecBipedalWalker(1, seed=seed, max_ep_len=max_ep_len, velocity_iterations=velocity_iterations,
-                                     position_iterations=position_iterations)
+                                     position_iterations=position_iterations, terrain=terrain)
         self.action_space = _WalkerActionSpace(self)
         self.observation_space = _WalkerObsSpace()
         self._fresh = True
@@ -450,11 +465,16 @@ class DeviceBipedalWalker(DeviceLunarLander):
     handle() is a one-env VecBipedalWalker, created on first use, that names the model to the library and owns the results block;
     host_env() is a `BipedalWalker` positioned at `episodes_played` (EPI is field 13 in this layout too: csrc/walker_device.h loads
     and stores it by csrc/env_device.h's enum).  Built by name, not by env.make / env.make_device, which keep refusing the walker;
-    workers._default_test_env builds it for `opt.env_model = "walker"` under `opt.test_on_device`."""
+    workers._default_test_env builds it for `opt.env_model = "walker"` under `opt.test_on_device`.  terrain="hardcore" raises
+    ValueError: the evaluation kernel keeps the episode's terrain in LDS and holds the grass generator only."""
 
     _host_class = BipedalWalker
 
-    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60):
+    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60, terrain="grass"):
+        if terrain != "grass":
+            raise ValueError("DeviceBipedalWalker(terrain=%r): the walker's evaluation kernel (ddrl_env_eval_policy_walker, "
+                             "csrc/walker_eval.hip) is missing for the Hardcore terrain — it builds the grass terrain only; evaluate on a "
+                             "host-stepped env.make(\"BipedalWalkerHardcore-v2\", model=\"walker\", terrain=\"hardcore\")" % (terrain,))
         self.seed, self.max_ep_len, self.model = int(seed) & 0xFFFFFFFF, int(max_ep_len), "walker"
         self.velocity_iterations, self.position_iterations = int(velocity_iterations), int(position_iterations)
         self.episodes_played = 0
@@ -549,16 +569,24 @@ def _walker_door(env_name, kw, who):
     """None for a lander name; for "BipedalWalker-v2" the BipedalWalker's keyword arguments.  The walker is asked for by name AND by
     model="walker": the bare name keeps raising ValueError, as it did before this env existed, because what stands behind it is this
     build's own model, unpinned against gym's (tests/walker_oracle.py) — a driver that names gym's env says so once, in its make call.
-    "BipedalWalkerHardcore-v2" (pits, stumps, stairs) is not built."""
+    "BipedalWalkerHardcore-v2" (pits, stumps, stairs: tests/walker_hardcore_oracle.py, unpinned likewise) needs one more word,
+    terrain="hardcore": name and terrain have to agree, so neither the Hardcore name alone nor "BipedalWalker-v2" with
+    terrain="hardcore" opens it."""
     if "BipedalWalker" not in env_name:
         if kw.get("model") == "walker":
             raise ValueError("%s(%r, model=\"walker\"): the walker's name is \"BipedalWalker-v2\"" % (who, env_name))
         return None
-    if "Hardcore" in env_name:
-        raise ValueError("%s(%r): the Hardcore terrain (pits, stumps, stairs) is not built; \"BipedalWalker-v2\" with model=\"walker\" is"
-                         % (who, env_name))
+    terrain = kw.get("terrain", "grass")
+    if env_name == "BipedalWalkerHardcore-v2":
+        if terrain != "hardcore" or kw.get("model") != "walker":
+            raise ValueError("%s(%r) needs model=\"walker\" and terrain=\"hardcore\": the Hardcore terrain (pits, stumps, stairs) is this "
+                             "build's own model of it, not pinned against gym's" % (who, env_name))
+        return {k: v for k, v in kw.items() if k != "model"}
     if env_name != "BipedalWalker-v2":
-        raise ValueError("%s(%r): the walker that is built is \"BipedalWalker-v2\"" % (who, env_name))
+        raise ValueError("%s(%r): the walkers that are built are \"BipedalWalker-v2\" and \"BipedalWalkerHardcore-v2\"" % (who, env_name))
+    if terrain != "grass":
+        raise ValueError("%s(\"BipedalWalker-v2\", terrain=%r): name and terrain do not agree — \"BipedalWalker-v2\" is the grass "
+                         "terrain; the Hardcore terrain's name is \"BipedalWalkerHardcore-v2\"" % (who, terrain))
     if kw.get("model") != "walker":
         raise ValueError("%s(\"BipedalWalker-v2\") needs model=\"walker\": the env behind the name is this build's own five-body model, "
                          "not pinned against gym's (only the LunarLanderContinuous-v2 stand-in is built without one; SURVEY §8(a) A7)" % who)
@@ -570,7 +598,8 @@ def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)
     on the one-body lander; the articulated model's marker is built by make_device.
     "BipedalWalker-v2" with model="walker" (+ seed, max_ep_len, velocity_iterations, position_iterations): the BipedalWalker facade
-    (_walker_door); on_device=True raises: the walker's evaluation kernel is reached through env.DeviceBipedalWalker, not this door."""
+    (_walker_door); on_device=True raises: the walker's evaluation kernel is reached through env.DeviceBipedalWalker, not this door.
+    "BipedalWalkerHardcore-v2" with model="walker" AND terrain="hardcore": the same facade on the Hardcore terrain."""
     walker = _walker_door(env_name, kw, "env.make")
     if walker is not None:
         if on_device:

@@ -45,14 +45,17 @@ def _default_test_env(name, args):
     """The test workers' env when the caller passes no make_env: the host env of _default_env — or, with `args.test_on_device` set
     (default False), the device marker of `args.env_model` (env.make_device with _env_model_kw; the walker's, which that door does not
     build: env.DeviceBipedalWalker): a round's evaluation episodes then run as one launch, on the one-body lander, the articulated
-    lander and the walker."""
+    lander and the walker — on its grass terrain: with `args.env_terrain = "hardcore"` the marker raises ValueError (the evaluation
+    kernel holds the grass terrain only), and the host loop, the default, is what plays that terrain."""
     if not getattr(args, "test_on_device", False):
         return _default_env(name, args)
     from . import env as _env
     kw = _env_model_kw(args)
     if kw.get("model") == "walker":
+        # (terrain="hardcore" raises there: the evaluation kernel is missing for it; the host loop, the default, plays it)
         return _env.DeviceBipedalWalker(seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len),
-                                        velocity_iterations=kw["velocity_iterations"], position_iterations=kw["position_iterations"])
+                                        velocity_iterations=kw["velocity_iterations"], position_iterations=kw["position_iterations"],
+                                        terrain=kw.get("terrain", "grass"))
     return _env.make_device(name, seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len), **kw)
 
 
@@ -617,12 +620,20 @@ def _env_model_kw(opt):
     `opt.fused_discrete_rollout_articulated`, the n-step worker (RolloutDeviceNStep) behind `opt.fused_nstep_rollout_articulated`
     (all default False).  The flags are the workers', and change nothing here.
     "walker" (env.VecBipedalWalker, 24 observations / 4 actions) is RolloutDevice's and RolloutDeviceNStep's, always unfused (the
-    n-step worker steps it through VecBipedalWalker.step_wrapped_walker): _no_walker() is what the discrete worker says to it."""
+    n-step worker steps it through VecBipedalWalker.step_wrapped_walker): _no_walker() is what the discrete worker says to it.
+    `opt.env_terrain` ("grass", the default, or "hardcore": VecBipedalWalker's terrain mode, stumps, pits and stairs) is the walker's:
+    any other value than "grass" with another model raises ValueError.  Both workers run the same unfused sequences on it."""
     model = getattr(opt, "env_model", "simple")
+    terrain = getattr(opt, "env_terrain", "grass")
+    if terrain != "grass" and model != "walker":
+        raise ValueError("opt.env_terrain = %r needs opt.env_model = \"walker\" (got %r): the terrain is the walker's" % (terrain, model))
     if model == "simple":
         return {}
-    return dict(model=model, velocity_iterations=int(getattr(opt, "env_velocity_iterations", 180)),
-                position_iterations=int(getattr(opt, "env_position_iterations", 60)))
+    kw = dict(model=model, velocity_iterations=int(getattr(opt, "env_velocity_iterations", 180)),
+              position_iterations=int(getattr(opt, "env_position_iterations", 60)))
+    if terrain != "grass":   # `opt.env_terrain` ("grass", the default, or "hardcore"): the walker's terrain mode (env.VecBipedalWalker)
+        kw["terrain"] = terrain
+    return kw
 
 
 def _vec_env(opt, worker_index, max_ep_len):

@@ -1,6 +1,7 @@
 /* C ABI of libddrl_hip.so, the walker's evaluation entry point beside include/ddrl.h and include/ddrl_walker.h: the evaluation
  * episodes of the bipedal walker (DDRL_ENV_WALKER) on the device.  Conventions, status codes, ddrl_last_error(), the stream contract
- * and the memory contract are ddrl.h's; include this header instead of, or after, ddrl.h. */
+ * and the memory contract are ddrl.h's; include this header instead of, or after, ddrl.h.  (A walker handle's terrain mode:
+ * include/ddrl_walker_hardcore.h; the function below refuses a Hardcore handle with DDRL_ERR_UNSUPPORTED, nothing touched.) */
 #ifndef DDRL_WALKER_EVAL_H
 #define DDRL_WALKER_EVAL_H
 
