@@ -1106,6 +1106,12 @@ static int build_direct(ddrl_sac1 *h, int Bv, int B) {
     DDRL_REQUIRE(!V.sacv || L.v_W1 - L.q_W1[1] == L.q_W1[1] - L.q_W1[0], "internal: the value networks must sit at equal distances");
     DDRL_REQUIRE(L.pi_bmu == pi_bmu_off(h1, Np2, h2, a) && L.pi_bls == pi_bls_off(h1, Np2, h2, a),   // (k_dfwd<1> forms these addresses itself)
                  "internal: policy-head bias offsets of the direct layout");
+    {   // (k_dfwd forms the addresses of its epilogue operands — b2 and the head kernels of a job's network — itself)
+        bool same = L.pi_b2 - L.pi_W1 == net_b2_off(h1, Np2) && L.pi_Wmu - L.pi_W1 == net_wh0_off(h1, Np2) && L.pi_Wls - L.pi_W1 == pi_wls_off(h1, Np2, h2, a);
+        for (int q = 0; q < 2; ++q) same = same && L.q_b2[q] - L.q_W1[q] == net_b2_off(h1, Np2) && L.q_W3[q] - L.q_W1[q] == net_wh0_off(h1, Np2);
+        if (V.sacv) same = same && L.v_b2 - L.v_W1 == net_b2_off(h1, Np2) && L.v_W3 - L.v_W1 == net_wh0_off(h1, Np2);
+        DDRL_REQUIRE(same, "internal: epilogue-operand offsets of the direct layout");
+    }
     h->fused_l1_wgrad = false;   // (direct path: the policy's layer-1 wgrad is a job of its own, no row-tile partials)
     const long long HP = (long long)DFH * B * DNT;
     const long long H1I = (long long)B * h->Lp1, H2C = (long long)Np2 * B, H2R = (long long)B * h->Lp2;

@@ -155,6 +155,13 @@ __host__ __device__ __forceinline__ int pi_bmu_off(int K, int Np, int h2, int ac
     return Kp * 16 + Kp * Np + Np + h2 * act;
 }
 __host__ __device__ __forceinline__ int pi_bls_off(int K, int Np, int h2, int act) { return ((pi_bmu_off(K, Np, h2, act) + act + 3) & ~3) + h2 * act; }
+// The epilogue operands of a forward tile, relative to its network's [W1 ; b1] block array (same layout; every network: block array,
+// k4-interleaved W2, b2, then the head kernel — Wmu for the policy, W3 for a value network; the policy's Wls follows bmu on a 16-byte
+// boundary).  k_dfwd forms these addresses from its preloaded scalars as well: a field of the job record read inside the K loop is a
+// scalar load from the kernarg segment plus its wait, and a pointer SELECTED there is a vector load of the pointer plus a queue drain.
+__host__ __device__ __forceinline__ int net_b2_off(int K, int Np) { return ((K + 31) & ~31) * (16 + Np); }
+__host__ __device__ __forceinline__ int net_wh0_off(int K, int Np) { return net_b2_off(K, Np) + Np; }
+__host__ __device__ __forceinline__ int pi_wls_off(int K, int Np, int h2, int act) { return (pi_bmu_off(K, Np, h2, act) + act + 3) & ~3; }
 
 // Side outputs of a row tile (what a forward launch leaves for the backward ones beside H2 and the head partials: the H1r4 image, the
 // augmented input rows, the generated noise).  Every column tile of a row tile computes the whole of that row tile's X1 from the same
@@ -217,14 +224,19 @@ struct DOps {
 // Only the first DPRE blocks are requested before the K loop; block bi + DPRE is requested when block bi's MFMAs are
 // issued, so the fetch path (one wave-load per ~15 cycles and CU: ~3.6k cycles for the 8 waves of two workgroups) works
 // beside the matrix pipe instead of in front of it.
-// Measured at config 2 (us per update): DPRE 1 / 2 / 3 / 4 (= everything up front) 54.1 / 54.5 / 55.2 / 55.3; the input rows
-// requested in front of the operand blocks 54.0, the epilogue operands from inside the loop 53.7; DGP 1 / 2 / 4 / 8 / 16
-// 52.4 / 52.35 / 52.6 / 53.2 / 53.7; DGMID 1 / 2 / 4 / 6 / 8 52.3 / 52.3 / 52.0 / 52.1 / 52.3.
+// Measured at config 2 with the epilogue operands free of any fetch chain (us per update, medians of 6 alternating runs of
+// tools/upd_bench.hip, parent 39.7; profiles/forward_kloop_before_after.txt).  First set: DPRE0 / DPRE1 = 1 / 1 39.50, 2 / 1 39.76,
+// 1 / 2 39.93, 2 / 2 40.17 (depth still loses).  Second set: the epilogue operands (DDRL_DMID) requested behind block 0 39.23,
+// behind block 1 39.31, at loop entry (-1) 39.33, with the first operand block in front of the prologue (-2) 39.49;
+// DGP0 1 / 2 / 4 40.45 / 39.23 / 39.48; DGMID 2 / 4 / 6 39.19 / 39.23 / 39.23.
 #ifndef DDRL_DPRE0
 #define DDRL_DPRE0 1
 #endif
 #ifndef DDRL_DPRE1
 #define DDRL_DPRE1 1
+#endif
+#ifndef DDRL_DMID
+#define DDRL_DMID 0    // k_dfwd: the block behind whose MFMAs the epilogue operands are requested (-1: at loop entry, -2: in front of the prologue)
 #endif
 constexpr int DPRE = 1;    // operand blocks of k_dfwd requested before its K loop (per phase: DDRL_DPRE0 / DDRL_DPRE1)
 #ifndef DDRL_DGP0
@@ -269,6 +281,10 @@ template <int NS, int MT, int PRE, class Mid>
 __device__ __forceinline__ void dkloop(DOps &o, const DSrc &src, int K, int lane, const float (&xin)[MT][7], floatx16 (&acc)[MT],
                                        float *__restrict__ h1r4, int h1own, int Lp1, int m0, float *__restrict__ tr, Mid &&mid) {
     const int l31 = lane & 31, h = lane >> 5, b0 = src.b0, nb = src.nb;
+    if (DDRL_DMID == -1) {
+        mid();
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int bi = 0; bi < 4; ++bi) {
         if (bi + PRE < 4) {
@@ -296,7 +312,7 @@ __device__ __forceinline__ void dkloop(DOps &o, const DSrc &src, int K, int lane
                 }
             }
         }
-        if (bi == 0) {  // whatever the epilogue needs and nothing in the K loop does: requested behind block 0's MFMAs
+        if (bi == DDRL_DMID) {  // whatever the epilogue needs and nothing in the K loop does: requested behind block DDRL_DMID's MFMAs
             mid();
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -446,16 +462,25 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
         DST(PH, 1);
         const DFJob &jb = a.job[ji];
         ktouch(kline<sizeof(DFJob)>(&jb) | kline<offsetof(DFArgs, do_sample)>(&a));
+        // The epilogue operands (the bias group of this thread's four columns, its element of the head kernels): addresses from the
+        // preloaded scalars (net_b2_off / net_wh0_off / pi_wls_off; the job record holds the same pointers, build_direct checks it), the
+        // head kernel chosen by a select on the two OFFSETS.  The requests are all that stands in the K loop; the mask of the head
+        // value is applied where the value is first used, behind the combine barrier.
         float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
         float whv = 0.f;
+        const bool pinet = net == 0;
+        const int nh = pinet ? 2 * act : 1, hsplit = pinet ? act : 1;   // heads, heads of the first kernel = the row stride of both
+        const int h2 = Np - ((K_Np >> 24) & 31);
+        const float *b2p = W1 + net_b2_off(K, Np) + n0 + 4 * (tid >> 5);
+        const int wh0o = net_wh0_off(K, Np), wh1o = pinet ? pi_wls_off(K, Np, h2, act) : wh0o;
+        const int hc = tid >> 5, hcol = n0 + (tid & 31);
+        const bool whok = hc < nh && hcol < h2;
+        const int who = (hc < hsplit ? wh0o : wh1o) + (whok ? hcol * hsplit + (hc < hsplit ? hc : hc - hsplit) : 0);
         auto epilogue_operands = [&]() {
-            b4 = *reinterpret_cast<const float4 *>(jb.b2 + n0 + 4 * (tid >> 5));
-            const int c = tid >> 5, col = n0 + (tid & 31);
-            const bool ok = c < jb.nh && col < a.h2;
-            const float *p = c < jb.hsplit ? jb.wh0 : jb.wh1;
-            const int cc = c < jb.hsplit ? c : c - jb.hsplit;
-            whv = p[ok ? (long long)col * jb.hstride + cc : 0] * (ok ? 1.0f : 0.f);
+            b4 = *reinterpret_cast<const float4 *>(b2p);
+            whv = W1[who];
         };
+        if (DDRL_DMID == -2) epilogue_operands();
         if (PH == 1 && !stored) {  // the sampled action of this tile's rows, in every lane of every wave (no LDS, no barrier)
             float hs[2][4];
     #pragma unroll
@@ -528,7 +553,6 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
         DST(PH, 3);
         // ---- the other side outputs of the row tile, one column tile each (nothing in this launch reads them, but a workgroup that
         // writes them ends that much later: side_aug_tile / side_noise_tile keep them apart where the row tile has the tiles)
-        s_wh[tid >> 5][tid & 31] = whv;
         if (nt == side_aug_tile(a.tiles_n) && (jb.aug || jb.xr4)) {  // augmented input rows of the layer-1 wgrads (their ones column is set once at create)
             for (int idx = tid; idx < 32 * MT * D; idx += 256) {
                 const int r = idx / D, d = idx - r * D;
@@ -559,7 +583,10 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     #pragma unroll
             for (int q = 0; q < 16; ++q) red[w][(q & 3) + 8 * (q >> 2) + 4 * h][l31] = acc[tt][q];
             __syncthreads();
-            if (tt == 0) DST(PH, 4);
+            if (tt == 0) {
+                DST(PH, 4);
+                s_wh[tid >> 5][tid & 31] = whv * (whok ? 1.0f : 0.f);   // read behind two more barriers
+            }
             float v[4];
     #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -580,7 +607,7 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
             }
             {
                 const int c = tid >> 5;
-                if (c < jb.nh) {
+                if (c < nh) {
                     float s = 0.f;
     #pragma unroll
                     for (int col = 0; col < 32; ++col) s = fmaf(red[0][r][col], s_wh[c][col], s);
