@@ -1126,6 +1126,9 @@ static int build_direct(ddrl_sac1 *h, int Bv, int B) {
     const int keep = V.sacv ? ct : bq_keep(B / 32, h1, h2);
     const bool split = keep < ct;
     if (!V.sacv) h->bq_cols = keep;
+    // DDRL_SAC1_XIN_GENERIC=1 (debug, read per learner, here): the forward launches fill their layer-1 input rows by the generic form
+    // at obs_dim == 8 too, so that one process can hold a learner of each form and compare them byte for byte
+    const int xin_generic = getenv("DDRL_SAC1_XIN_GENERIC") && atoi(getenv("DDRL_SAC1_XIN_GENERIC")) != 0;
     for (int st = 0; st < 2; ++st) {
         DFHead &HA = h->fh_a[st], &HB = h->fh_b[st];
         DFArgs &FA = h->f_a[st], &FB = h->f_b[st];
@@ -1134,6 +1137,7 @@ static int build_direct(ddrl_sac1 *h, int Bv, int B) {
         HA.x_off = (int)(h->in[st][0] - S);
         HA.main_off = (int)(Pm - S); HA.targ_off = (int)(Pt - S); HA.npi = (int)L.q_W1[0]; HA.perq = (int)(L.q_W1[1] - L.q_W1[0]);
         HA.hp_off = (int)(h->hp - S);
+        HA.xin_generic = xin_generic;
         HB = HA;
         FA = DFArgs{};
         FA.tiles_n = nt2; FA.act = a; FA.Lp1 = h->Lp1; FA.Lp2 = h->Lp2; FA.h2 = h2;

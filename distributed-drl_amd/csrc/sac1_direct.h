@@ -146,6 +146,7 @@ struct DFHead {
     int hp_off;              // head-partial buffer (phase 1 reads the policy evaluations' partials)
     int x_off;               // input set: obs1; obs2 and acts follow as consecutive 256-byte aligned items
     int pack;                // 6 bits per job: [1:0] layer-1 MFMA steps - 4 (input columns + the bias column, in pairs), [2] input is obs2, [3] target copy, [5:4] network; bit 30 (phase 1): jobs 3, 4 take the stored action
+    int xin_generic;         // host only (debug selector DDRL_SAC1_XIN_GENERIC, read when the learner is created): obs_dim == 8 keeps the generic input-row fill
 };
 
 // Policy-head biases inside a parameter buffer of the direct layout (make_layout: [W1 ; b1] block array, k4-interleaved W2, b2, Wmu, bmu,
@@ -215,7 +216,10 @@ __device__ __forceinline__ void dblock(const float (&w1)[8], const float (&xin)[
 // broadcast load costs the fetch path as much as a tile load.  A CU retires about one wave-load per 15 cycles WHATEVER its
 // width, so every load is a 16-byte one: the layer-1 parameters are stored in the order these MFMAs read them (two float4
 // per lane and block instead of seven dwords: 51 -> 30 loads per wave).  Issued first thing in the kernel from preloaded
-// scalars only; loads beyond nb re-read the last block (no branches in front of a load).
+// scalars only; loads beyond nb re-read the last block (no branches in front of a load).  The same count rule for the layer-1
+// INPUT row in front of them: seven dwords per lane in the generic fill (one per MFMA step slot, the bias and zero slots from a
+// dummy address), one float4 (+ at most two stored-action dwords) at obs_dim == 8 (k_dfwd's X8) — per wave 13 -> 7 requests in front
+// of the first MFMA of a policy tile, 13 -> 8 (act <= 2) or 9 for a stored-action tile, 25 -> 19 for a policy-dependent tile of phase 1.
 struct DOps {
     float4 bq[4][4];
     float w1[4][8];
@@ -322,7 +326,7 @@ __device__ __forceinline__ void dkloop(DOps &o, const DSrc &src, int K, int lane
 // MT = 2 (phase 0: 400 tiles of 32 rows would put two workgroups on most CUs, each fetching its own copy of a W2 tile —
 // the fetch phase, not the MFMAs, is what a stage waits for): one workgroup = 64 rows x 32 columns, the wave's W2 / W1
 // registers serve both row tiles.
-template <int PH, int MT>
+template <int PH, int MT, bool X8>
 __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int K_Np, int B_d0, int pack, int x_off, int main_off, int targ_off, int npi, int perq,
                                               int hp_off, DFArgs a) {  // 12 dwords: what the hardware preloads into SGPRs at wave launch
     static_assert(PH == 0 || MT == 1, "phase 1 computes one policy row per lane");
@@ -330,7 +334,7 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     __shared__ __attribute__((aligned(16))) float tr[4][32 * 36];
     __shared__ float s_wh[DFH][32];
     const int tpj = tpj_tm & 0xffff, tiles_m = (tpj_tm >> 16) & 0xfff, njobs = (unsigned)tpj_tm >> 28;
-    const int K = K_Np & 0xfff, Np = (K_Np >> 12) & 0xfff /* bits [28:24]: Np - hidden2 */, B = B_d0 & 0xffff, d0 = (B_d0 >> 16) & 0xff, act = B_d0 >> 24;
+    const int K = K_Np & 0xfff, Np = (K_Np >> 12) & 0xfff /* bits [28:24]: Np - hidden2 */, B = B_d0 & 0xffff, d0 = X8 ? 8 : (B_d0 >> 16) & 0xff, act = B_d0 >> 24;
 #ifdef DDRL_STAMPS
     unsigned long long *const st_ = a.st;
 #endif
@@ -392,6 +396,10 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     // ... and, in the same wave of requests, what else the row math consumes: the head biases of that evaluation's parameter copy
     // (wave-uniform addresses: scalar loads) and its noise rows.  Both addresses need only the preloaded scalars and the launch
     // header: the noise items follow the inputs in the input set, the biases sit at pi_bmu_off / pi_bls_off of the copy.
+    // Per wave that is 8 float4 of partials (16 at act > 2, twice that on the `two` tile) + 4 noise dwords in front of the input row.
+    // (Only ceil(tiles_n / 4) of the four float4 groups hold n-tiles and only `act` noise dwords are read; requesting just those under
+    // launch-uniform tests — 25 -> 15 requests with the obs-8 input row — was built and measured: 38.62 against 38.45 us per update,
+    // the tests in front of the requests cost more than the requests.  Not in: profiles/first_load_wave_before_after.txt.)
     float pbm[2][4], pbl[2][4], pep[2][4];
     const int pin = PH == 1 ? (a.pin_pack >> (3 * ji)) & 7 : 0;
     if (PH == 1) {   // (the biases: no branch in front — scalar loads whose values stay in SGPRs until the row math; a stored tile reads the main copy's)
@@ -439,7 +447,29 @@ __global__ void __launch_bounds__(256) k_dfwd(const float *base, int tpj_tm, int
     {
         // ---- the observation part of the layer-1 input: lane (row, h) holds input column d_slot(s, h) for step s
         float xin[MT][7];
-        {
+        if (X8) {
+            // obs_dim == 8: slots 0-3 of half h are the four consecutive floats x[row][4h .. 4h + 3] of a 32-byte row (the input items are
+            // 256-byte aligned) — ONE float4 per lane instead of four dwords.  Slots 4, 5 hold the action columns h and 2 + h (columns
+            // 8 + h, 10 + h), slot 6 column 12 + h: a stored action is loaded for the columns that exist (block-uniform tests: a policy
+            // tile, and a phase-1 tile whose action is computed below, issue nothing), the bias column D is the constant 1 and every
+            // other slot 0, neither with a load.  Same values in the same slots as the generic fill.
+            const float *in0 = base + ((jp & 4) ? x2_off : x_off), *in1 = base + a_off;
+            const bool lda = PH == 0 ? d1 > 0 : stored;   // block-uniform
+#pragma unroll
+            for (int tt = 0; tt < MT; ++tt) {
+                const long long row = m0 + 32 * tt + l31;
+                const float4 x4 = *reinterpret_cast<const float4 *>(in0 + row * 8 + 4 * h);
+                float a0 = 0.f, a1 = 0.f;
+                if (lda) {
+                    a0 = in1[row * d1 + (h < d1 ? h : 0)];
+                    if (d1 > 2) a1 = in1[row * d1 + (2 + h < d1 ? 2 + h : 0)];
+                }
+                xin[tt][0] = x4.x; xin[tt][1] = x4.y; xin[tt][2] = x4.z; xin[tt][3] = x4.w;
+                xin[tt][4] = (lda && h < d1) ? a0 : (8 + h == D ? 1.0f : 0.f);
+                xin[tt][5] = (lda && 2 + h < d1) ? a1 : (10 + h == D ? 1.0f : 0.f);
+                xin[tt][6] = 12 + h == D ? 1.0f : 0.f;
+            }
+        } else {
             const float *in0 = base + ((jp & 4) ? x2_off : x_off), *in1 = base + a_off;
     #pragma unroll
             for (int tt = 0; tt < MT; ++tt) {
@@ -639,10 +669,10 @@ static void launch_dfwd(const DFHead &d, const DFArgs &F_, hipStream_t s) {
     const int tiles_m = d.B / (32 * mt), tpj = tiles_m * F.tiles_n;
     const int grid = F.njobs * tpj + ((PH == 1 && F.do_sample) ? 1 : 0);
     const int a1 = tpj | (tiles_m << 16) | (F.njobs << 28), a2 = d.K | (d.Np << 12) | ((d.Np - F.h2) << 24), a3 = d.B | (d.d0 << 16) | (F.act << 24);
-    if (PH == 0 && mt == 2)
-        k_dfwd<0, 2><<<grid, 256, 0, s>>>(d.base, a1, a2, a3, d.pack, d.x_off, d.main_off, d.targ_off, d.npi, d.perq, d.hp_off, F);
-    else
-        k_dfwd<PH, 1><<<grid, 256, 0, s>>>(d.base, a1, a2, a3, d.pack, d.x_off, d.main_off, d.targ_off, d.npi, d.perq, d.hp_off, F);
+    const bool x8 = d.d0 == 8 && !d.xin_generic;   // the obs-8 form of the layer-1 input rows (k_dfwd: X8)
+    auto go = [&](auto kern) { kern<<<grid, 256, 0, s>>>(d.base, a1, a2, a3, d.pack, d.x_off, d.main_off, d.targ_off, d.npi, d.perq, d.hp_off, F); };
+    if (PH == 0 && mt == 2) x8 ? go(k_dfwd<0, 2, true>) : go(k_dfwd<0, 2, false>);
+    else x8 ? go(k_dfwd<PH, 1, true>) : go(k_dfwd<PH, 1, false>);
 }
 
 // ==========================================================================================
@@ -1147,7 +1177,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
         const float4 *p4 = reinterpret_cast<const float4 *>(jobs.hp + (jobs.q_ev0 + (c < jobs.q_nev ? c : 0)) * HP + (long long)(m0 + r) * DNT);
 #pragma unroll
         for (int q = 0; q < DNT / 4; ++q) qv[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (need_q) {  // block-uniform
+        if (need_q) {  // block-uniform (only the ceil(K / 128) groups that hold n-tiles, under launch-uniform tests: measured, no change — not in)
 #pragma unroll
             for (int q = 0; q < DNT / 4; ++q) qv[q] = p4[q];
         }
@@ -1326,6 +1356,10 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
     if (AG || AG2) {
         __builtin_amdgcn_sched_barrier(0);
         const int act = jb.nact, row = m0 + l31;
+        // (Requesting only the nparts written slots, under launch-uniform tests, was built and measured: no gain — 38.60 against 38.51 us
+        // per update — and of the saved rows the compiler requests only sv[0], sv[1] at act <= 2 already, where the terms of columns
+        // 2, 3 are compiled out; a run-time test c < act costs k_dg its 169th register and with it the third wave per SIMD.
+        // profiles/first_load_wave_before_after.txt)
         float4 dp[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) dp[q] = *reinterpret_cast<const float4 *>(jb.dap + ((long long)(q < jb.nparts ? q : 0) * Bn + row) * 4);
