@@ -735,7 +735,7 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
         ddrl_dqn_destroy(h);
         return lrc;
     }
-    {   // the acting forward, where k_actor_fwd takes the shape (direct_ok of sac1.hip on (obs, half, h1, h2))
+    {   // the acting forward, where k_actor_fwd takes the shape (direct_ok of sac1_layout.h on (obs, half, h1, h2))
         if (A > ddrl_sel::MAXQ) h->act_why = "n_actions > 8 (the acting forward has 8 head rows)";
         else if (o + 1 > 13 || o + h->half > 12) h->act_why = "observations too wide for the direct-operand layer 1 (obs_dim + ceil(n_actions / 2) <= 12)";
         else if (h1 % 4 || h2 % 4 || h1 > 512 || h2 > 512) h->act_why = "hidden sizes outside the direct-operand limits (multiples of 4, <= 512)";
@@ -1040,7 +1040,7 @@ int ddrl_dqn_versions_enable(ddrl_dqn_t *h, int32_t n_slots, void *stream) {
         return DDRL_ERR_UNSUPPORTED;
     }
     DDRL_REQUIRE(n_slots >= 2 && n_slots <= VER_MAX_SLOTS, "n_slots outside [2, 2048]");
-    DDRL_REQUIRE(ddrl_actor_internal_view(h->act_fwd).ver.n_slots == 0, "version store already enabled");
+    DDRL_REQUIRE(ddrl_actor_internal_versions(h->act_fwd) == 0, "version store already enabled");
     // slot 0 = the weights held now: a learner step's pending repack comes first
     if (const int rc = ddrl_dqn_internal_repack(h, stream)) return rc;
     return ddrl_actor_versions_enable(h->act_fwd, n_slots, stream);
@@ -1048,13 +1048,13 @@ int ddrl_dqn_versions_enable(ddrl_dqn_t *h, int32_t n_slots, void *stream) {
 
 int ddrl_dqn_versions_state(ddrl_dqn_t *h, int32_t *slot_of_env_d, int32_t *state_h, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
-    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).ver.n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
+    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_versions(h->act_fwd) > 0, "version store not enabled (ddrl_dqn_versions_enable)");
     return ddrl_actor_versions_state(h->act_fwd, slot_of_env_d, state_h, stream);
 }
 
 int ddrl_dqn_versions_adopt(ddrl_dqn_t *h, const uint8_t *ended_d, int64_t n, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
-    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_view(h->act_fwd).ver.n_slots > 0, "version store not enabled (ddrl_dqn_versions_enable)");
+    DDRL_REQUIRE(h->act_fwd != nullptr && ddrl_actor_internal_versions(h->act_fwd) > 0, "version store not enabled (ddrl_dqn_versions_enable)");
     return ddrl_actor_versions_adopt(h->act_fwd, ended_d, n, stream);
 }
 

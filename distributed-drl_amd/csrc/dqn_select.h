@@ -110,8 +110,8 @@ struct ddrl_dqn_rollout_view {
     const float *vb_lo, *vb_hi;
 };
 ddrl_dqn_rollout_view ddrl_dqn_internal_view(ddrl_dqn_t *h);
-// a learner step moved the parameters: the operand copy is packed again — with a version store that is an install (steps_since_install = 0),
-// so the fused step calls this before it reads that word
+// a learner step moved the parameters: the operand copy is packed again — with a version store that is an install,
+// so the fused step calls this before it asks the store whether the step is versioned (ddrl_actor_internal_step_begin)
 int ddrl_dqn_internal_repack(ddrl_dqn_t *h, void *stream);
 // the acting forward of rows [0, n) of the view's observation buffer (repacks first, like the above); versioned: every env against the
 // version in its slot (ddrl_actor_internal_forward)

@@ -137,19 +137,16 @@ static int launch_env_obs(ddrl_env_t *h, float *obs, void *stream) {
 }
 
 // The version store's side of ONE vector step of every fused loop, around `step(versioned, fused_plan)` — the entry point's own forward,
-// argument patch and launch.  versioned: once no install has happened for `horizon` steps (max_ep_len, or the wrapped step's
-// limit_steps) every env has been through an episode end and acts on the newest version — the plain launch on the handle's current
-// weights is then the same computation.  fused_plan: the next forward's plan rides in this launch (base offsets of the row lists must
-// fit the records' int).  Behind the launch plan_fresh says whether the launch's own tail has planned for the envs its episode ends
-// moved to the newest version, or the next forward has to.
+// argument patch and launch.  versioned: the store's own answer (ddrl_actor_internal_step_begin with the horizon max_ep_len, or the
+// wrapped step's limit_steps).  fused_plan: the next forward's plan rides in this launch (base offsets of the row lists must fit the
+// records' int); behind the launch the store is told whether that tail has planned for the envs the launch's episode ends moved to
+// the newest version, or the next forward has to.
 template <class Step>
 static int rollout_versioned_step(const ddrl_version_view &ver, long long n, long long horizon, Step step) {
-    const bool store = ver.n_slots > 0;
-    const bool versioned = store && *ver.steps_since_install < horizon;
+    const bool versioned = ver.n_slots > 0 && ddrl_actor_internal_step_begin(ver.owner, horizon) != 0;
     const bool fused_plan = versioned && ver.vcnt != nullptr && ver.perm2d_off + (long long)ver.n_slots * n < (1ll << 31) && n / 32 <= 1024;
-    if (store) *ver.steps_since_install += 1;
     if (const int rc = step(versioned, fused_plan)) return rc;
-    if (versioned) *ver.plan_fresh = fused_plan;
+    if (versioned) ddrl_actor_internal_step_end(ver.owner, fused_plan ? 1 : 0);
     return DDRL_OK;
 }
 // ... and the plan's tables as the launch takes them: k_env_step_q as they stand, the other argument structs field by field
@@ -243,7 +240,7 @@ static int rollout_discrete_step_loop(ddrl_env_t *h, ddrl_dqn_t *dqn, const ddrl
     a.deterministic = mode == DDRL_ACT_DETERMINISTIC; a.greedy_prob = greedy_prob; a.alpha = v.alpha; a.noise_seed = seed;
     a.rs = rv.state; a.ring = rv.ring; a.act_out = act_out_d; a.q_out = q_out_d; a.next_obs_out = next_obs_out_d;
     for (int k = 0; k < n_steps; ++k) {   // ddrl_rollout_step's loop body
-        // a learner step's pending repack is an install: before steps_since_install is read
+        // a learner step's pending repack is an install: before the store is asked whether this step is versioned
         if (const int rc = ddrl_dqn_internal_repack(dqn, stream)) return rc;
         const int rc = rollout_versioned_step(v.ver, h->n, h->max_ep_len, [&](bool versioned, bool fused_plan) -> int {
             if (const int frc = ddrl_dqn_internal_forward(dqn, h->n, stream, versioned ? 1 : 0)) return frc;
@@ -650,7 +647,7 @@ static int rollout_nstep_step_loop(int kind, const char *what, ddrl_env_t *h, dd
         a.ended_out = out->ended;
     }
     for (int k = 0; k < n_steps; ++k) {   // the loop body of worker_rollout, n_steps times with the weights the actor holds
-        // the horizon is the wrapped step's limit (ddrl_actor_act_versioned makes the same test)
+        // the horizon is the wrapped step's limit (as ddrl_actor_act_versioned's horizon_steps)
         const int rc = rollout_versioned_step(v.ver, h->n, limit_steps, [&](bool versioned, bool fused_plan) -> int {
             a.versioned = versioned ? 1 : 0;
             a.bmu = versioned ? v.vbmu : v.bmu; a.bls = versioned ? v.vbls : v.bls;
@@ -660,7 +657,7 @@ static int rollout_nstep_step_loop(int kind, const char *what, ddrl_env_t *h, dd
             a.rdy_in = q.rdy[*q.parity]; a.rdy_out = q.rdy[1 - *q.parity];
             if (const int lrc = h->model->step_nstep(a, h->vit, h->pit, stream)) return lrc;
             *q.parity = 1 - *q.parity;
-            if (!versioned && store && a.adopt) *v.ver.plan_fresh = false;   // an unplanned launch moved envs: the next forward plans
+            if (!versioned && store && a.adopt) ddrl_actor_internal_step_end(actor, 0);   // an unplanned launch moved envs: the next forward plans
             return DDRL_OK;
         });
         if (rc != DDRL_OK) return rc;

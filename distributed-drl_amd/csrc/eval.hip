@@ -4,7 +4,7 @@
 // one workgroup plays one episode from reset to its end without the host, n episodes are n workgroups.  Nothing crosses
 // workgroups (no ticket, no fence, no spin-wait).
 //
-// The policy row is the arithmetic of k_act_one (sac1.hip) statement for statement, so that with -ffp-contract=off it yields the same
+// The policy row is the arithmetic of k_act_one (actor.hip) statement for statement, so that with -ffp-contract=off it yields the same
 // bits as the get_action launch the host loop issues per step: layer-1 units summed in input order on the bias; layer 2 as 16 slices
 // of ceil(h1 / 16) contraction rows per column, each summed in row order from zero, the 16 slice sums added in slice order on the
 // bias; head partials per group of 16 columns in column order from zero, the groups added in group order, then the head bias; then

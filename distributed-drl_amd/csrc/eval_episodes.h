@@ -357,6 +357,6 @@ static EvalQArgs eval_q_args_of(const ddrl_dqn_config_t &cfg, const float *q_fla
 
 }  // namespace
 
-// What the handle-fed entry points (eval3.hip) ask of the agent handles: the configuration and the device (sac1.hip, dqn.hip)
+// What the handle-fed entry points (eval3.hip) ask of the agent handles: the configuration and the device (actor.hip, dqn.hip)
 int ddrl_actor_internal_config(ddrl_actor_t *h, ddrl_sac1_config_t *cfg_out, int *device_out);
 int ddrl_dqn_internal_config(ddrl_dqn_t *h, ddrl_dqn_config_t *cfg_out, int *device_out);

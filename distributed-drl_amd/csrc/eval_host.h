@@ -61,5 +61,5 @@ int eval_common_check(const char *what, ddrl_env *h, const void *agent, int32_t 
 
 }  // namespace
 
-// What the handle-fed entry points ask of the actor handle: the configuration and the device (sac1.hip)
+// What the handle-fed entry points ask of the actor handle: the configuration and the device (actor.hip)
 int ddrl_actor_internal_config(ddrl_actor_t *h, ddrl_sac1_config_t *cfg_out, int *device_out);

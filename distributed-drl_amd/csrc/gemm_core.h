@@ -1,4 +1,4 @@
-// Shared device core of the learners (included by sac1.hip and dqn.hip; every definition has internal linkage):
+// Shared device core of the learners (included by sac1.hip, actor.hip and dqn.hip; every definition has internal linkage):
 //   * the batched small-GEMM kernel on v_mfma_f32_32x32x2_f32 (exact fp32) with its job tables and builders
 //     (forward / dgrad / wgrad incl. bias rows, optional Adam + polyak in the wgrad epilogue),
 //   * the TF1-style Adam + polyak kernel over a flat padded parameter buffer,

@@ -18,7 +18,7 @@ __device__ __forceinline__ float normal_at(uint32_t seed, unsigned long long c) 
 }
 
 // One row of one policy evaluation, all action dims in one lane.  Same formulae and operation order as policy_head()
-// of sac1.hip (core.py:49-87, 104-106); mu / log_std pre-activations arrive as sums of per-column-tile partials.
+// of sac1_layout.h (core.py:49-87, 104-106); mu / log_std pre-activations arrive as sums of per-column-tile partials.
 struct PolRow {
     float act[4], a[4], std[4], t[4];
     float logp;
@@ -51,7 +51,7 @@ __device__ __forceinline__ PolRow policy_row(const float (&mu)[4], const float (
 
 }  // namespace ddrl_pol
 
-// ---- the versioned policy forward's tables (written by k_version_plan in sac1.hip and by the env-step launch's tail in env.hip)
+// ---- the versioned policy forward's tables (written by k_version_plan in actor.hip and by the env-step launch's tail in env.hip)
 // One WORKGROUP of the versioned forward: `count` (<= 32) envs perm[base .. base + count) that all act on policy version `slot`, and the
 // column tiles [cols & 255, + cols >> 8) of their row tile.
 struct VerTile { int slot, base, count, cols; };
@@ -99,14 +99,14 @@ __host__ __device__ inline VerSplit ver_split(int n_tiles, int col_tiles, int sl
 }
 
 // An actor's version store (n_slots > 0) as the fused rollout steps (env.hip) see it: filled by ddrl_actor_internal_view, handed on whole by
-// ddrl_dqn_internal_view.  Host side only: never a kernel argument.
+// ddrl_dqn_internal_view.  Host side only: never a kernel argument.  The store's host state stays in the handle (actor.hip): a fused
+// step reaches it through `owner` and ddrl_actor_internal_step_begin / _end below.
 struct ddrl_version_view {
     int n_slots;
+    ddrl_actor_t *owner;   // the actor handle that owns the store
     int *slot;          // the slot every env acts on (the head biases of slot s lie s * vstride floats behind slot 0's)
     VerState *vs;       // device state: .newest, its first word, is what an env adopts at its episode end
     long long vstride;
-    long long *steps_since_install;
-    bool *plan_fresh;   // host flag of the actor: the forward's tile table matches the slots (cleared behind every launch that moves an env)
     // the forward's plan as the env-step launch writes it (fused: no planning launch between a vector step and the next forward)
     int *vcnt;          // [VER_MAX_SLOTS] envs per slot, all zero between launches
     int *perm;          // the forward's row lists; the env-step launch's own region starts at perm2d_off: [n_slots][max_rows]
@@ -114,7 +114,7 @@ struct ddrl_version_view {
     VerTile *vtiles;
     int vt_cap, wg_slots;
 };
-// What the fused rollout step (env.hip) needs from an actor handle (sac1.hip): internal to libddrl_hip.so.
+// What the fused rollout step (env.hip) needs from an actor handle (actor.hip): internal to libddrl_hip.so.
 struct ddrl_actor_rollout_view {
     int ok, device;
     float *obs;         // [max_rows][obs_dim]: the observations the next forward launch acts on
@@ -128,3 +128,9 @@ struct ddrl_actor_rollout_view {
 };
 int ddrl_actor_internal_forward(ddrl_actor_t *h, long long n, void *stream, int versioned);
 ddrl_actor_rollout_view ddrl_actor_internal_view(ddrl_actor_t *h);
+// One vector step of a version store's envs, for whoever launches the step behind the forward itself: begin — before the step's
+// launches — answers whether the step is versioned (store enabled, fewer than `horizon` steps since the last install) and counts it;
+// end — only after the step's launch returned DDRL_OK — states whether the forward's plan matches the slots that launch left.
+int ddrl_actor_internal_step_begin(ddrl_actor_t *h, long long horizon);
+void ddrl_actor_internal_step_end(ddrl_actor_t *h, int planned);
+int ddrl_actor_internal_versions(ddrl_actor_t *h);   // slots of the version store (0: not enabled)

@@ -2,7 +2,7 @@
 // algos/sac1/sac_ray.py:208-262, in the policy phase), the sibling of k_env_step_pi / k_env_step_q (lander.hip) for the window-queue worker.
 // Behind the actor's forward launch, ONE kernel does per env, in this order, what the unfused sequence does in seven launches:
 //   a.  a = agent.get_action(o)       head partials summed in n-tile order + the bias of the env's version slot, counter-hash noise,
-//                                     ddrl_pol::policy_row (k_actor_finish of sac1.hip; the head of k_env_step_pi)
+//                                     ddrl_pol::policy_row (k_actor_finish of actor.hip; the head of k_env_step_pi)
 //   b.  o2, r, d = Wrapper.step(a)    k_env_step_wrapped of lander.hip, statement for statement (hyperparams.py:122-134, sac_ray.py:212-221)
 //   c.  the queues                    k_winq_push of winq.hip: the o / a / r / d windows slide by one and take (o2, noisy a, r, d);
 //                                     ready = t >= Ln && t % save_freq == 0; t += 1 (sac_ray.py:229-248)

@@ -1,4 +1,5 @@
-// Direct-operand stages of the SAC1 update (included by sac1.hip, inside its anonymous namespace).
+// Direct-operand stages of the SAC1 update and the actor's policy forward k_actor_fwd (included by sac1.hip and by actor.hip, inside
+// their anonymous namespaces, behind gemm_core.h and policy_row.h and in front of sac1_layout.h).
 //
 // Round-1's fused path staged every GEMM operand through LDS (coalesced float4 loads -> wave-private
 // transposition tile -> MFMA lane layout).  Measured on MI355X the matrix cores run at ~1.6 GHz under
@@ -30,6 +31,9 @@
 //   k_dg "pi"  policy layer-2 / head / layer-1 wgrads, Q layer-1 / head wgrads, Adam + polyak, loss means + optimizer books 210
 // The forward launches also leave what only the backward ones read (H1r4, augmented input rows, generated noise): spread over the
 // column tiles of each row tile (h1_owned, side_aug_tile, side_noise_tile below), not all on column tile 0.
+using ddrl_pol::normal_at;
+using ddrl_pol::PolRow;
+using ddrl_pol::policy_row;
 
 #ifdef DDRL_STAMPS  // diagnostic builds only (tools/upd_bench.hip): per-workgroup cycle stamps of thread 0
 // the stamp buffer travels in the kernel arguments ([kernel id][1024 workgroups][16]): a __device__ pointer variable would

@@ -50,7 +50,7 @@ __device__ __forceinline__ void ver_plan_tail(const VerPlan &a, int my_slot, lon
     if (!a.vcnt) return;
     __syncthreads();
     if (!s_last) return;   // block-uniform
-    // ---- the last workgroup (one wave): the counts -> the next forward's workgroup table (the tables of k_version_plan, sac1.hip; the
+    // ---- the last workgroup (one wave): the counts -> the next forward's workgroup table (the tables of k_version_plan, actor.hip; the
     // row lists are this launch's own: group s at perm2d_off + s * n, so a record's row-list base is known without a scatter pass)
     __shared__ int t_cnt[VER_MAX_SLOTS], t_start[VER_MAX_SLOTS];
     __shared__ unsigned short t_slot[VER_MAX_SLOTS + 1024];   // slot of row tile ti (n / 32 + live groups <= 1024 + 2048 tiles)

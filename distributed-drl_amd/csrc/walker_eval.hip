@@ -1,7 +1,7 @@
 // Evaluation episodes of the BIPEDAL WALKER on the device, fed from handles: ddrl_env_eval_policy_walker (include/ddrl_walker_eval.h),
 // read back by ddrl_env_eval_results (eval3.hip).  One workgroup of 256 threads per episode, nothing crosses workgroups, as
 // k_eval_episodes (eval_episodes.h) on the landers:
-//   * the policy row on all threads: k_act_one's arithmetic (sac1.hip) statement for statement at d0 = 24, act = 4 — layer-1 units
+//   * the policy row on all threads: k_act_one's arithmetic (actor.hip) statement for statement at d0 = 24, act = 4 — layer-1 units
 //     summed on the bias in input order; layer 2 as 16 slices of ceil(h1 / 16) rows per column, each summed in row order from zero and
 //     added in slice order on the bias; the eight head partials (mu 0..3, log_std 0..3) per group of 16 columns, each summed in column
 //     order from zero, added in group order, then the head bias, then ddrl_pol::policy_row with the noise elements eps0 = 0.  So a

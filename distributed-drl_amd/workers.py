@@ -796,7 +796,7 @@ class _RolloutWorker:
             env.sample_actions(out=self.act)
         o2, r, d, _, ended = env.step(self.act)
         if self._versions:
-            self.actor.adopt_where_ended(ended)   # (clears the forward's plan_fresh: the next versioned forward plans for the moved envs)
+            self.actor.adopt_where_ended(ended)   # (the next versioned forward plans for the moved envs)
         self.rb.store_batch(self.o, self.act, r, o2, d)
         self.t += self._t_per_step
         if not self._versions and self.auto_pull:

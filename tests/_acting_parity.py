@@ -63,9 +63,9 @@ ROW_COUNTS = (1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 37, 4096, 4128)      # 4128 = 
 
 # `ns` / `occ`: the k_actor_fwd<NS, OCC> instantiation the plain direct-operand launch of the case takes (NS from obs_dim, OCC = 2 when
 # rows / 32 * ceil(column tiles / 5) > 256); the versioned launch is <NS, 2, versioned> always.  The GPU half writes them into its table.
-# NS = 7 is instantiated in csrc/sac1.hip but cannot be reached: it needs obs_dim = 12, and the direct-operand envelope (direct_ok:
-# obs_dim + act_dim <= 12 with act_dim >= 1) ends at obs_dim = 11.  The instantiations are left in place: csrc/sac1.hip is one of the
-# sources profiles/traffic.json is keyed to (bench.kernel_source_hash), so even a comment there asks for a new profiling round.
+# NS = 7 is instantiated in csrc/actor.hip but cannot be reached: it needs obs_dim = 12, and the direct-operand envelope (direct_ok:
+# obs_dim + act_dim <= 12 with act_dim >= 1) ends at obs_dim = 11.  The instantiations are left in place, as they were when the actor
+# lived in csrc/sac1.hip (one of the sources profiles/traffic.json is keyed to, where even a comment asks for a new profiling round).
 def forward_instantiation(obs, hid, rows):
     """(NS, OCC) of the plain direct-operand launch, as ddrl_actor_internal_forward picks them."""
     d1 = obs + 1

@@ -679,6 +679,83 @@ def test_nstep_rollout_weight_adoption_equals_the_reference_workers():
     assert len(seen) >= 10 and not ro.actor.version_state(with_slots=False)[1]["out_of_slots"]
 
 
+def test_split_and_fused_vector_steps_follow_one_version_transition_rule():
+    """The version store is driven two ways: ddrl_actor_act_versioned + ddrl_actor_versions_adopt around an env.step of the caller's
+    (the split route), and ddrl_rollout_step (the fused route).  Both ask the store the same question per vector step — versioned
+    while fewer than `horizon` steps have passed since the last install, the plain forward on the newest weights after that — and
+    this test holds them to ONE answer: the same installs, vector steps and episode ends on both routes, and after EVERY call the
+    same newest slot, live count and out-of-slots flag, the same slot for every env, and (after a step) bit-equal actions and env states.
+    64 envs = two row tiles, a 4-slot store, hidden (64, 64), time limit 3 = the horizon; bias-coded versions (_coded_weights) make
+    the version behind an action readable.  Envs 0-7 are held back from ever ending an episode (a step count far below zero), so
+    they stay on version 0's slot: on a versioned step they act on version 0, on a plain step on the newest weights like everybody —
+    which makes the step at which a route leaves the versioned path visible in its actions.  Expected, from the rule alone: an
+    install sets the count to 0, step k after it is versioned iff k < horizon."""
+    import distributed_drl_amd as ddrl
+    from distributed_drl_amd import _lib
+    from distributed_drl_amd.agent import Actor, HyperParameters
+    from distributed_drl_amd.env import VecLunarLander
+    lib = _lib.load()
+    n, horizon, n_slots, late, EPLEN = 64, 3, 4, 8, 10
+    opt = HyperParameters()
+    opt.hidden_sizes, opt.num_envs, opt.seed = (64, 64), n, 7
+
+    def route():   # the same actor (weights, noise stream), store and envs for each route
+        actor, env = Actor(opt, max_rows=n), VecLunarLander(n, seed=5, max_ep_len=horizon)
+        st = env.get_state()
+        st[EPLEN] = torch.arange(n, device="cuda").float() % horizon   # episode ends in every step, env by env
+        st[EPLEN, :late] = -1000.0
+        env.set_state(st)
+        return actor, env
+    (a_split, e_split), (a_fused, e_fused) = route(), route()
+    keys, vals = a_split.get_weights()
+    for a in (a_split, a_fused):
+        a.set_weights(keys, _coded_weights(keys, vals, 0))
+        a.enable_versions(n_slots)
+    ring = ddrl.ReplayBufferSAC1(8, 2, 1024, seed=0)
+    act_fused = torch.empty(n, 2, dtype=torch.float32, device="cuda")
+    _lib.check(lib.ddrl_rollout_begin(e_fused._h, a_fused._h, _lib.stream_ptr()))
+
+    def same_store(what):
+        (s0, d0), (s1, d1) = a_split.version_state(), a_fused.version_state()
+        for k in ("newest", "live", "out_of_slots"):
+            assert d0[k] == d1[k], (what, k, d0, d1)
+        np.testing.assert_array_equal(s0.cpu().numpy(), s1.cpu().numpy(), err_msg=what)
+        return s0.cpu().numpy(), d0
+
+    holds, newest, since = np.zeros(n, int), 0, None       # the version each env holds; vector steps since the last install
+    plain_after_install, versions_seen = 0, set()
+    for i, op in enumerate("SISSISSSSSISSSSS"):
+        what = "call %d (%s)" % (i, op)
+        if op == "I":
+            newest, since = newest + 1, 0
+            for a in (a_split, a_fused):
+                a.set_weights(keys, _coded_weights(keys, vals, newest))
+            _, st = same_store(what)
+            assert not st["out_of_slots"], what
+            continue
+        versioned = since is not None and since < horizon
+        since = None if since is None else since + 1
+        # split route: act (noise from the actor's own counter stream), step, adopt
+        act_split = a_split.get_actions_versioned(e_split.obs, horizon)
+        ended = e_split.step(act_split)[4]
+        a_split.adopt_where_ended(ended)
+        # fused route: the same noise elements by seed and counter
+        _lib.check(lib.ddrl_rollout_step(e_fused._h, a_fused._h, ring._h, 1, a_fused._noise_seed, a_fused._noise_ctr, 0,
+                                         _lib.dptr(act_fused), _lib.dptr(e_fused.obs), _lib.stream_ptr()))
+        a_fused._noise_ctr += n * 2
+        assert torch.equal(act_split, act_fused), what
+        assert torch.equal(e_split.get_state(), e_fused.get_state()), what
+        want = holds if versioned else np.full(n, newest)
+        np.testing.assert_array_equal(_decode_version(act_split.cpu().numpy()), want, err_msg=what)
+        if not versioned and since is not None and (holds != newest).any():
+            plain_after_install += 1                       # the held-back envs show that this step took the plain forward
+        versions_seen.update(want.tolist())
+        holds[ended.cpu().numpy().astype(bool)] = newest
+        slots, _ = same_store(what)
+        assert (holds[:late] == 0).all() and len(set(slots[late:])) <= 2 and len(set(slots[:late])) == 1, what
+    assert plain_after_install >= 2 and versions_seen == {0, 1, 2, 3}
+
+
 def test_new_entry_points_refuse_what_they_cannot_do():
     """Error behaviour of the round-4 entry points (every function returns a status, nothing aborts): the version store twice / out of
     range / on a policy outside the direct-operand envelope, versioned get_action without a store, the fused rollout step on a compact
