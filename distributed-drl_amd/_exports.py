@@ -7,7 +7,7 @@ _TABLE = {
     "ParameterServer": "ps", "ParameterServerNode": "ps",
     "Learner": "agent", "Actor": "agent", "Model": "agent", "HyperParameters": "agent",
     "VecLunarLander": "env", "VecLunarLanderDiscrete": "env", "DeviceLunarLander": "env", "DeviceLunarLanderDiscrete": "env",
-    "DeviceBipedalWalker": "env",
+    "DeviceBipedalWalker": "env", "DeviceBipedalWalkerHardcore": "env",
     "worker_rollout": "workers", "worker_train": "workers", "worker_test": "workers",
     "worker_rollout_sac1": "workers", "worker_train_sac1": "workers", "worker_test_sac1": "workers",
     "worker_rollout_dqn": "workers", "worker_train_dqn": "workers", "worker_test_dqn": "workers", "BatchCache": "workers", "get_al_status": "workers",

@@ -249,6 +249,10 @@ SIGNATURES_WALKER_EVAL = {
 SIGNATURES_WALKER_HARDCORE = {
     "ddrl_env_create_walker": (c_int, [POINTER(_P), c_int, c_int64, c_uint32, c_int32, c_int32, c_int32, c_int32]),
 }
+# include/ddrl_walker_hardcore_eval.h, likewise
+SIGNATURES_WALKER_HARDCORE_EVAL = {
+    "ddrl_env_eval_policy_walker_hardcore": SIGNATURES["ddrl_env_eval_policy"],   # the arguments of the landers' entry point
+}
 
 
 def load():
@@ -264,7 +268,8 @@ def load():
             "libddrl_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C distributed-drl_amd/csrc`; there is no CPU fallback for the product path" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items()) + list(SIGNATURES_WALKER_HARDCORE.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items())
+                              + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

@@ -704,7 +704,8 @@ class Actor(_Net):
     def evaluate_env(self, dev_env, n=25, first_episode=None, trace=False):
         """n deterministic evaluation episodes of `dev_env`'s model — an env.DeviceLunarLander of either lander model or an
         env.DeviceBipedalWalker — as one launch fed from handles, through the model's entry point in env.MODELS (the landers:
-        ddrl_env_eval_policy, csrc/eval3.hip; the walker: ddrl_env_eval_policy_walker, csrc/walker_eval.hip): episode e is the
+        ddrl_env_eval_policy, csrc/eval3.hip; the walker: ddrl_env_eval_policy_walker, csrc/walker_eval.hip) or the one the marker names
+        itself (`eval_entry`; env.DeviceBipedalWalkerHardcore: ddrl_env_eval_policy_walker_hardcore, csrc/walker_hardcore_eval.hip): episode e is the
         (first_episode + e)-th episode a host env of the marker's seed, max_ep_len and model plays (default: from
         dev_env.episodes_played on; the count is NOT advanced here), acted on with this actor's current weights — the library reads them
         out of the actor handle — by get_action(o, deterministic=True)'s arithmetic.  -> the dict `evaluate` returns, read from the
@@ -714,7 +715,7 @@ class Actor(_Net):
         n = int(n)
         first = int(dev_env.episodes_played if first_episode is None else first_episode)
         vec = dev_env.handle()
-        entry, row = MODELS[dev_env.model]["eval"]
+        entry, row = getattr(dev_env, "eval_entry", None) or MODELS[dev_env.model]["eval"]   # a marker that names its own (a terrain is no model)
         _lib.check(getattr(self._lib, entry)(vec._h, self._h, n, first, 1 if trace else 0, _lib.stream_ptr()))
         return eval_results(vec, row)
 

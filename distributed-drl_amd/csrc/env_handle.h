@@ -15,7 +15,7 @@ struct ddrl_env {
     EnvStats *stats;
     int kind, vit, pit;   // ddrl_env_model_t; the iteration counts are the articulated model's and the walker's
     int terrain;          // DDRL_WALKER_TERRAIN_* (ddrl_walker_hardcore.h): the walker's terrain mode, read where ddrl_env_create_walker
-                          // chooses the handle's launches and where the walker's evaluation refuses the Hardcore terrain; 0 on a lander
+                          // chooses the handle's launches and where the walker's two evaluation entry points each refuse the other's terrain; 0 on a lander
     const struct EnvModel *model;   // the kind's row of env.hip's model table (widths, state fields, launches), set at create
     // ---- evaluation episodes (ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_results, eval3.hip; ddrl_env_eval_policy_walker,
     // walker_eval.hip).  Everything below is

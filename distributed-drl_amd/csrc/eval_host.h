@@ -1,6 +1,6 @@
 // What the handle-fed evaluation entry points share on the HOST: the results block of the env handle (env_handle.h) and the argument
 // check in front of every look at the agent.  Included by eval3.hip (ddrl_env_eval_policy / ddrl_env_eval_q: the landers) and
-// walker_eval.hip (ddrl_env_eval_policy_walker).  Host code only: nothing here is part of a kernel, so neither file's device code
+// walker_eval.hip / walker_hardcore_eval.hip (ddrl_env_eval_policy_walker / _walker_hardcore, through walker_eval_device.h).  Host code only: nothing here is part of a kernel, so neither file's device code
 // depends on it.  Internal linkage throughout.
 #pragma once
 #include "ddrl_common.h"

@@ -63,17 +63,19 @@ enum { RAX = 0, RAY, RBX, RBY, K11, K12, K22, IDET, JANG, MSPD, MMAX, W_JFIELDS 
 constexpr int W_LDS_FIELDS = 8 * W_CFIELDS + 4 * W_JFIELDS;
 constexpr int W_LDS_FIELDS_H = 16 * W_CFIELDS + 4 * W_JFIELDS;   // WalkerT<1>: 16 contact slots, 43 KiB per workgroup
 // (the kernel declares `__shared__ float wl[W_LDS_FIELDS][64]` — W_LDS_FIELDS_H for WalkerT<1> — and hands its lane's column to Walker::L)
-#define WCF(f, s) L[((f) * NS + (s)) * 64]
-#define WJF(f, j) L[(NS * W_CFIELDS + (f) * 4 + (j)) * 64]
+// (LS: WalkerT's lane stride, 64 in every such kernel; a kernel that steps ONE env in one lane packs the fields at LS = 1)
+#define WCF(f, s) L[((f) * NS + (s)) * LS]
+#define WJF(f, j) L[(NS * W_CFIELDS + (f) * 4 + (j)) * LS]
 // The compiler forwards a lane's own LDS stores to its later loads and hoists the loads out of the sweeps, which puts every field back
 // into a register.  An empty statement that may touch memory, at the head of each sweep, makes it read the fields where they are.
 #define W_LDS_FENCE() asm volatile("" ::: "memory")
 
 __device__ __forceinline__ float signf(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : v); }
 
-template <int HC>
+template <int HC, int LS = 64>
 struct WalkerT {
     static constexpr int NS = HC ? 16 : 8;               // contact slots; slot s belongs to corner qof(s)
+    static constexpr int LFIELDS = HC ? W_LDS_FIELDS_H : W_LDS_FIELDS;   // the floats of a lane's fields; its column spans LFIELDS * LS
     static __device__ constexpr int qof(int s) { return HC ? s >> 1 : s; }
     static __device__ constexpr int slot_row(int s) { return HC ? ((s & 1) ? WW0 : WK0) + 2 * (s >> 1) : WK0 + 2 * s; }
     float bx[5], by[5], ba[5], bvx[5], bvy[5], bom[5];   // bodies: centre of mass, angle, velocities
@@ -81,7 +83,7 @@ struct WalkerT {
     float can[NS], cat[NS];                              // contact impulses (warm start): corner q = 2 (body - 1) + k
     float px, py;                                        // hull origin
     float c1, c2, prev, hasp, eplen, epret, epi, pstep;
-    float *L;                                            // this lane's column of the workgroup's LDS fields: field f at L[f * 64]
+    float *L;                                            // this lane's column of the workgroup's LDS fields: field f at L[f * LS]
     float *Sc;                                           // this env's column of the state block: field f at Sc[f * n]
     float *T;                                            // ... and its terrain heights: T[k * n]
     float *B, *Cc;                                       // HC: its box table B[(4 b + f) * n] and per-column box index Cc[k * n]
@@ -630,5 +632,6 @@ struct WalkerT {
 };
 using Walker = WalkerT<0>;           // the grass walker (walker.hip, walker_nstep.hip, walker_eval.hip)
 using WalkerHardcore = WalkerT<1>;   // walker_hardcore.hip
+using WalkerHardcoreLane = WalkerT<1, 1>;   // walker_hardcore_eval.hip: one env in one lane, its 172 fields packed (688 bytes of LDS)
 
 }  // namespace

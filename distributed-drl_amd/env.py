@@ -152,7 +152,9 @@ class VecBipedalWalker(VecLunarLander):
     terrain="hardcore" (ddrl_env_create_walker, include/ddrl_walker_hardcore.h; csrc/walker_hardcore.hip; specification
     tests/walker_hardcore_oracle.py): gym's BipedalWalkerHardcore terrain generator — stumps, pits and stairs as boxes, a second (wall)
     contact slot per leg corner, a hull that ends the episode inside a box, lidar rays that see box edges — behind every method above,
-    with a state block of `state_fields` = 663 rows; the on-device evaluation refuses it (DdrlUnsupported naming the hardcore terrain).
+    with a state block of `state_fields` = 663 rows.  Its evaluation episodes run on the device through the marker
+    DeviceBipedalWalkerHardcore (ddrl_env_eval_policy_walker_hardcore, csrc/walker_hardcore_eval.hip); the grass terrain's entry point
+    refuses such a handle (DdrlUnsupported naming the hardcore terrain), as the Hardcore one refuses a grass handle.
     terrain="grass" is the env it always was, bit for bit."""
 
     obs_dim, act_dim, act_high = 24, 4, 1.0
@@ -466,15 +468,17 @@ class DeviceBipedalWalker(DeviceLunarLander):
     host_env() is a `BipedalWalker` positioned at `episodes_played` (EPI is field 13 in this layout too: csrc/walker_device.h loads
     and stores it by csrc/env_device.h's enum).  Built by name, not by env.make / env.make_device, which keep refusing the walker;
     workers._default_test_env builds it for `opt.env_model = "walker"` under `opt.test_on_device`.  terrain="hardcore" raises
-    ValueError: the evaluation kernel keeps the episode's terrain in LDS and holds the grass generator only."""
+    ValueError: this marker's evaluation kernel holds the grass terrain; the Hardcore terrain's marker is DeviceBipedalWalkerHardcore."""
 
     _host_class = BipedalWalker
+    terrain = "grass"
 
     def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60, terrain="grass"):
         if terrain != "grass":
-            raise ValueError("DeviceBipedalWalker(terrain=%r): the walker's evaluation kernel (ddrl_env_eval_policy_walker, "
-                             "csrc/walker_eval.hip) is missing for the Hardcore terrain — it builds the grass terrain only; evaluate on a "
-                             "host-stepped env.make(\"BipedalWalkerHardcore-v2\", model=\"walker\", terrain=\"hardcore\")" % (terrain,))
+            raise ValueError("DeviceBipedalWalker(terrain=%r): this marker holds the grass terrain — its evaluation kernel "
+                             "(ddrl_env_eval_policy_walker, csrc/walker_eval.hip) builds that one; the Hardcore terrain's is "
+                             "ddrl_env_eval_policy_walker_hardcore (csrc/walker_hardcore_eval.hip), reached through "
+                             "env.DeviceBipedalWalkerHardcore(seed, max_ep_len, velocity_iterations, position_iterations)" % (terrain,))
         self.seed, self.max_ep_len, self.model = int(seed) & 0xFFFFFFFF, int(max_ep_len), "walker"
         self.velocity_iterations, self.position_iterations = int(velocity_iterations), int(position_iterations)
         self.episodes_played = 0
@@ -500,6 +504,33 @@ class DeviceBipedalWalker(DeviceLunarLander):
         return self._lend
 
 
+class DeviceBipedalWalkerHardcore(DeviceBipedalWalker):
+    """DeviceBipedalWalker's twin for the HARDCORE terrain (model "walker", terrain "hardcore": stumps, pits, stairs): `Actor.test` given
+    one runs its episodes as one launch — `Actor.evaluate_env` through `eval_entry` (ddrl_env_eval_policy_walker_hardcore,
+    csrc/walker_hardcore_eval.hip), one workgroup per episode, the episode's terrain generated inside the kernel — and advances
+    `episodes_played`.  Episode e is the e-th a host `BipedalWalker(seed, max_ep_len, velocity_iterations, position_iterations,
+    terrain="hardcore")` plays (env.make("BipedalWalkerHardcore-v2", model="walker", terrain="hardcore")).  handle() is a one-env
+    VecBipedalWalker(terrain="hardcore"), host_env() a BipedalWalker(terrain="hardcore") positioned at `episodes_played`.
+    The marker names its entry point itself (`eval_entry`: the name and the floats of a trace row), which Actor.evaluate_env prefers
+    to env.MODELS[model]["eval"]: the terrain is no model, and the table keeps the grass walker's entry point.  Built by name, like the
+    grass marker; workers._default_test_env builds it for `opt.env_model = "walker"`, `opt.env_terrain = "hardcore"` under
+    `opt.test_on_device_hardcore`."""
+
+    terrain = "hardcore"
+    eval_entry = ("ddrl_env_eval_policy_walker_hardcore", 32)
+
+    def __init__(self, seed=0, max_ep_len=1600, velocity_iterations=180, position_iterations=60):
+        super().__init__(seed, max_ep_len, velocity_iterations, position_iterations)
+
+    def _model_kw(self):
+        return dict(super()._model_kw(), terrain="hardcore")
+
+    def step(self, a):
+        raise RuntimeError("DeviceBipedalWalkerHardcore is not steppable: its episodes run on the device (Actor.evaluate_env / Actor.test); "
+                           "use env.make(\"BipedalWalkerHardcore-v2\", model=\"walker\", terrain=\"hardcore\") for an env to step from "
+                           "the host")
+
+
 def _device_view(ptr, count, typestr, device):
     """`count` elements of device memory the library owns as a flat tensor (a __cuda_array_interface__ view: no copy, no ownership)."""
     class _Holder:
@@ -508,7 +539,7 @@ def _device_view(ptr, count, typestr, device):
 
 
 def eval_results(vec, want_row):
-    """The results of the last ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_policy_walker on `vec` (a VecLunarLander or a
+    """The results of the last ddrl_env_eval_policy / ddrl_env_eval_q / ddrl_env_eval_policy_walker / _walker_hardcore on `vec` (a VecLunarLander or a
     VecBipedalWalker; want_row: 12, 20 or 32) as NumPy: dict(ret float64 [n],
     len int32 [n]) and, where that call kept a trace, `trace` float32 [n, max_ep_len, want_row].  Read from the block the env handle
     owns (ddrl_env_eval_results) through __cuda_array_interface__ views, as replay.py reads its rings; synchronises the stream."""
@@ -593,21 +624,30 @@ def _walker_door(env_name, kw, who):
     return {k: v for k, v in kw.items() if k != "model"}
 
 
+def _walker_marker_of(walker_kw):
+    """(the evaluation entry point and its file, the marker's class name) of the terrain a walker door was asked for: what the two
+    doors below name when they refuse to build a marker."""
+    if walker_kw.get("terrain", "grass") == "hardcore":
+        return "ddrl_env_eval_policy_walker_hardcore, csrc/walker_hardcore_eval.hip", "DeviceBipedalWalkerHardcore"
+    return "ddrl_env_eval_policy_walker, csrc/walker_eval.hip", "DeviceBipedalWalker"
+
+
 def make(env_name="LunarLanderContinuous-v2", on_device=False, **kw):
     """gym.make stand-in (example/dsac.py:78).  model="simple" | "articulated" (+ velocity_iterations, position_iterations) is passed on to the env.  "LunarLander-v2": the discrete single-env facade.  on_device=True: the test-env marker whose episodes `Actor.test` /
     `Model.test_agent` run as one launch (DeviceLunarLander; "LunarLander-v2": DeviceLunarLanderDiscrete for dqn.Actor.test / ActorSQN.test)
     on the one-body lander; the articulated model's marker is built by make_device.
     "BipedalWalker-v2" with model="walker" (+ seed, max_ep_len, velocity_iterations, position_iterations): the BipedalWalker facade
     (_walker_door); on_device=True raises: the walker's evaluation kernel is reached through env.DeviceBipedalWalker, not this door.
-    "BipedalWalkerHardcore-v2" with model="walker" AND terrain="hardcore": the same facade on the Hardcore terrain."""
+    "BipedalWalkerHardcore-v2" with model="walker" AND terrain="hardcore": the same facade on the Hardcore terrain (on_device=True
+    raises likewise: that terrain's marker is env.DeviceBipedalWalkerHardcore)."""
     walker = _walker_door(env_name, kw, "env.make")
     if walker is not None:
         if on_device:
             raise ValueError("env.make(%r, on_device=True): this door builds the landers' markers only (ddrl_env_eval_policy / ddrl_env_eval_q, "
-                             "csrc/eval3.hip, run landers) — the evaluation kernel for the walker (ddrl_env_eval_policy_walker, "
-                             "csrc/walker_eval.hip) is reached through env.DeviceBipedalWalker(seed, max_ep_len, velocity_iterations, "
-                             "position_iterations) and Actor.test / Actor.evaluate_env; use on_device=False for a host-stepped "
-                             "env.make(%r, model=\"walker\")" % (env_name, env_name))
+                             "csrc/eval3.hip, run landers) — the evaluation kernel for the walker (%s) is reached through env.%s(seed, "
+                             "max_ep_len, velocity_iterations, position_iterations) and Actor.test / Actor.evaluate_env; use "
+                             "on_device=False for a host-stepped env.make(%r, model=\"walker\")"
+                             % ((env_name,) + _walker_marker_of(walker) + (env_name,)))
         return BipedalWalker(**walker)
     if on_device and _check_model(kw.get("model", "simple")) != "simple":
         raise ValueError("env.make(on_device=True, model=%r): this door builds the one-body lander's marker only (ddrl_policy_eval, csrc/eval.hip; "
@@ -627,13 +667,13 @@ def make_device(env_name="LunarLanderContinuous-v2", **kw):
     """The test-env marker of an on-device evaluation for EITHER model: seed, max_ep_len and model="simple" | "articulated"
     (+ velocity_iterations, position_iterations) as env.make takes them.  "LunarLander-v2": DeviceLunarLanderDiscrete (dqn.Actor.test /
     ActorSQN.test), else DeviceLunarLander (Actor.test / Model.test_agent).  The one-body marker is what make(on_device=True) returns.
-    "BipedalWalker-v2" raises: the walker's marker is env.DeviceBipedalWalker."""
-    if _walker_door(env_name, kw, "env.make_device") is not None:
+    "BipedalWalker-v2" raises: the walker's marker is env.DeviceBipedalWalker ("BipedalWalkerHardcore-v2": env.DeviceBipedalWalkerHardcore)."""
+    walker = _walker_door(env_name, kw, "env.make_device")
+    if walker is not None:
         raise ValueError("env.make_device(%r): this door builds the landers' markers only (ddrl_env_eval_policy / ddrl_env_eval_q, "
-                         "csrc/eval3.hip, run landers) — the evaluation kernel for the walker (ddrl_env_eval_policy_walker, "
-                         "csrc/walker_eval.hip) is reached through env.DeviceBipedalWalker(seed, max_ep_len, velocity_iterations, "
-                         "position_iterations) and Actor.test / Actor.evaluate_env; a host-stepped env is env.make(%r, model=\"walker\")"
-                         % (env_name, env_name))
+                         "csrc/eval3.hip, run landers) — the evaluation kernel for the walker (%s) is reached through env.%s(seed, "
+                         "max_ep_len, velocity_iterations, position_iterations) and Actor.test / Actor.evaluate_env; a host-stepped env "
+                         "is env.make(%r, model=\"walker\")" % ((env_name,) + _walker_marker_of(walker) + (env_name,)))
     _check_model(kw.get("model", "simple"))
     if env_name == "LunarLander-v2":
         return DeviceLunarLanderDiscrete(**kw)

@@ -45,18 +45,31 @@ def _default_test_env(name, args):
     """The test workers' env when the caller passes no make_env: the host env of _default_env — or, with `args.test_on_device` set
     (default False), the device marker of `args.env_model` (env.make_device with _env_model_kw; the walker's, which that door does not
     build: env.DeviceBipedalWalker): a round's evaluation episodes then run as one launch, on the one-body lander, the articulated
-    lander and the walker — on its grass terrain: with `args.env_terrain = "hardcore"` the marker raises ValueError (the evaluation
-    kernel holds the grass terrain only), and the host loop, the default, is what plays that terrain."""
+    lander and the walker — on its grass terrain: with `args.env_terrain = "hardcore"` that marker raises ValueError (its evaluation
+    kernel holds the grass terrain).  The Hardcore terrain's marker has a flag of its own, read first:
+    `args.test_on_device_hardcore` (default False) with `args.env_model = "walker"` and `args.env_terrain = "hardcore"` builds
+    env.DeviceBipedalWalkerHardcore; on any other model or terrain it raises ValueError."""
+    seed, max_ep_len = int(getattr(args, "seed", 0)), int(args.max_ep_len)
+    if getattr(args, "test_on_device_hardcore", False):
+        from . import env as _env
+        kw = _env_model_kw(args)
+        if kw.get("model") != "walker" or kw.get("terrain") != "hardcore":
+            raise ValueError("opt.test_on_device_hardcore needs opt.env_model = \"walker\" and opt.env_terrain = \"hardcore\" (got %r, %r): "
+                             "every other env's marker is opt.test_on_device's" % (kw.get("model", "simple"), kw.get("terrain", "grass")))
+        return _env.DeviceBipedalWalkerHardcore(seed=seed, max_ep_len=max_ep_len, velocity_iterations=kw["velocity_iterations"],
+                                                position_iterations=kw["position_iterations"])
     if not getattr(args, "test_on_device", False):
         return _default_env(name, args)
     from . import env as _env
     kw = _env_model_kw(args)
     if kw.get("model") == "walker":
-        # (terrain="hardcore" raises there: the evaluation kernel is missing for it; the host loop, the default, plays it)
-        return _env.DeviceBipedalWalker(seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len),
-                                        velocity_iterations=kw["velocity_iterations"], position_iterations=kw["position_iterations"],
-                                        terrain=kw.get("terrain", "grass"))
-    return _env.make_device(name, seed=int(getattr(args, "seed", 0)), max_ep_len=int(args.max_ep_len), **kw)
+        if kw.get("terrain", "grass") == "hardcore":
+            raise ValueError("opt.test_on_device with opt.env_terrain = \"hardcore\": this flag's walker marker (env.DeviceBipedalWalker) "
+                             "holds the grass terrain's evaluation kernel; the Hardcore terrain's marker "
+                             "(env.DeviceBipedalWalkerHardcore) is built under opt.test_on_device_hardcore")
+        return _env.DeviceBipedalWalker(seed=seed, max_ep_len=max_ep_len, velocity_iterations=kw["velocity_iterations"],
+                                        position_iterations=kw["position_iterations"], terrain=kw.get("terrain", "grass"))
+    return _env.make_device(name, seed=seed, max_ep_len=max_ep_len, **kw)
 
 
 def _stop(args):
@@ -140,7 +153,8 @@ def worker_train(ps, replay_buffer, args, make_agent=None):
 def worker_test(ps, args, start_time=None, n=10, make_env=None, make_agent=None, log=print, max_rounds=None):
     """example/dsac.py:153-177: pull, run n deterministic episodes, log, repeat.  With `args.logger_kwargs`
     (dsac.py:205) the rounds also go to an EpochLogger: config.json + progress.txt (AverageTestEpRet, Time).
-    make_env None and `args.test_on_device` set: the test env is the device marker of `args.env_model` (_default_test_env)."""
+    make_env None and `args.test_on_device` set: the test env is the device marker of `args.env_model` (_default_test_env); the
+    Hardcore walker's marker: `args.test_on_device_hardcore`."""
     logger = None
     if getattr(args, "logger_kwargs", None):
         from .logx import EpochLogger
@@ -259,7 +273,8 @@ def worker_train_sac1(ps, replay_buffer, opt, learner_index, make_agent=None, ma
 def worker_test_sac1(ps, replay_buffer, opt, make_env=None, make_agent=None, log=print, sleep=time.sleep, max_rounds=None, n=25):
     """algos/sac1/sac1.py:214-252: pull, 25 deterministic episodes, print test_reward / counters / update frequency,
     `ps.save_weights()` whenever the return beats the best so far, sleep 5 s, repeat.
-    make_env None and `opt.test_on_device` set: the test env is the device marker of `opt.env_model` (_default_test_env)."""
+    make_env None and `opt.test_on_device` set: the test env is the device marker of `opt.env_model` (_default_test_env); the
+    Hardcore walker's marker: `opt.test_on_device_hardcore`."""
     if make_env is None:
         make_env = lambda name: _default_test_env(name, opt)
     if make_agent is None:

@@ -597,10 +597,10 @@ int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noi
                                       float *next_obs_d, uint8_t *ended_d, void *stream);
 /* The same step on the WALKER (kind = DDRL_ENV_WALKER) is ddrl_env_step_wrapped_walker, declared with its memory contract in
  * include/ddrl_walker.h: this header's set of declarations is closed, and entry points added since live in headers beside it —
- * include/ddrl_walker.h (the walker's wrapped step), include/ddrl_walker_eval.h (its evaluation episodes) and
+ * include/ddrl_walker.h (the walker's wrapped step), include/ddrl_walker_eval.h (its evaluation episodes),
  * include/ddrl_walker_hardcore.h (ddrl_env_create_walker: a walker handle with a terrain mode, DDRL_WALKER_TERRAIN_HARDCORE being gym's
  * BipedalWalkerHardcore terrain; such a handle's state block has DDRL_ENVWH_STATE_FIELDS rows, and everything said of a walker handle in
- * this header holds for it). */
+ * this header holds for it) and include/ddrl_walker_hardcore_eval.h (the evaluation episodes of such a Hardcore handle). */
 /* RolloutDevice.step fused: ONE vector step of worker_rollout's policy phase (example/dsac.py:96-130; SAC1 flavour
  * algos/sac1/sac1.py:177-213) for all n envs, as two launches with no host work in between:
  *   a = agent.get_action(o)  (Actor.get_action, actor_learner.py:195-197; noise element i*act+c of the counter stream

@@ -1,7 +1,8 @@
 /* C ABI of libddrl_hip.so, the walker's entry points beside include/ddrl.h: what has been added for the bipedal walker
  * (DDRL_ENV_WALKER) since ddrl.h's set of declarations was closed.  Conventions, status codes, ddrl_last_error(), the stream contract
  * and the memory contract are ddrl.h's; include this header instead of, or after, ddrl.h.  (A walker handle's terrain mode:
- * include/ddrl_walker_hardcore.h; on a Hardcore handle the function below runs that terrain's kernel, contract unchanged.) */
+ * include/ddrl_walker_hardcore.h; on a Hardcore handle the function below runs that terrain's kernel, contract unchanged.  The
+ * walker's evaluation episodes: include/ddrl_walker_eval.h on grass, include/ddrl_walker_hardcore_eval.h on the Hardcore terrain.) */
 #ifndef DDRL_WALKER_H
 #define DDRL_WALKER_H
 

@@ -1,7 +1,8 @@
 /* C ABI of libddrl_hip.so, the walker's evaluation entry point beside include/ddrl.h and include/ddrl_walker.h: the evaluation
  * episodes of the bipedal walker (DDRL_ENV_WALKER) on the device.  Conventions, status codes, ddrl_last_error(), the stream contract
  * and the memory contract are ddrl.h's; include this header instead of, or after, ddrl.h.  (A walker handle's terrain mode:
- * include/ddrl_walker_hardcore.h; the function below refuses a Hardcore handle with DDRL_ERR_UNSUPPORTED, nothing touched.) */
+ * include/ddrl_walker_hardcore.h; the function below holds the grass terrain and refuses a Hardcore handle with DDRL_ERR_UNSUPPORTED,
+ * nothing touched: the Hardcore terrain's twin is ddrl_env_eval_policy_walker_hardcore, include/ddrl_walker_hardcore_eval.h.) */
 #ifndef DDRL_WALKER_EVAL_H
 #define DDRL_WALKER_EVAL_H
 

@@ -1,6 +1,6 @@
 /* C ABI of libddrl_hip.so, the walker's terrain modes beside include/ddrl.h, include/ddrl_walker.h (the walker's wrapped step) and
  * include/ddrl_walker_eval.h (its evaluation episodes): the HARDCORE terrain — stumps, pits and stairs — as a mode of the walker kind,
- * carried on the env handle.  Conventions, status codes, ddrl_last_error(), the stream contract and the memory contract are ddrl.h's;
+ * carried on the env handle (its evaluation episodes: include/ddrl_walker_hardcore_eval.h).  Conventions, status codes, ddrl_last_error(), the stream contract and the memory contract are ddrl.h's;
  * include this header instead of, or after, ddrl.h. */
 #ifndef DDRL_WALKER_HARDCORE_H
 #define DDRL_WALKER_HARDCORE_H
@@ -30,7 +30,8 @@ extern "C" {
  * and actions [n,4] on the 16-byte grid); ddrl_env_state_fields returns DDRL_ENVWH_STATE_FIELDS.  The handle's kind stays
  * DDRL_ENV_WALKER, so every lander entry point refuses it as it refuses any walker handle.  ddrl_env_eval_policy_walker
  * (ddrl_walker_eval.h) returns DDRL_ERR_UNSUPPORTED on it, the message starting "ddrl_env_eval_policy_walker:" and naming the
- * hardcore terrain, nothing touched: the evaluation kernel keeps the episode's terrain in LDS and holds the grass generator only.
+ * hardcore terrain, nothing touched: that entry point holds the grass terrain.  The evaluation episodes of a Hardcore handle are
+ * ddrl_env_eval_policy_walker_hardcore's (ddrl_walker_hardcore_eval.h), which in turn refuses a grass handle.
  * Allocates and resets every env (a host synchronisation), like ddrl_env_create_ex.
  * DDRL_ERR_BAD_ARG with *out untouched: what ddrl_env_create_ex refuses (a NULL out, n_envs < 1, max_ep_len < 1 or >= 2^24, an
  * iteration count < 1), and a terrain that is neither of the two values above. */

@@ -1,6 +1,7 @@
 """Evaluation episodes on the WALKER: the one-launch device path fed from handles (ddrl_env_eval_policy_walker, csrc/walker_eval.hip)
 against the host loop it replaces, at hidden (400, 300) and gym's 180 velocity / 60 position iterations, on the same glorot weights and
-the same env seed, for the continuous policy (agent.Actor).
+the same env seed, for the continuous policy (agent.Actor).  --terrain hardcore: the same two measurements on the Hardcore terrain
+(ddrl_env_eval_policy_walker_hardcore, csrc/walker_hardcore_eval.hip; the host loop on env.BipedalWalker(terrain="hardcore")).
 
   device  the C call between HIP events (the pack launch of the weights and the episodes' launch), n = 25 episodes at
           max_ep_len = 1600: one warm-up call, then five; the median, every run, the env steps played, the longest episode
@@ -11,7 +12,8 @@ the same env seed, for the continuous policy (agent.Actor).
 Every measurement is a child process of its own under its own `timeout` (this process never opens the GPU); after a child that fails
 or runs into its limit nothing more is started.
 
-    python tools/walker_eval_probe.py [--out profiles/eval_on_device_walker.txt]"""
+    python tools/walker_eval_probe.py [--out profiles/eval_on_device_walker.txt]
+    python tools/walker_eval_probe.py --terrain hardcore [--out profiles/eval_on_device_walker_hardcore.txt]"""
 import argparse
 import os
 import statistics
@@ -40,8 +42,10 @@ def device_step(a):
     lib = _lib.load()
     n, L = a.episodes, a.max_ep_len
     actor = _agent(L)
-    vec = env.DeviceBipedalWalker(a.seed, L, **ITERATIONS).handle()
-    call = lambda: lib.ddrl_env_eval_policy_walker(vec._h, actor._h, n, 0, 0, _lib.stream_ptr())
+    marker = env.DeviceBipedalWalkerHardcore if a.terrain == "hardcore" else env.DeviceBipedalWalker
+    vec = marker(a.seed, L, **ITERATIONS).handle()
+    entry = getattr(lib, getattr(marker, "eval_entry", env.MODELS["walker"]["eval"])[0])
+    call = lambda: entry(vec._h, actor._h, n, 0, 0, _lib.stream_ptr())
     ms = []
     for _ in range(6):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -75,7 +79,7 @@ def host_step(a):
             return super().step(act)
     runs = []
     for _ in range(6):
-        e, Counting.steps = Counting(a.seed, L, **ITERATIONS), 0
+        e, Counting.steps = Counting(a.seed, L, terrain=a.terrain, **ITERATIONS), 0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         actor.test(e, None, n)
@@ -93,6 +97,7 @@ def main():
     ap.add_argument("--max-ep-len", type=int, default=1600)
     ap.add_argument("--host-max-ep-len", type=int, default=150)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--terrain", choices=("grass", "hardcore"), default="grass")
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", default=None, help="internal: run ONE measurement in this process (device | host)")
     a = ap.parse_args()
@@ -104,12 +109,13 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
-    say("walker_eval_probe: bipedal walker, 180 velocity / 60 position iterations, hidden (400, 300), glorot weights (seed 0), env seed %d" % a.seed)
+    say("walker_eval_probe: bipedal walker%s, 180 velocity / 60 position iterations, hidden (400, 300), glorot weights (seed 0), env seed %d"
+        % (" on the hardcore terrain" if a.terrain == "hardcore" else "", a.seed))
     res, ok = {}, True
     for which in ("device", "host"):
         cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "--step", which,
                "--episodes", str(a.episodes), "--host-episodes", str(a.host_episodes), "--max-ep-len", str(a.max_ep_len),
-               "--host-max-ep-len", str(a.host_max_ep_len), "--seed", str(a.seed)]
+               "--host-max-ep-len", str(a.host_max_ep_len), "--seed", str(a.seed), "--terrain", a.terrain]
         p = subprocess.run(cmd, capture_output=True, text=True)
         for s in p.stdout.splitlines():
             if s.startswith("RESULT "):
