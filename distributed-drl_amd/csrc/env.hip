@@ -1,7 +1,7 @@
 // The C ABI of the env family: every ddrl_env_* and ddrl_rollout_* entry point that takes an env handle (the evaluation episodes:
 // eval3.hip, walker_eval.hip), the fused-step drivers and their envelopes, behind ONE model table — a row per DDRL_ENV_* kind with the model's widths
 // and its launch functions.  Host code only: every kernel lives in its model's own translation unit (lander.hip; env3.hip,
-// rollout3*.hip; walker*.hip; rollout_nstep.hip) and is reached through env_launch.h, so an edit here cannot change what a kernel
+// rollout3*.hip; walker.hip; rollout_nstep.hip) and is reached through env_launch.h, so an edit here cannot change what a kernel
 // compiles to.
 #include "ddrl_common.h"
 #include "../../include/ddrl_walker.h"
@@ -56,24 +56,18 @@ static const EnvModel ENV_MODELS[] = {
      [](float *S, long long n, uint32_t, float *obs_d, void *stream) { return ddrl_rollout3_launch_obs(S, n, obs_d, stream); },
      ddrl_rollout3_launch_step, ddrl_rollout3_launch_step_q, ddrl_nstep3_launch_step, rollout3_check},
     {DDRL_ENV_WALKER, DDRL_ENVW_STATE_FIELDS, 24, 4, 16, true, "DDRL_ENV_WALKER", "the walker", "_walker",
-     ddrl_walker_launch_reset,
-     [](int, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d, float *rew_d,
-        float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream) {
-         return ddrl_walker_launch_step(S, n, seed, max_ep_len, vit, pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, stats_d, stream);
-     },
-     ddrl_walker_launch_step_wrapped, nullptr, nullptr, nullptr, nullptr, nullptr},
+     [](auto... a) { return ddrl_walker_launch_reset(0, a...); },
+     [](int, auto... a) { return ddrl_walker_launch_step(0, a...); },
+     [](auto... a) { return ddrl_walker_launch_step_wrapped(0, a...); }, nullptr, nullptr, nullptr, nullptr, nullptr},
 };
 // The walker on the HARDCORE terrain (ddrl_walker_hardcore.h) is no kind and no row of the table: a terrain mode of the walker kind.
-// Its launches and its state block's rows stand here, as the walker row with those four members exchanged; ddrl_env_create_walker
+// Its state block's rows and its launches' terrain argument stand here, the walker row otherwise; ddrl_env_create_walker
 // hands a handle this object by the handle's `terrain`, so every entry point above and below serves it through h->model unchanged.
 static const EnvModel ENV_WALKER_HARDCORE = {
     DDRL_ENV_WALKER, DDRL_ENVWH_STATE_FIELDS, 24, 4, 16, true, "DDRL_ENV_WALKER", "the walker", "_walker",
-    ddrl_walker_hc_launch_reset,
-    [](int, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d, float *rew_d,
-       float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream) {
-        return ddrl_walker_hc_launch_step(S, n, seed, max_ep_len, vit, pit, act_d, obs2_d, rew_d, done_d, next_obs_d, ended_d, stats_d, stream);
-    },
-    ddrl_walker_hc_launch_step_wrapped, nullptr, nullptr, nullptr, nullptr, nullptr};
+    [](auto... a) { return ddrl_walker_launch_reset(1, a...); },
+    [](int, auto... a) { return ddrl_walker_launch_step(1, a...); },
+    [](auto... a) { return ddrl_walker_launch_step_wrapped(1, a...); }, nullptr, nullptr, nullptr, nullptr, nullptr};
 // the table lookup: the row of `kind`, nullptr where no model has it
 static const EnvModel *env_model_of(int kind) {
     for (const EnvModel &m : ENV_MODELS)
@@ -398,7 +392,7 @@ int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noi
     return env_step_wrapped(DDRL_ENV_ARTICULATED, "ddrl_env_step_wrapped_articulated", "NULL pointer", "action_repeat and limit_steps must be >= 1", h,
                             act_d, act_noise, obs_noise, reward_scale, action_repeat, limit_steps, obs2_d, rew_d, done_d, next_obs_d, ended_d, stream);
 }
-// ... on the walker (kernel: walker_nstep.hip, k_walker_step_wrapped): [n,4] actions as one float4, [n,24] observations as six
+// ... on the walker (kernel: walker.hip, k_walker_step_wrapped): [n,4] actions as one float4, [n,24] observations as six
 int ddrl_env_step_wrapped_walker(ddrl_env_t *h, float *act_d, float act_noise, float obs_noise, float reward_scale, int32_t action_repeat,
                                  int32_t limit_steps, float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d,
                                  void *stream) {

@@ -1,5 +1,5 @@
 // Every env model's launch functions as env.hip's model table reaches them, declared once: the one-body lander's (lander.hip), the
-// articulated lander's (env3.hip, rollout3*.hip), the walker's (walker*.hip) and the n-step fused step's (rollout_nstep.hip).
+// articulated lander's (env3.hip, rollout3*.hip), the walker's (walker.hip) and the n-step fused step's (rollout_nstep.hip).
 // Host side only, and no device header: a translation unit that includes this sees no kernel code it did not see before.
 // Internal to libddrl_hip.so.  The callers have checked the arguments and selected the device; vit / pit are the handle's iteration
 // counts (the one-body model has none and ignores them: its launches take them so that one table row type holds all three models).
@@ -40,17 +40,12 @@ int ddrl_rollout3_launch_step(const void *args, int vit, int pit, void *stream);
 int ddrl_rollout3_launch_step_q(const void *args, int versioned, int vit, int pit, void *stream);
 int ddrl_nstep3_launch_step(const NStepLaunch &a, int vit, int pit, void *stream);
 
-// ---- the walker (walker.hip; its wrapped step: walker_nstep.hip): [n,24] observations, [n,4] actions; on the Hardcore terrain
-// (walker_hardcore.hip, state block [DDRL_ENVWH_STATE_FIELDS][n]): the ddrl_walker_hc_* three, argument for argument
-int ddrl_walker_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
-int ddrl_walker_launch_step(float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d,
-                            float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
-int ddrl_walker_launch_step_wrapped(float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d, float act_noise,
-                                    float obs_noise, float reward_scale, int action_repeat, float *obs2_d, float *rew_d, float *done_d,
-                                    float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
-int ddrl_walker_hc_launch_reset(float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d, void *stream);
-int ddrl_walker_hc_launch_step(float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d, float *obs2_d,
-                               float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
-int ddrl_walker_hc_launch_step_wrapped(float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d, float act_noise,
-                                       float obs_noise, float reward_scale, int action_repeat, float *obs2_d, float *rew_d, float *done_d,
-                                       float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+// ---- the walker (walker.hip): [n,24] observations, [n,4] actions.  hardcore selects the terrain mode's instantiation: 0 the grass
+// walker (state block [DDRL_ENVW_STATE_FIELDS][n]), 1 the Hardcore terrain ([DDRL_ENVWH_STATE_FIELDS][n])
+int ddrl_walker_launch_reset(int hardcore, float *S, long long n, uint32_t seed, int vit, int pit, const uint8_t *mask_d, float *obs_d,
+                             void *stream);
+int ddrl_walker_launch_step(int hardcore, float *S, long long n, uint32_t seed, int max_ep_len, int vit, int pit, const float *act_d,
+                            float *obs2_d, float *rew_d, float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);
+int ddrl_walker_launch_step_wrapped(int hardcore, float *S, long long n, uint32_t seed, int limit_steps, int vit, int pit, float *act_d,
+                                    float act_noise, float obs_noise, float reward_scale, int action_repeat, float *obs2_d, float *rew_d,
+                                    float *done_d, float *next_obs_d, uint8_t *ended_d, void *stats_d, void *stream);

@@ -10,7 +10,7 @@
 // unrolled constants only (a run-time index would move it to scratch memory).  The 200 terrain heights stay in the state block: a contact
 // point or hull vertex loads the two heights of the segment under it once per step, outside the sweeps, and the lidar walks its 14
 // heights once per step.
-// Walker is a template over the TERRAIN MODE (include/ddrl_walker_hardcore.h): WalkerT<0>, named Walker, is the grass walker, whose
+// Walker is a template over the TERRAIN MODE (include/ddrl_walker_hardcore.h): WalkerT<0> is the grass walker, whose
 // instantiation is the code it was before the parameter existed (every addition below stands behind `if constexpr (HC)`, and the slot
 // count NS folds to 8); WalkerT<1> is the HARDCORE terrain (stumps, pits, stairs: axis-aligned boxes in the state block behind row 286),
 // specified by tests/walker_hardcore_oracle.py: 16 contact slots (corner q: floor slot 2 q, wall slot 2 q + 1), the hull's box test and
@@ -62,7 +62,7 @@ enum { CRX = 0, CRY, CNX, CNY, CX0, CH0, CNM, CTM, W_CFIELDS };
 enum { RAX = 0, RAY, RBX, RBY, K11, K12, K22, IDET, JANG, MSPD, MMAX, W_JFIELDS };
 constexpr int W_LDS_FIELDS = 8 * W_CFIELDS + 4 * W_JFIELDS;
 constexpr int W_LDS_FIELDS_H = 16 * W_CFIELDS + 4 * W_JFIELDS;   // WalkerT<1>: 16 contact slots, 43 KiB per workgroup
-// (the kernel declares `__shared__ float wl[W_LDS_FIELDS][64]` — W_LDS_FIELDS_H for WalkerT<1> — and hands its lane's column to Walker::L)
+// (the kernel declares `__shared__ float wl[WalkerT<HC>::LFIELDS][64]` and hands its lane's column to WalkerT::L)
 // (LS: WalkerT's lane stride, 64 in every such kernel; a kernel that steps ONE env in one lane packs the fields at LS = 1)
 #define WCF(f, s) L[((f) * NS + (s)) * LS]
 #define WJF(f, j) L[(NS * W_CFIELDS + (f) * 4 + (j)) * LS]
@@ -630,8 +630,7 @@ struct WalkerT {
         }
     }
 };
-using Walker = WalkerT<0>;           // the grass walker (walker.hip, walker_nstep.hip, walker_eval.hip)
-using WalkerHardcore = WalkerT<1>;   // walker_hardcore.hip
+using WalkerHardcore = WalkerT<1>;   // the Hardcore terrain at the step kernels' lane stride (walker.hip: WalkerT<HC>, HC = 1)
 using WalkerHardcoreLane = WalkerT<1, 1>;   // walker_hardcore_eval.hip: one env in one lane, its 172 fields packed (688 bytes of LDS)
 
 }  // namespace

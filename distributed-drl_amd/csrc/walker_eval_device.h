@@ -8,8 +8,8 @@
 //     added in slice order on the bias; the eight head partials (mu 0..3, log_std 0..3) per group of 16 columns, each summed in column
 //     order from zero, added in group order, then the head bias, then ddrl_pol::policy_row with the noise elements eps0 = 0.  So a
 //     step's action is bit for bit what Actor.get_action(o, deterministic=True) returns for the same observation;
-//   * then ONE lane runs the terrain's WalkerT (walker_device.h, unchanged) as the terrain's reset / step kernels run it (walker.hip,
-//     walker_hardcore.hip): seed = the handle's, id = 0, epi = first_episode + blockIdx.x; build(), one zero-action physics(), obs();
+//   * then ONE lane runs the terrain's WalkerT (walker_device.h, unchanged) as the terrain's reset / step kernels run it
+//     (walker.hip): seed = the handle's, id = 0, epi = first_episode + blockIdx.x; build(), one zero-action physics(), obs();
 //     per step eplen += 1, epret += rew, ended = done_env || eplen >= max_ep_len.  Episode e is the (first_episode + e)-th a host
 //     env.BipedalWalker of the handle's seed, max_ep_len, iteration counts and terrain plays.
 // The kernel holds ONE inlined physics(): the reset's zero-action step is the first trip through the loop body, whose policy row it

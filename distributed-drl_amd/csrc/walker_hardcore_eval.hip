@@ -2,13 +2,13 @@
 // ddrl_env_eval_policy_walker_hardcore (include/ddrl_walker_hardcore_eval.h), read back by ddrl_env_eval_results (eval3.hip).
 // k_walker_hc_eval is k_walker_eval's twin (walker_eval.hip): one workgroup of 256 threads per episode, nothing crosses workgroups; the
 // policy row on all threads in Actor.get_action's summation order, then ONE lane running the Hardcore walker — WalkerT<1, 1>
-// (WalkerHardcoreLane, walker_device.h: WalkerHardcore's text, the solver unchanged) with n = 1 — as k_walker_hc_reset /
-// k_walker_hc_step run it (walker_hardcore.hip): build() per episode with id = 0, epi = first_episode + blockIdx.x, the reset's
+// (WalkerHardcoreLane, walker_device.h: WalkerHardcore's text, the solver unchanged) with n = 1 — as k_walker_reset<1> /
+// k_walker_step<1> run it (walker.hip): build() per episode with id = 0, epi = first_episode + blockIdx.x, the reset's
 // zero-action trip through the one inlined physics(), the block-uniform ended flag as the loop's only exit.  The body is the text of
 // walker_eval_body.h with WE_HC = 1 (see walker_eval_device.h): the episode loop and the policy row exist once, for both terrains.
 // LDS: Sc / T / B / Cc point into a state-block column of NFWH = 663 floats (2652 bytes: the terrain, the box count, the box table and
 // the per-column box index the generator writes).  The one lane's 172 sweep fields are packed at lane stride 1 (688 bytes, inside the
-// bytes of the layer-2 slice sums): at walker_hardcore.hip's stride of 64 they would be 43 KiB for one lane and the kernel about 67 KiB.
+// bytes of the layer-2 slice sums): at the step kernels' stride of 64 they would be 43 KiB for one lane and the kernel about 67 KiB.
 // The compiler's report — no scratch, no spilled VGPRs, the LDS bytes — is profiles/walker_hardcore_eval_resource_usage.txt.
 // Compiled with -ffp-contract=off.  A translation unit of its own: no other file's kernels depend on it.
 #include "ddrl_common.h"

@@ -144,12 +144,12 @@ class VecBipedalWalker(VecLunarLander):
     shape — hull, two two-segment legs on four motorised joints, 10 lidar rays, 24 observations, 4 actions — on the articulated
     lander's solver with `velocity_iterations` / `position_iterations` sweeps (gym's world.Step arguments by default).  Specification,
     and what is gym's, Box2D's and this build's own: tests/walker_oracle.py.  NOT pinned against gym.  It has reset / step /
-    step_wrapped_walker (the n-step worker's step, csrc/walker_nstep.hip) / sample_actions / stats / get_state / set_state; the
+    step_wrapped_walker (the n-step worker's step, csrc/walker.hip) / sample_actions / stats / get_state / set_state; the
     landers' wrapped steps (the inherited step_wrapped and step_wrapped_articulated), every fused rollout launch and the landers'
     on-device evaluation (ddrl_env_eval_policy / ddrl_env_eval_q) hold a lander, and the library refuses this env there (DdrlUnsupported
     naming the entry point and the walker).  Its evaluation episodes run on the device through a door of their own: the marker
     DeviceBipedalWalker and Actor.evaluate_env (ddrl_env_eval_policy_walker, csrc/walker_eval.hip), which borrows a handle of this class.
-    terrain="hardcore" (ddrl_env_create_walker, include/ddrl_walker_hardcore.h; csrc/walker_hardcore.hip; specification
+    terrain="hardcore" (ddrl_env_create_walker, include/ddrl_walker_hardcore.h; csrc/walker.hip; specification
     tests/walker_hardcore_oracle.py): gym's BipedalWalkerHardcore terrain generator — stumps, pits and stairs as boxes, a second (wall)
     contact slot per leg corner, a hull that ends the episode inside a box, lidar rays that see box edges — behind every method above,
     with a state block of `state_fields` = 663 rows.  Its evaluation episodes run on the device through the marker
@@ -202,7 +202,7 @@ class VecBipedalWalker(VecLunarLander):
         return self.obs2, self.rew, self.done, self.obs, self.ended
 
     def step_wrapped_walker(self, act, act_noise=0.0, obs_noise=0.0, reward_scale=1.0, action_repeat=3, limit_steps=None):
-        """step_wrapped on the walker (ddrl_env_step_wrapped_walker, csrc/walker_nstep.hip; specification
+        """step_wrapped on the walker (ddrl_env_step_wrapped_walker, csrc/walker.hip; specification
         tests/walker_wrapped_oracle.py): the same Wrapper and bookkeeping around the five-body solver with this env's iteration counts;
         same arguments and outputs as step_wrapped_articulated, observations [n, 24], done the raw d.  `act` ([n, 4], a contiguous
         float32 device tensor) receives the noisy action in place.  The library reads and writes an action row as one float4, so `act`

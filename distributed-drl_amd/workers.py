@@ -1014,7 +1014,7 @@ class RolloutDeviceNStep(_RolloutWorker):
 
     The walker (`opt.env_model = "walker"`: env.VecBipedalWalker with the same iteration options — the env sac_ray.py itself names)
     sets `opt.obs_dim, opt.act_dim = 24, 4`, as RolloutDevice does, and steps through VecBipedalWalker.step_wrapped_walker
-    (ddrl_env_step_wrapped_walker, csrc/walker_nstep.hip).  Every ring handed to it must be a ReplayBufferNStep of 24 / 4: the
+    (ddrl_env_step_wrapped_walker, csrc/walker.hip).  Every ring handed to it must be a ReplayBufferNStep of 24 / 4: the
     constructor checks that before it allocates anything and raises ValueError otherwise.  The worker is always unfused there — no
     fused launch holds the walker — and has no version store: an actor of 24 observations lies outside the direct-operand envelope,
     _enable_versions' ValueError is caught as for any such actor, and weight adoption is the whole-vector swap after the step

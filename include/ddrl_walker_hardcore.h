@@ -22,7 +22,7 @@ extern "C" {
 /* A walker handle (kind DDRL_ENV_WALKER) with a terrain mode.  terrain = DDRL_WALKER_TERRAIN_GRASS: the handle
  * ddrl_env_create_ex(kind = DDRL_ENV_WALKER, velocity_iterations, position_iterations) returns, bit for bit — same kernels, same
  * 286-row state block.  terrain = DDRL_WALKER_TERRAIN_HARDCORE: the model of tests/walker_hardcore_oracle.py (kernels
- * csrc/walker_hardcore.hip, reproduced bit for bit): gym's hardcore terrain generator, axis-aligned boxes in the state block, two
+ * csrc/walker.hip, reproduced bit for bit): gym's hardcore terrain generator, axis-aligned boxes in the state block, two
  * contact slots per leg corner (floor and wall), a hull that ends the episode inside a box, lidar rays that see box edges; unpinned
  * against gym like the grass walker.
  * On a Hardcore handle ddrl_env_reset / _step / _stats / _get_state / _set_state / _state_fields (ddrl.h) and

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: crafted start states for the walker on the HARDCORE terrain (tests/walker_hardcore_oracle.py,
-csrc/walker_hardcore.hip) and the census of the branches this terrain adds.
+csrc/walker.hip) and the census of the branches this terrain adds.
 
 The walker under any policy reaches its first obstacle late or never inside a test's budget (the first one starts 4.7 m ahead of the
 start pose), so every contact branch of the terrain is reached from crafted states: `build()` -> (state block [663, N] float32, actions

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: crafted starts for the walker's WRAPPED step (tests/walker_wrapped_oracle.py, csrc/walker_nstep.hip) and the
+"""TEST INFRASTRUCTURE: crafted starts for the walker's WRAPPED step (tests/walker_wrapped_oracle.py, csrc/walker.hip) and the
 census of the Wrapper's branches a run reaches.
 
 `build()` -> (state block [286, N] float32, actions [N, 4] float32): the 96 envs of tests/_walker_scenarios.build() with their step-0

@@ -3,6 +3,8 @@
 * csrc/env.hip is host code only — no `__global__`, no `<<<`: every kernel lives in its model's own translation unit, so an edit to the
   entry points cannot change what a kernel compiles to;
 * every DDRL_ENV_* kind of include/ddrl.h has exactly one row in env.hip's model table;
+* the walker's reset / step / wrapped-step kernels exist once, in csrc/walker.hip, as templates over the terrain mode, with one
+  put_obs24 and one put_stats, behind three launch functions that take the mode as their first argument;
 * a handle's kind is read or tested (`h->kind` but on the left of an assignment, `->kind ==` / `!=`) only inside the table lookup
   (env_model_of) and the one guard function (ddrl_env_refuse) — and in eval3.hip's two choices between the Env3 evaluation launch and the one-body entry point,
   which are the evaluation family's own and are counted here so that they cannot multiply;
@@ -55,6 +57,24 @@ def test_every_kind_has_exactly_one_table_row():
     a, b = _function_body(code, "static const EnvModel ENV_MODELS[]")
     rows = re.findall(r"\{\s*(DDRL_ENV_[A-Z_]+)\s*,", code[a:b])
     assert sorted(rows) == sorted(kinds), rows
+
+
+def test_the_walkers_step_kernels_exist_once_behind_the_terrain_mode():
+    assert not os.path.exists(os.path.join(CSRC, "walker_nstep.hip")) and not os.path.exists(os.path.join(CSRC, "walker_hardcore.hip"))
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".hip", ".h")):
+            text = _read(CSRC, name)
+            assert not any(old in text for old in ("k_walker_hc_reset", "k_walker_hc_step", "ddrl_walker_hc_launch")), name
+    code = _code(_read(CSRC, "walker.hip"))
+    kernels = re.findall(r"(template <int HC>\s*)?__global__[^;{]*\b(k_\w+)\(", code)
+    assert kernels and all(t for t, _ in kernels)
+    assert sorted(k for _, k in kernels) == ["k_walker_reset", "k_walker_step", "k_walker_step_wrapped"] and code.count("__global__") == 3
+    assert code.count("e.physics(") == 3
+    for helper in ("put_obs24", "put_stats"):
+        assert len(re.findall(r"\bvoid %s\(" % helper, code)) == 1, helper
+    launches = re.findall(r"^int (ddrl_walker_launch_\w+)\(int hardcore,", _code(_read(CSRC, "env_launch.h")), flags=re.M)
+    assert sorted(launches) == ["ddrl_walker_launch_reset", "ddrl_walker_launch_step", "ddrl_walker_launch_step_wrapped"]
+    assert len(re.findall(r"\bddrl_walker_\w*launch_\w+\(", _code(_read(CSRC, "env_launch.h")))) == 3
 
 
 def test_a_handles_kind_is_read_in_the_lookup_and_the_guard_only():

@@ -1,4 +1,4 @@
-"""GPU parity of the walker on the HARDCORE terrain (ddrl_env_create_walker, include/ddrl_walker_hardcore.h; csrc/walker_hardcore.hip
+"""GPU parity of the walker on the HARDCORE terrain (ddrl_env_create_walker, include/ddrl_walker_hardcore.h; csrc/walker.hip
 over csrc/walker_device.h's WalkerT<1>) vs its specification tests/walker_hardcore_oracle.py — BIT-EXACT, live at 8 / 3 iterations: the
 plain step, the wrapped step against the reused wrapped oracle — plus the C-ABI around it: the grass door, the block size, the refusals
 (with everything left as it was), the rollout workers' unfused sequences with a learner update, and env.make / Wrapper.

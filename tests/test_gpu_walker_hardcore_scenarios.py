@@ -1,6 +1,6 @@
 """GPU: the crafted obstacle states of tests/_walker_hardcore_scenarios.py — a foot on a stump top, on the ground and against a stump
 side at once, against each pit wall, on stair treads, the tie rule, a hull vertex inside a box, rays on box edges — through the
-Hardcore kernels (csrc/walker_hardcore.hip) BIT-EXACT against the oracle's trajectory, at 8 / 3 and at gym's 180 / 60 iterations, and
+Hardcore kernels (csrc/walker.hip) BIT-EXACT against the oracle's trajectory, at 8 / 3 and at gym's 180 / 60 iterations, and
 the golden file tests/golden/walker_hardcore.npz reproduced at 180 / 60."""
 import os
 import sys

@@ -1,4 +1,4 @@
-"""ddrl_env_step_wrapped_walker (VecBipedalWalker.step_wrapped_walker, kernel k_walker_step_wrapped of csrc/walker_nstep.hip) BIT-EXACT
+"""ddrl_env_step_wrapped_walker (VecBipedalWalker.step_wrapped_walker, kernel k_walker_step_wrapped of csrc/walker.hip) BIT-EXACT
 against tests/walker_wrapped_oracle.py — after every step the observation, reward, raw done, next observation, ended mask, the in-place
 action and the whole 286-field state block, at the end the episode statistics — live, at gym's iteration counts, and from the crafted
 starts of tests/_walker_wrapped_scenarios.py, with a census on the oracle's side of every branch of the Wrapper; the optional outputs;

@@ -210,8 +210,8 @@ def test_walker_hardcore_eval_hip_runs_the_hardcore_walker_and_shares_the_episod
     # the one-lane instantiation packs its fields; every other kernel keeps the stride of 64 by default
     wd = _read(CSRC, "walker_device.h")
     assert "template <int HC, int LS = 64>" in wd and "using WalkerHardcoreLane = WalkerT<1, 1>;" in wd and "using WalkerHardcore = WalkerT<1>;" in wd
-    # the landers' files and the Hardcore step kernels do not see it; the Makefile rebuilds on the new headers
-    for name in ("eval.hip", "eval_q.hip", "eval_episodes.h", "eval3.hip", "walker_hardcore.hip", "walker.hip", "walker_nstep.hip"):
+    # the landers' files and the walker's step kernels do not see it; the Makefile rebuilds on the new headers
+    for name in ("eval.hip", "eval_q.hip", "eval_episodes.h", "eval3.hip", "walker.hip"):
         assert "k_walker_hc_eval" not in _read(CSRC, name) and "walker_eval_body.h" not in _read(CSRC, name), name
     mk = _read(CSRC, "Makefile")
     for dep in ("walker_eval_device.h", "walker_eval_body.h", "../../include/ddrl_walker_hardcore_eval.h"):

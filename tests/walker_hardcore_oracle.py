@@ -1,7 +1,7 @@
 """ORACLE — TEST INFRASTRUCTURE ONLY.
 
 NumPy (float32, vectorised over envs) specification of the HARDCORE terrain mode of the bipedal walker: the handle of
-ddrl_env_create_walker(terrain = DDRL_WALKER_TERRAIN_HARDCORE) (include/ddrl_walker_hardcore.h; kernels csrc/walker_hardcore.hip over
+ddrl_env_create_walker(terrain = DDRL_WALKER_TERRAIN_HARDCORE) (include/ddrl_walker_hardcore.h; kernels csrc/walker.hip over
 csrc/walker_device.h's WalkerT<1>).  The arithmetic rules, the constants, the bodies, the joints, the solver's structure, the reward and the
 episode bookkeeping are tests/walker_oracle.py's; this file imports its constants and restates `_physics`, `_build` and `lidar` because the
 grass oracle's are one function each.  With no box near a corner, a hull vertex or a ray, every statement below reduces to the grass

@@ -2,7 +2,7 @@
 
 `Wrapper.step` (algos/sac1/hyperparams.py:123-134) and the n-step rollout's bookkeeping (algos/sac1/sac_ray.py:212-258) on the BIPEDAL
 WALKER: tests/lander3_wrapped_oracle.py restated line for line over WalkerOracle._physics / _rng / reset, statistics included, with 4
-actions and 24 observations (the noise sizes hard-coded in the reference's Wrapper are this env's).  csrc/walker_nstep.hip
+actions and 24 observations (the noise sizes hard-coded in the reference's Wrapper are this env's).  csrc/walker.hip
 (k_walker_step_wrapped) mirrors it statement by statement.  Like the model itself (tests/walker_oracle.py) this is not pinned against gym.
 
 `_physics` returns an observation per call and the Wrapper keeps only the last; `obs()` is a pure function of the state, so a kernel may

@@ -1,5 +1,5 @@
-"""Time one 4096-env ddrl_env_step of the bipedal walker on the HARDCORE terrain (csrc/walker_hardcore.hip) beside the grass walker's
-(csrc/walker.hip, which the terrain mode does not touch: the reference side) at gym's 180 / 60 iterations and at 8 / 3, and the wrapped
+"""Time one 4096-env ddrl_env_step of the bipedal walker on the HARDCORE terrain (csrc/walker.hip's kernels at terrain mode 1) beside
+the grass walker's (the same kernels at mode 0: the reference side) at gym's 180 / 60 iterations and at 8 / 3, and the wrapped
 step (ddrl_env_step_wrapped_walker, repeat 3) of both, all in this process by tools/walker_step_time.py's method (the HIP-event loop of
 tools/lander3_step_time.py): per figure five runs of `--steps` back-to-back launches after a warm-up of mixed steps, the median run and
 the spread (min .. max) in microseconds per launch, and the ratio Hardcore / grass.
