@@ -254,6 +254,11 @@ SIGNATURES_WALKER_HARDCORE_EVAL = {
     "ddrl_env_eval_policy_walker_hardcore": SIGNATURES["ddrl_env_eval_policy"],   # the arguments of the landers' entry point
 }
 
+# include/ddrl_actor_wide.h, likewise
+SIGNATURES_ACTOR_WIDE = {
+    "ddrl_actor_create_wide": SIGNATURES["ddrl_actor_create"],             # the arguments of ddrl_actor_create
+}
+
 
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
@@ -269,7 +274,8 @@ def load():
             "or `make -C distributed-drl_amd/csrc`; there is no CPU fallback for the product path" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items())
-                              + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())):
+                              + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())
+                              + list(SIGNATURES_ACTOR_WIDE.items())):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

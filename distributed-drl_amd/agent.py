@@ -577,14 +577,18 @@ def _device_episodes(actor, test_env, n, max_ep_len):
 
 
 class Actor(_Net):
-    """algos/sac1/actor_learner.py:151-229 (policy-only graph)."""
+    """algos/sac1/actor_learner.py:151-229 (policy-only graph).
+    `opt.wide_policy` (default False): build through ddrl_actor_create_wide — the direct-operand policy for up to 31 observations
+    (the walker's 24 / 4), which is what enable_versions / get_actions_versioned need; a shape outside that call's envelope raises
+    _lib.DdrlUnsupported (no other kernels stand in)."""
 
     def __init__(self, opt, job="worker", max_rows=None, index=0):
         self._setup(opt, ("pi",), job, index)
         self.cfg = opt.config()
         self.max_rows = int(max_rows if max_rows is not None else max(1, getattr(opt, "num_envs", 1)))
         h = ctypes.c_void_p()
-        _lib.check(self._lib.ddrl_actor_create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg), self.max_rows))
+        create = self._lib.ddrl_actor_create_wide if getattr(opt, "wide_policy", False) else self._lib.ddrl_actor_create
+        _lib.check(create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg), self.max_rows))
         self._h = h
         self.job = job
         self._flat_set(torch.from_numpy(glorot_init(self.specs, opt.seed)).to(self.device))

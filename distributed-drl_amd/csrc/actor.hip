@@ -12,8 +12,11 @@ namespace {
 #include "sac1_direct.h"
 }  // namespace
 #include "sac1_layout.h"
+#include "../../include/ddrl_actor_wide.h"
 
 namespace {
+#include "actor_wide.h"   // k_actor_fwd_wide, its layer-1 layout and pack kernels (a handle of ddrl_actor_create_wide)
+
 // ------------------------------------------------------------------------------------------
 // K: batched get_action — one wave per observation row (Actor.get_action, actor_learner.py:195-197)
 // ------------------------------------------------------------------------------------------
@@ -166,6 +169,7 @@ struct ddrl_actor {
     // fused rollout step (ddrl_rollout_step): the policy in the direct-operand layout + the observation rows it acts on +
     // the head partials of the forward launch, in ONE slab (k_dfwd addresses everything as base + 32-bit offset)
     bool direct = false;
+    bool wide = false;      // ddrl_actor_create_wide: Ld holds the wide layer-1 block array (actor_wide.h), the forward is k_actor_fwd_wide
     Layout Ld;
     float *dslab = nullptr, *pi_d = nullptr, *obs_d = nullptr, *hp_d = nullptr;
     Seg *segs_dd = nullptr;
@@ -396,12 +400,36 @@ __global__ void __launch_bounds__(256) k_version_adopt(int *__restrict__ slot, c
     if (i < n && ended[i]) slot[i] = vs->newest;
 }
 
-extern "C" {
+// the direct-layout policy <-> a dense flat vector (to_internal 1: flat -> direct layout, 0: the reverse), by the handle's layout
+static void actor_pack_direct(const ddrl_actor *h, const float *src, float *dst, int to_internal, hipStream_t s) {
+    const dim3 grid(64, (unsigned)h->Ld.segs.size());
+    if (!h->wide) k_pack<<<grid, 256, 0, s>>>(h->segs_dd, src, dst, nullptr, to_internal);
+    else if (to_internal) k_pack_wide<1><<<grid, 256, 0, s>>>(h->segs_dd, src, dst, nullptr, 0, nullptr);
+    else k_pack_wide<0><<<grid, 256, 0, s>>>(h->segs_dd, src, dst, nullptr, 0, nullptr);
+}
 
-int ddrl_actor_create(ddrl_actor_t **out, int device, const ddrl_sac1_config_t *cfg, int64_t max_rows) {
+// Why ddrl_actor_create_wide has no kernel for a shape (nullptr: inside the envelope of k_actor_fwd_wide)
+static const char *wide_refusal(const ddrl_sac1_config_t &c, long long max_rows) {
+    if (c.obs_dim > 31) return "obs_dim > 31 (the layer-1 contraction holds 31 observation columns and the bias column)";
+    if (c.act_dim > 4 || 2 * c.act_dim > DFH) return "act_dim > 4 (eight head partials per row)";
+    if (c.hidden1 % 4 != 0 || c.hidden2 % 4 != 0) return "hidden sizes must be multiples of 4";
+    if (c.hidden1 > 512) return "hidden1 > 512";
+    if (c.hidden2 > 32 * DNT) return "hidden2 > 512 (16 column tiles)";
+    if (max_rows % 32 != 0) return "max_rows must be a multiple of 32";
+    if (max_rows > 32 * 4095) return "max_rows > 131040";
+    return nullptr;
+}
+
+static int actor_create(ddrl_actor_t **out, int device, const ddrl_sac1_config_t *cfg, int64_t max_rows, bool wide) {
     DDRL_REQUIRE(out != nullptr && max_rows > 0, "bad out/max_rows");
     int rc = check_cfg(cfg);
     if (rc != DDRL_OK) return rc;
+    if (wide) {
+        if (const char *why = wide_refusal(*cfg, max_rows)) {
+            ddrl::set_error("ddrl_actor_create_wide: no wide direct-operand policy for this shape: %s", why);
+            return DDRL_ERR_UNSUPPORTED;
+        }
+    }
     ddrl::DeviceGuard g(device);
     if (!g.ok) { ddrl::set_error("cannot select device %d", device); return DDRL_ERR_HIP; }
     ddrl_actor *h = new ddrl_actor();
@@ -419,13 +447,16 @@ int ddrl_actor_create(ddrl_actor_t **out, int device, const ddrl_sac1_config_t *
         return DDRL_ERR_NOMEM;
     }
     DDRL_HIP_CHECK(hipMemcpy(h->segs_d, h->L.segs.data(), h->L.segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
-    {
+    h->wide = wide;
+    if (wide) {
+        h->direct = true;   // (wide_refusal above: the whole envelope is direct)
+    } else {
         ddrl_sac1_config_t c2 = *cfg;
         c2.batch = 32;
         h->direct = direct_ok(c2) && max_rows % 32 == 0 && max_rows <= 32 * 4095 && cfg->obs_dim + 1 <= 13;
     }
     if (h->direct) {
-        h->Ld = make_layout(*cfg, true, true);
+        h->Ld = make_layout(*cfg, true, true, wide);
         const size_t np = policy_slab_floats(h->Ld), no = ((size_t)max_rows * cfg->obs_dim + 63) & ~(size_t)63;
         const size_t nh = (size_t)DFH * max_rows * DNT;
         e = dev_alloc(&h->dslab, np + no + nh + 2048);
@@ -441,6 +472,16 @@ int ddrl_actor_create(ddrl_actor_t **out, int device, const ddrl_sac1_config_t *
     }
     *out = h;
     return DDRL_OK;
+}
+
+extern "C" {
+
+int ddrl_actor_create(ddrl_actor_t **out, int device, const ddrl_sac1_config_t *cfg, int64_t max_rows) {
+    return actor_create(out, device, cfg, max_rows, false);
+}
+
+int ddrl_actor_create_wide(ddrl_actor_t **out, int device, const ddrl_sac1_config_t *cfg, int64_t max_rows) {
+    return actor_create(out, device, cfg, max_rows, true);
 }
 
 int ddrl_actor_destroy(ddrl_actor_t *h) {
@@ -464,12 +505,14 @@ int ddrl_actor_set_weights(ddrl_actor_t *h, const float *flat_pi_d, void *stream
         // table of the next forward) and ONE pack into the current copy and that slot (round 4: two packs, the pick, a 0.5 MB copy
         // and, in the step, the grouping: five launches)
         k_version_plan<<<1, 1024, 0, s>>>(h->slot_d, h->max_rows, h->n_slots, h->perm_d, h->vtiles_d, h->vs_d, 1, (h->cfg.hidden2 + 31) / 32, h->wg_slots, h->vt_cap);
-        k_pack_version<<<dim3(64, (unsigned)h->Ld.segs.size()), 256, 0, s>>>(h->segs_dd, flat_pi_d, h->pi_d, h->vslab, h->vstride, h->vs_d);
+        const dim3 pgrid(64, (unsigned)h->Ld.segs.size());
+        if (h->wide) k_pack_wide<2><<<pgrid, 256, 0, s>>>(h->segs_dd, flat_pi_d, h->pi_d, h->vslab, h->vstride, h->vs_d);
+        else k_pack_version<<<pgrid, 256, 0, s>>>(h->segs_dd, flat_pi_d, h->pi_d, h->vslab, h->vstride, h->vs_d);
         h->plan_fresh = true;
         h->steps_since_install = 0;
         h->pi_p_stale = true;
     } else {
-        k_pack<<<dim3(64, (unsigned)h->Ld.segs.size()), 256, 0, s>>>(h->segs_dd, flat_pi_d, h->pi_d, nullptr, 1);
+        actor_pack_direct(h, flat_pi_d, h->pi_d, 1, s);
         h->pi_p_stale = true;   // the row-major copy only serves ddrl_actor_act / get_weights: rebuilt there
     }
     DDRL_LAUNCH_CHECK();
@@ -479,7 +522,7 @@ int ddrl_actor_set_weights(ddrl_actor_t *h, const float *flat_pi_d, void *stream
 // direct actors: the row-major policy (generic kernels of ddrl_actor_act, ddrl_actor_get_weights) from the direct-layout one, on demand
 static void actor_refresh_row_major(ddrl_actor *h, hipStream_t s) {
     if (!h->pi_p_stale) return;
-    k_pack<<<dim3(64, (unsigned)h->Ld.segs.size()), 256, 0, s>>>(h->segs_dd, h->pi_d, h->flat_tmp, nullptr, 0);
+    actor_pack_direct(h, h->pi_d, h->flat_tmp, 0, s);
     k_pack<<<dim3(64, (unsigned)h->L.segs.size()), 256, 0, s>>>(h->segs_d, h->flat_tmp, h->pi_p, nullptr, 1);
     h->pi_p_stale = false;
 }
@@ -583,7 +626,7 @@ int ddrl_actor_get_weights(ddrl_actor_t *h, float *flat_pi_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && flat_pi_d != nullptr, "NULL pointer");
     ddrl::DeviceGuard g(h->device);
     if (h->direct) {   // straight from the direct-layout policy
-        k_pack<<<dim3(64, (unsigned)h->Ld.segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_dd, h->pi_d, flat_pi_d, nullptr, 0);
+        actor_pack_direct(h, h->pi_d, flat_pi_d, 0, ddrl::as_stream(stream));
         DDRL_LAUNCH_CHECK();
         return DDRL_OK;
     }
@@ -662,14 +705,14 @@ int ddrl_actor_internal_forward(ddrl_actor *h, long long n, void *stream, int ve
     const Layout &L = h->Ld;
     const int nt2 = (c.hidden2 + 31) / 32;
     ActFwdArgs A{};
-    A.W1 = h->pi_d + L.pi_W1; A.W2p = A.W1 + ((c.hidden1 + 31) & ~31) * 16;   // the k4-interleaved W2 follows the layer-1 block array
+    A.W1 = h->pi_d + L.pi_W1; A.W2p = h->pi_d + L.pi_W2;   // the k4-interleaved W2 follows the layer-1 block array (16 or 32 floats per unit)
     A.b2 = h->pi_d + L.pi_b2; A.wmu = h->pi_d + L.pi_Wmu; A.wls = h->pi_d + L.pi_Wls; A.obs = h->obs_d; A.hp = h->hp_d;
     A.rows = (int)n; A.K = c.hidden1; A.Np = L.Np2; A.h2 = c.hidden2; A.d0 = c.obs_dim; A.act = c.act_dim; A.tiles_n = nt2;
     A.ngroups = (nt2 + ANT - 1) / ANT;   // 10 column tiles -> 2 workgroups of 5 per row tile
 #ifdef DDRL_STAMPS
     A.st = g_actor_st;
 #endif
-    const int D1 = c.obs_dim + 1, ns = D1 <= 8 ? 4 : 4 + (D1 - 8 + 1) / 2;
+    const int D1 = c.obs_dim + 1, ns = h->wide ? wide_steps(D1) : (D1 <= 8 ? 4 : 4 + (D1 - 8 + 1) / 2);
     hipStream_t s = ddrl::as_stream(stream);
     if (versioned) {
         // envs grouped by the policy version they act on; a row tile = up to 32 envs of one version.  The launch covers the worst
@@ -677,16 +720,20 @@ int ddrl_actor_internal_forward(ddrl_actor *h, long long n, void *stream, int ve
         DDRL_REQUIRE(h->n_slots > 0 && n == h->max_rows, "versioned forward: store not enabled, or n != max_rows");
         if (!h->plan_fresh) k_version_plan<<<1, 1024, 0, s>>>(h->slot_d, n, h->n_slots, h->perm_d, h->vtiles_d, h->vs_d, 0, nt2, h->wg_slots, h->vt_cap);
         h->plan_fresh = true;
-        A.W1 = h->vslab + L.pi_W1; A.W2p = A.W1 + ((c.hidden1 + 31) & ~31) * 16;
+        A.W1 = h->vslab + L.pi_W1; A.W2p = h->vslab + L.pi_W2;
         A.b2 = h->vslab + L.pi_b2; A.wmu = h->vslab + L.pi_Wmu; A.wls = h->vslab + L.pi_Wls;
         A.vtiles = h->vtiles_d; A.perm = h->perm_d; A.vs = h->vs_d; A.vstride = h->vstride; A.vt_max = h->vt_cap;
         const unsigned vgrid = (unsigned)h->vt_cap;   // (the plan's workgroup count is at most that; the rest leave at once)
-        launch_actor_fwd<2, true>(ns, vgrid, s, A);
+        if (h->wide) launch_actor_fwd_wide<2, true>(ns, vgrid, s, A);
+        else launch_actor_fwd<2, true>(ns, vgrid, s, A);
         DDRL_LAUNCH_CHECK();
         return DDRL_OK;
     }
     const unsigned grid = (unsigned)(n / 32) * A.ngroups;
-    if (grid > 256) launch_actor_fwd<2, false>(ns, grid, s, A);   // more than one workgroup per CU: the two-per-CU register budget
+    if (h->wide) {
+        if (grid > 256) launch_actor_fwd_wide<2, false>(ns, grid, s, A);
+        else launch_actor_fwd_wide<1, false>(ns, grid, s, A);
+    } else if (grid > 256) launch_actor_fwd<2, false>(ns, grid, s, A);   // more than one workgroup per CU: the two-per-CU register budget
     else launch_actor_fwd<1, false>(ns, grid, s, A);
     DDRL_LAUNCH_CHECK();
     return DDRL_OK;
@@ -718,7 +765,7 @@ int ddrl_actor_internal_config(ddrl_actor *h, ddrl_sac1_config_t *cfg_out, int *
 
 ddrl_actor_rollout_view ddrl_actor_internal_view(ddrl_actor *h) {
     ddrl_actor_rollout_view v{};
-    if (!h || !h->direct) return v;
+    if (!h || !h->direct || h->wide) return v;   // (no fused step reads the wide layout: the rollout entry points refuse such a handle)
     v.ok = 1; v.obs = h->obs_d; v.hp = h->hp_d; v.bmu = h->pi_d + h->Ld.pi_bmu; v.bls = h->pi_d + h->Ld.pi_bls;
     v.ver = ddrl_version_view{h->n_slots, h, h->slot_d, h->vs_d, h->vstride, h->vcnt_d, h->perm_d, h->perm2d_off, h->vtiles_d, h->vt_cap, h->wg_slots};
     v.vbmu = h->n_slots ? h->vslab + h->Ld.pi_bmu : nullptr; v.vbls = h->n_slots ? h->vslab + h->Ld.pi_bls : nullptr;

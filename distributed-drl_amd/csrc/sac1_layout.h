@@ -158,7 +158,9 @@ struct Layout {
     int Kp1, Np2;
 };
 
-static Layout make_layout(const ddrl_sac1_config_t &c, bool pi_only, bool direct = false) {
+// wide (policy-only direct layouts: ddrl_actor_create_wide): the policy's layer-1 block array holds 32 floats per hidden unit, mode 3
+// (actor_wide.h: w1wide_index) instead of 16, mode 2.  The learner's layouts never set it.
+static Layout make_layout(const ddrl_sac1_config_t &c, bool pi_only, bool direct = false, bool wide = false) {
     // Internal layout: every kernel is followed IMMEDIATELY by its bias (so that a bias gradient
     // is just one more row of the kernel's wgrad GEMM); each (kernel, bias) pair starts on a
     // 16-byte boundary.  Direct path: the layer-2 kernels are stored k4-interleaved and padded to
@@ -189,11 +191,12 @@ static Layout make_layout(const ddrl_sac1_config_t &c, bool pi_only, bool direct
         if (!direct) { add(wslot, D * h1, false); add(bslot, h1, true); return; }
         in = pad4(in);
         wslot = bslot = in;   // one block array holds the kernel rows and, as input column D, the bias
-        L.segs.push_back(Seg{ext, in, D * h1, (int)h1, 0, 2, 0});
+        const int mode = wide ? 3 : 2;
+        L.segs.push_back(Seg{ext, in, D * h1, (int)h1, 0, mode, 0});
         ext += D * h1;
-        L.segs.push_back(Seg{ext, in, h1, (int)h1, 0, 2, (int)D});
+        L.segs.push_back(Seg{ext, in, h1, (int)h1, 0, mode, (int)D});
         ext += h1;
-        in += (long long)L.Kp1 * 16;
+        in += (long long)L.Kp1 * (wide ? 32 : 16);
     };
     add_w1(L.pi_W1, L.pi_b1, o); add_w2(L.pi_W2, L.pi_b2);
     add(L.pi_Wmu, h2 * a, false); add(L.pi_bmu, a, true); add(L.pi_Wls, h2 * a, false); add(L.pi_bls, a, true);

@@ -806,7 +806,10 @@ class _RolloutWorker:
         self._fused_live = False
         self.o.copy_(env.obs)
         if self.t > self.opt.start_steps:
-            self.actor.get_actions(self.o, out=self.act)
+            if self._versions:   # a store on the unfused sequence (the walker's wide policy): every env against the version it holds
+                self.actor.get_actions_versioned(self.o, self.opt.max_ep_len, out=self.act)
+            else:
+                self.actor.get_actions(self.o, out=self.act)
         else:
             env.sample_actions(out=self.act)
         o2, r, d, _, ended = env.step(self.act)
@@ -828,8 +831,12 @@ class RolloutDevice(_RolloutWorker):
     holds on that model too.  The one-body worker ignores the flag.
 
     The walker (`opt.env_model = "walker"`: env.VecBipedalWalker with the same iteration options) sets `opt.obs_dim, opt.act_dim =
-    24, 4` and always runs the unfused sequence: no fused launch holds it (ddrl_rollout_begin* refuse a walker handle), and an actor of
-    obs + act = 28 has no direct-operand policy anyway.  The n-step driver's worker on this env is RolloutDeviceNStep."""
+    24, 4` and always runs the unfused sequence: no fused launch holds it (ddrl_rollout_begin* refuse a walker handle).  By default its
+    actor (obs + act = 28) has no direct-operand policy either, and the worker adopts per step.  With `opt.wide_policy = True` the
+    actor is built through ddrl_actor_create_wide (k_actor_fwd_wide, csrc/actor_wide.h) and, under `adopt = "episode"`, the version
+    store is enabled in the constructor with horizon max_ep_len, behind the initial pull: the unfused sequence then acts through
+    get_actions_versioned and adopt_where_ended moves an env to the newest weights at ITS episode end, as on the landers' fused steps.
+    The n-step driver's worker on this env is RolloutDeviceNStep."""
 
     def __init__(self, ps, replay_buffer, opt, worker_index=0):
         import torch
@@ -843,6 +850,8 @@ class RolloutDevice(_RolloutWorker):
         self._start(ps, getattr(opt, "fused_rollout", True), "episode")
         if self.adopt == "episode":
             self._fused_ready()   # the version store starts from the initial pull, before any step
+            if not self._versions and getattr(opt, "wide_policy", False):
+                self._enable_versions(opt.max_ep_len)   # no fused pair takes a wide actor (the walker's): the store serves the unfused sequence
 
     _family = "pi"
 
@@ -1016,9 +1025,12 @@ class RolloutDeviceNStep(_RolloutWorker):
     sets `opt.obs_dim, opt.act_dim = 24, 4`, as RolloutDevice does, and steps through VecBipedalWalker.step_wrapped_walker
     (ddrl_env_step_wrapped_walker, csrc/walker.hip).  Every ring handed to it must be a ReplayBufferNStep of 24 / 4: the
     constructor checks that before it allocates anything and raises ValueError otherwise.  The worker is always unfused there — no
-    fused launch holds the walker — and has no version store: an actor of 24 observations lies outside the direct-operand envelope,
-    _enable_versions' ValueError is caught as for any such actor, and weight adoption is the whole-vector swap after the step
-    (`adopt = "step"` behaviour whatever opt.adopt says: never staler than the reference, not identical to it)."""
+    fused launch holds the walker.  By default it has no version store either: an ordinary actor of 24 observations lies outside the
+    direct-operand envelope, _enable_versions' ValueError is caught as for any such actor, and weight adoption is the whole-vector
+    swap after the step (`adopt = "step"` behaviour whatever opt.adopt says: never staler than the reference, not identical to it).
+    With `opt.wide_policy = True` the actor is built through ddrl_actor_create_wide (k_actor_fwd_wide, csrc/actor_wide.h),
+    _enable_versions(limit_steps) succeeds, and the unfused sequence acts through get_actions_versioned and adopts through
+    adopt_where_ended: every env pulls at its own episode end, as sac_ray.py:255-259 does."""
 
     WRAPPER_REPEAT = 3  # the literal in sac_ray.py:189 (opt.action_repeat only scales the episode limit)
 

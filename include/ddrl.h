@@ -600,7 +600,8 @@ int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noi
  * include/ddrl_walker.h (the walker's wrapped step), include/ddrl_walker_eval.h (its evaluation episodes),
  * include/ddrl_walker_hardcore.h (ddrl_env_create_walker: a walker handle with a terrain mode, DDRL_WALKER_TERRAIN_HARDCORE being gym's
  * BipedalWalkerHardcore terrain; such a handle's state block has DDRL_ENVWH_STATE_FIELDS rows, and everything said of a walker handle in
- * this header holds for it) and include/ddrl_walker_hardcore_eval.h (the evaluation episodes of such a Hardcore handle). */
+ * this header holds for it), include/ddrl_walker_hardcore_eval.h (the evaluation episodes of such a Hardcore handle) and
+ * include/ddrl_actor_wide.h (an actor handle whose direct-operand policy takes up to 31 observations: the walker's actor). */
 /* RolloutDevice.step fused: ONE vector step of worker_rollout's policy phase (example/dsac.py:96-130; SAC1 flavour
  * algos/sac1/sac1.py:177-213) for all n envs, as two launches with no host work in between:
  *   a = agent.get_action(o)  (Actor.get_action, actor_learner.py:195-197; noise element i*act+c of the counter stream
