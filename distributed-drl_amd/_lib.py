@@ -259,6 +259,12 @@ SIGNATURES_ACTOR_WIDE = {
     "ddrl_actor_create_wide": SIGNATURES["ddrl_actor_create"],             # the arguments of ddrl_actor_create
 }
 
+# include/ddrl_sac1_wide.h, likewise
+SIGNATURES_SAC1_WIDE = {
+    "ddrl_sac1_create_wide": SIGNATURES["ddrl_sac1_create"],               # the arguments of ddrl_sac1_create
+    "ddrl_sac1_is_wide": SIGNATURES["ddrl_sac1_is_fused"],
+}
+
 
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
@@ -275,7 +281,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items())
                               + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())
-                              + list(SIGNATURES_ACTOR_WIDE.items())):
+                              + list(SIGNATURES_ACTOR_WIDE.items()) + list(SIGNATURES_SAC1_WIDE.items())):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

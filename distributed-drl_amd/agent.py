@@ -84,6 +84,9 @@ class HyperParameters:
         self.Ln, self.action_repeat, self.save_freq = 8, 2, 1
         self.obs_shape, self.act_shape = (obs_dim,), (act_dim,)
         self.num_envs = 1     # vectorised rollouts: envs stepped together by one worker
+        # Learner: build through ddrl_sac1_create_wide — the five-launch direct-operand update for obs_dim + act_dim <= 31 (the walker's
+        # 24 / 4, which ddrl_sac1_create updates on the nine-launch generic kernels).  Off by default: profiles/sac1_wide_time.txt
+        self.wide_learner = False
         import os
         self.summary_dir = os.getcwd() + "/tboard_ray"   # hyperparams.py:99 (TensorBoard scalars of the job == "main" actor)
 
@@ -160,7 +163,9 @@ class _Net:
 
 
 class Learner(_Net):
-    """algos/sac1/actor_learner.py:19-148."""
+    """algos/sac1/actor_learner.py:19-148.
+    `opt.wide_learner` (default False): the handle comes from ddrl_sac1_create_wide (include/ddrl_sac1_wide.h); train, the ring and
+    n-step paths, the captured loop, weights and export / import are unchanged, the split API (compute_grads / apply_grads) refuses it."""
 
     NETS = ("pi", "q1", "q2")
     VARIANT = 0   # _lib.SAC1
@@ -170,7 +175,9 @@ class Learner(_Net):
         self._setup(opt, self.NETS, job, index)
         self.cfg = opt.config(variant=self.VARIANT)
         h = ctypes.c_void_p()
-        _lib.check(self._lib.ddrl_sac1_create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg)))
+        # (a configuration outside ddrl_sac1_create_wide's envelope raises _lib.DdrlUnsupported: no other kernels stand in)
+        create = self._lib.ddrl_sac1_create_wide if getattr(opt, "wide_learner", False) else self._lib.ddrl_sac1_create
+        _lib.check(create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg)))
         self._h = h
         self.losses = torch.zeros(self.N_LOSSES, dtype=torch.float32, device=self.device)
         # tf.global_variables_initializer with tf.set_random_seed(opt.seed): glorot / zeros

@@ -23,8 +23,11 @@ namespace {
 #include "sac1_direct.h"
 }  // namespace
 #include "sac1_layout.h"
+#include "../../include/ddrl_sac1_wide.h"
 
 namespace {
+#include "wide_pack.h"   // w1wide_index, SEG_W1WIDE: the layer-1 block layout of a wide handle (make_layout(..., wide))
+
 // ------------------------------------------------------------------------------------------
 // K: heads, stage A — one wave per (row, eval in {pi@x, pi@x2, piT@x2, q1(x,a), q2(x,a)})
 // ------------------------------------------------------------------------------------------
@@ -497,6 +500,7 @@ struct ddrl_sac1 {
     AdamArgs ad;
     int rows_b_blocks;
     bool fused;          // direct-operand path (sac1_direct.h) instead of the generic kernels
+    bool wide;           // ... its wide form (ddrl_sac1_create_wide): mode-3 layer-1 blocks, k_dfwd_wide, sac1_wide.hip's k_dg — the third kernel path
     DFHead fh_a[2], fh_b[2];
     DFArgs f_a[2], f_b[2];
     DGJobs dg_bq[2], dg_mid, dg_pi;
@@ -529,6 +533,11 @@ struct ddrl_sac1 {
 };
 
 static void refresh_shadows(ddrl_sac1 *h, hipStream_t s);
+// sac1_wide.hip: the launches of a wide handle (k_dfwd_wide, k_dg over the mode-3 layer-1 blocks, k_pack_wide); `head` / `args` / `jobs`
+// point to a DFHead / DFArgs / DGJobs, `segs_d` to the handle's device segment table
+void ddrl_sac1_wide_launch_fwd(int phase, const void *head, const void *args, void *stream);
+void ddrl_sac1_wide_launch_dg(const void *jobs, void *stream, int kid);
+void ddrl_sac1_wide_pack(const void *segs_d, int nsegs, const float *src, float *dst, float *dst2, int to_internal, void *stream);
 int ddrl_internal_normal_fill_ctr(float *out_d, int64_t n, uint32_t seed, const uint32_t *ctr_d, uint64_t base, void *stream);   // common.hip
 int ddrl_internal_host_block_up(const float *src, float *dst_d, int64_t n, float *e0, float *e1, float *e2, int64_t m, uint32_t seed,
                                 const uint32_t *ctr, void *stream);                                                              // common.hip
@@ -724,7 +733,7 @@ static int bq_keep(int tm, int h1, int h2) {
 // ---- job tables of the update on the direct-operand kernels (sac1_direct.h).  B = rows of every image (whole 32-row tiles), Bv = the
 // batch.  Image slots — H1r4 / H2c4: 0 pi(x) 1 q1(x,a) 2 q2(x,a) 3 q1(x,pi) 4 v(x);  H2r4: 0 pi 1 q1 2 q2 3 v;  dZ1r4: the value
 // networks, then the policy.
-static int build_direct(ddrl_sac1 *h, int Bv, int B) {
+static int build_direct_tables(ddrl_sac1 *h, int Bv, int B, bool wide) {
     const Variant &V = variant_of(h);
     const ddrl_sac1_config_t *cfg = &h->cfg;
     const Layout &L = h->L;
@@ -732,24 +741,26 @@ static int build_direct(ddrl_sac1 *h, int Bv, int B) {
     const int Kp1 = L.Kp1, Np2 = L.Np2, nt2 = (h2 + 31) / 32, ct = (h1 + 31) / 32;
     const float *Pm = h->main_p, *Pt = h->target_p, *S = h->slab;
     DDRL_REQUIRE(!V.sacv || L.v_W1 - L.q_W1[1] == L.q_W1[1] - L.q_W1[0], "internal: the value networks must sit at equal distances");
-    DDRL_REQUIRE(L.pi_bmu == pi_bmu_off(h1, Np2, h2, a) && L.pi_bls == pi_bls_off(h1, Np2, h2, a),   // (k_dfwd<1> forms these addresses itself)
+    const int wx = wide ? Kp1 * 16 : 0;   // a wide layer-1 block array holds 32 floats per unit: everything behind it lies Kp1 * 16 further (sac1_wide.h: wnet_*_off)
+    DDRL_REQUIRE(L.pi_bmu == pi_bmu_off(h1, Np2, h2, a) + wx && L.pi_bls == pi_bls_off(h1, Np2, h2, a) + wx,   // (k_dfwd<1> forms these addresses itself)
                  "internal: policy-head bias offsets of the direct layout");
     {   // (k_dfwd forms the addresses of its epilogue operands — b2 and the head kernels of a job's network — itself)
-        bool same = L.pi_b2 - L.pi_W1 == net_b2_off(h1, Np2) && L.pi_Wmu - L.pi_W1 == net_wh0_off(h1, Np2) && L.pi_Wls - L.pi_W1 == pi_wls_off(h1, Np2, h2, a);
-        for (int q = 0; q < 2; ++q) same = same && L.q_b2[q] - L.q_W1[q] == net_b2_off(h1, Np2) && L.q_W3[q] - L.q_W1[q] == net_wh0_off(h1, Np2);
-        if (V.sacv) same = same && L.v_b2 - L.v_W1 == net_b2_off(h1, Np2) && L.v_W3 - L.v_W1 == net_wh0_off(h1, Np2);
+        const int b2o = net_b2_off(h1, Np2) + wx, wh0o = net_wh0_off(h1, Np2) + wx;
+        bool same = L.pi_b2 - L.pi_W1 == b2o && L.pi_Wmu - L.pi_W1 == wh0o && L.pi_Wls - L.pi_W1 == pi_wls_off(h1, Np2, h2, a) + wx;
+        for (int q = 0; q < 2; ++q) same = same && L.q_b2[q] - L.q_W1[q] == b2o && L.q_W3[q] - L.q_W1[q] == wh0o;
+        if (V.sacv) same = same && L.v_b2 - L.v_W1 == b2o && L.v_W3 - L.v_W1 == wh0o;
         DDRL_REQUIRE(same, "internal: epilogue-operand offsets of the direct layout");
     }
     h->fused_l1_wgrad = false;   // (direct path: the policy's layer-1 wgrad is a job of its own, no row-tile partials)
     const long long HP = (long long)DFH * B * DNT;
     const long long H1I = (long long)B * h->Lp1, H2C = (long long)Np2 * B, H2R = (long long)B * h->Lp2;
     auto steps = [](int D) { return D + 1 <= 8 ? 4 : 4 + (D + 1 - 8 + 1) / 2; };  // input columns + the bias column, two per MFMA step
-    const int ns_pi = steps(o) - 4, ns_q = steps(o + a) - 4;
+    const int ns_pi = wide ? 0 : steps(o) - 4, ns_q = wide ? 0 : steps(o + a) - 4;   // (k_dfwd_wide counts its steps from the widths themselves)
     // SAC1: Q1(x, a), Q2(x, a) need nothing from the policy: they run in phase 1 beside the policy-dependent evaluations (k_dfwd:
     // "stored") when the tile counts allow the per-XCD split, else in phase 0 as before.  DDRL_QXA_PHASE=0 forces phase 0.
     const int tpj_f = (B / 32) * nt2;
     static const int qxa_phase = getenv("DDRL_QXA_PHASE") ? atoi(getenv("DDRL_QXA_PHASE")) : 1;
-    const bool q_late = !V.sacv && qxa_phase == 1 && (3 * tpj_f) % 8 == 0 && (2 * tpj_f) % 8 == 0;
+    const bool q_late = !wide && !V.sacv && qxa_phase == 1 && (3 * tpj_f) % 8 == 0 && (2 * tpj_f) % 8 == 0;   // (k_dfwd_wide: phase 0 always)
     // SAC1: the column tiles of the q2(x, a) dgrad that stay in launch "bq"
     const int keep = V.sacv ? ct : bq_keep(B / 32, h1, h2);
     const bool split = keep < ct;
@@ -933,6 +944,16 @@ static int build_direct(ddrl_sac1 *h, int Bv, int B) {
     return DDRL_OK;
 }
 
+static int build_direct(ddrl_sac1 *h, int Bv, int B) { return build_direct_tables(h, Bv, B, false); }
+
+// ---- job tables of the update on the wide direct-operand kernels (sac1_wide.h, sac1_wide.hip): the same five launches, evaluations,
+// images and k_dg job kinds as build_direct — the tables do not depend on the input width; what differs is read from the layout (the
+// mode-3 block arrays, 32 floats per unit) and decided by the kernels (k_dfwd_wide's step counts; no stored-action tiles in phase 1).
+static int build_wide(ddrl_sac1 *h, int Bv, int B) {
+    DDRL_REQUIRE(h->cfg.variant == DDRL_SAC1 && h->L.segs[0].mode == SEG_W1WIDE, "internal: build_wide on a handle without the wide SAC1 layout");
+    return build_direct_tables(h, Bv, B, true);
+}
+
 // ---- row kernels of the generic path
 static void build_rows(ddrl_sac1 *h) {
     const Variant &V = variant_of(h);
@@ -969,8 +990,8 @@ static void build_rows(ddrl_sac1 *h) {
 // ---- create, step 2: the kernel path, the parameter layout and the leading dimensions
 static void init_shape(ddrl_sac1 *h) {
     const ddrl_sac1_config_t &c = h->cfg;
-    h->fused = direct_ok(c);
-    h->L = make_layout(c, false, h->fused);
+    h->fused = h->wide || direct_ok(c);   // (a wide handle was checked against its own envelope: wide_refusal)
+    h->L = make_layout(c, false, h->fused, h->wide);
     h->Lp1 = rup32(c.hidden1 + 1); h->Lp2 = rup32(c.hidden2 + 1);  // activation images keep room for the ones column
     // activations carry one extra physical column of ones (the bias-gradient row of the wgrads)
     h->ldh1 = (int)pad4(c.hidden1 + 1); h->ldh2 = (int)pad4(c.hidden2 + 1);
@@ -1075,7 +1096,7 @@ static int build_tables(ddrl_sac1 *h) {
     const ddrl_sac1_config_t *cfg = &h->cfg;
     const Layout &L = h->L;
     const int B = rows_of(h), o = cfg->obs_dim, h1 = cfg->hidden1;
-    const int rc = h->fused ? build_direct(h, cfg->batch, B) : build_generic(h);
+    const int rc = h->wide ? build_wide(h, cfg->batch, B) : h->fused ? build_direct(h, cfg->batch, B) : build_generic(h);
     if (rc != DDRL_OK) return rc;
     if (h->fused && V.sacv) h->rc.nl = V.nl;   // (the direct path reads the loss count only; SAC1 has always filled its row tables there too)
     else build_rows(h);
@@ -1099,15 +1120,35 @@ int ddrl_sac1_param_counts(const ddrl_sac1_config_t *cfg, int64_t *n_pi, int64_t
     return DDRL_OK;
 }
 
-int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) {
+}  // extern "C"
+
+// Why ddrl_sac1_create_wide has no kernels for a configuration (nullptr: inside the envelope of the wide update)
+static const char *wide_refusal(const ddrl_sac1_config_t &c) {
+    if (c.variant != DDRL_SAC1) return "variant must be DDRL_SAC1 (the wide update is built for SAC1 only)";
+    if (c.act_dim > 4 || 2 * c.act_dim > DFH) return "act_dim > 4 (eight head partials per row)";
+    if (c.obs_dim + c.act_dim > 31) return "obs_dim + act_dim > 31 (the layer-1 contraction holds 31 input columns and the bias column)";
+    if (c.hidden1 % 4 != 0 || c.hidden2 % 4 != 0) return "hidden sizes must be multiples of 4";
+    if (c.hidden1 > 512 || c.hidden2 > 32 * DNT) return "hidden sizes > 512";
+    if (c.batch > 4 * DGMAX * 8) return "batch > 512 (a wgrad tile contracts the whole batch inside one workgroup)";
+    return nullptr;
+}
+
+static int sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg, bool wide) {
     DDRL_REQUIRE(out != nullptr, "out is NULL");
     int rc = check_cfg(cfg);                                                      // 1. check
     if (rc != DDRL_OK) return rc;
+    if (wide) {
+        if (const char *why = wide_refusal(*cfg)) {
+            ddrl::set_error("ddrl_sac1_create_wide: no wide direct-operand update for this configuration: %s", why);
+            return DDRL_ERR_UNSUPPORTED;
+        }
+    }
     ddrl::DeviceGuard g(device);
     if (!g.ok) { ddrl::set_error("cannot select device %d", device); return DDRL_ERR_HIP; }
     ddrl_sac1 *h = new ddrl_sac1();  // value-initialised: every pointer/job table starts zeroed
     h->device = device;
     h->cfg = *cfg;
+    h->wide = wide;
     init_shape(h);                                                                // 2. layout
     rc = alloc_slab(h, plan_slab(h));                                             // 3. plan and allocate the slab
     if (rc == DDRL_OK) rc = fill_ones(h);                                         // 4. the ones columns
@@ -1116,6 +1157,26 @@ int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cf
     *out = h;
     return DDRL_OK;
 }
+
+// A wide handle is kept off the split API (the flat optimizer step and the data-parallel stepper are not built over its layout)
+static int refuse_wide(const ddrl_sac1 *h, const char *fn) {
+    if (!h || !h->wide) return DDRL_OK;
+    ddrl::set_error("%s: not supported on a handle of ddrl_sac1_create_wide (the split gradient / apply API runs on ddrl_sac1_create's handles)", fn);
+    return DDRL_ERR_UNSUPPORTED;
+}
+// the segment table's pack of a handle: flat external order <-> its internal layout (dst2: a second destination, set_weights' target copy)
+static void sac1_pack(ddrl_sac1 *h, const float *src, float *dst, float *dst2, int to_internal, void *stream) {
+    if (h->wide) ddrl_sac1_wide_pack(h->segs_d, (int)h->L.segs.size(), src, dst, dst2, to_internal, stream);
+    else k_pack<<<dim3(64, (unsigned)h->L.segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, src, dst, dst2, to_internal);
+}
+
+extern "C" {
+
+int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg, false); }
+
+int ddrl_sac1_create_wide(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg, true); }
+
+int ddrl_sac1_is_wide(ddrl_sac1_t *h) { return h ? (h->wide ? 1 : 0) : DDRL_ERR_BAD_ARG; }
 
 int ddrl_sac1_destroy(ddrl_sac1_t *h) {
     if (!h) return DDRL_OK;
@@ -1148,7 +1209,7 @@ int ddrl_sac1_export(ddrl_sac1_t *h, int which, float *flat_d, void *stream) {
         else
             k_reduce_parts<<<(unsigned)((n + 255) / 256), 256, 0, ddrl::as_stream(stream)>>>(h->part, h->grad + h->L.pi_W1, n, n, h->ad.nparts);
     }
-    k_pack<<<dim3(64, (unsigned)h->L.segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, buf, flat_d, nullptr, 0);
+    sac1_pack(h, buf, flat_d, nullptr, 0, stream);
     DDRL_LAUNCH_CHECK();
     return DDRL_OK;
 }
@@ -1181,7 +1242,7 @@ int ddrl_sac1_import(ddrl_sac1_t *h, int which, const float *flat_d, void *strea
     float *buf = which_buf(h, which);
     DDRL_REQUIRE(buf != nullptr, "unknown buffer id");
     ddrl::DeviceGuard g(h->device);
-    k_pack<<<dim3(64, (unsigned)h->L.segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_d, buf, nullptr, 1);
+    sac1_pack(h, flat_d, buf, nullptr, 1, stream);
     if (which == DDRL_SAC1_MAIN) refresh_shadows(h, ddrl::as_stream(stream));
     DDRL_LAUNCH_CHECK();
     if (which == DDRL_SAC1_GRAD) h->ls.grad_imported = true;
@@ -1192,8 +1253,7 @@ int ddrl_sac1_set_weights(ddrl_sac1_t *h, const float *flat_main_d, void *stream
     DDRL_REQUIRE(h != nullptr && flat_main_d != nullptr, "NULL pointer");
     ddrl::DeviceGuard g(h->device);
     // copy into main AND target: Learner.set_weights runs target_init (actor_learner.py:125-127)
-    k_pack<<<dim3(64, (unsigned)h->L.segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_main_d, h->main_p,
-                                                                                    h->target_p, 1);
+    sac1_pack(h, flat_main_d, h->main_p, h->target_p, 1, stream);
     refresh_shadows(h, ddrl::as_stream(stream));
     DDRL_LAUNCH_CHECK();
     return DDRL_OK;
@@ -1287,7 +1347,7 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
     const dim3 l1grid((c.hidden1 + 255) / 256, (B + L1_ROWS - 1) / L1_ROWS, 1);
     if (h->fused) {
         switch (stage) {
-            case 2: h->f_a[st].opt = h->opt + h->ls.opt_cur; launch_dfwd<0>(h->fh_a[st], h->f_a[st], s); break;
+            case 2: h->f_a[st].opt = h->opt + h->ls.opt_cur; if (h->wide) ddrl_sac1_wide_launch_fwd(0, &h->fh_a[st], &h->f_a[st], s); else launch_dfwd<0>(h->fh_a[st], h->f_a[st], s); break;
             case 5: {
                 DFArgs &F = h->f_b[st];
                 F.do_sample = h->ls.sample_armed ? 1 : 0;
@@ -1296,13 +1356,14 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
                     float **b = h->in[h->smp_set];
                     F.sout = ddrl_replay_dev::BatchPtrs{{b[0], b[1], b[2], b[3], b[4], nullptr}};
                 }
-                launch_dfwd<1>(h->fh_b[st], F, s);
+                if (h->wide) ddrl_sac1_wide_launch_fwd(1, &h->fh_b[st], &F, s);
+                else launch_dfwd<1>(h->fh_b[st], F, s);
                 break;
             }
             case 7: {
                 DGJobs &J = h->dg_bq[st];
                 if (h->mid_rest_job >= 0) J.job[h->bq_q2_job].B = q2_image(h, h->ls.sh_cur);   // q2(x, a) dgrad: the current image of q2's layer-2 kernel
-                launch_dg(J, s, 2);
+                if (h->wide) ddrl_sac1_wide_launch_dg(&J, s, 2); else launch_dg(J, s, 2);
                 break;
             }
             case 8: {
@@ -1318,7 +1379,7 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
                     J.job[h->mid_rest_job].B = q2_image(h, h->ls.sh_cur) + (long long)h->bq_cols * 32 * 4;
                     J.job[h->mid_q2w_job].shadow = J.ad.on ? q2_image(h, h->ls.sh_cur ^ 1) : nullptr;
                 }
-                launch_dg(J, s, 3);
+                if (h->wide) ddrl_sac1_wide_launch_dg(&J, s, 3); else launch_dg(J, s, 3);
                 break;
             }
             case 9: {
@@ -1328,7 +1389,7 @@ static void launch_stage(ddrl_sac1 *h, int stage, int st, hipStream_t s) {
                 J.job[h->pi_w2_job].shadow = h->c4_pi[h->ls.sh_cur ^ 1];  // ... the optimizer epilogue of the policy's layer-2 wgrad writes the next one
                 J.ad.opt_next = h->opt + (h->ls.opt_cur ^ 1);  // the optimizer bookkeeping rides in this launch (its loss tile)
                 J.ad.noise_adv = h->ls.noise_pending;
-                launch_dg(J, s, 4);
+                if (h->wide) ddrl_sac1_wide_launch_dg(&J, s, 4); else launch_dg(J, s, 4);
                 if (J.ad.on) { h->ls.opt_cur ^= 1; h->ls.sh_cur ^= 1; }
                 break;
             }
@@ -1474,10 +1535,11 @@ int ddrl_sac1_stage_time(ddrl_sac1_t *h, int stage, int reps, float *ms_per_laun
     return DDRL_OK;
 }
 
-int ddrl_sac1_compute_grads(ddrl_sac1_t *h, const float *obs1_d, const float *obs2_d, const float *acts_d,
-                            const float *rews_d, const float *done_d, const float *eps_x_d, const float *eps_x2_d,
-                            const float *eps_t_d, float *losses_d, float *q1_d, float *q2_d, float *logp_pi_d,
-                            void *stream) {
+}  // extern "C"
+
+static int compute_grads(ddrl_sac1 *h, const float *obs1_d, const float *obs2_d, const float *acts_d, const float *rews_d, const float *done_d,
+                         const float *eps_x_d, const float *eps_x2_d, const float *eps_t_d, float *losses_d, float *q1_d, float *q2_d,
+                         float *logp_pi_d, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     DDRL_REQUIRE(obs1_d && obs2_d && acts_d && rews_d && done_d && eps_x_d && eps_x2_d && eps_t_d, "NULL batch/noise pointer");
     ddrl::DeviceGuard g(h->device);
@@ -1485,8 +1547,19 @@ int ddrl_sac1_compute_grads(ddrl_sac1_t *h, const float *obs1_d, const float *ob
                         logp_pi_d, ddrl::as_stream(stream));
 }
 
+extern "C" {
+
+int ddrl_sac1_compute_grads(ddrl_sac1_t *h, const float *obs1_d, const float *obs2_d, const float *acts_d,
+                            const float *rews_d, const float *done_d, const float *eps_x_d, const float *eps_x2_d,
+                            const float *eps_t_d, float *losses_d, float *q1_d, float *q2_d, float *logp_pi_d,
+                            void *stream) {
+    if (const int rc = refuse_wide(h, "ddrl_sac1_compute_grads")) return rc;
+    return compute_grads(h, obs1_d, obs2_d, acts_d, rews_d, done_d, eps_x_d, eps_x2_d, eps_t_d, losses_d, q1_d, q2_d, logp_pi_d, stream);
+}
+
 int ddrl_sac1_apply_grads(ddrl_sac1_t *h, void *stream) {
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
+    if (const int rc = refuse_wide(h, "ddrl_sac1_apply_grads")) return rc;
     ddrl::DeviceGuard g(h->device);
     return launch_apply(h, ddrl::as_stream(stream));
 }
@@ -1530,6 +1603,7 @@ extern "C" {
 
 int ddrl_sac1_apply_grads_and_sample(ddrl_sac1_t *h, ddrl_replay_t *replay, int set, void *stream) {
     DDRL_REQUIRE(h != nullptr && replay != nullptr && (set == 0 || set == 1), "NULL pointer or set not in {0,1}");
+    if (const int rc = refuse_wide(h, "ddrl_sac1_apply_grads_and_sample")) return rc;
     ddrl::DeviceGuard g(h->device);
     ddrl_replay_dev::SamplerView v;
     bool rides;
@@ -1557,8 +1631,7 @@ int ddrl_sac1_step(ddrl_sac1_t *h, const float *obs1_d, const float *obs2_d, con
     DDRL_REQUIRE(h != nullptr, "handle is NULL");
     // fused path: the optimizer runs in the epilogues of the last GEMM launch — no Adam kernel
     h->ls.fuse_apply = h->fused;
-    int rc = ddrl_sac1_compute_grads(h, obs1_d, obs2_d, acts_d, rews_d, done_d, eps_x_d, eps_x2_d, eps_t_d, losses_d,
-                                     q1_d, q2_d, logp_pi_d, stream);
+    int rc = compute_grads(h, obs1_d, obs2_d, acts_d, rews_d, done_d, eps_x_d, eps_x2_d, eps_t_d, losses_d, q1_d, q2_d, logp_pi_d, stream);
     const bool applied = h->ls.fuse_apply;
     h->ls.fuse_apply = false;
     if (rc != DDRL_OK || applied) return rc;
@@ -1700,6 +1773,7 @@ int ddrl_sac1_capture_abort(ddrl_sac1_t *h) {
 int ddrl_sac1_compute_grads_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t *replay, int set_out, void *stream) {
     DDRL_REQUIRE(h != nullptr && replay != nullptr && (set_in == 0 || set_in == 1) && (set_out == 0 || set_out == 1) && set_in != set_out,
                  "NULL pointer, or input sets not {0,1} / not distinct");
+    if (const int rc = refuse_wide(h, "ddrl_sac1_compute_grads_and_sample")) return rc;
     ddrl::DeviceGuard g(h->device);
     float **b = h->in[set_in];
     ddrl_replay_dev::SamplerView v;
@@ -1727,6 +1801,10 @@ int ddrl_sac1_step_and_sample(ddrl_sac1_t *h, int set_in, ddrl_replay_t *replay,
     bool rides;
     const int vrc = learner_sampler(h, replay, h->fused, &v, &rides);
     if (vrc != DDRL_OK) return vrc;
+    if (!rides && h->wide) {  // (rows too large for the one-workgroup sampler, or an empty ring: the whole update, then the draw as a launch of its own)
+        const int rc = ddrl_sac1_step(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
+        return rc != DDRL_OK ? rc : learner_sample_alone(h, replay, v, set_out, stream);
+    }
     if (!rides) {  // generic kernels: sampler beside the Adam kernel (or on its own)
         int rc = ddrl_sac1_compute_grads(h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr, nullptr, nullptr, nullptr, stream);
         if (rc != DDRL_OK) return rc;

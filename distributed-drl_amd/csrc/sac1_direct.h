@@ -907,6 +907,11 @@ __global__ void __launch_bounds__(256, OCC) k_actor_fwd(ActFwdArgs a) {
 // k_dg: the backward launches.  One workgroup = one 32x32 output tile of one job; the four waves split the contraction
 // in 8-deep groups; both operands are x4 images read straight into the MFMA lane layout.
 // ==========================================================================================
+// The layer-1 block layout k_dg addresses (the W1Y wgrad's gradient / optimizer-state elements, the action rows of dQ/da): the narrow one
+// (gemm_core.h) unless the translation unit names another before it includes this file — sac1_wide.hip: w1wide_index, 32 floats per unit.
+#ifndef DDRL_W1_INDEX
+#define DDRL_W1_INDEX w1y_index
+#endif
 enum { DG_DGRAD_Q = 0, DG_DGRAD = 1, DG_WGRAD_J4 = 2, DG_WGRAD_RM = 3, DG_ROWS_C = 4, DG_LOSS = 5, DG_WGRAD_W1Y = 6 };
 // The first 64 bytes are the "hot line": every scalar the first operand loads of a tile need.  k_dg fetches it with ONE
 // s_load_dwordx16 (and starts one load per remaining line of the record and of the launch header at the same time), waits ONCE,
@@ -1282,7 +1287,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
         constexpr int KIND = decltype(kind)::value;
         if (KIND >= 4) {
             mk = *reinterpret_cast<const float4 *>(jb.mask + ((long long)(m0 / 4 + cg) * jb.ldmask + n0 + r) * 4);  // mapping C: (col r, row group cg)
-            if (KIND == 5 || (KIND == 6 && has_da)) wa_v = jb.wa[wa_ok() ? w1y_index(jb.wa_d0 + (tid >> 5), n0 + (tid & 31)) : 0];
+            if (KIND == 5 || (KIND == 6 && has_da)) wa_v = jb.wa[wa_ok() ? DDRL_W1_INDEX(jb.wa_d0 + (tid >> 5), n0 + (tid & 31)) : 0];
         } else if (KIND >= 1) {
             b1p_pi = jobs.ad.opt->b1p_pi; b2p_pi = jobs.ad.opt->b2p_pi; b1p_q = jobs.ad.opt->b1p_q; b2p_q = jobs.ad.opt->b2p_q;
         }
@@ -1309,7 +1314,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
                 const int gi = m0 + (nar ? (o >> 3) : (o >> 5)), gj = n0 + (nar ? (o & 7) : (o & 31));
                 okv[q] = gi < jb.M && gj < jb.N;
                 if (KIND == 2 || KIND == 3) {
-                    const long long idx = !okv[q] ? jb.adam_off : jb.adam_off + (type == DG_WGRAD_W1Y ? w1y_index(gi, gj) : (long long)gi * jb.ldc + gj);
+                    const long long idx = !okv[q] ? jb.adam_off : jb.adam_off + (type == DG_WGRAD_W1Y ? DDRL_W1_INDEX(gi, gj) : (long long)gi * jb.ldc + gj);
                     am[q] = jobs.ad.m[idx]; av[q] = jobs.ad.v[idx]; ap[q] = jobs.ad.p[idx]; at[q] = jobs.ad.t[idx];
                 }
             }
@@ -1671,7 +1676,7 @@ __global__ void __launch_bounds__(256) k_dg(int total_tiles, int tsA, int tsB, i
             const int row = narrow ? (o >> 3) : (o >> 5), col = narrow ? (o & 7) : (o & 31);
             const float gv = ((red[0][row][col] + red[1][row][col]) + red[2][row][col]) + red[3][row][col];
             if (okv[q]) {
-                const long long idx = jb.adam_off + (type == DG_WGRAD_W1Y ? w1y_index(m0 + row, n0 + col) : (long long)(m0 + row) * jb.ldc + n0 + col);
+                const long long idx = jb.adam_off + (type == DG_WGRAD_W1Y ? DDRL_W1_INDEX(m0 + row, n0 + col) : (long long)(m0 + row) * jb.ldc + n0 + col);
                 jobs.ad.g[idx] = gv;
                 if (do_adam) {
                     const float al = idx < jobs.ad.n_pi ? al_pi : al_q;

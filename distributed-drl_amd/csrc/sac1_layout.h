@@ -158,8 +158,8 @@ struct Layout {
     int Kp1, Np2;
 };
 
-// wide (policy-only direct layouts: ddrl_actor_create_wide): the policy's layer-1 block array holds 32 floats per hidden unit, mode 3
-// (actor_wide.h: w1wide_index) instead of 16, mode 2.  The learner's layouts never set it.
+// wide (ddrl_actor_create_wide's policy-only layout, ddrl_sac1_create_wide's learner layout): every layer-1 block array holds 32 floats
+// per hidden unit, mode 3 (wide_pack.h: w1wide_index) instead of 16, mode 2.  ddrl_sac1_create's layouts never set it.
 static Layout make_layout(const ddrl_sac1_config_t &c, bool pi_only, bool direct = false, bool wide = false) {
     // Internal layout: every kernel is followed IMMEDIATELY by its bias (so that a bias gradient
     // is just one more row of the kernel's wgrad GEMM); each (kernel, bias) pair starts on a
