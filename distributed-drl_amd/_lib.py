@@ -265,6 +265,11 @@ SIGNATURES_SAC1_WIDE = {
     "ddrl_sac1_is_wide": SIGNATURES["ddrl_sac1_is_fused"],
 }
 
+# include/ddrl_sacv_wide.h, likewise
+SIGNATURES_SACV_WIDE = {
+    "ddrl_sacv_create_wide": SIGNATURES["ddrl_sac1_create"],               # the arguments of ddrl_sac1_create
+}
+
 
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
@@ -281,7 +286,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items())
                               + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())
-                              + list(SIGNATURES_ACTOR_WIDE.items()) + list(SIGNATURES_SAC1_WIDE.items())):
+                              + list(SIGNATURES_ACTOR_WIDE.items()) + list(SIGNATURES_SAC1_WIDE.items()) + list(SIGNATURES_SACV_WIDE.items())):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

@@ -175,13 +175,16 @@ class Learner(_Net):
         self._setup(opt, self.NETS, job, index)
         self.cfg = opt.config(variant=self.VARIANT)
         h = ctypes.c_void_p()
-        # (a configuration outside ddrl_sac1_create_wide's envelope raises _lib.DdrlUnsupported: no other kernels stand in)
-        create = self._lib.ddrl_sac1_create_wide if getattr(opt, "wide_learner", False) else self._lib.ddrl_sac1_create
+        # (a configuration outside a wide door's envelope raises _lib.DdrlUnsupported: no other kernels stand in)
+        create = self._create(opt)
         _lib.check(create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg)))
         self._h = h
         self.losses = torch.zeros(self.N_LOSSES, dtype=torch.float32, device=self.device)
         # tf.global_variables_initializer with tf.set_random_seed(opt.seed): glorot / zeros
         self._flat_set(torch.from_numpy(glorot_init(self.specs, opt.seed)).to(self.device))
+
+    def _create(self, opt):
+        return self._lib.ddrl_sac1_create_wide if getattr(opt, "wide_learner", False) else self._lib.ddrl_sac1_create
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -496,6 +499,9 @@ class _ModelOpt:
         sp = args.ac_kwargs.get("action_space") if hasattr(args, "ac_kwargs") else None
         self.act_scale = float(sp.high[0]) if sp is not None else float(getattr(args, "act_scale", 1.0))
         self.max_ep_len = int(getattr(args, "max_ep_len", 1000))
+        # Model: build through ddrl_sacv_create_wide — the five-launch direct-operand update for obs_dim + act_dim <= 31 (the walker's
+        # 24 / 4, which ddrl_sac1_create updates on the generic kernels).  Off by default: profiles/sacv_wide_time.txt
+        self.wide_model = bool(getattr(args, "wide_model", False))
 
     def config(self, batch=None, variant=0):
         return _lib.Sac1Config(obs_dim=self.obs_dim, act_dim=self.act_dim, hidden1=self.hidden_sizes[0], hidden2=self.hidden_sizes[1],
@@ -506,7 +512,9 @@ class _ModelOpt:
 class Model(Learner):
     """example/model.py:12-118 — the SAC-v learner of example/dsac.py (policy + twin Q + V + target V):
     `Model(args)`, set_weights / get_weights ("main" variables: pi, q1, q2, v), get_action(o, deterministic),
-    train(replay_buffer, args) = one sample_batch + one sess.run(step_ops), test_agent(test_env, args, n)."""
+    train(replay_buffer, args) = one sample_batch + one sess.run(step_ops), test_agent(test_env, args, n).
+    `args.wide_model` (default False): the handle comes from ddrl_sacv_create_wide (include/ddrl_sacv_wide.h); everything above is
+    unchanged, the split API (compute_grads / apply_grads) refuses it.  (`wide_learner` is the SAC1 Learner's flag: not read here.)"""
     NETS = ("pi", "q1", "q2", "v")
     VARIANT = 1   # _lib.SAC_V
     N_LOSSES = 4  # pi_loss, q1_loss, q2_loss, v_loss (model.py:66)
@@ -514,6 +522,9 @@ class Model(Learner):
     def __init__(self, args):
         super().__init__(_ModelOpt(args) if not isinstance(args, (HyperParameters, _ModelOpt)) else args)
         self._actor = None
+
+    def _create(self, opt):
+        return self._lib.ddrl_sacv_create_wide if getattr(opt, "wide_model", False) else self._lib.ddrl_sac1_create
 
     def _policy(self):
         if self._actor is None:

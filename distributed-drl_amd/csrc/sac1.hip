@@ -24,6 +24,7 @@ namespace {
 }  // namespace
 #include "sac1_layout.h"
 #include "../../include/ddrl_sac1_wide.h"
+#include "../../include/ddrl_sacv_wide.h"
 
 namespace {
 #include "wide_pack.h"   // w1wide_index, SEG_W1WIDE: the layer-1 block layout of a wide handle (make_layout(..., wide))
@@ -500,7 +501,7 @@ struct ddrl_sac1 {
     AdamArgs ad;
     int rows_b_blocks;
     bool fused;          // direct-operand path (sac1_direct.h) instead of the generic kernels
-    bool wide;           // ... its wide form (ddrl_sac1_create_wide): mode-3 layer-1 blocks, k_dfwd_wide, sac1_wide.hip's k_dg — the third kernel path
+    bool wide;           // ... its wide form (ddrl_sac1_create_wide, ddrl_sacv_create_wide): mode-3 layer-1 blocks, k_dfwd_wide, sac1_wide.hip's k_dg — the third kernel path
     DFHead fh_a[2], fh_b[2];
     DFArgs f_a[2], f_b[2];
     DGJobs dg_bq[2], dg_mid, dg_pi;
@@ -949,8 +950,10 @@ static int build_direct(ddrl_sac1 *h, int Bv, int B) { return build_direct_table
 // ---- job tables of the update on the wide direct-operand kernels (sac1_wide.h, sac1_wide.hip): the same five launches, evaluations,
 // images and k_dg job kinds as build_direct — the tables do not depend on the input width; what differs is read from the layout (the
 // mode-3 block arrays, 32 floats per unit) and decided by the kernels (k_dfwd_wide's step counts; no stored-action tiles in phase 1).
+// SAC-v (ddrl_sacv_create_wide) walks the V.sacv branches of the same builder: V and target V are observation-only jobs of phase 0
+// (network 3, a block array like the policy's), q1(x, pi) and q2(x, pi) the two jobs of phase 1, both fed by evaluation 0's head partials.
 static int build_wide(ddrl_sac1 *h, int Bv, int B) {
-    DDRL_REQUIRE(h->cfg.variant == DDRL_SAC1 && h->L.segs[0].mode == SEG_W1WIDE, "internal: build_wide on a handle without the wide SAC1 layout");
+    DDRL_REQUIRE(h->L.segs[0].mode == SEG_W1WIDE, "internal: build_wide on a handle without the wide layout");
     return build_direct_tables(h, Bv, B, true);
 }
 
@@ -1122,9 +1125,12 @@ int ddrl_sac1_param_counts(const ddrl_sac1_config_t *cfg, int64_t *n_pi, int64_t
 
 }  // extern "C"
 
-// Why ddrl_sac1_create_wide has no kernels for a configuration (nullptr: inside the envelope of the wide update)
-static const char *wide_refusal(const ddrl_sac1_config_t &c) {
-    if (c.variant != DDRL_SAC1) return "variant must be DDRL_SAC1 (the wide update is built for SAC1 only)";
+// Why a wide door has no kernels for a configuration (nullptr: inside the envelope of the wide update).  `variant`: the learner that door
+// builds — ddrl_sac1_create_wide DDRL_SAC1, ddrl_sacv_create_wide DDRL_SAC_V
+static const char *wide_refusal(const ddrl_sac1_config_t &c, int variant) {
+    if (c.variant != variant)
+        return variant == DDRL_SAC1 ? "variant must be DDRL_SAC1 (ddrl_sacv_create_wide builds the wide SAC-v learner)"
+                                    : "variant must be DDRL_SAC_V (ddrl_sac1_create_wide builds the wide SAC1 learner)";
     if (c.act_dim > 4 || 2 * c.act_dim > DFH) return "act_dim > 4 (eight head partials per row)";
     if (c.obs_dim + c.act_dim > 31) return "obs_dim + act_dim > 31 (the layer-1 contraction holds 31 input columns and the bias column)";
     if (c.hidden1 % 4 != 0 || c.hidden2 % 4 != 0) return "hidden sizes must be multiples of 4";
@@ -1133,13 +1139,14 @@ static const char *wide_refusal(const ddrl_sac1_config_t &c) {
     return nullptr;
 }
 
-static int sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg, bool wide) {
+// `wide_door`: the name of the wide entry point called (nullptr: ddrl_sac1_create), `variant`: the learner it builds
+static int sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg, const char *wide_door = nullptr, int variant = DDRL_SAC1) {
     DDRL_REQUIRE(out != nullptr, "out is NULL");
     int rc = check_cfg(cfg);                                                      // 1. check
     if (rc != DDRL_OK) return rc;
-    if (wide) {
-        if (const char *why = wide_refusal(*cfg)) {
-            ddrl::set_error("ddrl_sac1_create_wide: no wide direct-operand update for this configuration: %s", why);
+    if (wide_door) {
+        if (const char *why = wide_refusal(*cfg, variant)) {
+            ddrl::set_error("%s: no wide direct-operand update for this configuration: %s", wide_door, why);
             return DDRL_ERR_UNSUPPORTED;
         }
     }
@@ -1148,7 +1155,7 @@ static int sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *
     ddrl_sac1 *h = new ddrl_sac1();  // value-initialised: every pointer/job table starts zeroed
     h->device = device;
     h->cfg = *cfg;
-    h->wide = wide;
+    h->wide = wide_door != nullptr;
     init_shape(h);                                                                // 2. layout
     rc = alloc_slab(h, plan_slab(h));                                             // 3. plan and allocate the slab
     if (rc == DDRL_OK) rc = fill_ones(h);                                         // 4. the ones columns
@@ -1161,7 +1168,7 @@ static int sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *
 // A wide handle is kept off the split API (the flat optimizer step and the data-parallel stepper are not built over its layout)
 static int refuse_wide(const ddrl_sac1 *h, const char *fn) {
     if (!h || !h->wide) return DDRL_OK;
-    ddrl::set_error("%s: not supported on a handle of ddrl_sac1_create_wide (the split gradient / apply API runs on ddrl_sac1_create's handles)", fn);
+    ddrl::set_error("%s: not supported on a handle of ddrl_sac1_create_wide / ddrl_sacv_create_wide (the split gradient / apply API runs on ddrl_sac1_create's handles)", fn);
     return DDRL_ERR_UNSUPPORTED;
 }
 // the segment table's pack of a handle: flat external order <-> its internal layout (dst2: a second destination, set_weights' target copy)
@@ -1172,9 +1179,11 @@ static void sac1_pack(ddrl_sac1 *h, const float *src, float *dst, float *dst2, i
 
 extern "C" {
 
-int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg, false); }
+int ddrl_sac1_create(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg); }
 
-int ddrl_sac1_create_wide(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg, true); }
+int ddrl_sac1_create_wide(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg, "ddrl_sac1_create_wide", DDRL_SAC1); }
+
+int ddrl_sacv_create_wide(ddrl_sac1_t **out, int device, const ddrl_sac1_config_t *cfg) { return sac1_create(out, device, cfg, "ddrl_sacv_create_wide", DDRL_SAC_V); }
 
 int ddrl_sac1_is_wide(ddrl_sac1_t *h) { return h ? (h->wide ? 1 : 0) : DDRL_ERR_BAD_ARG; }
 

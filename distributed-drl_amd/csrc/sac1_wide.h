@@ -1,4 +1,4 @@
-// k_dfwd_wide: the two forward launches of the SAC1 update for input rows of up to 31 columns (obs_dim + act_dim <= 31; the bipedal
+// k_dfwd_wide: the two forward launches of the SAC1 and the SAC-v update for input rows of up to 31 columns (obs_dim + act_dim <= 31; the bipedal
 // walker: 24 / 4) — the roles of k_dfwd<0> and k_dfwd<1> (sac1_direct.h) over the WIDE layer-1 block layout (wide_pack.h, actor_wide.h:
 // 32 floats per hidden unit, input column d in MFMA step 4 (d / 8) + d % 4 of lane half (d / 4) % 2, the bias as input column D).
 // Included by sac1_wide.hip inside its unnamed namespace, behind sac1_direct.h (DFHead / DFArgs / DFJob, DSrc, the side-output rules,
@@ -23,6 +23,22 @@
 //   in the combine, then the bias; columns 0..31 in the head dot).  Layer 1 sums its steps 0 .. NS - 1 in order.
 // NOT HERE  two row tiles per workgroup, and the stored-action evaluations riding in phase 1: phase 0 runs evaluations 0-4, phase 1
 //   evaluations 5-7 (+ the next update's sampler workgroup, as in k_dfwd<1>).
+// SAC-v (ddrl_sacv_create_wide; example/model.py:38-50)  the same kernel, the roles k_dfwd has on the narrow SAC-v handle, told by the
+//   job table alone (sac1.hip: EV_SACV_DIR).  Tiles per job stay (batch / 32) x (hidden2 / 32), one job per evaluation:
+//   phase 0 = 5 jobs: pi(x), q1(x, a), q2(x, a), v(x), v_targ(x2).  Network 3 (V) sits one network stride behind q2 in either parameter
+//     copy and is an observation-only job like the policy (d1 = 0: its bias is input column obs_dim), so on the walker the two V jobs
+//     and the policy run the 13-step loop of the NQ = 4 kernel beside the 16-step Q jobs.  v(x) leaves the H1r4 / H2c4 / H2r4 images of
+//     V's wgrads and the [x | 1] rows (xv_r4) of its layer-1 wgrad; v_targ(x2) leaves head partials only.  The values v / v_targ
+//     themselves are summed from the head partials by k_dg's first launch (its SAC-v row prologue), not here.
+//   phase 1 = 2 jobs: q1(x, pi), q2(x, pi).  BOTH name evaluation 0 (pi(x), main copy, eps_x) in pev_pack / pin_pack: every workgroup
+//     of either job sums that evaluation's head partials for its 32 rows and samples the action in registers — the action reaches both
+//     Q networks without passing through memory; the tile of job 0 on column tile 0 also stores act0 / logp0 / save0 (side 1) for
+//     the backward launches.  No evaluation at x2 needs the policy (php1 == nullptr: the `two` tile never forms).
+//   Splitting 5 + 2 rather than 3 + 4 (the stored-action Q jobs in phase 1, as k_dfwd<1> takes them on the narrow SAC1 handle) keeps
+//   phase 1, the launch behind the policy's head partials, at the two evaluations that need them: 160 workgroups at the walker's
+//   (400, 300), batch 256 — under one per CU — against 400 in phase 0, which waits for nothing.
+//   Every (NQ, steps) pair a SAC-v table produces is compiled: the observation-only jobs need wide_steps(obs + 1) <= the Q jobs'
+//   wide_steps(obs + act + 1) <= 4 NQ steps, and each NQ's largest loop is 4 NQ.
 #pragma once
 
 // inside a network of the wide layout, relative to its [W1 ; b1] block array (make_layout(..., wide)): the k4-interleaved W2, b2, the head kernel(s)

@@ -1,5 +1,5 @@
-// The kernels of a WIDE SAC1 learner (ddrl_sac1_create_wide, include/ddrl_sac1_wide.h; obs_dim + act_dim <= 31: the bipedal walker's
-// 24 / 4) and their launch functions, called by sac1.hip's launch state for a handle on its third kernel path:
+// The kernels of a WIDE learner — SAC1 (ddrl_sac1_create_wide, include/ddrl_sac1_wide.h) or SAC-v (ddrl_sacv_create_wide,
+// include/ddrl_sacv_wide.h); obs_dim + act_dim <= 31: the bipedal walker's 24 / 4 — and their launch functions, called by sac1.hip's launch state for a handle on its third kernel path:
 //   * k_dfwd_wide<0 / 1> (sac1_wide.h): the two forward launches over the wide layer-1 block layout;
 //   * k_dg (sac1_direct.h) compiled HERE with DDRL_W1_INDEX = w1wide_index: the three backward launches with their existing job kinds —
 //     the layer-1 wgrad tile (DG_WGRAD_W1Y: 32 input columns, bias row included, x 32 hidden units, the batch contracted in 8-deep groups

@@ -601,8 +601,9 @@ int ddrl_env_step_wrapped_articulated(ddrl_env_t *h, float *act_d, float act_noi
  * include/ddrl_walker_hardcore.h (ddrl_env_create_walker: a walker handle with a terrain mode, DDRL_WALKER_TERRAIN_HARDCORE being gym's
  * BipedalWalkerHardcore terrain; such a handle's state block has DDRL_ENVWH_STATE_FIELDS rows, and everything said of a walker handle in
  * this header holds for it), include/ddrl_walker_hardcore_eval.h (the evaluation episodes of such a Hardcore handle) and
- * include/ddrl_actor_wide.h (an actor handle whose direct-operand policy takes up to 31 observations: the walker's actor) and
- * include/ddrl_sac1_wide.h (a SAC1 learner handle whose direct-operand update takes obs_dim + act_dim <= 31: the walker's learner). */
+ * include/ddrl_actor_wide.h (an actor handle whose direct-operand policy takes up to 31 observations: the walker's actor),
+ * include/ddrl_sac1_wide.h (a SAC1 learner handle whose direct-operand update takes obs_dim + act_dim <= 31: the walker's learner) and
+ * include/ddrl_sacv_wide.h (the same for a DDRL_SAC_V learner handle). */
 /* RolloutDevice.step fused: ONE vector step of worker_rollout's policy phase (example/dsac.py:96-130; SAC1 flavour
  * algos/sac1/sac1.py:177-213) for all n envs, as two launches with no host work in between:
  *   a = agent.get_action(o)  (Actor.get_action, actor_learner.py:195-197; noise element i*act+c of the counter stream
