@@ -270,6 +270,12 @@ SIGNATURES_SACV_WIDE = {
     "ddrl_sacv_create_wide": SIGNATURES["ddrl_sac1_create"],               # the arguments of ddrl_sac1_create
 }
 
+# include/ddrl_dqn_direct.h, likewise
+SIGNATURES_DQN_DIRECT = {
+    "ddrl_dqn_create_direct": SIGNATURES["ddrl_dqn_create"],               # the arguments of ddrl_dqn_create
+    "ddrl_dqn_is_direct": SIGNATURES["ddrl_dqn_wide_sk"],
+}
+
 
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
@@ -286,7 +292,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items())
                               + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())
-                              + list(SIGNATURES_ACTOR_WIDE.items()) + list(SIGNATURES_SAC1_WIDE.items()) + list(SIGNATURES_SACV_WIDE.items())):
+                              + list(SIGNATURES_ACTOR_WIDE.items()) + list(SIGNATURES_SAC1_WIDE.items()) + list(SIGNATURES_SACV_WIDE.items())
+                              + list(SIGNATURES_DQN_DIRECT.items())):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

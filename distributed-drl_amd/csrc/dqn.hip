@@ -4,6 +4,8 @@
 #include "wide_l1.h"
 #include "policy_row.h"
 #include "dqn_select.h"
+#include "dqn_direct.h"
+#include "../../include/ddrl_dqn_direct.h"
 
 // ==========================================================================================
 // Double-DQN learner (algos/dqn/actor_learner.py:19-107 on algos/dqn/core.py:40-50):
@@ -252,53 +254,7 @@ __device__ __forceinline__ void head_body(const HeadArgs &a) {
 }
 __global__ void __launch_bounds__(256) k_dqn_head(HeadArgs a) { head_body(a); }
 
-// ------------------------------------------------------------------------------------------
-// The learner loop's sampler (ddrl_dqn_loop_*): `idxs = np.random.randint(0, size, B)` of the ring's own MT19937 stream
-// (ddrl_replay_dev::sample_block, the draw every other path runs) and the five gathers, written where the update reads them — rows of
-// ldx floats in the padded images x1 / x2 of one of the learner's two input sets (their ones column is physical and untouched), acts /
-// rew / done beside them — so that an update of the loop has no staging launch.  One workgroup of 256 lanes.  The draw leaves the
-// indices in `idx` (B words of the learner's slab); the gather behind the barrier reads them back: the workgroup's own stores through
-// the CU's vector cache, one round trip, off every update's dependent chain (the sampler rides beside an update, see below).
-// sample_block and its dense gather (replay_device.h) are used as they are: the SAC1 launches that embed them compile from unchanged
-// sources.  A feed plan is not followed here (fuse_gather = 0 skips it): ddrl_dqn_loop_run refuses a fed ring.
-// ------------------------------------------------------------------------------------------
-struct SetSampler {
-    ddrl_replay_dev::RingState *st;
-    ddrl_replay_dev::RingPtrs ring;   // (obs1[obs], obs2[obs], acts, rews, done), float32
-    long long *idx;
-    float *x1, *x2, *acts, *rew, *done;
-    int B, obs, ldx;
-};
-__device__ __forceinline__ void sample_into_set(const SetSampler &m) {
-    const bool rows = m.st->size > 0;   // (nothing in this launch stores into the ring) an empty ring: the draw raises the sticky error
-    ddrl_replay_dev::sample_block(m.st, m.ring, ddrl_replay_dev::BatchPtrs{}, m.B, m.idx, 0);
-    if (!rows) return;
-    __syncthreads();
-    const int tid = threadIdx.x;
-    const float *r1 = m.ring.a[0], *r2 = m.ring.a[1];
-    if ((m.obs & 3) == 0 && ddrl_replay_dev::aligned16(r1, r2) && ddrl_replay_dev::aligned16(m.x1, m.x2)) {   // (ldx is a multiple of 4)
-        const int w4 = m.obs >> 2, l4 = m.ldx >> 2;
-        const float4 *s1 = reinterpret_cast<const float4 *>(r1), *s2 = reinterpret_cast<const float4 *>(r2);
-        float4 *d1 = reinterpret_cast<float4 *>(m.x1), *d2 = reinterpret_cast<float4 *>(m.x2);
-        for (int e = tid; e < m.B * w4; e += 256) {
-            const int b = e / w4, c = e - b * w4;
-            const long long r = m.idx[b] * w4 + c;
-            const float4 u = s1[r], v = s2[r];
-            d1[b * l4 + c] = u; d2[b * l4 + c] = v;
-        }
-    } else {
-        for (int e = tid; e < m.B * m.obs; e += 256) {
-            const int b = e / m.obs, c = e - b * m.obs;
-            const long long r = m.idx[b] * m.obs + c;
-            const float u = r1[r], v = r2[r];
-            m.x1[b * m.ldx + c] = u; m.x2[b * m.ldx + c] = v;
-        }
-    }
-    for (int b = tid; b < m.B; b += 256) {
-        const long long r = m.idx[b];
-        m.acts[b] = m.ring.a[2][r]; m.rew[b] = m.ring.a[3][r]; m.done[b] = m.ring.a[4][r];
-    }
-}
+#include "dqn_sample.h"
 // a call's first draw: a launch of its own
 __global__ void __launch_bounds__(256) k_dqn_sample(SetSampler m) { sample_into_set(m); }
 // The sampler of update u + 1 rides in update u's HEAD launch, as the workgroup behind the head's own: it writes the other input set and
@@ -489,6 +445,8 @@ struct ddrl_dqn {
     long long act_rows;              // rows of either set: batch rounded up to whole 32-row tiles
     int half;                        // ceil(n_actions / 2): Q columns per head of the actor
     bool pack_stale;                 // a learner step moved main since the last pack
+    ddrl_dqn_dx *dx;                 // ddrl_dqn_create_direct: the direct-operand update (dqn_direct.hip) owns the parameters; main_p is then a copy of
+    bool shadow_stale;               // main in the generic layout for ddrl_dqn_q and the acting pack, rewritten from dx when an update has moved main
     bool poisoned;                   // that word was seen: the parameters carry at least one step from a wrong layer-1 gradient.  Every step / export
                                      // fails until fresh parameters arrive (set_weights, import of MAIN), so they cannot be pushed or checkpointed
 };
@@ -511,6 +469,17 @@ static int dqn_poison_check(ddrl_dqn *h, hipStream_t s, bool drain) {
                     "refuses to step or export until it is given fresh parameters (set_weights / import of the main parameters, e.g. from a "
                     "checkpoint); it then runs the tile-per-workgroup kernel (DDRL_WIDE_SK=0 selects that from the start).");
     return DDRL_ERR_HIP;
+}
+
+// A direct handle: main in the generic layout (what ddrl_dqn_q's launches and k_q_to_pi read) out of the direct layout, two pack launches
+static int dqn_shadow_sync(ddrl_dqn *h, hipStream_t s) {
+    if (!h->dx || !h->shadow_stale) return DDRL_OK;
+    const float *flat = ddrl_dqn_dx_unpack(h->dx, DDRL_SAC1_MAIN, nullptr, s);
+    if (!flat) return DDRL_ERR_HIP;
+    k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, s>>>(h->segs_d, flat, h->main_p, nullptr, 1);
+    DDRL_LAUNCH_CHECK();
+    h->shadow_stale = false;
+    return DDRL_OK;
 }
 
 // Dynamic LDS of a head launch: the attribute belongs to the function (which: 0 k_dqn_head, 1 k_dqn_head_sample) on this device, not to
@@ -537,6 +506,7 @@ int ddrl_dqn_destroy(ddrl_dqn_t *h) {
     if (!h) return DDRL_OK;
     ddrl::DeviceGuard g(h->device);
     (void)hipFree(h->slab);
+    ddrl_dqn_dx_destroy(h->dx);
     if (h->act_fwd) (void)ddrl_actor_destroy(h->act_fwd);
     if (h->act_sel) (void)ddrl_actor_destroy(h->act_sel);
     (void)hipFree(h->sk_frags_d); (void)hipFree(h->sk_slab); (void)hipFree(h->sk_flag);
@@ -762,6 +732,7 @@ int ddrl_dqn_create(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) 
 // network 0 of main -> the acting forwards' operand layout (three launches on `s`)
 static int dqn_pack_acting(ddrl_dqn *h, hipStream_t s) {
     if (!h->act_fwd) return DDRL_OK;
+    if (const int src = dqn_shadow_sync(h, s)) return src;
     const ddrl_dqn_config_t &c = h->cfg;
     QPiArgs a{h->main_p + h->W1[0], h->main_p + h->W2[0], h->main_p + h->W3[0], h->main_p + h->b3[0], h->pi_flat,
               (long long)c.obs_dim * c.hidden1 + c.hidden1, (long long)c.hidden1 * c.hidden2 + c.hidden2, c.hidden2, c.n_actions, h->half};
@@ -780,6 +751,10 @@ int ddrl_dqn_set_weights(ddrl_dqn_t *h, const float *flat_main_d, void *stream) 
     // main AND target: Learner.set_weights runs target_init (algos/dqn/actor_learner.py:99-101)
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_main_d, h->main_p, h->target_p, 1);
     DDRL_LAUNCH_CHECK();
+    if (h->dx) {
+        if (const int rc = ddrl_dqn_dx_pack(h->dx, DDRL_SAC1_MAIN, flat_main_d, true, ddrl::as_stream(stream))) return rc;
+        h->shadow_stale = false;
+    }
     return dqn_pack_acting(h, ddrl::as_stream(stream));   // eagerly: a captured acting call never replays a stale pack
 }
 
@@ -791,6 +766,7 @@ int ddrl_dqn_export(ddrl_dqn_t *h, int which, float *flat_d, void *stream) {
                  which == DDRL_SAC1_ADAM_V ? h->v : which == DDRL_SAC1_GRAD ? h->grad : nullptr;
     DDRL_REQUIRE(buf != nullptr, "unknown buffer id");
     ddrl::DeviceGuard g(h->device);
+    if (h->dx) return ddrl_dqn_dx_unpack(h->dx, which, flat_d, ddrl::as_stream(stream)) ? DDRL_OK : DDRL_ERR_HIP;
     if (int prc = dqn_poison_check(h, ddrl::as_stream(stream), true)) return prc;   // (drains the stream while the stream-K kernel is in use)
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, buf, flat_d, nullptr, 0);
     DDRL_LAUNCH_CHECK();
@@ -805,6 +781,11 @@ int ddrl_dqn_import(ddrl_dqn_t *h, int which, const float *flat_d, void *stream)
     DDRL_REQUIRE(buf != nullptr, "unknown or read-only buffer id");
     ddrl::DeviceGuard g(h->device);
     if (which == DDRL_SAC1_MAIN) h->poisoned = false;   // fresh main parameters (a resumed learner imports target and moments next)
+    if (h->dx) {
+        if (const int rc = ddrl_dqn_dx_pack(h->dx, which, flat_d, false, ddrl::as_stream(stream))) return rc;
+        if (which != DDRL_SAC1_MAIN) return DDRL_OK;
+        h->shadow_stale = false;   // (the copy in the generic layout is written below)
+    }
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_d, buf, nullptr, 1);
     DDRL_LAUNCH_CHECK();
     if (which == DDRL_SAC1_MAIN) return dqn_pack_acting(h, ddrl::as_stream(stream));
@@ -910,6 +891,16 @@ int ddrl_dqn_step(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d, const
                   float *loss_d, float *q_d, void *stream) {
     DDRL_REQUIRE(h != nullptr && obs1_d && obs2_d && acts_d && rews_d && done_d, "NULL pointer");
     ddrl::DeviceGuard g(h->device);
+    if (h->dx) {   // the staging launch, then the three launches of dqn_direct.hip on input set 0
+        hipStream_t s = ddrl::as_stream(stream);
+        const int B = h->cfg.batch, o = h->cfg.obs_dim, n = B * o > B ? B * o : B;
+        k_dqn_stage<<<(n + 255) / 256, 256, 0, s>>>(obs1_d, obs2_d, acts_d, rews_d, done_d, h->x1, h->x2, h->acts, h->rew, h->done, B, o, h->ldx);
+        if (const int rc = ddrl_dqn_dx_update(h->dx, 0, nullptr, loss_d, s)) return rc;
+        h->pack_stale = h->shadow_stale = true;
+        ++h->steps_launched;
+        if (q_d) DDRL_HIP_CHECK(hipMemcpyAsync(q_d, ddrl_dqn_dx_qrows(h->dx), (size_t)B * h->cfg.n_actions * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return DDRL_OK;
+    }
     return dqn_step_launch(h, obs1_d, obs2_d, acts_d, rews_d, done_d, loss_d, q_d, ddrl::as_stream(stream), nullptr);
 }
 
@@ -950,6 +941,10 @@ int ddrl_dqn_step_timed(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d,
                         int reps, float *stage_ms_h, void *stream) {
     DDRL_REQUIRE(h != nullptr && obs1_d && obs2_d && acts_d && rews_d && done_d && stage_ms_h, "NULL pointer");
     DDRL_REQUIRE(reps > 0 && reps <= 64, "reps outside [1, 64]");
+    if (h->dx) {
+        ddrl::set_error("ddrl_dqn_step_timed: its stage list describes the generic launches; a handle of ddrl_dqn_create_direct runs three others");
+        return DDRL_ERR_UNSUPPORTED;
+    }
     ddrl::DeviceGuard g(h->device);
     hipStream_t s = ddrl::as_stream(stream);
     constexpr int NE = DDRL_DQN_STAGES + 1;
@@ -978,6 +973,7 @@ int ddrl_dqn_q(ddrl_dqn_t *h, const float *obs_d, int64_t n, float *q_d, void *s
     ddrl::DeviceGuard g(h->device);
     hipStream_t s = ddrl::as_stream(stream);
     const int o = h->cfg.obs_dim;
+    if (const int src = dqn_shadow_sync(h, s)) return src;
     DDRL_HIP_CHECK(hipMemcpy2DAsync(h->x1, (size_t)h->ldx * sizeof(float), obs_d, (size_t)o * sizeof(float), (size_t)o * sizeof(float), (size_t)n,
                                     hipMemcpyDeviceToDevice, s));
     if (h->wide) launch_wide_fwd(h->wf, s);   // (evaluations read the staged images here)
@@ -1019,6 +1015,7 @@ int ddrl_dqn_act(ddrl_dqn_t *h, const float *obs_d, int64_t n, int mode, float g
     // outside the acting forward's envelope (wide observations, ...): ddrl_dqn_q's launches + the selection kernel on its Q image.  The staged
     // rows, H1 / H2 / Q are scratch that every learner step rewrites before it reads them; parameters and optimizer state are not touched.
     const int o = c.obs_dim;
+    if (const int src = dqn_shadow_sync(h, s)) return src;
     DDRL_HIP_CHECK(hipMemcpy2DAsync(h->x1, (size_t)h->ldx * sizeof(float), obs_d, (size_t)o * sizeof(float), (size_t)o * sizeof(float), (size_t)n,
                                     hipMemcpyDeviceToDevice, s));
     if (h->wide) launch_wide_fwd(h->wf, s);
@@ -1160,6 +1157,14 @@ int ddrl_dqn_internal_update(ddrl_dqn_t *h, int set, ddrl_replay_t *ride, float 
     ddrl::DeviceGuard g(h->device);
     hipStream_t s = ddrl::as_stream(stream);
     const int B = h->cfg.batch;
+    if (h->dx) {
+        const SetSampler m = ride ? dqn_set_sampler(h, ride, set ^ 1) : SetSampler{};
+        if (const int rc = ddrl_dqn_dx_update(h->dx, set, ride ? &m : nullptr, loss_d, s)) return rc;
+        h->pack_stale = h->shadow_stale = true;
+        ++h->steps_launched;
+        if (ride) ddrl_replay_note_sample(ride);
+        return DDRL_OK;
+    }
     launch_gemm(set ? h->g_f1_s1 : h->g_f1, s);
     launch_gemm(h->g_f2, s);
     HeadArgs H = h->head;
@@ -1180,7 +1185,7 @@ int ddrl_dqn_internal_update(ddrl_dqn_t *h, int set, ddrl_replay_t *ride, float 
 // Make copy 0 of the double-buffered optimizer state the current one, so that a captured graph starts and ends on the same copy whatever
 // the number of updates it holds (a copy node of sizeof(OptState) bytes in a graph of odd length)
 int ddrl_dqn_internal_opt_sync(ddrl_dqn_t *h, void *stream) {
-    if (h->opt_cur == 0) return DDRL_OK;
+    if (h->opt_cur == 0) return DDRL_OK;   // (a direct handle's optimizer state is single: always)
     ddrl::DeviceGuard g(h->device);
     DDRL_HIP_CHECK(hipMemcpyAsync(h->opt, h->opt + 1, sizeof(OptState), hipMemcpyDeviceToDevice, ddrl::as_stream(stream)));
     h->opt_cur = 0;
@@ -1190,6 +1195,28 @@ int ddrl_dqn_internal_opt_sync(ddrl_dqn_t *h, void *stream) {
 // `n` updates ran out of captured graphs: what their launches do to the host-side state when they are issued eagerly
 void ddrl_dqn_internal_note_updates(ddrl_dqn_t *h, long long n) {
     if (n <= 0) return;
-    h->pack_stale = true;
+    h->pack_stale = h->shadow_stale = true;
     h->steps_launched += n;
 }
+
+// ---- ddrl_dqn_create_direct (include/ddrl_dqn_direct.h) -----------------------------------------------------------
+extern "C" {
+
+int ddrl_dqn_create_direct(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) {
+    DDRL_REQUIRE(out != nullptr && cfg != nullptr, "NULL pointer");
+    if (const int rc = ddrl_dqn_dx_check(cfg)) return rc;   // (before anything is allocated)
+    ddrl_dqn_t *h = nullptr;
+    if (const int rc = ddrl_dqn_create(&h, device, cfg)) return rc;
+    ddrl::DeviceGuard g(device);
+    float *const sets[2][5] = {{h->x1, h->x2, h->acts, h->rew, h->done}, {h->set1[0], h->set1[1], h->set1[2], h->set1[3], h->set1[4]}};
+    if (const int rc = ddrl_dqn_dx_create(&h->dx, device, cfg, sets, h->ldx)) {
+        ddrl_dqn_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return DDRL_OK;
+}
+
+int ddrl_dqn_is_direct(ddrl_dqn_t *h) { return h ? (h->dx ? 1 : 0) : DDRL_ERR_BAD_ARG; }
+
+}  // extern "C"

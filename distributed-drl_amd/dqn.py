@@ -91,7 +91,10 @@ class Learner:
                                   gamma=opt.gamma, lr=opt.lr, polyak=opt.polyak, variant=self.VARIANT,
                                   alpha=float(getattr(opt, "alpha", 0.1)))
         h = ctypes.c_void_p()
-        _lib.check(self._lib.ddrl_dqn_create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg)))
+        # opt.direct_learner (absent or False by default): the three-launch direct-operand update (ddrl_dqn_create_direct,
+        # include/ddrl_dqn_direct.h); outside its envelope the create refuses, nothing falls back
+        create = self._lib.ddrl_dqn_create_direct if getattr(opt, "direct_learner", False) else self._lib.ddrl_dqn_create
+        _lib.check(create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg)))
         self._h = h
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._flat_set(torch.from_numpy(glorot_init(self.specs, getattr(opt, "seed", 0))).to(self.device))
