@@ -79,6 +79,25 @@ def _handle(ctx, destroy, create, *args):
     return h
 
 
+class Door:
+    """Another creator behind a builder's handle (the `door` keyword of _sac / _dqn / _actor and of the builders over them; None: the
+    creator, the shape dict and the variant argument the builder has always used).  create: the library function's name; dims: the
+    shape as the builder's shape dict holds it — (obs, act or n_actions, hidden1, hidden2, batch); variant: the learner it builds; query:
+    the name of the library function that must answer 1 for the handle (no query: the creator's return code is the evidence);
+    max_rows: an actor's rows."""
+
+    def __init__(self, create, dims, variant=0, query=None, max_rows=None):
+        self.create, self.dims, self.variant, self.query, self.max_rows = create, tuple(dims), variant, query, max_rows
+
+
+def _made(ctx, door, h):
+    """The handle came through the door it was asked at: never a case that passes on the other kernels by accident."""
+    if door is not None and door.query:
+        got = getattr(ctx.lib, door.query)(h)
+        assert got == 1, "%s answered %r for a handle of %s" % (door.query, got, door.create)
+    return h
+
+
 # ---- rings ------------------------------------------------------------------------------------------------------------------------
 CAP = 50
 RING_SHAPES = {"o3a1": (3, 1, 0), "o8a2": (8, 2, 0), "o16a4u8": (16, 4, 2), "o20a1u8": (20, 1, 2)}   # obs, act, flags (2 = DDRL_REPLAY_U8_OBS)
@@ -215,23 +234,23 @@ WINDOWS = {"Ln1o8": (1, 8), "Ln3o5": (3, 5), "Ln8o8": (8, 8)}
 WACT, GAMMA = 2, 0.99
 
 
-def _wwidths(Ln, obs):
-    return ((Ln + 1) * obs, Ln * WACT, Ln, Ln)
+def _wwidths(Ln, obs, act=WACT):
+    return ((Ln + 1) * obs, Ln * act, Ln, Ln)
 
 
-def _wrows(Ln, obs, n, seed):
+def _wrows(Ln, obs, n, seed, act=WACT):
     r = _rs(seed)
-    w = _wwidths(Ln, obs)
+    w = _wwidths(Ln, obs, act)
     return [_f32(r.randn(n, w[0])), _f32(r.uniform(-1, 1, (n, w[1]))), _f32(r.randn(n, w[2])), _f32(r.rand(n, w[3]) < 0.2)]
 
 
-def _wring(ctx, Ln, obs, fill=0, seed=3, cap=CAP):
+def _wring(ctx, Ln, obs, fill=0, seed=3, cap=CAP, act=WACT):
     L = ctx.lib
-    w = (ctypes.c_int32 * 4)(*_wwidths(Ln, obs))
+    w = (ctypes.c_int32 * 4)(*_wwidths(Ln, obs, act))
     h = _handle(ctx, L.ddrl_replay_destroy, L.ddrl_replay_create_ex, _dev(ctx), cap, 4, w, 1, 1)
     _ok(ctx, L.ddrl_replay_seed(h, seed, None))
     if fill:
-        t = [ctx.tmp(x) for x in _wrows(Ln, obs, fill, 100 + seed)]
+        t = [ctx.tmp(x) for x in _wrows(Ln, obs, fill, 100 + seed, act)]
         _ok(ctx, L.ddrl_replay_store_ex(h, _ptrs(*[x.data_ptr() for x in t]), fill, None))
     return h
 
@@ -388,9 +407,9 @@ def _sac_counts(o, a, h1, h2, variant):
     return pi, pi + 2 * q + (v if variant else 0)
 
 
-def _sac_cfg(shape, variant=0, batch=None):
+def _sac_cfg(shape, variant=0, batch=None, dims=None):
     from distributed_drl_amd import _lib
-    o, a, h1, h2, B = SAC_SHAPES[shape]
+    o, a, h1, h2, B = dims or SAC_SHAPES[shape]
     return _lib.Sac1Config(obs_dim=o, act_dim=a, hidden1=h1, hidden2=h2, batch=batch or B, variant=variant, lr=1e-3)
 
 
@@ -398,31 +417,33 @@ def _weights(n, seed):
     return _f32(_rs(seed).randn(n) * 0.2)
 
 
-def _sac(ctx, shape, variant=0, seed=21):
+def _sac(ctx, shape, variant=0, seed=21, door=None):
     L = ctx.lib
-    cfg = _sac_cfg(shape, variant)
-    h = _handle(ctx, L.ddrl_sac1_destroy, L.ddrl_sac1_create, _dev(ctx), byref(cfg))
-    o, a, h1, h2, B = SAC_SHAPES[shape]
+    dims = door.dims if door else SAC_SHAPES[shape]
+    cfg = _sac_cfg(shape, variant, dims=dims)
+    h = _made(ctx, door, _handle(ctx, L.ddrl_sac1_destroy, getattr(L, door.create) if door else L.ddrl_sac1_create, _dev(ctx), byref(cfg)))
+    o, a, h1, h2, B = dims
     n = _sac_counts(o, a, h1, h2, variant)[1]
     _ok(ctx, L.ddrl_sac1_set_weights(h, _tp(ctx.tmp(_weights(n, seed))), None))
     return h, n
 
 
-def _sac_batch(shape, seed):
-    o, a, _, _, B = SAC_SHAPES[shape]
+def _sac_batch(shape, seed, dims=None):
+    o, a, _, _, B = dims or SAC_SHAPES[shape]
     r = _rs(seed)
     return [("obs1_d", _f32(r.randn(B, o))), ("obs2_d", _f32(r.randn(B, o))), ("acts_d", _f32(r.uniform(-1, 1, (B, a)))),
             ("rews_d", _f32(r.randn(B))), ("done_d", _f32(r.rand(B) < 0.2)), ("eps_x_d", _f32(r.randn(B, a))),
             ("eps_x2_d", _f32(r.randn(B, a))), ("eps_t_d", _f32(r.randn(B, a)))]
 
 
-def _mk_sac_step(shape, variant, grads, rows):
-    B = SAC_SHAPES[shape][4]
+def _mk_sac_step(shape, variant, grads, rows, door=None):
+    dims = door.dims if door else SAC_SHAPES[shape]
+    B = dims[4]
 
     def fn(ctx):
         L = ctx.lib
-        h, n = _sac(ctx, shape, variant)
-        ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(shape, 31)]
+        h, n = _sac(ctx, shape, variant, door=door)
+        ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(shape, 31, dims)]
         losses = P(ctx.out("losses_d", 4 if variant else 3, F32))
         per = [P(ctx.out(k, B, F32)) if rows else None for k in ("q1_d", "q2_d", "logp_pi_d")]
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in ((4,) if grads else (0, 1, 2, 3))]
@@ -438,10 +459,10 @@ for _s in SAC_SHAPES:
         case("%s_compute_grads-%s" % (_vn, _s), "ddrl_sac1_compute_grads", "ddrl_sac1_export")(_mk_sac_step(_s, _v, True, True))
 
 
-def _mk_sac_io(shape, variant, mode):
+def _mk_sac_io(shape, variant, mode, door=None):
     def fn(ctx):
         L = ctx.lib
-        h, n = _sac(ctx, shape, variant)
+        h, n = _sac(ctx, shape, variant, door=door)
         if mode == "get_weights":
             o = ctx.out("flat_main_d", n, F32, ma=True)
             return lambda: L.ddrl_sac1_get_weights(h, P(o), ctx.stream_arg)
@@ -451,7 +472,7 @@ def _mk_sac_io(shape, variant, mode):
             return lambda: [L.ddrl_sac1_set_weights(h, P(src), ctx.stream_arg)] + [L.ddrl_sac1_export(h, w, p, ctx.stream_arg) for w, p in enumerate(o)]
         which = int(mode[-1])
         if mode.startswith("export"):
-            ins = [_tp(ctx.tmp(x)) for _, x in _sac_batch(shape, 31)]      # one update first: moments, target and gradient are not the initial ones
+            ins = [_tp(ctx.tmp(x)) for _, x in _sac_batch(shape, 31, door.dims if door else None)]      # one update first: moments, target and gradient are not the initial ones
             _ok(ctx, L.ddrl_sac1_step(h, *ins, _tp(ctx.tmp(np.zeros(4, np.float32))), None, None, None, None))
             o = ctx.out("flat_d", n, F32, ma=True)
             return lambda: L.ddrl_sac1_export(h, which, P(o), ctx.stream_arg)
@@ -469,12 +490,14 @@ case("sacv_set_weights", "ddrl_sac1_set_weights")(_mk_sac_io("o8a2h64x48B37", 1,
 case("sacv_get_weights", "ddrl_sac1_get_weights")(_mk_sac_io("o8a2h64x48B37", 1, "get_weights"))
 
 
-def _mk_sac_step_host(shape):
-    o, a, h1, h2, B = SAC_SHAPES[shape]
+def _mk_sac_step_host(shape, door=None):
+    dims = door.dims if door else SAC_SHAPES[shape]
+    o, a, h1, h2, B = dims
+    variant = door.variant if door else 0
 
     def fn(ctx):
         L = ctx.lib
-        h, n = _sac(ctx, shape)
+        h, n = _sac(ctx, shape, variant, door=door)
         bufs = (P * 8)()
         _ok(ctx, L.ddrl_sac1_input_buffers(h, 0, bufs))
         p = [int(bufs[i]) for i in range(5)]
@@ -482,9 +505,9 @@ def _mk_sac_step_host(shape):
         span = off[4] + B
         host = ctx.keep(torch.zeros(span + 2, dtype=torch.float32).pin_memory())
         hv = host.numpy()
-        for j, (_, x) in enumerate(_sac_batch(shape, 31)[:5]):
+        for j, (_, x) in enumerate(_sac_batch(shape, 31, dims)[:5]):
             hv[off[j]:off[j] + x.size] = x.reshape(-1)
-        losses = ctx.out("losses_d", 3, F32)
+        losses = ctx.out("losses_d", 4 if variant else 3, F32)
         exp = [P(ctx.out("export%d" % w, n, F32)) for w in (0, 2)]
         return lambda: [L.ddrl_sac1_step_host(h, P(host.data_ptr()), span, 5, 1000, P(losses), ctx.stream_arg)] + [
             L.ddrl_sac1_export(h, w, e, ctx.stream_arg) for w, e in zip((0, 2), exp)]
@@ -499,21 +522,23 @@ for _s in SAC_SHAPES:
 ACTOR_SHAPE, MAX_ROWS = "o8a2h64x48B37", 64
 
 
-def _actor(ctx, shape=ACTOR_SHAPE, max_rows=MAX_ROWS, seed=41):
+def _actor(ctx, shape=ACTOR_SHAPE, max_rows=MAX_ROWS, seed=41, door=None):
     L = ctx.lib
-    cfg = _sac_cfg(shape)
-    h = _handle(ctx, L.ddrl_actor_destroy, L.ddrl_actor_create, _dev(ctx), byref(cfg), max_rows)
-    o, a, h1, h2, _ = SAC_SHAPES[shape]
+    dims = door.dims if door else SAC_SHAPES[shape]
+    cfg = _sac_cfg(shape, dims=dims)
+    h = _made(ctx, door, _handle(ctx, L.ddrl_actor_destroy, getattr(L, door.create) if door else L.ddrl_actor_create, _dev(ctx), byref(cfg),
+                                 door.max_rows if door else max_rows))
+    o, a, h1, h2, _ = dims
     n_pi = _sac_counts(o, a, h1, h2, 0)[0]
     _ok(ctx, L.ddrl_actor_set_weights(h, _tp(ctx.tmp(_weights(n_pi, seed))), None))
     return h, n_pi
 
 
-def _mk_actor_act(shape, n, det):
-    o, a = SAC_SHAPES[shape][:2]
+def _mk_actor_act(shape, n, det, door=None):
+    o, a = (door.dims if door else SAC_SHAPES[shape])[:2]
 
     def fn(ctx):
-        h, _ = _actor(ctx, shape)
+        h, _ = _actor(ctx, shape, door=door)
         r = _rs(n)
         obs = ctx.inp("obs_d", _f32(r.randn(n, o)), ma=True)
         eps = None if det else ctx.inp("eps_d", _f32(r.randn(n, a)), ma=True)
@@ -528,11 +553,11 @@ for _s in SAC_SHAPES:
     case("actor_act-%s-deterministic" % _s, "ddrl_actor_act")(_mk_actor_act(_s, 5, 1))
 
 
-def _mk_actor_one(shape, det):
-    o, a = SAC_SHAPES[shape][:2]
+def _mk_actor_one(shape, det, door=None):
+    o, a = (door.dims if door else SAC_SHAPES[shape])[:2]
 
     def fn(ctx):
-        h, _ = _actor(ctx, shape)
+        h, _ = _actor(ctx, shape, door=door)
         obs = ctx.inp("obs_d", _f32(_rs(4).randn(o)), ma=True)
         act = ctx.out("act_d", a, F32, ma=True)
         return lambda: ctx.lib.ddrl_actor_act_one(h, P(obs), 9, (1 << 32) - 1, det, P(act), ctx.stream_arg)
@@ -544,10 +569,10 @@ for _s in SAC_SHAPES:
 case("actor_act_one-deterministic", "ddrl_actor_act_one")(_mk_actor_one(ACTOR_SHAPE, 1))
 
 
-def _mk_actor_weights(setw):
+def _mk_actor_weights(setw, door=None):
     def fn(ctx):
         L = ctx.lib
-        h, n_pi = _actor(ctx)
+        h, n_pi = _actor(ctx, door=door)
         if setw:
             src = ctx.inp("flat_pi_d", _weights(n_pi, 79), ma=True)
             o = ctx.out("get_weights", n_pi, F32)
@@ -561,36 +586,38 @@ case("actor_set_weights", "ddrl_actor_set_weights", "ddrl_actor_get_weights")(_m
 case("actor_get_weights", "ddrl_actor_get_weights")(_mk_actor_weights(False))
 
 
-def _versioned_actor(ctx):
+def _versioned_actor(ctx, door=None):
     """Two versions live: envs 0, 3, 40 have adopted the second install, the others act on the first."""
     L = ctx.lib
-    h, n_pi = _actor(ctx)
+    h, n_pi = _actor(ctx, door=door)
     _ok(ctx, L.ddrl_actor_versions_enable(h, 8, None))
     _ok(ctx, L.ddrl_actor_set_weights(h, _tp(ctx.tmp(_weights(n_pi, 43))), None))
-    ended = np.zeros(MAX_ROWS, np.uint8)
+    ended = np.zeros(door.max_rows if door else MAX_ROWS, np.uint8)
     ended[[0, 3, 40]] = 1
     return h, ended
 
 
 @case("actor_act_versioned", "ddrl_actor_act_versioned")
-def _act_versioned(ctx):
+def _act_versioned(ctx, door=None):
     L = ctx.lib
-    h, ended = _versioned_actor(ctx)
-    _ok(ctx, L.ddrl_actor_versions_adopt(h, _tp(ctx.tmp(ended)), MAX_ROWS, None))
+    o, a, rows = (door.dims[0], door.dims[1], door.max_rows) if door else (8, 2, MAX_ROWS)
+    h, ended = _versioned_actor(ctx, door)
+    _ok(ctx, L.ddrl_actor_versions_adopt(h, _tp(ctx.tmp(ended)), rows, None))
     r = _rs(6)
-    obs, eps = ctx.inp("obs_d", _f32(r.randn(MAX_ROWS, 8)), ma=True), ctx.inp("eps_d", _f32(r.randn(MAX_ROWS, 2)), ma=True)
-    act = ctx.out("act_d", MAX_ROWS * 2, F32, ma=True)
-    return lambda: L.ddrl_actor_act_versioned(h, P(obs), P(eps), MAX_ROWS, 0, 1000, P(act), ctx.stream_arg)
+    obs, eps = ctx.inp("obs_d", _f32(r.randn(rows, o)), ma=True), ctx.inp("eps_d", _f32(r.randn(rows, a)), ma=True)
+    act = ctx.out("act_d", rows * a, F32, ma=True)
+    return lambda: L.ddrl_actor_act_versioned(h, P(obs), P(eps), rows, 0, 1000, P(act), ctx.stream_arg)
 
 
 @case("actor_versions_adopt_and_state", "ddrl_actor_versions_adopt", "ddrl_actor_versions_state")
-def _versions_adopt(ctx):
+def _versions_adopt(ctx, door=None):
     L = ctx.lib
-    h, ended = _versioned_actor(ctx)
+    rows = door.max_rows if door else MAX_ROWS
+    h, ended = _versioned_actor(ctx, door)
     e = ctx.inp("ended_d", ended)
-    slots = ctx.out("slot_of_env_d", MAX_ROWS, I32)
+    slots = ctx.out("slot_of_env_d", rows, I32)
     st = ctx.keep((ctypes.c_int32 * 4)())
-    return lambda: [L.ddrl_actor_versions_adopt(h, P(e), MAX_ROWS, ctx.stream_arg), L.ddrl_actor_versions_state(h, P(slots), st, ctx.stream_arg)]
+    return lambda: [L.ddrl_actor_versions_adopt(h, P(e), rows, ctx.stream_arg), L.ddrl_actor_versions_state(h, P(slots), st, ctx.stream_arg)]
 
 
 # ---- evaluation -----------------------------------------------------------------------------------------------------------------------
@@ -818,37 +845,38 @@ DQN_SHAPES = {"o8A2h64x48B37": (8, 2, 64, 48, 37), "o3A1h36x8B5": (3, 1, 36, 8, 
 VARIANTS = {"ddqn": 0, "sqn": 1}
 
 
-def _dqn_cfg(shape, variant):
+def _dqn_cfg(shape, variant, dims=None):
     from distributed_drl_amd import _lib
-    o, A, h1, h2, B = DQN_SHAPES[shape]
+    o, A, h1, h2, B = dims or DQN_SHAPES[shape]
     return _lib.DqnConfig(o, A, h1, h2, B, variant=variant)
 
 
-def _dqn(ctx, shape, variant=0, seed=51):
+def _dqn(ctx, shape, variant=0, seed=51, door=None):
     L = ctx.lib
-    cfg = ctx.keep(_dqn_cfg(shape, variant))
+    cfg = ctx.keep(_dqn_cfg(shape, door.variant if door else variant, door.dims if door else None))
     n = ctypes.c_int64()
     _ok(ctx, L.ddrl_dqn_param_count(byref(cfg), byref(n)))
-    h = _handle(ctx, L.ddrl_dqn_destroy, L.ddrl_dqn_create, _dev(ctx), byref(cfg))
+    h = _made(ctx, door, _handle(ctx, L.ddrl_dqn_destroy, getattr(L, door.create) if door else L.ddrl_dqn_create, _dev(ctx), byref(cfg)))
     _ok(ctx, L.ddrl_dqn_set_weights(h, _tp(ctx.tmp(_weights(n.value, seed) * 0.25)), None))
     return h, int(n.value), cfg
 
 
-def _dqn_batch(shape, seed):
-    o, A, _, _, B = DQN_SHAPES[shape]
+def _dqn_batch(shape, seed, dims=None):
+    o, A, _, _, B = dims or DQN_SHAPES[shape]
     r = _rs(seed)
     return [("obs1_d", _f32(r.randn(B, o))), ("obs2_d", _f32(r.randn(B, o))), ("acts_d", _f32(r.randint(0, A, B))),
             ("rews_d", _f32(r.randn(B))), ("done_d", _f32(r.rand(B) < 0.2))]
 
 
-def _mk_dqn_step(shape, variant, outs):
-    o, A, _, _, B = DQN_SHAPES[shape]
+def _mk_dqn_step(shape, variant, outs, door=None):
+    dims = door.dims if door else DQN_SHAPES[shape]
+    o, A, _, _, B = dims
 
     def fn(ctx):
         L = ctx.lib
-        h, n, _ = _dqn(ctx, shape, variant)
+        h, n, _ = _dqn(ctx, shape, variant, door=door)
         # wide observations: 16-byte aligned rows are read in place, rows off that grid are staged (the header's words) — both run
-        ins = [P(ctx.inp(k, x, ma=(o >= 1024 and k in ("obs1_d", "obs2_d")))) for k, x in _dqn_batch(shape, 61)]
+        ins = [P(ctx.inp(k, x, ma=(o >= 1024 and k in ("obs1_d", "obs2_d")))) for k, x in _dqn_batch(shape, 61, dims)]
         loss = P(ctx.out("loss_d", 1, F32)) if outs else None
         q = P(ctx.out("q_d", B * A, F32)) if outs else None
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3, 4)]
@@ -864,17 +892,17 @@ for _s in ("o8A2h64x48B37", "o3A1h36x8B5", "o1028A2h64x48B37"):
         case("%s_step-%s-outputs_null" % (_vn, _s), "ddrl_dqn_step", "ddrl_dqn_export")(_mk_dqn_step(_s, _v, False))
 
 
-def _mk_dqn_io(shape, variant, mode):
+def _mk_dqn_io(shape, variant, mode, door=None):
     def fn(ctx):
         L = ctx.lib
-        h, n, _ = _dqn(ctx, shape, variant)
+        h, n, _ = _dqn(ctx, shape, variant, door=door)
         if mode == "set_weights":
             src = ctx.inp("flat_main_d", _weights(n, 80) * 0.25, ma=True)
             o = [P(ctx.out("export%d" % w, n, F32)) for w in (0, 1)]
             return lambda: [L.ddrl_dqn_set_weights(h, P(src), ctx.stream_arg)] + [L.ddrl_dqn_export(h, w, p, ctx.stream_arg) for w, p in enumerate(o)]
         which = int(mode[-1])
         if mode.startswith("export"):
-            ins = [_tp(ctx.tmp(x)) for _, x in _dqn_batch(shape, 61)]      # one update first: moments, target and gradient are not the initial ones
+            ins = [_tp(ctx.tmp(x)) for _, x in _dqn_batch(shape, 61, door.dims if door else None)]      # one update first: moments, target and gradient are not the initial ones
             _ok(ctx, L.ddrl_dqn_step(h, *ins, None, None, None))
             o = ctx.out("flat_d", n, F32, ma=True)
             return lambda: L.ddrl_dqn_export(h, which, P(o), ctx.stream_arg)
@@ -891,12 +919,16 @@ for _s in ("o8A2h64x48B37", "o3A1h36x8B5"):
             case("%s_%s-%s" % (_vn, _m, _s), _f)(_mk_dqn_io(_s, _v, _m))
 
 
-def _mk_dqn_q(shape, variant, n, act):
-    o, A, _, _, B = DQN_SHAPES[shape]
+def _mk_dqn_q(shape, variant, n, act, door=None, updated=False):
+    """updated: one update stands in the setup, so that the call under test is the first acting call behind it."""
+    dims = door.dims if door else DQN_SHAPES[shape]
+    o, A, _, _, B = dims
 
     def fn(ctx):
         L = ctx.lib
-        h, _, _ = _dqn(ctx, shape, variant)
+        h, _, _ = _dqn(ctx, shape, variant, door=door)
+        if updated:
+            _ok(ctx, L.ddrl_dqn_step(h, *[_tp(ctx.tmp(x)) for _, x in _dqn_batch(shape, 61, dims)], None, None, None))
         obs = P(ctx.inp("obs_d", _f32(_rs(n).randn(n, o)), ma=True))
         if act is None:
             q = P(ctx.out("q_d", n * A, F32, ma=True))
@@ -938,13 +970,13 @@ case("ddqn_step_ring", "ddrl_dqn_step_ring")(_mk_dqn_step_ring(True))
 case("ddqn_step_ring-outputs_null", "ddrl_dqn_step_ring")(_mk_dqn_step_ring(False))
 
 
-def _mk_dqn_loop(variant, loss):
+def _mk_dqn_loop(variant, loss, door=None):
     shape = "o8A2h64x48B37"
-    o, A, _, _, B = DQN_SHAPES[shape]
+    o, A, _, _, B = door.dims if door else DQN_SHAPES[shape]
 
     def fn(ctx):
         L = ctx.lib
-        h, n, _ = _dqn(ctx, shape, variant)
+        h, n, _ = _dqn(ctx, shape, variant, door=door)
         ring = _ring5(ctx, o, 1, 0, fill=0)
         r = _rs(72)
         rows = [_f32(r.randn(CAP, o)), _f32(r.randint(0, A, (CAP, 1))), _f32(r.randn(CAP)), _f32(r.randn(CAP, o)), _f32(r.rand(CAP) < 0.2)]
@@ -965,9 +997,10 @@ DSHAPE = "o8A4h64x48B64"
 
 
 @case("dqn_versions_adopt_and_state", "ddrl_dqn_versions_adopt", "ddrl_dqn_versions_state")
-def _dqn_versions(ctx):
+def _dqn_versions(ctx, door=None):
+    """(a door keeps DSHAPE's widths: 64 rows, 4 actions)"""
     L = ctx.lib
-    h, n, _ = _dqn(ctx, DSHAPE)
+    h, n, _ = _dqn(ctx, DSHAPE, door=door)
     _ok(ctx, L.ddrl_dqn_versions_enable(h, 8, None))
     _ok(ctx, L.ddrl_dqn_set_weights(h, _tp(ctx.tmp(_weights(n, 53) * 0.25)), None))
     ended = np.zeros(64, np.uint8)
@@ -978,11 +1011,11 @@ def _dqn_versions(ctx):
     return lambda: [L.ddrl_dqn_versions_adopt(h, P(e), 64, ctx.stream_arg), L.ddrl_dqn_versions_state(h, P(slots), st, ctx.stream_arg)]
 
 
-def _mk_rollout_discrete(variant, n_steps, present):
+def _mk_rollout_discrete(variant, n_steps, present, door=None):
     def fn(ctx):
         L = ctx.lib
         h, fields = _env(ctx, RN, "one_body", max_ep_len=3)
-        d, _, _ = _dqn(ctx, DSHAPE, variant)
+        d, _, _ = _dqn(ctx, DSHAPE, variant, door=door)
         ring = _ring5(ctx, 8, 1, cap=RCAP, fill=7)
         _ok(ctx, L.ddrl_rollout_begin_discrete(h, d, None))
         _ok(ctx, L.ddrl_rollout_step_discrete(h, d, ring, 2, 0, 0.5, 5, 0, None, None, None, None))
@@ -1170,8 +1203,14 @@ def _append_ring(ctx):
 LSHAPE = "o8a2h64x48B37"     # SAC_SHAPES' direct-operand one
 
 
-def _sac_ring(ctx, cap=CAP, fill=37):
-    return _ring5(ctx, 8, 2, cap=cap, fill=fill)
+def _sac_ring(ctx, cap=CAP, fill=37, dims=None):
+    o, a = dims[:2] if dims else (8, 2)
+    return _ring5(ctx, o, a, cap=cap, fill=fill)
+
+
+def _ldims(door):
+    """The learner builders' shape: LSHAPE's, or the door's own."""
+    return door.dims if door else SAC_SHAPES[LSHAPE]
 
 
 def _sac_sets(ctx, h):
@@ -1201,13 +1240,14 @@ stream_case("sacv_grad_finalize_apply_grads", "ddrl_sac1_grad_finalize", "ddrl_s
 
 
 @stream_case("sac1_opt_state_set_get_steps", "ddrl_sac1_opt_state_set", "ddrl_sac1_opt_state_get", "ddrl_sac1_opt_steps")
-def _opt_state(ctx):
+def _opt_state(ctx, door=None):
     """One update (the call ahead: it takes the batch and moves the counts) -> set(3, 4, ctr) -> one update (its lr_t depends on the
     counts) -> the counts read back both ways, behind the update.  A set that ran during the gate is counted on by two updates."""
     L = ctx.lib
-    h, n = _sac(ctx, LSHAPE)
-    ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31)]
-    losses = P(ctx.out("losses_d", 3, F32))
+    variant = door.variant if door else 0
+    h, n = _sac(ctx, LSHAPE, variant, door=door)
+    ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31, _ldims(door))]
+    losses = P(ctx.out("losses_d", 4 if variant else 3, F32))
     e0 = P(ctx.out("export0", n, F32))
     t, g, c = ctx.host("opt_steps_h", 2, c_int64), ctx.host("opt_state_h", 2, c_int64), ctx.host("noise_ctr_h", 1, c_uint64)
     s = lambda: ctx.stream_arg
@@ -1217,20 +1257,32 @@ def _opt_state(ctx):
                     L.ddrl_sac1_opt_state_get(h, _at(g, 0), _at(g, 1), _at(c), s())]
 
 
-def _mk_sac_and_sample(mode):
+def _mk_sac_and_sample(mode, door=None, window=0):
     """The learner's own input sets: set 0 holds a drawn batch (setup), the call under test updates from it while its sampler draws
     the next batch into set 1; both sets' transition arrays and the generated noise of set 0 are copied out.
     Calls ahead: a set_weights of the learner and a store of three rows into the ring the sampler draws from (ddrl_sac1_fill_noise
-    launches nothing: it arms the next update's first kernel)."""
-    o, a, _, _, B = SAC_SHAPES[LSHAPE]
+    launches nothing: it arms the next update's first kernel).
+    A door brings its own shape and variant; window = Ln > 0: the ring is an n-step window ring of Ln steps (the learner's sampler
+    folds), set 0 holds a folded draw and the store ahead is a ddrl_replay_store_ex of three windows."""
+    dims = _ldims(door)
+    o, a, _, _, B = dims
+    variant = door.variant if door else 0
 
     def fn(ctx):
         L = ctx.lib
-        h, n = _sac(ctx, LSHAPE)
-        ring = _sac_ring(ctx)
+        h, n = _sac(ctx, LSHAPE, variant, door=door)
+        ring = _wring(ctx, window, o, fill=37, act=a) if window else _sac_ring(ctx, dims=dims)
         sets = _sac_sets(ctx, h)
-        _ok(ctx, L.ddrl_replay_sample(ring, B, *[P(x) for x in sets[0][:5]], None, None))
-        flat, store = P(ctx.inp("ahead.flat_d", _weights(n, 23))), _store_ahead(ctx, ring, _rows5(8, 2, 3, 9, 0))
+        if window:
+            _ok(ctx, L.ddrl_replay_sample_nstep(ring, B, _sac_cfg(LSHAPE, variant, dims=dims).gamma, *[P(x) for x in sets[0][:5]], None, None))
+        else:
+            _ok(ctx, L.ddrl_replay_sample(ring, B, *[P(x) for x in sets[0][:5]], None, None))
+        flat = P(ctx.inp("ahead.flat_d", _weights(n, 23)))
+        if window:
+            src = _ptrs(*[ctx.inp("ahead.src_h[%d]" % j, x) for j, x in enumerate(_wrows(window, o, 3, 9, a))])
+            store = lambda: L.ddrl_replay_store_ex(ring, src, 3, ctx.stream_arg)
+        else:
+            store = _store_ahead(ctx, ring, _rows5(o, a, 3, 9, 0))
         # (the two fused entries take no losses pointer: the loss words stay in the handle)
         losses = P(ctx.out("losses_d", 3, F32)) if mode == "apply_grads_and_sample" else None
         exp =[(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 2)]
@@ -1267,13 +1319,14 @@ for _m, _f in (("step_and_sample", ("ddrl_sac1_step_and_sample", "ddrl_sac1_fill
 
 
 @stream_case("sac1_graph_sync", "ddrl_sac1_graph_sync")
-def _graph_sync(ctx):
+def _graph_sync(ctx, door=None):
     """One update leaves the double-buffered optimizer state on copy 1; graph_sync puts it back on copy 0 (a copy node on `stream`);
     the update behind it continues from there."""
     L = ctx.lib
-    h, n = _sac(ctx, LSHAPE)
-    ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31)]
-    losses = P(ctx.out("losses_d", 3, F32))
+    variant = door.variant if door else 0
+    h, n = _sac(ctx, LSHAPE, variant, door=door)
+    ins = [P(ctx.inp(k, x)) for k, x in _sac_batch(LSHAPE, 31, _ldims(door))]
+    losses = P(ctx.out("losses_d", 4 if variant else 3, F32))
     exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3)]
     s = lambda: ctx.stream_arg
     return lambda: [L.ddrl_sac1_step(h, *ins, losses, None, None, None, s()), L.ddrl_sac1_graph_sync(h, s()),
@@ -1283,14 +1336,16 @@ def _graph_sync(ctx):
 LOOP_ROWS = 64
 
 
-def _mk_loop_run(per_graph):
+def _mk_loop_run(per_graph, door=None):
     """Two calls: per_graph - 1 updates (below the capture threshold: eager), then 2 per_graph + 1 (one eager update, the capture, replays).
     Calls ahead: a set_weights of the learner and a store of three rows into the ring the loop draws from."""
+    dims = _ldims(door)
+
     def fn(ctx):
         L = ctx.lib
-        h, n = _sac(ctx, LSHAPE)
-        ring = _sac_ring(ctx, cap=LOOP_ROWS, fill=LOOP_ROWS)
-        flat, store = P(ctx.inp("ahead.flat_d", _weights(n, 23))), _store_ahead(ctx, ring, _rows5(8, 2, 3, 9, 0))
+        h, n = _sac(ctx, LSHAPE, door.variant if door else 0, door=door)
+        ring = _sac_ring(ctx, cap=LOOP_ROWS, fill=LOOP_ROWS, dims=dims)
+        flat, store = P(ctx.inp("ahead.flat_d", _weights(n, 23))), _store_ahead(ctx, ring, _rows5(dims[0], dims[1], 3, 9, 0))
         loop = _handle(ctx, L.ddrl_loop_destroy, L.ddrl_loop_create, h, ring, per_graph, 13)
         exp = [(w, P(ctx.out("export%d" % w, n, F32))) for w in (0, 1, 2, 3)]
         t = ctx.host("opt_steps_h", 2, c_int64)
@@ -1302,13 +1357,13 @@ def _mk_loop_run(per_graph):
     return fn
 
 
-def _mk_dqn_loop_run(per_graph):
+def _mk_dqn_loop_run(per_graph, door=None):
     shape = "o8A2h64x48B37"
-    o, A, _, _, B = DQN_SHAPES[shape]
+    o, A, _, _, B = door.dims if door else DQN_SHAPES[shape]
 
     def fn(ctx):
         L = ctx.lib
-        h, n, _ = _dqn(ctx, shape, 0)
+        h, n, _ = _dqn(ctx, shape, 0, door=door)
         ring = _ring5(ctx, o, 1, 0, cap=LOOP_ROWS, fill=0)
         r = _rs(72)
         rows = [_f32(r.randn(LOOP_ROWS, o)), _f32(r.randint(0, A, (LOOP_ROWS, 1))), _f32(r.randn(LOOP_ROWS)), _f32(r.randn(LOOP_ROWS, o)),
@@ -1334,32 +1389,33 @@ for _pg in (2, 3):
 
 
 @stream_case("actor_versions_enable", "ddrl_actor_versions_enable")
-def _actor_enable(ctx):
+def _actor_enable(ctx, door=None):
     """A set_weights (the call ahead: what enable keeps as the first version) -> enable -> a second install -> three envs adopt it:
     the slot words and the action of every env against its version."""
     L = ctx.lib
-    h, n_pi = _actor(ctx)
+    o, a, rows = (door.dims[0], door.dims[1], door.max_rows) if door else (8, 2, MAX_ROWS)
+    h, n_pi = _actor(ctx, door=door)
     src0 = P(ctx.inp("ahead.flat_pi_d", _weights(n_pi, 44)))
     src = P(ctx.inp("flat_pi_d", _weights(n_pi, 43)))
-    ended = np.zeros(MAX_ROWS, np.uint8)
+    ended = np.zeros(rows, np.uint8)
     ended[[0, 3, 40]] = 1
     e = P(ctx.inp("ended_d", ended))
     r = _rs(6)
-    obs, eps = P(ctx.inp("obs_d", _f32(r.randn(MAX_ROWS, 8)))), P(ctx.inp("eps_d", _f32(r.randn(MAX_ROWS, 2))))
-    slots, act = P(ctx.out("slot_of_env_d", MAX_ROWS, I32)), P(ctx.out("act_d", MAX_ROWS * 2, F32))
+    obs, eps = P(ctx.inp("obs_d", _f32(r.randn(rows, o)))), P(ctx.inp("eps_d", _f32(r.randn(rows, a))))
+    slots, act = P(ctx.out("slot_of_env_d", rows, I32)), P(ctx.out("act_d", rows * a, F32))
     st = ctx.host("state_h", 4, c_int32)
     s = lambda: ctx.stream_arg
     return lambda: [L.ddrl_actor_set_weights(h, src0, s()), L.ddrl_actor_versions_enable(h, 8, s()), L.ddrl_actor_set_weights(h, src, s()),
-                    L.ddrl_actor_versions_adopt(h, e, MAX_ROWS, s()), L.ddrl_actor_act_versioned(h, obs, eps, MAX_ROWS, 0, 1000, act, s()),
+                    L.ddrl_actor_versions_adopt(h, e, rows, s()), L.ddrl_actor_act_versioned(h, obs, eps, rows, 0, 1000, act, s()),
                     L.ddrl_actor_versions_state(h, slots, st, s())]
 
 
 @stream_case("dqn_versions_enable", "ddrl_dqn_versions_enable")
-def _dqn_enable(ctx):
+def _dqn_enable(ctx, door=None):
     """_actor_enable's on the Q network; the Q values of every env against its version come out of one fused rollout step (the only
-    versioned forward of this family)."""
+    versioned forward of this family).  (A door keeps DSHAPE's widths.)"""
     L = ctx.lib
-    h, n, _ = _dqn(ctx, DSHAPE)
+    h, n, _ = _dqn(ctx, DSHAPE, door=door)
     env, _ = _env(ctx, RN, "one_body", max_ep_len=3)
     ring = _ring5(ctx, 8, 1, cap=RCAP, fill=7)
     src0 = P(ctx.inp("ahead.flat_main_d", _weights(n, 54) * 0.25))
@@ -1405,16 +1461,16 @@ stream_case("rollout_begin", "ddrl_rollout_begin")(_mk_rollout_begin("one_body")
 stream_case("rollout_begin_articulated", "ddrl_rollout_begin_articulated")(_mk_rollout_begin("articulated"))
 
 
-def _mk_rollout_begin_discrete(model):
+def _mk_rollout_begin_discrete(model, door=None):
     """The discrete pair likewise, the set_state ahead included.  The articulated pair takes handles only: its mirrors live in the env
-    handle and are copied out."""
+    handle and are copied out.  (A door keeps DSHAPE's widths.)"""
     artic = model == "articulated"
 
     def fn(ctx):
         L = ctx.lib
         h, fields = _env(ctx, RN, model, max_ep_len=3)
         ahead = P(ctx.inp("ahead.state_d", _other_state(ctx, RN, model, 3, discrete=True)))
-        d, _, _ = _dqn(ctx, DSHAPE)
+        d, _, _ = _dqn(ctx, DSHAPE, door=door)
         ring = _ring5(ctx, 8, 1, cap=RCAP, fill=7)
         s = lambda: ctx.stream_arg
         st = P(ctx.out("state_d", fields * RN, F32))
@@ -1511,16 +1567,16 @@ for _m in MODELS:
     stream_case("env_stats-%s" % _m, "ddrl_env_stats")(_mk_env_stats(_m))
 
 
-def _mk_env_eval(model, discrete):
+def _mk_env_eval(model, discrete, door=None):
     """The evaluation entries fed from handles: the results live in a block of the env handle (ddrl_env_eval_results) and are copied
     out.  A first evaluation of the same size (setup) has allocated that block, so that the call under test only launches.
-    Call ahead: a set_weights of the network that the episodes are played with."""
+    Call ahead: a set_weights of the network that the episodes are played with.  (A door keeps the lander's widths.)"""
     row = 20 if discrete else 12
 
     def fn(ctx):
         L = ctx.lib
         h, _ = _env(ctx, 1, model, seed=5, max_ep_len=EP_LEN)
-        src, n, _ = _dqn(ctx, DSHAPE) if discrete else _actor(ctx) + (None,)
+        src, n, _ = _dqn(ctx, DSHAPE, door=door) if discrete else _actor(ctx, door=door) + (None,)
         flat = P(ctx.inp("ahead.flat_d", _weights(n, 58) * (0.25 if discrete else 1.0)))
         setw = L.ddrl_dqn_set_weights if discrete else L.ddrl_actor_set_weights
         s = lambda: ctx.stream_arg
