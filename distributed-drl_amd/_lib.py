@@ -276,6 +276,12 @@ SIGNATURES_DQN_DIRECT = {
     "ddrl_dqn_is_direct": SIGNATURES["ddrl_dqn_wide_sk"],
 }
 
+# include/ddrl_dqn_direct_tail.h, likewise
+SIGNATURES_DQN_DIRECT_TAIL = {
+    "ddrl_dqn_create_direct_tail": SIGNATURES["ddrl_dqn_create"],          # the arguments of ddrl_dqn_create
+    "ddrl_dqn_is_direct_tail": SIGNATURES["ddrl_dqn_wide_sk"],
+}
+
 
 def load():
     """Load libddrl_hip.so; raise loudly when it is absent (no fallback path exists)."""
@@ -293,7 +299,7 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_WALKER.items()) + list(SIGNATURES_WALKER_EVAL.items())
                               + list(SIGNATURES_WALKER_HARDCORE.items()) + list(SIGNATURES_WALKER_HARDCORE_EVAL.items())
                               + list(SIGNATURES_ACTOR_WIDE.items()) + list(SIGNATURES_SAC1_WIDE.items()) + list(SIGNATURES_SACV_WIDE.items())
-                              + list(SIGNATURES_DQN_DIRECT.items())):
+                              + list(SIGNATURES_DQN_DIRECT.items()) + list(SIGNATURES_DQN_DIRECT_TAIL.items())):
         try:
             fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         except AttributeError:

@@ -5,7 +5,9 @@
 #include "policy_row.h"
 #include "dqn_select.h"
 #include "dqn_direct.h"
+#include "dqn_direct_tail.h"
 #include "../../include/ddrl_dqn_direct.h"
+#include "../../include/ddrl_dqn_direct_tail.h"
 
 // ==========================================================================================
 // Double-DQN learner (algos/dqn/actor_learner.py:19-107 on algos/dqn/core.py:40-50):
@@ -446,7 +448,9 @@ struct ddrl_dqn {
     int half;                        // ceil(n_actions / 2): Q columns per head of the actor
     bool pack_stale;                 // a learner step moved main since the last pack
     ddrl_dqn_dx *dx;                 // ddrl_dqn_create_direct: the direct-operand update (dqn_direct.hip) owns the parameters; main_p is then a copy of
-    bool shadow_stale;               // main in the generic layout for ddrl_dqn_q and the acting pack, rewritten from dx when an update has moved main
+    ddrl_dqn_tx *tx;                 // ddrl_dqn_create_direct_tail: the direct-operand tail (dqn_direct_tail.hip) owns W2, b2, W3, b3 of every buffer;
+                                     // W1 / b1 stay here, and main_p's copy of the others is rewritten from tx like dx's shadow
+    bool shadow_stale;               // main in the generic layout for ddrl_dqn_q and the acting pack, rewritten from dx / tx when an update has moved main
     bool poisoned;                   // that word was seen: the parameters carry at least one step from a wrong layer-1 gradient.  Every step / export
                                      // fails until fresh parameters arrive (set_weights, import of MAIN), so they cannot be pushed or checkpointed
 };
@@ -473,6 +477,11 @@ static int dqn_poison_check(ddrl_dqn *h, hipStream_t s, bool drain) {
 
 // A direct handle: main in the generic layout (what ddrl_dqn_q's launches and k_q_to_pi read) out of the direct layout, two pack launches
 static int dqn_shadow_sync(ddrl_dqn *h, hipStream_t s) {
+    if (h->tx && h->shadow_stale) {   // a tail handle: only W2, b2, W3, b3 live elsewhere — one launch
+        if (const int rc = ddrl_dqn_tx_shadow(h->tx, h->main_p, s)) return rc;
+        h->shadow_stale = false;
+        return DDRL_OK;
+    }
     if (!h->dx || !h->shadow_stale) return DDRL_OK;
     const float *flat = ddrl_dqn_dx_unpack(h->dx, DDRL_SAC1_MAIN, nullptr, s);
     if (!flat) return DDRL_ERR_HIP;
@@ -507,6 +516,7 @@ int ddrl_dqn_destroy(ddrl_dqn_t *h) {
     ddrl::DeviceGuard g(h->device);
     (void)hipFree(h->slab);
     ddrl_dqn_dx_destroy(h->dx);
+    ddrl_dqn_tx_destroy(h->tx);
     if (h->act_fwd) (void)ddrl_actor_destroy(h->act_fwd);
     if (h->act_sel) (void)ddrl_actor_destroy(h->act_sel);
     (void)hipFree(h->sk_frags_d); (void)hipFree(h->sk_slab); (void)hipFree(h->sk_flag);
@@ -755,6 +765,10 @@ int ddrl_dqn_set_weights(ddrl_dqn_t *h, const float *flat_main_d, void *stream) 
         if (const int rc = ddrl_dqn_dx_pack(h->dx, DDRL_SAC1_MAIN, flat_main_d, true, ddrl::as_stream(stream))) return rc;
         h->shadow_stale = false;
     }
+    if (h->tx) {
+        if (const int rc = ddrl_dqn_tx_pack(h->tx, DDRL_SAC1_MAIN, flat_main_d, true, ddrl::as_stream(stream))) return rc;
+        h->shadow_stale = false;
+    }
     return dqn_pack_acting(h, ddrl::as_stream(stream));   // eagerly: a captured acting call never replays a stale pack
 }
 
@@ -770,6 +784,7 @@ int ddrl_dqn_export(ddrl_dqn_t *h, int which, float *flat_d, void *stream) {
     if (int prc = dqn_poison_check(h, ddrl::as_stream(stream), true)) return prc;   // (drains the stream while the stream-K kernel is in use)
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, buf, flat_d, nullptr, 0);
     DDRL_LAUNCH_CHECK();
+    if (h->tx) return ddrl_dqn_tx_unpack(h->tx, which, flat_d, ddrl::as_stream(stream));   // W2, b2, W3, b3 over the generic buffer's copies
     return DDRL_OK;
 }
 
@@ -785,6 +800,10 @@ int ddrl_dqn_import(ddrl_dqn_t *h, int which, const float *flat_d, void *stream)
         if (const int rc = ddrl_dqn_dx_pack(h->dx, which, flat_d, false, ddrl::as_stream(stream))) return rc;
         if (which != DDRL_SAC1_MAIN) return DDRL_OK;
         h->shadow_stale = false;   // (the copy in the generic layout is written below)
+    }
+    if (h->tx) {   // (W1 / b1 of every buffer live in the generic layout: the launch below stays)
+        if (const int rc = ddrl_dqn_tx_pack(h->tx, which, flat_d, false, ddrl::as_stream(stream))) return rc;
+        if (which == DDRL_SAC1_MAIN) h->shadow_stale = false;
     }
     k_pack<<<dim3(64, (unsigned)h->segs.size()), 256, 0, ddrl::as_stream(stream)>>>(h->segs_d, flat_d, buf, nullptr, 1);
     DDRL_LAUNCH_CHECK();
@@ -804,6 +823,20 @@ static void dqn_launch_adam(ddrl_dqn_t *h, float *loss_d, hipStream_t s) {
     h->opt_cur ^= 1;
     h->ad.loss_part = h->hpart; h->ad.loss_out = h->loss; h->ad.loss_out2 = loss_d; h->ad.loss_n = (B + HEAD_ROWS - 1) / HEAD_ROWS; h->ad.loss_scale = 0.5f / (float)B;
     k_adam_polyak<<<(unsigned)blocks + 1, 256, 0, s>>>(h->ad);
+}
+
+// A tail handle's last launches: the same kernel over [W1 ; b1] of each network alone (a contiguous, 16-byte aligned range of the generic
+// layout), out of the copy of the optimizer state k_qtlast has just read into the other one; no loss workgroup (k_qtlast's duty)
+static void dqn_launch_adam_l1(ddrl_dqn_t *h, hipStream_t s) {
+    AdamArgs a = h->ad;
+    a.opt = h->opt + h->opt_cur; a.opt_next = h->opt + (h->opt_cur ^ 1);
+    h->opt_cur ^= 1;
+    for (int n = 0; n < h->nnet; ++n) {   // (every network's launch writes the same advanced powers)
+        a.base4 = h->W1[n] / 4; a.n = h->W2[n];
+        const long long blocks = (a.n / 4 - a.base4 + 255) / 256;
+        a.adam_blocks = (int)blocks;
+        k_adam_polyak<<<(unsigned)blocks, 256, 0, s>>>(a);
+    }
 }
 
 // The launches of one update.  ev != nullptr: an event after every stage (DDRL_DQN_STAGES + 1 events, ev[0] first) for
@@ -839,18 +872,23 @@ static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2
         launch_gemm(h->g_f1, s);
     }
     STAGE_MARK();   // 1 layer-1 forward (+ split-K reduce)
-    launch_gemm(h->g_f2, s);
-    STAGE_MARK();   // 2 layer-2 forward
-    {
-        HeadArgs H = h->head;
-        if (in_place) { H.acts = acts_d; H.rew = rews_d; H.done = done_d; }
-        k_dqn_head<<<(unsigned)((B + HEAD_ROWS - 1) / HEAD_ROWS), 256, head_lds_bytes(H), s>>>(H);
+    if (h->tx) {   // k_qtfwd, k_qtmid in the place of the layer-2 forward, the head and the layer-2 dgrad (never timed: ev == nullptr)
+        if (const int rc = ddrl_dqn_tx_fwd_mid(h->tx, in_place ? acts_d : h->acts, in_place ? rews_d : h->rew, in_place ? done_d : h->done,
+                                               h->head.zero_words, h->head.n_zero, s)) return rc;
+    } else {
+        launch_gemm(h->g_f2, s);
+        STAGE_MARK();   // 2 layer-2 forward
+        {
+            HeadArgs H = h->head;
+            if (in_place) { H.acts = acts_d; H.rew = rews_d; H.done = done_d; }
+            k_dqn_head<<<(unsigned)((B + HEAD_ROWS - 1) / HEAD_ROWS), 256, head_lds_bytes(H), s>>>(H);
+        }
+        STAGE_MARK();   // 3 head: Q of every evaluation, backup / loss / dQ, dZ2
+        STAGE_MARK();   // 4 (folded into 3)
+        STAGE_MARK();   // 5 (folded into 3 and 6)
+        launch_gemm(h->g_b2, s);
+        STAGE_MARK();   // 6 layer-2 dgrad + wgrad
     }
-    STAGE_MARK();   // 3 head: Q of every evaluation, backup / loss / dQ, dZ2
-    STAGE_MARK();   // 4 (folded into 3)
-    STAGE_MARK();   // 5 (folded into 3 and 6)
-    launch_gemm(h->g_b2, s);
-    STAGE_MARK();   // 6 layer-2 dgrad + wgrad
     if (h->wide) {
         // ring rows (ridx): the gradient contracts over the batch rows, so it reads a gathered copy of obs1 (the one array of the
         // batch that is still materialised: 58 MB of the 231)
@@ -874,12 +912,22 @@ static int dqn_step_launch(ddrl_dqn_t *h, const float *obs1_d, const float *obs2
         launch_gemm(h->g_b1, s);
     }
     STAGE_MARK();   // 7 layer-1 wgrad
-    dqn_launch_adam(h, loss_d, s);
+    if (h->tx) {   // k_qtlast (the step size from the optimizer state as it stands), then layer 1's Adam, which advances it
+        if (const int rc = ddrl_dqn_tx_last(h->tx, h->opt + h->opt_cur, loss_d, s)) return rc;
+        dqn_launch_adam_l1(h, s);
+        h->shadow_stale = true;
+    } else {
+        dqn_launch_adam(h, loss_d, s);
+    }
     STAGE_MARK();   // 8 flat Adam + polyak
 #undef STAGE_MARK
     DDRL_LAUNCH_CHECK();
     h->pack_stale = true;   // main moved: the next acting forward repacks its operand copy first
     if (++h->steps_launched == h->poison_after && h->sk_on && h->sk_err_h) *h->sk_err_h = 1;   // (test hook: what a timed-out combine stores)
+    if (q_d && h->tx) {
+        DDRL_HIP_CHECK(hipMemcpyAsync(q_d, ddrl_dqn_tx_qrows(h->tx), (size_t)B * h->cfg.n_actions * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return DDRL_OK;
+    }
     if (q_d) DDRL_HIP_CHECK(hipMemcpy2DAsync(q_d, (size_t)h->cfg.n_actions * sizeof(float), h->Q, (size_t)h->ldq * sizeof(float),
                                              (size_t)h->cfg.n_actions * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s));
     return DDRL_OK;
@@ -943,6 +991,11 @@ int ddrl_dqn_step_timed(ddrl_dqn_t *h, const float *obs1_d, const float *obs2_d,
     DDRL_REQUIRE(reps > 0 && reps <= 64, "reps outside [1, 64]");
     if (h->dx) {
         ddrl::set_error("ddrl_dqn_step_timed: its stage list describes the generic launches; a handle of ddrl_dqn_create_direct runs three others");
+        return DDRL_ERR_UNSUPPORTED;
+    }
+    if (h->tx) {
+        ddrl::set_error("ddrl_dqn_step_timed: its stage list describes the generic launches; a handle of ddrl_dqn_create_direct_tail runs k_qtfwd, "
+                        "k_qtmid and k_qtlast between the layer-1 launches");
         return DDRL_ERR_UNSUPPORTED;
     }
     ddrl::DeviceGuard g(h->device);
@@ -1102,6 +1155,11 @@ int ddrl_dqn_internal_loop_check(ddrl_dqn_t *h, ddrl_replay_t *replay) {
     const int B = h->cfg.batch, o = h->cfg.obs_dim;
     const ddrl_replay_dev::SamplerView rv = ddrl_replay_sampler_view(replay);
     DDRL_REQUIRE(rv.device == h->device, "the replay ring lives on another device than the learner");
+    if (h->tx) {
+        ddrl::set_error("ddrl_dqn_loop_create: the captured loop describes the generic and the narrow direct launch sequences; a handle of "
+                        "ddrl_dqn_create_direct_tail is stepped with ddrl_dqn_step / ddrl_dqn_step_ring");
+        return DDRL_ERR_UNSUPPORTED;
+    }
     if (h->wide) {
         ddrl::set_error("ddrl_dqn_loop: the wide layer-1 path (obs_dim >= 1024, its stream-K weight gradient spins on flags and can poison the learner) "
                         "is kept out of graphs: use ddrl_dqn_step_ring per update");
@@ -1218,5 +1276,25 @@ int ddrl_dqn_create_direct(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t
 }
 
 int ddrl_dqn_is_direct(ddrl_dqn_t *h) { return h ? (h->dx ? 1 : 0) : DDRL_ERR_BAD_ARG; }
+
+// ---- ddrl_dqn_create_direct_tail (include/ddrl_dqn_direct_tail.h) -------------------------------------------------
+int ddrl_dqn_create_direct_tail(ddrl_dqn_t **out, int device, const ddrl_dqn_config_t *cfg) {
+    DDRL_REQUIRE(out != nullptr && cfg != nullptr, "NULL pointer");
+    if (const int rc = ddrl_dqn_tx_check(cfg)) return rc;   // (before anything is allocated)
+    ddrl_dqn_t *h = nullptr;
+    if (const int rc = ddrl_dqn_create(&h, device, cfg)) return rc;
+    ddrl::DeviceGuard g(device);
+    ddrl_dqn_tx_bind b{};
+    b.H1 = h->H1; b.ldh1 = h->ldh1; b.dZ1 = h->dZ1; b.loss = h->loss;
+    for (int n = 0; n < h->nnet; ++n) { b.gen_off[n][0] = h->W2[n]; b.gen_off[n][1] = h->b2[n]; b.gen_off[n][2] = h->W3[n]; }
+    if (const int rc = ddrl_dqn_tx_create(&h->tx, device, cfg, &b)) {
+        ddrl_dqn_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return DDRL_OK;
+}
+
+int ddrl_dqn_is_direct_tail(ddrl_dqn_t *h) { return h ? (h->tx ? 1 : 0) : DDRL_ERR_BAD_ARG; }
 
 }  // extern "C"

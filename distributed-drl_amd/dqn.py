@@ -92,8 +92,11 @@ class Learner:
                                   alpha=float(getattr(opt, "alpha", 0.1)))
         h = ctypes.c_void_p()
         # opt.direct_learner (absent or False by default): the three-launch direct-operand update (ddrl_dqn_create_direct,
-        # include/ddrl_dqn_direct.h); outside its envelope the create refuses, nothing falls back
-        create = self._lib.ddrl_dqn_create_direct if getattr(opt, "direct_learner", False) else self._lib.ddrl_dqn_create
+        # include/ddrl_dqn_direct.h); "tail": the direct-operand layers 2 / 3 behind the layer 1 of a wider observation
+        # (ddrl_dqn_create_direct_tail, include/ddrl_dqn_direct_tail.h: obs_dim >= 14); outside its envelope a create refuses, nothing falls back
+        direct = getattr(opt, "direct_learner", False)
+        create = (self._lib.ddrl_dqn_create_direct_tail if direct == "tail" else self._lib.ddrl_dqn_create_direct if direct
+                  else self._lib.ddrl_dqn_create)
         _lib.check(create(ctypes.byref(h), self.device.index, ctypes.byref(self.cfg)))
         self._h = h
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)

@@ -1285,7 +1285,9 @@ class TrainDeviceDQN:
         if id(rb) not in self._loops:
             h = ctypes.c_void_p()
             rc = self.agent._lib.ddrl_dqn_loop_create(ctypes.byref(h), self.agent._h, rb._h, self.updates_per_graph, _lib.dptr(self.agent.loss))
-            if rc != _lib.DDRL_ERR_UNSUPPORTED:
+            # (a learner of ddrl_dqn_create_direct_tail is refused by name whatever the ring: asking for graphs with it is an error, not a
+            # buffer outside the envelope)
+            if rc != _lib.DDRL_ERR_UNSUPPORTED or self.agent._lib.ddrl_dqn_is_direct_tail(self.agent._h) == 1:
                 _lib.check(rc)
             self._loops[id(rb)] = (rb, h if rc == _lib.DDRL_OK else None)
         return self._loops[id(rb)][1]
